@@ -13,6 +13,20 @@ Multi-GPU: one process per GPU, streams sharded (weak scaling, no collective on 
 barrier + synchronize around the K timed steps, max elapsed over ranks.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c2|c3|c4|c5]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: it generates the inputs, runs W untimed and K
+timed steps, writes the outputs of the last timed step if --dump-outputs is given, and prints the
+line (`roofline` comes from HIP events of the last timed step and the committed profiles, not from
+runs of its own).  --full adds the legs measured beside the headline: `e2e_host_buffers`,
+`other_workloads`, `cpu_baseline`, and C1's oracle comparison (`parity_vs_oracle`) -- null without it.
+
+--dump-outputs DIR writes what the timed path left in the caller's output buffer in its last timed
+step, as float32: DIR/rendered.npy, the rendered PCM channel-samples [streams, frames, 2]; for an
+output above 8 Mi samples a fixed sample of it (the first and last frames of every stream and
+seeded random positions) with the flat positions in DIR/rendered_index.npy, and DIR/meters.npy
+(per stream: clips L, R, peak dB L, R, de-subnormal count).  The inputs are generated from fixed
+seeds, so two builds run with the same arguments can be compared output for output.
 
 --gpus N without a launcher (RANK unset) starts N rank processes itself, before anything here
 touches the GPU, and exits with the worst rank's status; under torch.distributed.run the world
@@ -22,14 +36,14 @@ no collective, so the 8-GPU run executes the same code as the 2-rank tests.  Wit
 than ranks (the 1-GPU box) the ranks share devices.
 
 --workload picks one of the BASELINE.json configs; the default, c2, is the one the
-headline metric is quoted on.  A default run at N=1 also measures the other configs briefly
-(C3/C4/C5: 1 warmup + 2 steps each; C1: one pass) and reports them under `other_workloads` in the
-same line -- beside the headline, never in `value`; --no-other-workloads or --no-cpu-baseline skip
-them.
+headline metric is quoted on.  A --full run at N=1 also measures the other configs briefly
+(C3/C4/C5 and the FIR forms: 2 warmup + 3 steps each; C1: one pass) and reports them under
+`other_workloads` in the same line -- beside the headline, never in `value`; --no-other-workloads
+or --no-cpu-baseline skip them.
 c1 is the single-stream drop-in: the C host examples/icw_transcode (no Python in its loop) decodes
 a 30 s 44.1 kHz stereo track through icw_amod_process_samples in 576-frame blocks from host
-memory, timing every call; its CPU baseline is the oracle on the same track on one core, and the
-two outputs are compared byte for byte.
+memory, timing every call; under --full its CPU baseline is the oracle on the same track on one
+core, and the two outputs are compared byte for byte.
 
 Roofline: the dominant kernel is the serial IIR recurrence K1; its bound is FP64
 VALU issue, so `roofline` reports its algorithmic FP64 rate (the loop-back Kahan sum,
@@ -148,16 +162,21 @@ def parse():
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--streams", type=int, default=None, help="streams per GPU (default: the workload's)")
     ap.add_argument("--frames", type=int, default=None, help="frames per stream per step (default: the workload's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: e2e_host_buffers, other_workloads, "
+                         "cpu_baseline, C1's oracle comparison")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="c2 at N=1: skip the short C1/C3/C4/C5 runs reported under other_workloads")
+                    help="--full, c2 at N=1: skip the short C1/C3/C4/C5 runs reported under other_workloads")
     ap.add_argument("--cpu-workers", type=int, default=0, help="0: one per physical core available here")
     ap.add_argument("--cpu-frames", type=int, default=1 << 25)
     ap.add_argument("--other-frames", type=int, default=None,
                     help="frames per stream of the other_workloads legs (default: each workload's)")
     ap.add_argument("--block", type=int, default=576, help="c1: frames per boundary call (NS_PERTIME)")
     ap.add_argument("--e2e-steps", type=int, default=2,
-                    help="extra steps with host buffers (H2D + D2H included), reported beside `value`")
+                    help="--full: extra steps with host buffers (H2D + D2H included), reported beside `value`")
     return ap.parse_args()
 
 
@@ -298,10 +317,11 @@ def _wav_i16(path, raw, rate, ch):
 
 
 def bench_c1(a):
-    print(json.dumps(measure_c1(a.steps, a.warmup, a.block, not a.no_cpu_baseline)), flush=True)
+    print(json.dumps(measure_c1(a.steps, a.warmup, a.block, a.full and not a.no_cpu_baseline, a.dump_outputs)),
+          flush=True)
 
 
-def measure_c1(steps, warmup, block, with_cpu):
+def measure_c1(steps, warmup, block, with_cpu, dump_dir=None):
     """single-stream drop-in: K runs of the C host over the track, W untimed"""
     import tempfile
     from in_cwave_amd import synth
@@ -323,6 +343,9 @@ def measure_c1(steps, warmup, block, with_cpu):
         if i >= warmup:
             runs.append(json.loads(r.stdout.strip().splitlines()[-1]))
     out = np.frombuffer(dst.read_bytes()[44:], dtype=np.uint8)
+    if dump_dir:
+        Path(dump_dir).mkdir(parents=True, exist_ok=True)
+        np.save(Path(dump_dir) / "rendered.npy", out.view("<i2").astype(np.float32).reshape(1, -1, 2))
     decode_s = sum(x["decode_s"] for x in runs)
     value = 2.0 * W["frames"] * len(runs) / decode_s / 1e6
     cpu = parity = None
@@ -434,7 +457,39 @@ def fir_roofline(wname, W, S, T, kf_ms, kf_n, k2_ms, k2_n, fused):
                     "frame-parallel (no recurrence), so it fills the chip"}
 
 
-def measure_gpu(wname, streams, frames, steps, warmup, e2e_steps, dev, local_dev, dist, rank, world):
+DUMP_WHOLE = 8 << 20           # --dump-outputs: an output of up to this many channel-samples is written whole
+DUMP_RANDOM = 3 << 20          # above it: this many seeded random positions ...
+DUMP_EDGES = 1 << 20           # ... and about this many samples at the two ends of the streams
+DUMP_SEED = 20240
+
+
+def dump_outputs(dump_dir, tag, ctx, d_out, S, T):
+    """--dump-outputs: the output buffer of the last timed step as float32 channel-samples (16- and
+    24-bit PCM are exact in float32), whole or a fixed sample gathered on the device, and the meters"""
+    import torch
+    rs = ctx.render_size
+    total = S * T * 2
+    flat = d_out.view(-1, rs)                       # one row per little-endian channel-sample
+    d = Path(dump_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    if total <= DUMP_WHOLE:
+        b, shape = flat.cpu().numpy(), (S, T, 2)
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        e = 2 * min(512, T // 2, DUMP_EDGES // (4 * S))
+        ends = np.concatenate([np.arange(e), np.arange(2 * T - e, 2 * T)])
+        idx = np.unique(np.concatenate([rng.integers(0, total, size=DUMP_RANDOM, dtype=np.int64),
+                                        (np.arange(S, dtype=np.int64)[:, None] * (2 * T) + ends[None, :]).ravel()]))
+        b, shape = flat.index_select(0, torch.from_numpy(idx).to(d_out.device)).cpu().numpy(), (idx.size,)
+        np.save(d / f"rendered_index{tag}.npy", idx.astype(np.float64))
+    v = np.zeros((b.shape[0], 4), dtype=np.uint8)
+    v[:, 4 - rs:] = b                               # left-justified in an int32, then an arithmetic shift
+    np.save(d / f"rendered{tag}.npy", (v.view("<i4").ravel() >> (8 * (4 - rs))).astype(np.float32).reshape(shape))
+    m = [ctx.meters(s) for s in range(S)]
+    np.save(d / f"meters{tag}.npy", np.array([[*x["clips"], *x["peak_db"], x["desubnorm"]] for x in m], dtype=np.float64))
+
+
+def measure_gpu(wname, streams, frames, steps, warmup, e2e_steps, dev, local_dev, dist, rank, world, dump_dir=None):
     """one workload on this rank's device: W untimed steps, then K steps between barriers +
     synchronize, max over ranks; the K1 roofline from the HIP-event timing of the timed steps"""
     import torch
@@ -485,6 +540,9 @@ def measure_gpu(wname, streams, frames, steps, warmup, e2e_steps, dev, local_dev
                          device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if dump_dir:
+        dump_outputs(dump_dir, f"_rank{rank}" if world > 1 else "", ctx, d_out, S, T)
 
     frames_total = float(S) * T * steps * world
     value = 2.0 * frames_total / elapsed / 1e6
@@ -627,18 +685,18 @@ def main():
     dev = torch.device("cuda", local_dev)
     torch.cuda.set_device(dev)
 
-    r = measure_gpu(a.workload, a.streams, a.frames, a.steps, a.warmup, a.e2e_steps, dev, local_dev, dist, rank,
-                    world)
+    r = measure_gpu(a.workload, a.streams, a.frames, a.steps, a.warmup, a.e2e_steps if a.full else 0, dev,
+                    local_dev, dist, rank, world, a.dump_outputs)
     W, S, T, fs = r["W"], r["S"], r["T"], r["fs"]
     value, ms_per_step, roof, e2e = r["value"], r["ms_per_step"], r["roofline"], r["e2e"]
 
-    # ---- the other BASELINE configs, measured in the same run: short runs of the same harness,
+    # ---- --full: the other BASELINE configs, measured in the same run: short runs of the same harness,
     # reported beside the headline, never in `value`.  N = 1: C3 / C4 / C5 and their FIR forms, and
     # the C1 drop-in.  N > 1: the configs BASELINE.json quotes "sharded across 8xMI355X" -- C4 and
     # C5 (and their 255 / 1023-tap FIR forms) at their per-GPU shard sizes (2 048 / 256 streams per
     # rank: 16 384 / 2 048 at N = 8), timed like the headline (barriers, max over ranks), whole-job
     others = None
-    want_others = a.workload == "c2" and not a.no_other_workloads and (
+    want_others = a.full and a.workload == "c2" and not a.no_other_workloads and (
         world > 1 or (not a.no_cpu_baseline and a.streams is None and a.frames is None))
     if want_others:
         others = {}
@@ -672,13 +730,13 @@ def main():
             except (SystemExit, Exception) as e:      # reported, never silently replaced
                 others["c1"] = {"error": repr(e)}
 
-    # ---- the CPU baseline: at N = 1 only (the task's contract), after the GPU legs (never beside GPU
-    # timing); a multi-GPU line carries null
+    # ---- the CPU baseline: under --full at N = 1 only, after the GPU legs (never beside GPU timing);
+    # a plain or a multi-GPU line carries null
     if dist:
         torch.cuda.synchronize()
         dist.barrier()
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         try:
             cpu = cpu_baseline(a.cpu_workers, a.cpu_frames, a.workload)
         except Exception as e:  # reported, never silently replaced

@@ -57,7 +57,8 @@ def test_bench_gpus_flag_self_launches():
     time) and the roofline from rank 0's K1 events; the CPU baseline is an N = 1 field (null here)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1",
-                        "--frames", "32768", "--streams", "64", "--e2e-steps", "0", "--other-frames", "16384"],
+                        "--frames", "32768", "--streams", "64", "--e2e-steps", "0", "--other-frames", "16384",
+                        "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
@@ -79,7 +80,7 @@ def test_bench_line_fields():
     """the roofline is FP64-bound with HBM and issue-floor fields, the e2e host-buffer rate is
     reported beside `value`"""
     r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--frames", "65536",
-                        "--no-cpu-baseline", "--e2e-steps", "1"], cwd=ROOT, capture_output=True, text=True,
+                        "--full", "--no-cpu-baseline", "--e2e-steps", "1"], cwd=ROOT, capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -92,10 +93,52 @@ def test_bench_line_fields():
     assert d["e2e_host_buffers"]["value"] > 0
 
 
+@pytest.mark.parametrize("streams,frames,whole", [(4, 3001, True), (64, 65601, False)])
+def test_bench_plain_run_dumps_outputs(icw, tmp_path, streams, frames, whole):
+    """a plain run carries none of the --full legs, and --dump-outputs writes the rendered samples of
+    the last timed step: whole for a small output, else the fixed sample (every stream's first and
+    last frames among its positions) -- equal to what the host path renders from the same input"""
+    import numpy as np
+    import bench
+    from in_cwave_amd import synth
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "1", "--warmup", "0", "--streams",
+                        str(streams), "--frames", str(frames), "--dump-outputs", str(tmp_path / "d")], cwd=ROOT,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _line(r.stdout)
+    assert d["steps"] == 1 and d["ms_per_step"] > 0 and d["roofline"]["avg_launch_ms"] > 0
+    assert d["e2e_host_buffers"] is None and d["cpu_baseline"] is None and d["other_workloads"] is None
+    W = bench.WORKLOADS["c2"]
+    cfg, nodes, fmt = bench.workload_config(W)
+    ctx = icw.Context(cfg, nodes, streams, device=0)
+    out, _ = ctx.process(synth.batch_pcm(streams, frames, W["fs"], workers=synth.cpu_workers()), frames)
+    want = out.view("<i2").reshape(streams, frames, 2)
+    got = np.load(tmp_path / "d" / "rendered.npy")
+    m_bytes = (tmp_path / "d" / "meters.npy").stat().st_size
+    assert got.dtype == np.float32
+    if whole:
+        assert not (tmp_path / "d" / "rendered_index.npy").exists()
+        assert np.array_equal(got, want)
+    else:
+        idx = np.load(tmp_path / "d" / "rendered_index.npy")
+        assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and got.shape == idx.shape
+        assert bench.DUMP_RANDOM // 2 < idx.size and idx.nbytes + got.nbytes + m_bytes <= 64 << 20
+        pos = idx.astype(np.int64)
+        first = np.arange(streams, dtype=np.int64) * 2 * frames
+        assert np.isin(first, pos).all() and np.isin(first + 2 * frames - 1, pos).all()
+        assert np.array_equal(got, want.reshape(-1)[pos])
+    m = np.load(tmp_path / "d" / "meters.npy")
+    assert m.shape == (streams, 5)
+    for s in (0, streams - 1):
+        ref = ctx.meters(s)
+        assert tuple(m[s, :2]) == ref["clips"] and tuple(m[s, 2:4]) == ref["peak_db"] and m[s, 4] == ref["desubnorm"]
+    ctx.close()
+
+
 def test_bench_c1_drop_in_line():
     """C1: the C host through the drop-in boundary in 576-frame blocks; its output equals the oracle's"""
-    r = subprocess.run([sys.executable, "bench.py", "--workload", "c1", "--steps", "1", "--warmup", "0"], cwd=ROOT,
-                       capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, "bench.py", "--workload", "c1", "--steps", "1", "--warmup", "0", "--full"],
+                       cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
     assert d["parity_vs_oracle"] == "bit-exact"

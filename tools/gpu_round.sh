@@ -17,7 +17,7 @@ for s in "$@"; do
     test)  step pytest_gpu 900 python -m pytest tests -m gpu -q -x; ok $? || exit 2 ;;
     testall) step pytest_gpu 900 python -m pytest tests -m gpu -q; ok $? || exit 2 ;;
     bench) step bench 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline || exit 2 ;;
-    benchfull) step bench_full 900 python bench.py || exit 2 ;;
+    benchfull) step bench_full 900 python bench.py --full || exit 2 ;;
     benchall)
       for w in c2 c3 c4 c5; do
         step bench_$w 600 python bench.py --workload $w --steps 3 --warmup 1 --no-cpu-baseline || exit 2
