@@ -22,7 +22,6 @@ struct IcwProg;
 
 /* Arguments of the input prep kernel (one thread = one frame). */
 struct IcwK0Args {
-    uint32_t lds_guard;            /* dynamic LDS bytes: > 0 keeps the launch off the CUs K1 holds */
     const unsigned char *in;       /* stream s at in + s*in_stride */
     size_t in_stride;
     uint32_t fmt, csz, fsz, nch;   /* sample format, channel/frame bytes, channels */
@@ -70,7 +69,6 @@ struct IcwFirArgs {
  * kernel reads the call-start position / phases / frame counter and adds its block offset; this
  * kernel advances them once, after the last block. */
 struct IcwAdvArgs {
-    uint32_t lds_guard;            /* dynamic LDS bytes: > 0 keeps the launch off the CUs K1 holds */
     int32_t n_streams, cw;
     long long n;                   /* frames processed by the call */
     uint32_t *hq_phase;
@@ -86,7 +84,6 @@ struct IcwAdvArgs {
 
 /* Arguments of the serial graph kernel (bus form; one lane = one stream, loops over frames). */
 struct IcwK4Args {
-    uint32_t lds_guard;            /* dynamic LDS bytes: > 0 keeps the launch off the CUs K1 holds */
     const double *iq;              /* [n_streams][T][4] `in` per frame (lre, lim, rre, rim) */
     int32_t n_streams, T;
     long long t0;
@@ -117,8 +114,6 @@ struct IcwK1Args {
     long long t0;                  /* block offset into the call */
     int *err;                      /* set by a bounded spin that gave up (never in a healthy run) */
     int32_t wg_waves;              /* waves per workgroup of the plain / row kernels (1..4) */
-    uint32_t lds_hold;             /* LDS bytes a K1 workgroup holds (static + dynamic): the CU's whole
-                                      LDS keeps every LDS-using workgroup off K1's CUs; 0: static only */
     int32_t dedup;                 /* mono, every stream's converters identical: left chains only */
     double pc[20];                 /* loop-back coefficients -a[i+1]/a0 */
     uint32_t *fes;                 /* FP_CHECK: [n_streams][4][ICW_FES_PITCH] census (Hilbert L, R,
@@ -164,17 +159,28 @@ struct IcwProg {
                                       before it: values stay in registers (no LDS register file) */
     int32_t sig;                   /* chain programs: op count | (mode | chain_in << 2) << (4 + 4 i), ops in
                                       execution order; the fused FIR kernel runs a few of these straight
-                                      (ICW_SIG_*, icw_kernels.hip); 0: not a chain */
+                                      (ICW_SIG_*, below); 0: not a chain */
     int32_t persist_reg[ICW_MAX_REGS], persist_slot[ICW_MAX_REGS];
     IcwOp ops[ICW_MAX_OPS];
 };
+
+/* Chain-program signatures compiled straight (IcwProg.sig: the op count in bits 0-3, then per op in
+ * execution order (tail first) 4 bits: mode | chain_in << 2).  Each is one of the BASELINE graphs:
+ * Master on `in` (C3 / C5), Shift -> Master (C1 / C2), PM -> Shift -> Mix(in + B) -> Master (C4).  Any
+ * other chain runs the generic op loop (icw_chain_sig, icw_kernels.hip). */
+#define ICW_SIG_M    0x41
+#define ICW_SIG_SM   0x852
+#define ICW_SIG_PSXM 0x8F964
+/* flag: every op but the Master has gain 1.0 on both channels (the BASELINE lists' Shift / PM / Mix,
+ * DEF_GAIN_MOD in_cwave.h:166), so the render-only form skips those multiplies at compile time */
+#define ICW_SIG_UNIT (1 << 30)
 
 /* Render constants computed on the host by the sound_render_recalc arithmetic
  * (sound_render.c:499-581), so pow() runs once on the CPU exactly as in the reference. */
 struct IcwRenderK {
     double norm_mul, dth_mul, hi, lo, round_offset;
     double clip_abs;               /* min(hi, -lo): a q with |q| below it clips at neither bound */
-    double spec_thr;               /* K3r: a 20-sample block whose every x * norm_mul is <= this in magnitude,
+    double spec_thr;               /* K3c: a 20-sample block whose every x * norm_mul is <= this in magnitude,
                                       after a block whose every |q| < clip_abs, clips nowhere (render_consts);
                                       -1: no clamp-free blocks */
     int32_t sign_delta, norm_shift, is24;
@@ -200,15 +206,14 @@ struct IcwK3Args {
     IcwRenderK rk;
     double *dith;                  /* rnd * dth_mul per sample (K3a -> the render); null: ROUND.  dith_gm 0:
                                       time-major [T][dith_pitch] (K3b, K3f: a lane per channel reads one
-                                      row coalesced); 1: generator-major [n_gen][dith_pitch] (K3r and the
+                                      row coalesced); 1: generator-major [n_gen][dith_pitch] (K3c and the
                                       frame-parallel renders read runs of one channel; K3a writes 512-byte runs) */
     size_t dith_pitch;
     uint32_t *fes;                 /* FP_CHECK census, as in IcwK1Args; null: no FC() */
-    int32_t row;                   /* render kernel: 1 row broadcast (K3r, small batches), 0 lane per channel */
+    int32_t row;                   /* render kernel: 1 row broadcast (K3c, small batches), 0 lane per channel */
     int32_t dith_gm;               /* layout of dith (above) */
-    int32_t comp;                  /* K3r: 1 with a companion wave (staging and flush off the chain's wave) */
     int32_t *err;                  /* nonzero after a companion hand-off that never came (never in a healthy run) */
-    /* the split dither generator (icw_launch_dither; null wbuf: the one-kernel K3a, ICW_DITHER=coop) */
+    /* the split dither generator (icw_launch_dither) */
     uint32_t *wbuf;                /* [n_gen][wpitch] tempered MT words of a chunk (K3t -> K3s) */
     size_t wpitch, wcap;           /* words per generator row; rows' capacity in words (chunking) */
     int32_t *dflag;                /* [n_gen] a rejected dsopen pair in the chunk: K3f redoes the channel */
@@ -263,7 +268,6 @@ struct IcwK2Args {
 /* Per-frame rotation table (one thread per frame): the Shift / PM factors depend only on the frame
  * counter, so streams in step share them -- computed once per block, not once per stream. */
 struct IcwTrigArgs {
-    uint32_t lds_guard;            /* dynamic LDS bytes: > 0 keeps the launch off the CUs K1 holds */
     const IcwProg *prog;
     const unsigned long long *n_frame;   /* the reference stream's call-start counter (stream 0) */
     long long t0;

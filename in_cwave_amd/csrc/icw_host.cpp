@@ -23,6 +23,7 @@
 #include "../../include/icw.h"
 #include "icw_device.h"
 #include "icw_tables.inc"
+#include "icw_tuning.h"
 
 extern "C" hipError_t icw_launch_unpack(const IcwK0Args *a, hipStream_t st);
 extern "C" hipError_t icw_launch_iir_state(const IcwK1Args *a, int nord, int kahan, int subn, hipStream_t st);
@@ -30,14 +31,14 @@ extern "C" hipError_t icw_launch_iir_row(const IcwK1Args *a, int nord, int kahan
 extern "C" hipError_t icw_launch_iir_fc(const IcwK1Args *a, int nord, int kahan, int subn, hipStream_t st);
 extern "C" hipError_t icw_launch_render(const IcwK3Args *a, hipStream_t st);
 extern "C" hipError_t icw_launch_dither(const IcwK3Args *a, hipStream_t st);
-extern "C" hipError_t icw_launch_dither_lane(const IcwK3Args *a, hipStream_t st);
 extern "C" hipError_t icw_launch_output(const IcwK2Args *a, int nord, int kahan, hipStream_t st);
 extern "C" hipError_t icw_launch_trig_table(const IcwTrigArgs *a, hipStream_t st);
 extern "C" hipError_t icw_launch_graph_serial(const IcwK4Args *a, hipStream_t st);
 extern "C" hipError_t icw_launch_advance(const IcwAdvArgs *a, hipStream_t st);
 extern "C" hipError_t icw_launch_stream1(const IcwS1Args *a, int nord, hipStream_t st);
 extern "C" hipError_t icw_launch_fir(const IcwFirArgs *a, hipStream_t st);
-extern "C" hipError_t icw_launch_fir_graph(const IcwFirArgs *f, const IcwK2Args *a, int in_step, hipStream_t st);
+extern "C" hipError_t icw_launch_fir_graph(const IcwFirArgs *f, const IcwK2Args *a, int in_step, int sig_on,
+                                           hipStream_t st);
 extern "C" size_t icw_fir_graph_lds(int M, int nt, int nch, int n_regs);
 
 #define ICW_PI_H (3.1415926535897932384626433832795029)
@@ -51,10 +52,6 @@ double u2d(unsigned long long u)
     return d;
 }
 
-/* frames per kernel launch: bounds the w scratch buffer (n_chains * (T+N) doubles) */
-constexpr int kMaxBlockFrames = 1 << 16;
-constexpr int kDefBlockFrames = 1 << 14;   /* launch block: shorter pipeline fill / drain */
-constexpr int kSets = 3;                    /* most block scratch sets (ICW_SETS); default 2 */
 constexpr double kAutoTaper = 0.85;          /* tail block ratio where the taper is on by default */
 constexpr double kRowTaper = 0.25;           /* tail ratio of the row kernel's long blocks (no serial render) */
 /* FIR converter + serial render: the first blocks grow by this ratio from kFirRenderFirst frames, so
@@ -104,6 +101,7 @@ struct CuSplit {
 
 struct icw_ctx {
     icw_config cfg{};
+    IcwTuning tn;                         /* the ICW_* switches as icw_create found them */
     std::vector<icw_node> nodes;
     int n_streams = 0;
     int device = 0;
@@ -126,41 +124,6 @@ struct icw_ctx {
     hipStream_t stream2 = nullptr;
     hipEvent_t k1done[kSets] = {}, k2done[kSets] = {}, join = nullptr;
     hipEvent_t k0done[kSets] = {};
-    bool cu_split = true;                 /* ICW_CU_SPLIT=0 disables the partition */
-    /* ICW_K1_WPC: K1 waves per CU.  Two: measured under a working partition, 4 per CU (one per
-     * SIMD) made K1 +21 % slower even alone (C3, 4-wave workgroups), 3 per CU +27 % beside K2, and 1
-     * per CU leaves the frame-parallel kernels too few CUs (C4 K2 2.57 -> 3.70 ms) */
-    int k1_wpc = 2;
-    /* ICW_REST_CUS: at most this many CUs for the frame-parallel kernels beside K1 (0: all the rest).
-     * Default (-1): all but 32 (4 per XCD) -- idle CUs leave K1 power headroom: C3 41.6-42.2k ->
-     * 42.6-42.9k, C4 20.9k -> 21.1-21.3k Msamples/s at 160 and 176 (profiles/r04_rest_cus.txt);
-     * below 160 K2 falls behind (C3 38.0k at 144 and 128) */
-    int rest_cus = -1;
-    double fir_ramp = 0.0;                /* ICW_FIR_RAMP: the ramp of a FIR + serial-render call (0: kFirRenderRamp) */
-    /* ICW_K1_WG: K1 waves per workgroup.  Default 1 for the lane kernel, 2 for the row kernel: its I and
-     * Q filter waves of the same streams then share a CU, so the second one reads the channel rows
-     * (one per channel since round 3) from the L2 / L1 the first one filled (C2 +0.7 %, C5 +0.4 %; the
-     * lane kernel loses 2-2.5 % on C3 / C4 with 2) */
-    int k1_wg = 1;
-    bool k1_wg_env = false;
-    bool k1_lds = false;                  /* ICW_K1_LDS=1: K1 workgroups hold the CU's LDS (A/B) */
-    bool fill_drain = true;               /* ICW_FILL_DRAIN=0: first K0 / last K2 stay partitioned (A/B) */
-    uint32_t lds_cu = 0;                  /* LDS bytes per CU a workgroup may hold */
-    int max_block = kDefBlockFrames;      /* ICW_BLOCK: frames per launch block */
-    bool block_env = false;               /* ICW_BLOCK given */
-    bool dedup_ok = true;                 /* ICW_DEDUP=0 disables the mono K1 dedup (A/B) */
-    int max_sets = 2;                     /* ICW_SETS: block scratch sets (2..kSets) */
-    /* block schedule of long calls (plan_blocks): a short first block (the pipeline fill is K0 of
-     * block 0 alone: C3 +2.5 %, C4 +1.4 %) and an optional geometric tail (the drain is K2 / K3 of
-     * the last block alone).  The tail pays only if K0 + K2 (and K3) of a block fit beside K1 of a
-     * block r times shorter: in C3 / C4 they take 0.87 / 0.94 of K1's time per frame, and r = 0.85
-     * measured C3 -4 %, C4 -8 %; in C5 (K1r, K2 0.12 and the row render K3r 0.64 of K1r on their own
-     * streams) r = 0.85 measured +2 %.  So it is on by default for the row kernel with a serial
-     * render only (icw_process_streams). */
-    int first_block = 4096;               /* ICW_FIRST_BLOCK (0: uniform blocks) */
-    bool first_block_env = false;
-    double taper = -1.0;                  /* ICW_TAPER: tail block ratio (0: no tail; -1: auto) */
-    int taper_min = 1024;                 /* ICW_TAPER_MIN: smallest tail block */
     /* dither generation (K3a) runs on its own stream, double-buffered like the block scratch */
     hipStream_t stream3 = nullptr;
     hipEvent_t ditdone[kSets] = {};
@@ -183,10 +146,6 @@ struct icw_ctx {
     unsigned char *h_stage = nullptr;
     unsigned char *h_stage_dev = nullptr; /* the same memory as the device addresses it */
     size_t h_stage_bytes = 0;
-    /* ICW_ZEROCOPY=0: small calls copy the staging buffer to and from HBM instead of the kernels
-     * reading the input from, and writing the output to, the pinned buffer directly */
-    bool zero_copy = true;
-    bool spin_wait = true;                /* ICW_SPIN=0: K5 zero-copy calls wait on the stream instead */
     uint32_t s1_seq = 0;                  /* K5 completion sequence number (host-polled) */
     /* the serial render (K4 bus-form graph + K3b) runs on a fourth stream, one block behind K2:
      * its inputs are double-buffered like the block scratch */
@@ -216,14 +175,6 @@ struct icw_ctx {
     hipStream_t stream = nullptr;
     std::vector<hipEvent_t> ev;
     int n_cu = 256;
-    int k1_mode = -1;         /* K1 variant: -1 auto (row / plain), 0 plain lanes, 3 row broadcast
-                                 (ICW_K1_MODE=plain|row, A/B runs) */
-    bool dither_lane = false; /* ICW_DITHER=lane: lane-per-channel dither generator (A/B only) */
-    bool dither_coop = false; /* ICW_DITHER=coop: the one-kernel wave-per-channel generator K3a (A/B only) */
-    bool k3r_comp = true;     /* ICW_K3R_COMP=0: the row render without its companion wave (K3r, A/B) */
-    int render_row = -1;      /* serial render kernel: -1 auto (row broadcast for <= kRowRenderMax
-                                 channels), 0 lane per channel, 1 row (ICW_RENDER=serial|row) */
-    bool serialize = false;   /* ICW_SERIALIZE=1: every kernel on the caller's stream (profiling) */
     double last_ms[2]{};
     int last_launches[2]{};
     int last_k1 = -1;                     /* ICW_K1_* of the last real-input call */
@@ -234,10 +185,6 @@ struct icw_ctx {
     double *d_fir_g = nullptr;
     double *fir_hist[2] = {};
     int fir_par = 0;
-    bool fir_fuse = true;                 /* ICW_FIR_FUSED=0: KF + K2 as two kernels (A/B) */
-    bool stream1 = true;                  /* ICW_STREAM1=0: one-stream calls keep the four kernels (A/B) */
-    bool s1_ovl = true;                   /* ICW_S1_OVL=0: K5's output phase after the recurrence (A/B) */
-    bool chain_ok = true;                 /* ICW_CHAIN=0: chain programs keep the LDS register file (A/B) */
     unsigned long long *s1_stamps = nullptr;   /* ICW_S1_STAMPS=1: K5 phase stamps, printed per call */
     unsigned long long calls = 0;         /* icw_process_* calls so far (icw_prepare needs a fresh context) */
     /* per-stream state set by an entry point other than a call (stream_open, seek, set_state, the
@@ -538,14 +485,15 @@ int compile_graph(const std::vector<icw_node> &nodes, int bypass, IcwProg &P)
         bool unit = true;
         for (int oi = 0; oi < n_ops; ++oi)
             if (P.ops[oi].mode != ICW_MODE_MASTER) unit &= P.ops[oi].gain[0] == 1.0 && P.ops[oi].gain[1] == 1.0;
-        if (unit) P.sig |= 1 << 30;
+        if (unit) P.sig |= ICW_SIG_UNIT;
     }
     set_needs_omega(P);
     return ICW_OK;
 }
 
-/* sound_render_recalc arithmetic (sound_render.c:499-581) */
-void render_consts(const icw_render_cfg &cfg, int is24, IcwRenderK &k)
+/* sound_render_recalc arithmetic (sound_render.c:499-581); spec: the row render's clamp-free blocks
+ * (IcwTuning.k3r_spec) */
+void render_consts(const icw_render_cfg &cfg, int is24, bool spec, IcwRenderK &k)
 {
     memset(&k, 0, sizeof(k));
     k.dth_mul = pow(2.0, cfg.dth_bits) - 1.0;
@@ -579,7 +527,7 @@ void render_consts(const icw_render_cfg &cfg, int is24, IcwRenderK &k)
     k.ns_n = icw_ns_n[t];
     const int nc = k.ns_kind == 2 ? 2 * k.ns_n : k.ns_n;
     for (int i = 0; i < nc; ++i) k.ns_c[i] = u2d(icw_ns_c[t][i]);
-    /* K3r's clamp-free blocks (icw_render_row).  Without a clip the error fed back is small: with
+    /* the row render's clamp-free blocks (icw_render_rowc).  Without a clip the error fed back is small: with
      * q = input + d and the integer trunc(q) + delta (mid-riser) or trunc(q +- 0.5) (mid-tread),
      * |ev| = |(double)val - input| <= 1.5 + Dm, Dm the largest |rnd * dth_mul| of the render type
      * (sound_render.c:711-751: RPDF |dsopen| / SQRT2 < 0.708, TPDF and STPDF < 1, GAUSS 12 / (2 SQRT6)
@@ -589,7 +537,6 @@ void render_consts(const icw_render_cfg &cfg, int is24, IcwRenderK &k)
      * sample: nothing clips and the clamp is the identity, so the block runs without it.  The IIR
      * shaper feeds back its own output: never. */
     k.spec_thr = -1.0;
-    static const bool spec = !getenv("ICW_K3R_SPEC") || atoi(getenv("ICW_K3R_SPEC")) != 0;
     if (spec && k.ns_kind != 2 && cfg.render_type <= ICW_RENDER_GAUSS) {
         static const double cdm[5] = {0.0, 0.708, 1.0, 1.0, 2.45};
         double B = 0.0;
@@ -630,23 +577,17 @@ int build_prog(const icw_config &cfg, std::vector<icw_node> nodes, IcwProg &P)
  * shaper feeds each sample's error into the next: serial per channel, in the serial render kernel --
  * as is every render behind a bus-form graph (frame-serial, hands lOut / rOut over) or with FP_CHECK
  * (the FC() render arithmetic lives in the serial render kernel only). */
-bool dith_par_on()
+bool needs_serial(const icw_config &cfg, const IcwRenderK &rk, const IcwProg &P, bool dith_par)
 {
-    static const bool on = !getenv("ICW_DITH_PAR") || atoi(getenv("ICW_DITH_PAR")) != 0;
-    return on;
-}
-
-bool needs_serial(const icw_config &cfg, const IcwRenderK &rk, const IcwProg &P)
-{
-    const bool elementwise = rk.ns_kind == 0 && (cfg.render.render_type == ICW_RENDER_ROUND || dith_par_on());
+    const bool elementwise = rk.ns_kind == 0 && (cfg.render.render_type == ICW_RENDER_ROUND || dith_par);
     return !elementwise || P.is_bus || cfg.fp_check;
 }
 
 /* the per-channel render state (MT19937 words, prev_rnd, shaper rings): a serial render, or a dithered
  * one rendered frame-parallel (its generator still runs, K3a) */
-bool needs_render_state(const icw_config &cfg, const IcwRenderK &rk, const IcwProg &P)
+bool needs_render_state(const icw_config &cfg, const IcwRenderK &rk, const IcwProg &P, bool dith_par)
 {
-    return needs_serial(cfg, rk, P) || cfg.render.render_type != ICW_RENDER_ROUND;
+    return needs_serial(cfg, rk, P, dith_par) || cfg.render.render_type != ICW_RENDER_ROUND;
 }
 
 bool render_cfg_ok(const icw_render_cfg &r)
@@ -779,7 +720,7 @@ void split_ref(int device, int delta)
 const CuSplit *cu_split(icw_ctx *c, int k1_cus)
 {
     std::lock_guard<std::mutex> lk(g_split_mu);
-    const int rest_cus = c->rest_cus >= 0 ? c->rest_cus : std::max(c->n_cu - k1_cus - 32, c->n_cu / 2);
+    const int rest_cus = c->tn.rest_cus >= 0 ? c->tn.rest_cus : std::max(c->n_cu - k1_cus - 32, c->n_cu / 2);
     for (auto &x : g_splits)
         if (x.first == c->device && x.second.k1_cus == k1_cus && x.second.rest_cus == rest_cus) return &x.second;
     const int n = c->n_cu, words = (n + 31) / 32;
@@ -963,8 +904,8 @@ int apply_graph(icw_ctx *c, std::vector<icw_node> &nv, int bypass, const std::ve
     IcwProg P;
     int rc = build_prog(cfg, nv, P);
     if (rc) return rc;
-    if (!c->chain_ok) P.chain = P.sig = 0;
-    const bool serial = needs_serial(cfg, c->rk, P), rstate = needs_render_state(cfg, c->rk, P);
+    if (!c->tn.chain_ok) P.chain = P.sig = 0;
+    const bool serial = needs_serial(cfg, c->rk, P, c->tn.dith_par), rstate = needs_render_state(cfg, c->rk, P, c->tn.dith_par);
     if (rstate && (rc = ensure_render_state(c))) return rc;
     if (hipMemcpy(c->d_prog, &P, sizeof(IcwProg), hipMemcpyHostToDevice) != hipSuccess) return ICW_EDEVICE;
     c->cfg.bypass_list = cfg.bypass_list;
@@ -1021,12 +962,14 @@ int icw_create(const icw_config *cfg, const icw_node *nodes, int n_nodes, int n_
     const bool ok = graph_accept(c->nodes);
     if (!ok) c->nodes.assign(1, default_master());
     if (accepted) *accepted = ok ? 1 : 0;
+    c->tn = icw_read_tuning();
     int rc = build_prog(*cfg, c->nodes, c->prog);
     if (rc) { delete c; return rc; }
+    if (!c->tn.chain_ok) c->prog.chain = c->prog.sig = 0;
     set_filter(c);
-    render_consts(cfg->render, cfg->need24bits, c->rk);
-    c->serial_render = needs_serial(*cfg, c->rk, c->prog);
-    c->render_state = needs_render_state(*cfg, c->rk, c->prog);
+    render_consts(cfg->render, cfg->need24bits, c->tn.k3r_spec, c->rk);
+    c->serial_render = needs_serial(*cfg, c->rk, c->prog, c->tn.dith_par);
+    c->render_state = needs_render_state(*cfg, c->rk, c->prog, c->tn.dith_par);
     for (int ch = 0; ch < 2; ++ch) {
         uint32_t *st = c->mt_seed_state[ch];
         st[0] = ch ? cfg->seed_right : cfg->seed_left;         /* mtrnd_init_seed, mt_jrnd.c:28-47 */
@@ -1081,79 +1024,8 @@ int icw_create(const icw_config *cfg, const icw_node *nodes, int n_nodes, int n_
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, c->device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
-        c->k1_mode = -1;
-        const char *m = getenv("ICW_K1_MODE");
-        if (m && !strcmp(m, "plain")) c->k1_mode = 0;
-        if (m && !strcmp(m, "row")) c->k1_mode = 3;
-        const char *rr = getenv("ICW_RENDER");
-        if (rr && !strcmp(rr, "serial")) c->render_row = 0;
-        if (rr && !strcmp(rr, "row")) c->render_row = 1;
-        const char *d = getenv("ICW_DITHER");
-        c->dither_lane = d && !strcmp(d, "lane");
-        c->dither_coop = d && !strcmp(d, "coop");
-        const char *kc = getenv("ICW_K3R_COMP");
-        if (kc && !strcmp(kc, "0")) c->k3r_comp = false;
-
-        const char *z = getenv("ICW_SERIALIZE");
-        c->serialize = z && !strcmp(z, "1");
-        const char *cs = getenv("ICW_CU_SPLIT");
-        if (cs && !strcmp(cs, "0")) c->cu_split = false;
-        const char *wpc = getenv("ICW_K1_WPC");
-        if (wpc && atoi(wpc) >= 1 && atoi(wpc) <= 8) c->k1_wpc = atoi(wpc);
-        const char *fr = getenv("ICW_FIR_RAMP");
-        if (fr && atof(fr) > 1.0 && atof(fr) <= 16.0) c->fir_ramp = atof(fr);
-        const char *rc = getenv("ICW_REST_CUS");
-        if (rc && (atoi(rc) == 0 || atoi(rc) >= 8)) c->rest_cus = atoi(rc);
-        const char *bl = getenv("ICW_BLOCK");
-        if (bl && atoi(bl) >= 256 && atoi(bl) <= kMaxBlockFrames) { c->max_block = atoi(bl); c->block_env = true; }
-        const char *ns = getenv("ICW_SETS");
-        if (ns && atoi(ns) >= 2 && atoi(ns) <= kSets) c->max_sets = atoi(ns);
-        const char *zc = getenv("ICW_ZEROCOPY");
-        if (zc && !strcmp(zc, "0")) c->zero_copy = false;
-        const char *sw = getenv("ICW_SPIN");
-        if (sw && !strcmp(sw, "0")) c->spin_wait = false;
-        const char *fb = getenv("ICW_FIRST_BLOCK");
-        if (fb && atoi(fb) >= 0) { c->first_block = atoi(fb); c->first_block_env = true; }
-        const char *tp = getenv("ICW_TAPER");
-        if (tp && atof(tp) >= 0.0 && atof(tp) < 1.0) c->taper = atof(tp);
-        const char *tm = getenv("ICW_TAPER_MIN");
-        if (tm && atoi(tm) >= 64) c->taper_min = atoi(tm);
-        const char *dd = getenv("ICW_DEDUP");
-        if (dd && !strcmp(dd, "0")) c->dedup_ok = false;
-        const char *fd = getenv("ICW_FILL_DRAIN");
-        if (fd && !strcmp(fd, "0")) c->fill_drain = false;
-        const char *ff = getenv("ICW_FIR_FUSED");
-        if (ff && !strcmp(ff, "0")) c->fir_fuse = false;
-        const char *che = getenv("ICW_CHAIN");
-        if (che && !strcmp(che, "0")) {
-            c->chain_ok = false;
-            c->prog.chain = c->prog.sig = 0;
-            if (hipMemcpy(c->d_prog, &c->prog, sizeof(IcwProg), hipMemcpyHostToDevice) != hipSuccess) {
-                free_all(c);
-                delete c;
-                return ICW_EDEVICE;
-            }
-        }
-        const char *s1e = getenv("ICW_STREAM1");
-        if (s1e && !strcmp(s1e, "0")) c->stream1 = false;
-        const char *s1o = getenv("ICW_S1_OVL");
-        if (s1o && !strcmp(s1o, "0")) c->s1_ovl = false;
-        const char *s1s = getenv("ICW_S1_STAMPS");
-        if (s1s && !strcmp(s1s, "1") && dalloc(&c->s1_stamps, 8) != ICW_OK) c->s1_stamps = nullptr;
-        const char *kl = getenv("ICW_K1_LDS");
-        c->k1_lds = kl && !strcmp(kl, "1");
-        {
-            hipDeviceProp_t p2;
-            if (hipGetDeviceProperties(&p2, c->device) == hipSuccess) {
-                size_t l = p2.sharedMemPerBlock;
-                if (p2.maxSharedMemoryPerMultiProcessor && p2.maxSharedMemoryPerMultiProcessor < l)
-                    l = p2.maxSharedMemoryPerMultiProcessor;
-                c->lds_cu = (uint32_t)l;
-            }
-        }
-        const char *wg = getenv("ICW_K1_WG");
-        if (wg && atoi(wg) >= 1 && atoi(wg) <= 4) { c->k1_wg = atoi(wg); c->k1_wg_env = true; }
     }
+    if (c->tn.s1_stamps && dalloc(&c->s1_stamps, 8) != ICW_OK) c->s1_stamps = nullptr;
     rc = icw_stream_init(c, 0, n_streams);
     if (rc) { free_all(c); delete c; return rc; }
     split_ref(c->device, +1);
@@ -1442,10 +1314,10 @@ int icw_set_render(icw_ctx *c, const icw_render_cfg *r)
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     IcwRenderK k;
-    render_consts(*r, c->cfg.need24bits, k);
+    render_consts(*r, c->cfg.need24bits, c->tn.k3r_spec, k);
     icw_config cfg = c->cfg;
     cfg.render = *r;
-    const bool serial = needs_serial(cfg, k, c->prog), rstate = needs_render_state(cfg, k, c->prog);
+    const bool serial = needs_serial(cfg, k, c->prog, c->tn.dith_par), rstate = needs_render_state(cfg, k, c->prog, c->tn.dith_par);
     int rc;
     if (rstate && (rc = ensure_render_state(c))) return rc;
     if (k.hi != c->rk.hi && !fold_peaks(c)) return ICW_EDEVICE;
@@ -1471,10 +1343,10 @@ int icw_set_outbits(icw_ctx *c, int need24bits)
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     IcwRenderK k;
-    render_consts(c->cfg.render, is24, k);
+    render_consts(c->cfg.render, is24, c->tn.k3r_spec, k);
     icw_config cfg = c->cfg;
     cfg.need24bits = is24;
-    const bool serial = needs_serial(cfg, k, c->prog), rstate = needs_render_state(cfg, k, c->prog);
+    const bool serial = needs_serial(cfg, k, c->prog, c->tn.dith_par), rstate = needs_render_state(cfg, k, c->prog, c->tn.dith_par);
     int rc;
     if (rstate && (rc = ensure_render_state(c))) return rc;
     /* peaks so far in dB against the old bound (sound_render.c:769-780 converts each sample with the
@@ -1564,7 +1436,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
     const bool bus = c->prog.is_bus;
     /* mono dedup: every stream of the call known to hold identical left / right converters */
     const bool fcm = c->cfg.fp_check != 0;                /* FP_CHECK: FC() kernels, no shortcuts */
-    bool dedup = !cw && !fcm && nch == 1 && c->dedup_ok && (c->k1_mode <= 0 || c->k1_mode == 3);   /* plain / row K1 */
+    bool dedup = !cw && !fcm && nch == 1 && c->tn.dedup_ok && (c->tn.k1_mode <= 0 || c->tn.k1_mode == 3);   /* plain / row K1 */
     for (int i = 0; dedup && i < count; ++i) dedup = c->lr_known[first + i] != 0;
     /* K1 variant of this call.  Auto: the row-broadcast kernel (4 chains per wave, ~17 % fewer
      * instructions per sample) when its waves fit k1_wpc per CU on at most half the chip, else the
@@ -1572,8 +1444,8 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
      * 1 kept it off with a serial render; with the partition working, C5 gains 9 % from it.) */
     const int row_waves = (int)(((dedup ? count : 2L * count) + 3) / 4) * 2;
     const bool row_ok = cfg.iir_kahan && cfg.iir_subnorm_reject;
-    int k1_mode = c->k1_mode;
-    if (k1_mode < 0) k1_mode = (row_ok && row_waves <= (c->n_cu / 2) * c->k1_wpc) ? 3 : 0;
+    int k1_mode = c->tn.k1_mode;
+    if (k1_mode < 0) k1_mode = (row_ok && row_waves <= (c->n_cu / 2) * c->tn.k1_wpc) ? 3 : 0;
     if (k1_mode == 3 && !row_ok) k1_mode = 0;
     if (fcm) k1_mode = ICW_K1_FC;
     if (!cw) c->last_k1 = k1_mode;
@@ -1585,34 +1457,34 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
      * else KF on its own stream (the caller's: K1's, idle without the IIR) beside K2.  KF2 needs no
      * block scratch and has no recurrence to pipeline against, so its blocks are as long as the
      * scratch bound allows (fewer launches, fewer partly filled waves of workgroups at their ends) */
-    const bool fir_fused = fir && c->fir_fuse &&
+    const bool fir_fused = fir && c->tn.fir_fuse &&
                            icw_fir_graph_lds(c->fir_M, c->fir_nt, (int)nch, c->prog.chain ? 0 : c->prog.n_regs) > 0 &&
                            !c->prog.is_bus;
     /* The row kernel without a serial render (C2) has K2 at ~0.16 of K1r's time per frame: 65 536-frame
      * blocks (a quarter of the launches, of their gaps and prologues) ending in a steep tail
      * (65 536 -> 16 384 -> 4 096 -> 1 024: the drain stays one short K2) measured +0.8 % on C2
      * (3 170 -> 3 196 Msamples/s; 32 768 with r = 0.5 +0.5 %, 65 536 with no tail +0.5 %). */
-    const bool row_long = !cw && k1_mode == 3 && !c->serial_render && !c->block_env && n_frames >= 4 * kMaxBlockFrames;
+    const bool row_long = !cw && k1_mode == 3 && !c->serial_render && !c->tn.block_env && n_frames >= 4 * kMaxBlockFrames;
     /* a dithered render with the flat shaper, rendered frame-parallel in the output kernel (K2 / KF2 /
      * K5) from K3a's dither rows (needs_serial) */
     const bool dith_par = !c->serial_render && cfg.render.render_type != ICW_RENDER_ROUND;
     /* (with a dither generator, blocks of kMaxBlockFrames let K3a of the next block run beside KF2) */
     const bool fir_long = fir_fused && dev && !c->serial_render && !bus && !dith_par;
-    const int Tb = std::min(n_frames, ((fir_fused || row_long) && !c->block_env)
-                                          ? (fir_long ? kMaxFirBlockFrames : kMaxBlockFrames) : c->max_block);
-    const double taper = c->taper >= 0.0 ? c->taper
+    const int Tb = std::min(n_frames, ((fir_fused || row_long) && !c->tn.block_env)
+                                          ? (fir_long ? kMaxFirBlockFrames : kMaxBlockFrames) : c->tn.max_block);
+    const double taper = c->tn.taper >= 0.0 ? c->tn.taper
                        : (!cw && k1_mode == 3) ? (c->serial_render ? kAutoTaper : (row_long ? kRowTaper : 0.0)) : 0.0;
     /* the fused FIR converter with a serial render (c5fir): the render of block 0 waits for its
      * converter and dither alone, so block 0 is short and the next ones ramp up (kFirRenderRamp:
      * profiles/r04_c5fir_timeline_after.txt had 2.2 ms of fill in a 24.3 ms step) */
-    const bool fir_ramp = fir_fused && c->serial_render && !c->block_env && c->first_block > 0;
+    const bool fir_ramp = fir_fused && c->serial_render && !c->tn.block_env && c->tn.first_block > 0;
     const std::vector<std::pair<int, int>> blocks =
-        fir_ramp ? plan_blocks(n_frames, Tb, c->first_block_env ? c->first_block : kFirRenderFirst, 0.0, c->taper_min,
-                               c->fir_ramp > 0.0 ? c->fir_ramp : kFirRenderRamp)
-                 : plan_blocks(n_frames, Tb, fir_fused ? 0 : c->first_block, taper, c->taper_min);
+        fir_ramp ? plan_blocks(n_frames, Tb, c->tn.first_block_env ? c->tn.first_block : kFirRenderFirst, 0.0, c->tn.taper_min,
+                               c->tn.fir_ramp > 0.0 ? c->tn.fir_ramp : kFirRenderRamp)
+                 : plan_blocks(n_frames, Tb, fir_fused ? 0 : c->tn.first_block, taper, c->tn.taper_min);
     const int n_blocks = (int)blocks.size();
     /* K5 (icw_stream1): one stream, one block, the row recurrence, register-form graph, ROUND / flat */
-    const bool s1 = c->stream1 && count == 1 && n_blocks == 1 && !cw && !fcm && k1_mode == 3 && !c->serial_render &&
+    const bool s1 = c->tn.stream1 && count == 1 && n_blocks == 1 && !cw && !fcm && k1_mode == 3 && !c->serial_render &&
                     !bus && n_frames <= ICW_S1_MAX && !xin;
 
     const unsigned char *d_in;
@@ -1623,7 +1495,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
     const bool pinned = !dev && stage_in + stage_out + 16 <= kPinnedStage;
     /* pinned host buffers on a call of several launch blocks: each block's input slice goes in and
      * its output slice comes out on the copy stream, beside the other blocks' kernels */
-    const bool pipe_io = !dev && !pinned && n_blocks > 1 && !c->serialize && host_pinned(in, c->device) && host_pinned(out, c->device);
+    const bool pipe_io = !dev && !pinned && n_blocks > 1 && !c->tn.serialize && host_pinned(in, c->device) && host_pinned(out, c->device);
     bool zcopy = false;
     if (pinned) {
         if (c->h_stage_bytes < stage_in + stage_out + 16) {
@@ -1636,7 +1508,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
             c->h_stage_dev = hipHostGetDevicePointer(&dp, c->h_stage, 0) == hipSuccess ? (unsigned char *)dp : nullptr;
             if (!c->h_stage_dev) (void)hipGetLastError();
         }
-        zcopy = c->zero_copy && c->h_stage_dev && !(flags & ICW_F_DEBUG_PRE);
+        zcopy = c->tn.zero_copy && c->h_stage_dev && !(flags & ICW_F_DEBUG_PRE);
     }
     if (dev) {
         d_in = (const unsigned char *)in;
@@ -1666,7 +1538,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
     /* K5 on the zero-copy buffer: the kernel stores the call's sequence number after its output and
      * the host polls for it -- no completion signal and no waking of a waiting thread.  The word is
      * 4-byte aligned inside the output's 16 spare bytes, after the error flag. */
-    const bool s1_poll = s1 && zcopy && c->spin_wait && !timing && !c->s1_stamps;
+    const bool s1_poll = s1 && zcopy && c->tn.spin_wait && !timing && !c->s1_stamps;
     const size_t done_off = ((stage_in + dos * S + sizeof(int) + 3) & ~(size_t)3) - stage_in;
     uint32_t s1_seq = 0u;
     if (s1_poll) {
@@ -1699,7 +1571,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
     const int N = c->nord;
     const size_t w_pitch = (size_t)Tb + N + 1;
     const size_t x_pitch = ((size_t)Tb + ICW_MAX_IIR_ORDER + 2) & ~(size_t)1;   /* look-ahead pad */
-    const int n_sets = std::min(n_blocks, c->max_sets);
+    const int n_sets = std::min(n_blocks, c->tn.max_sets);
     for (int p = 0; p < n_sets && !fir_fused; ++p) {
         if (!cw && grow((void **)&c->w[p], &c->w_bytes[p], S * 4 * w_pitch * sizeof(double))) return ICW_ENOMEM;
         if (grow((void **)&c->xd[p], &c->xd_bytes[p], S * 4 * x_pitch * sizeof(double))) return ICW_ENOMEM;
@@ -1720,9 +1592,11 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
     if (dither)
         for (int p = 0; p < n_sets; ++p)
             if (grow((void **)&c->dith[p], &c->dith_bytes[p], S * 2 * (size_t)(Tb + 1) * sizeof(double))) return ICW_ENOMEM;
-    if (dither && !c->dither_coop && !c->dither_lane) {
-        /* chunk rows of at most 2^26 words in all (256 MB), at least 1 024 frames of the widest draw (GAUSS,
-         * 24 words per sample), at most the block's */
+    if (dither) {
+        /* chunk rows: 2^26 words (256 MB) shared among the G generators, but never less than 1 024 frames
+         * of the widest draw (GAUSS, 24 words per sample) and never more than the block's.  The floor
+         * wins over the 2^26 share from 2 731 generators on, so the buffer is G * cap <= max(2^26,
+         * 24 576 G) words: 256 MB up to there, 96 KB per generator beyond */
         const size_t G = S * 2;
         size_t cap = std::max<size_t>(((size_t)1 << 26) / G, (size_t)24 * 1024);
         cap = std::min(cap, (size_t)24 * (size_t)(Tb + 1));
@@ -1746,28 +1620,28 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
     /* One launch block: K0 -> K1 -> K2 run in sequence anyway, so everything goes on the caller's
      * stream -- no cross-stream event waits, which cost the 576-frame drop-in call ~135 us (C1
      * p50 361 -> 226 us per call). */
-    if (c->serialize || n_blocks == 1) {
+    if (c->tn.serialize || n_blocks == 1) {
         sA = sD = sR = st;
     } else if (!cw) {
         /* plain K1: 128-lane groups of 32 streams (64 with the dedup); the variants: a lane per chain */
         const int k1_waves = (k1_mode == 0 || k1_mode == ICW_K1_FC) ? ((count + (dedup ? 63 : 31)) / (dedup ? 64 : 32)) * 2
                            : row_waves;
         constexpr int kXcd = 8;                               /* MI355X: 8 XCDs */
-        const int k1_cus = ((k1_waves + c->k1_wpc - 1) / c->k1_wpc + kXcd - 1) / kXcd * kXcd;
-        if (c->cu_split && !c->k1_lds && k1_cus * 2 <= c->n_cu) {
+        const int k1_cus = ((k1_waves + c->tn.k1_wpc - 1) / c->tn.k1_wpc + kXcd - 1) / kXcd * kXcd;
+        if (c->tn.cu_split && k1_cus * 2 <= c->n_cu) {
             const CuSplit *cs = cu_split(c, k1_cus);
             if (!cs) return ICW_EDEVICE;
             sK = cs->k1;
             sA = cs->rest;
             sD = cs->dith;
             sR = cs->render;
-            if (c->fill_drain) sF = c->stream2;
+            if (c->tn.fill_drain) sF = c->stream2;
         }
     } else {
         /* complex input or the FIR converter: no recurrence kernel, so the dither generator runs after
          * the converter / output kernel on sA, beside the serial render of the previous block on sR.
          * On its own stream it shared a hardware queue with the render (4 queues per process,
-         * GPU_MAX_HW_QUEUES, streams dealt round-robin): K3a of block b + 1 waited for K3r of block b,
+         * GPU_MAX_HW_QUEUES, streams dealt round-robin): K3a of block b + 1 waited for the render of block b,
          * 1.2 of every 6.7 ms per c5fir block (profiles/r04_c5fir_timeline.txt).  With a frame-parallel
          * render (no render stream) it gets a stream of its own, ahead of the converter. */
         sD = dith_par ? c->stream3 : sA;
@@ -1829,9 +1703,9 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         af.sig = c->prog.chain ? c->prog.sig : 0;
         {
             /* mono input through a Master-only chain (signature count 1, mode MASTER, chain_in `in`:
-             * ICW_SIG_M in icw_kernels.hip) whose gains are bit-identical: L and R are one computation */
+             * ICW_SIG_M) whose gains are bit-identical: L and R are one computation */
             const IcwOp &m = c->prog.ops[0];
-            af.lr_same = nch == 1 && c->prog.chain && (c->prog.sig & ~(1 << 30)) == 0x41 &&
+            af.lr_same = nch == 1 && c->prog.chain && (c->prog.sig & ~ICW_SIG_UNIT) == ICW_SIG_M &&
                          !memcmp(&m.gain[0], &m.gain[1], sizeof(double)) && m.unit_gain[0] == m.unit_gain[1];
         }
         return af;
@@ -1853,7 +1727,6 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         const int t0 = blocks[b].first, T = blocks[b].second, p = b % n_sets;
         IcwK0Args a0;
         memset(&a0, 0, sizeof(a0));
-        a0.lds_guard = c->k1_lds ? 256u : 0u;
         a0.in = d_in + (size_t)t0 * fsz;
         a0.in_stride = dis;
         a0.fmt = cfg.in_format;
@@ -1920,8 +1793,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         a1.t0 = blocks[b].first;
         a1.info_dup = c->info_dup[p];
         memcpy(a1.pc, c->pc, sizeof(a1.pc));
-        a1.wg_waves = c->k1_lds ? 4 : (c->k1_wg_env || k1_mode != 3) ? c->k1_wg : 2;
-        a1.lds_hold = c->k1_lds ? c->lds_cu : 0;
+        a1.wg_waves = (c->tn.k1_wg_env || k1_mode != 3) ? c->tn.k1_wg : 2;
         a1.dedup = dedup ? 1 : 0;
         a1.fes = fcm ? ds.fes + f0 * 4 * ICW_FES_PITCH : nullptr;
         return a1;
@@ -1993,8 +1865,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         a3.fes = fcm ? ds.fes + f0 * 4 * ICW_FES_PITCH : nullptr;
         /* the row-broadcast render (16 lanes per channel) while its waves stay few; FP_CHECK
          * keeps the compact lane-per-channel form */
-        a3.row = c->serial_render && !fcm && (c->render_row == 1 || (c->render_row < 0 && a3.n_gen <= kRowRenderMax)) ? 1 : 0;
-        a3.comp = a3.row && c->k3r_comp;
+        a3.row = c->serial_render && !fcm && (c->tn.render_row == 1 || (c->tn.render_row < 0 && a3.n_gen <= kRowRenderMax)) ? 1 : 0;
         a3.err = ds.err;
         if (dither) {
             a3.dith = c->dith[p];
@@ -2003,19 +1874,16 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
              * [T][count*2] */
             a3.dith_gm = (a3.row || !c->serial_render) ? 1 : 0;
             a3.dith_pitch = a3.dith_gm ? (size_t)(T + (T & 1)) : (size_t)count * 2;
-            if (!c->dither_coop && !c->dither_lane) {
-                a3.wbuf = c->dwords;
-                a3.wpitch = a3.wcap = c->dwcap;
-                a3.dflag = c->dflag;
-                a3.dbk = c->dbk;
-            }
+            a3.wbuf = c->dwords;
+            a3.wpitch = a3.wcap = c->dwcap;
+            a3.dflag = c->dflag;
+            a3.dbk = c->dbk;
         }
         return a3;
     };
     auto adv_args = [&]() {
         IcwAdvArgs av;
         memset(&av, 0, sizeof(av));
-        av.lds_guard = c->k1_lds ? 256u : 0u;
         av.n_streams = count;
         av.cw = cw ? 1 : 0;
         av.n = n_frames;
@@ -2044,7 +1912,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         a5.k2 = k2_args(0);
         a5.adv = adv_args();
         a5.stamps = c->s1_stamps;
-        a5.ovl = c->s1_ovl ? 1 : 0;
+        a5.ovl = c->tn.s1_ovl ? 1 : 0;
         if (c->prog.needs_omega && c->prog.n_trig > 0 && !bus) {
             /* the one stream's rotation factors, computed by the kernel's idle waves beside the
              * recurrence: the output phase reads them instead of evaluating sin / cos per frame */
@@ -2067,8 +1935,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         if (dith_par) {
             /* the dithered flat render: K3a of the call's block first, on the same stream */
             const IcwK3Args a3 = k3_args(0, a5.k2);
-            if ((c->dither_lane ? icw_launch_dither_lane(&a3, st) : icw_launch_dither(&a3, st)) != hipSuccess)
-                return ICW_EDEVICE;
+            if (icw_launch_dither(&a3, st) != hipSuccess) return ICW_EDEVICE;
             a5.k2.dith = a3.dith;
             a5.k2.dith_pitch = a3.dith_pitch;
         }
@@ -2123,7 +1990,6 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         if (table) {
             IcwTrigArgs at;
             memset(&at, 0, sizeof(at));
-            at.lds_guard = c->k1_lds ? 256u : 0u;
             at.prog = c->d_prog;
             at.n_frame = a2.n_frame;
             at.t0 = t0;
@@ -2150,7 +2016,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
              * by the output kernel of block b - n_sets */
             const IcwK3Args a3 = k3_args(b, a2);
             if (b >= n_sets && sD != s2 && hipStreamWaitEvent(sD, c->k2done[p], 0) != hipSuccess) return ICW_EDEVICE;
-            const hipError_t ed = c->dither_lane ? icw_launch_dither_lane(&a3, sD) : icw_launch_dither(&a3, sD);
+            const hipError_t ed = icw_launch_dither(&a3, sD);
             if (ed != hipSuccess || hipEventRecord(c->ditdone[p], sD) != hipSuccess ||
                 (sD != s2 && hipStreamWaitEvent(s2, c->ditdone[p], 0) != hipSuccess))
                 return ICW_EDEVICE;
@@ -2162,7 +2028,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
             const IcwFirArgs af = fir_args(b);
             if (io_in(b, s2) != ICW_OK) return ICW_EDEVICE;
             if (timing && hipEventRecord(c->ev[4 * b], s2) != hipSuccess) return ICW_EDEVICE;
-            if (icw_launch_fir_graph(&af, &a2, in_step, s2) != hipSuccess) return ICW_EDEVICE;
+            if (icw_launch_fir_graph(&af, &a2, in_step, c->tn.fir_sig, s2) != hipSuccess) return ICW_EDEVICE;
             if (timing && hipEventRecord(c->ev[4 * b + 1], s2) != hipSuccess) return ICW_EDEVICE;
         } else {
             if (fir_async && hipStreamWaitEvent(s2, c->k0done[p], 0) != hipSuccess) return ICW_EDEVICE;
@@ -2175,7 +2041,6 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         if (bus) {
             IcwK4Args a4;
             memset(&a4, 0, sizeof(a4));
-            a4.lds_guard = c->k1_lds ? 256u : 0u;
             a4.iq = c->iq[p];
             a4.n_streams = count;
             a4.T = T;
@@ -2195,7 +2060,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
             if (dither) {
                 /* K3a for this block on its own stream: dith[p] was last read by K3b of block b-2 */
                 if (b >= n_sets && sD != sR && hipStreamWaitEvent(sD, c->k3done[p], 0) != hipSuccess) return ICW_EDEVICE;
-                const hipError_t ed = c->dither_lane ? icw_launch_dither_lane(&a3, sD) : icw_launch_dither(&a3, sD);
+                const hipError_t ed = icw_launch_dither(&a3, sD);
                 if (ed != hipSuccess || hipEventRecord(c->ditdone[p], sD) != hipSuccess ||
                     (sD != sR && hipStreamWaitEvent(sR, c->ditdone[p], 0) != hipSuccess))
                     return ICW_EDEVICE;

@@ -12,7 +12,7 @@
  *                   window (frame-parallel), the fs/4 un-mix (lpf_hilbert_quad.c:129-156), the
  *                   DSP graph (adv_modulator.c:637-751) and the elementwise render
  *                   (sound_render.c:691-809, ROUND/flat).  Coalesced tile loads via LDS.
- *   icw_graph_serial / icw_dither_coop / icw_render_serial   K4 / K3a / K3b (serial forms).
+ *   icw_graph_serial / icw_dith_* / icw_render_serial   K4 / K3a / K3b (serial forms).
  */
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -958,16 +958,7 @@ __device__ __forceinline__ bool icw_exec_op(icw_cop &op, IcwLR d, double omega, 
  * hand-off, or the DSP list (adv_modulator.c:637-751) on the LDS register file, the pre-render
  * doubles and the elementwise ROUND render with the meters' per-thread parts. */
 /* DEFER: the rendered integers go to dv[0..1] instead of the output row (KF2 stores 4 frames at once) */
-/* Chain-program signatures compiled straight (IcwProg.sig, the host's encoding: the op count in bits
- * 0-3, then per op in execution order (tail first) 4 bits: mode | chain_in << 2).  Each is one of
- * the BASELINE graphs: Master on `in` (C3 / C5), Shift -> Master (C1 / C2), PM -> Shift ->
- * Mix(in + B) -> Master (C4).  Any other chain runs the generic op loop.  (icw_chain_sig below.) */
-#define ICW_SIG_M    0x41
-#define ICW_SIG_SM   0x852
-#define ICW_SIG_PSXM 0x8F964
-/* flag: every op but the Master has gain 1.0 on both channels (the BASELINE lists' Shift / PM / Mix,
- * DEF_GAIN_MOD in_cwave.h:166), so the render-only form skips those multiplies at compile time */
-#define ICW_SIG_UNIT (1 << 30)
+/* the chain-program signatures compiled straight (ICW_SIG_*, icw_device.h) */
 template <bool TRIG, int R, bool ROWP, int SIG, int I>
 __device__ __forceinline__ void icw_chain_sig(const IcwK2Args &a, icw_cprog *P, int t0, int T, const IcwLR (&in)[R],
                                               IcwLR (&prev)[R], double (&lOut)[R], double (&rOut)[R], double *bus_s,
@@ -2651,44 +2642,13 @@ __global__ __launch_bounds__(ICW_K2_TILE) void icw_stream1(IcwS1Args a)
 
 /* ------------------------------------------------------ serial render kernel (K3) ------ */
 /* sound_render_value (sound_render.c:691-809) for the dithered / noise-shaped renders, whose
- * state (MT19937 position, sloped-TPDF memory, noise-shaper feedback) is serial per channel:
- * one lane per channel, the channel's MT19937 state held in LDS ([624][64] words, 156 KB: the
- * twist of mt_jrnd.c:99-124 runs in place per lane), shaper history in registers as shift
- * registers (age 0 = newest, identical sums to the ring of ns_fir/ns_iir, sound_render.c:403-489). */
+ * state (MT19937 position, sloped-TPDF memory, noise-shaper feedback) is serial per channel: the
+ * dither generator (the MT19937 words, mt_jrnd.c:99-124) first, then the renders, shaper history in
+ * registers (identical sums to the ring of ns_fir/ns_iir, sound_render.c:403-489). */
 __device__ __forceinline__ uint32_t icw_mt_twist_word(uint32_t u, uint32_t v)
 {
     const uint32_t y = (u & 0x80000000u) | (v & 0x7fffffffu);
     return (y >> 1) ^ ((v & 1u) ? 0x9908b0dfu : 0u);
-}
-
-__device__ __forceinline__ void icw_mt_regen(uint32_t *mt, int lane)
-{
-    /* in-place generation of the next 624 words (mtrnd_gen_ui32, mt_jrnd.c:105-120), 8 words per
-     * batch: a batch's LDS reads are independent of its writes (they read words >= i and, in the
-     * second part, words written >= 220 positions earlier), so its loads issue back to back */
-    uint32_t *m = mt + lane;
-    int i = 0;
-    for (; i + 8 <= 227; i += 8) {
-        uint32_t u[9], f[8];
-#pragma unroll
-        for (int j = 0; j < 9; ++j) u[j] = m[(i + j) * 64];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = m[(i + j + 397) * 64];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) m[(i + j) * 64] = f[j] ^ icw_mt_twist_word(u[j], u[j + 1]);
-    }
-    for (; i < 227; ++i) m[i * 64] = m[(i + 397) * 64] ^ icw_mt_twist_word(m[i * 64], m[(i + 1) * 64]);
-    for (; i + 8 <= 623; i += 8) {
-        uint32_t u[9], f[8];
-#pragma unroll
-        for (int j = 0; j < 9; ++j) u[j] = m[(i + j) * 64];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = m[(i + j - 227) * 64];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) m[(i + j) * 64] = f[j] ^ icw_mt_twist_word(u[j], u[j + 1]);
-    }
-    for (; i < 623; ++i) m[i * 64] = m[(i - 227) * 64] ^ icw_mt_twist_word(m[i * 64], m[(i + 1) * 64]);
-    m[623 * 64] = m[396 * 64] ^ icw_mt_twist_word(m[623 * 64], m[0]);
 }
 
 __device__ __forceinline__ uint32_t icw_mt_temper(uint32_t y)
@@ -2700,153 +2660,9 @@ __device__ __forceinline__ uint32_t icw_mt_temper(uint32_t y)
     return y;
 }
 
-__device__ __forceinline__ uint32_t icw_mt_u32(uint32_t *mt, int lane, int &idx)
-{
-    if (idx >= 624) {
-        icw_mt_regen(mt, lane);
-        idx = 0;
-    }
-    const uint32_t y = mt[idx * 64 + lane];
-    ++idx;
-    return icw_mt_temper(y);
-}
-
-/* mtrnd_gen_dsopen (mt_jrnd.c:218-256): (-1, 1) with 53-bit resolution, +-1 rejected */
-__device__ __forceinline__ double icw_mt_dsopen(uint32_t *mt, int lane, int &idx)
-{
-    double r;
-    do {
-        const uint32_t a = icw_mt_u32(mt, lane, idx) >> 5;
-        const uint32_t b = icw_mt_u32(mt, lane, idx) >> 6;
-        r = ((a * 67108864.0 + b) * (1.0 / 9007199254740992.0)) * 2.0 - 1.0;
-    } while (-1.0 == r || 1.0 == r);
-    return r;
-}
-
 #define ICW_SQRT6 (2.4494897427831780981972840747059)
 
-/* Dither generation (K3a): the random term rnd * dth_mul of sound_render_value
- * (sound_render.c:711-756) for every sample of the block.  It depends only on the channel's MT19937
- * state and the sloped-TPDF memory, never on the audio, so it runs on its own stream ahead of /
- * beside the Hilbert and output kernels; one lane per render channel, MT words in LDS. */
-/* dsopen from two tempered words (mtrnd_gen_dsopen, mt_jrnd.c:218-256) without the rejection */
-__device__ __forceinline__ double icw_dsopen2(uint32_t ua, uint32_t ub)
-{
-    const uint32_t a = ua >> 5, b = ub >> 6;
-    return ((a * 67108864.0 + b) * (1.0 / 9007199254740992.0)) * 2.0 - 1.0;
-}
-
-template <int RT>
-struct IcwDith {
-    static constexpr int W = RT == ICW_RENDER_GAUSS ? 24 : (RT == ICW_RENDER_TPDF ? 4 : 2);   /* words/sample */
-    static constexpr int C = RT == ICW_RENDER_GAUSS ? 2 : (RT == ICW_RENDER_TPDF ? 8 : 16);  /* samples/chunk */
-};
-
-/* the dither of one sample from its words (no rejection among them) */
-template <int RT>
-__device__ __forceinline__ double icw_dith_from_words(const uint32_t *u, double &prev_rnd)
-{
-    double rnd, tr;
-    if (RT == ICW_RENDER_RPDF) {
-        rnd = icw_dsopen2(u[0], u[1]) / ICW_SQRT2;
-    } else if (RT == ICW_RENDER_TPDF) {
-        rnd = icw_dsopen2(u[0], u[1]);
-        rnd += icw_dsopen2(u[2], u[3]);
-        rnd /= 2.0;
-    } else if (RT == ICW_RENDER_STPDF) {
-        rnd = ((tr = icw_dsopen2(u[0], u[1])) - prev_rnd) / 2.0;
-        prev_rnd = tr;
-    } else {
-        rnd = icw_dsopen2(u[0], u[1]);
-#pragma unroll
-        for (int i = 1; i < 12; ++i) rnd += icw_dsopen2(u[2 * i], u[2 * i + 1]);
-        rnd /= (2.0 * ICW_SQRT6);
-    }
-    return rnd;
-}
-
-/* the reference's sequential form, rejection and twist included */
-template <int RT>
-__device__ __forceinline__ double icw_dith_slow(uint32_t *mt, int lane, int &idx, double &prev_rnd)
-{
-    double rnd, tr;
-    if (RT == ICW_RENDER_RPDF) {
-        rnd = icw_mt_dsopen(mt, lane, idx) / ICW_SQRT2;
-    } else if (RT == ICW_RENDER_TPDF) {
-        rnd = icw_mt_dsopen(mt, lane, idx);
-        rnd += icw_mt_dsopen(mt, lane, idx);
-        rnd /= 2.0;
-    } else if (RT == ICW_RENDER_STPDF) {
-        rnd = ((tr = icw_mt_dsopen(mt, lane, idx)) - prev_rnd) / 2.0;
-        prev_rnd = tr;
-    } else {
-        rnd = icw_mt_dsopen(mt, lane, idx);
-        for (int i = 1; i < 12; ++i) rnd += icw_mt_dsopen(mt, lane, idx);
-        rnd /= (2.0 * ICW_SQRT6);
-    }
-    return rnd;
-}
-
-/* Dither generation (K3a): the random term rnd * dth_mul of sound_render_value
- * (sound_render.c:711-756) for every sample of the block.  It depends only on the channel's MT19937
- * state and the sloped-TPDF memory, never on the audio, so it runs on its own stream beside the
- * Hilbert and output kernels; one lane per render channel, MT words in LDS.  Fast path: a chunk of
- * C samples whose W*C words are all left before the next twist is read as one batch of
- * independent LDS loads; a chunk that would hit a rejected draw (probability ~2^-53 per draw) or
- * the twist runs through the sequential form instead. */
-template <int RT>
-__global__ __launch_bounds__(64) void icw_dither_gen(IcwK3Args a)
-{
-    using D = IcwDith<RT>;
-    constexpr int NW = D::W * D::C;
-    __shared__ uint32_t mt[624 * 64];
-    const int lane = threadIdx.x;
-    const int g0 = blockIdx.x * 64 + lane;
-    const bool valid = g0 < a.n_gen;
-    const int g = valid ? g0 : a.n_gen - 1;
-    for (int i = 0; i < 624; ++i) mt[i * 64 + lane] = a.mt[(size_t)i * a.mt_pitch + g];
-    int idx = a.mt_idx[g];
-    double *rs = a.rs + (size_t)g * ICW_RSTATE;
-    double prev_rnd = rs[0];
-    const double dth_mul = a.rk.dth_mul;
-    /* time-major [t][dith_pitch]: one store per sample is coalesced; generator-major: a lane's own run */
-    double *dd = a.dith_gm ? a.dith + (size_t)g * a.dith_pitch : a.dith + g;
-    const size_t dp = a.dith_gm ? 1 : a.dith_pitch;
-    const int T = a.T;
-    int t = 0;
-    while (t < T) {
-        if (t + D::C <= T && idx + NW <= 624) {
-            uint32_t u[NW];
-#pragma unroll
-            for (int j = 0; j < NW; ++j) u[j] = icw_mt_temper(mt[(idx + j) * 64 + lane]);
-            bool rej = false;
-#pragma unroll
-            for (int j = 0; j < NW; j += 2) rej |= ((u[j] >> 5) == 0u) && ((u[j + 1] >> 6) == 0u);
-            if (!rej) {
-                double pr = prev_rnd;
-#pragma unroll
-                for (int c = 0; c < D::C; ++c) {
-                    const double rnd = icw_dith_from_words<RT>(u + c * D::W, pr);
-                    if (valid) dd[(size_t)(t + c) * dp] = rnd * dth_mul;
-                }
-                prev_rnd = pr;
-                idx += NW;
-                t += D::C;
-                continue;
-            }
-        }
-        /* one sample the sequential way (twists, rejections) */
-        const double rnd = icw_dith_slow<RT>(mt, lane, idx, prev_rnd);
-        if (valid) dd[(size_t)t * dp] = rnd * dth_mul;
-        ++t;
-    }
-    if (!valid) return;
-    for (int i = 0; i < 624; ++i) a.mt[(size_t)i * a.mt_pitch + g] = mt[i * 64 + lane];
-    a.mt_idx[g] = idx;
-    rs[0] = prev_rnd;
-}
-
-/* Cooperative dither generation (K3a): one wave per render channel.  The random term of
+/* Cooperative dither generation (K3f's redo, icw_dither_coop_body): one wave per render channel.  The random term of
  * sound_render_value (sound_render.c:711-756) depends only on the channel's MT19937 stream, so the
  * stream is produced 624 words at a time by the whole wave:
  *   twist     the 624-word regeneration (mt_jrnd.c:105-120) in three dependency phases
@@ -3008,12 +2824,6 @@ __device__ __forceinline__ void icw_dither_coop_body(const IcwK3Args &a, int g, 
         a.mt_idx[g] = idx;
         rs[0] = prev_rnd;
     }
-}
-
-template <int RT>
-__global__ __launch_bounds__(64) void icw_dither_coop(IcwK3Args a)
-{
-    icw_dither_coop_body<RT>(a, blockIdx.x, nullptr);
 }
 
 /* ------------------------------------------------------ split dither generator (K3t/K3s/K3f) ---- */
@@ -3314,7 +3124,7 @@ __global__ __launch_bounds__(64) void icw_render_serial(IcwK3Args a)
     if (pk > 0.0) atomicMax(&a.peak_bits[g], (unsigned long long)__double_as_longlong(pk));
 }
 
-/* ------------------------------------------------------- render, row broadcast (K3r) ------- */
+/* ------------------------------------------- render, row broadcast: the chain (K3c) ------- */
 /* The serial render of K3b with one 16-lane DPP row per channel instead of one lane, built like the
  * IIR kernel K1r (icw_iir.hip): every lane of a row runs the channel's chain redundantly, so each
  * value is row-uniform, and what is not on the chain leaves the per-sample instruction stream --
@@ -3397,7 +3207,7 @@ __device__ __forceinline__ void icw_rrow_step(double xs, double d, double &prev_
         dd = 0.0;
     }
     /* the clip stage as it reaches the integer (icw_clamp_int); clips and peak from the staged q.  A
-     * clamp-free block (FAST, icw_render_row) has lo < q < hi for every sample, where the reference's
+     * clamp-free block (FAST, icw_render_rowc) has lo < q < hi for every sample, where the reference's
      * clip stage changes nothing and trunc(q) is already in [lo + 1, hi - 1] */
     double vd;
     if constexpr (FAST) {
@@ -3431,7 +3241,7 @@ __device__ __forceinline__ void icw_rrow_step(double xs, double d, double &prev_
 }
 
 /* look-ahead reads: the next block's inputs and dither values of the row's channel, staged in LDS
- * (icw_rrow_stage_*): sample J of this block reads sample J of the next -- a whole block ahead of
+ * (icw_k3c_stage_*): sample J of this block reads sample J of the next -- a whole block ahead of
  * its use, at an immediate offset (no address arithmetic per sample, no wait on global memory) */
 template <int KIND, int NN, int R, int J, bool MR, bool FAST>
 __device__ __forceinline__ void icw_rrow_block(double (&xin)[ICW_MAX_NS_TAPS], double (&dv)[ICW_MAX_NS_TAPS],
@@ -3474,98 +3284,13 @@ __device__ __forceinline__ void icw_rrow_block_lim(const double (&xin)[ICW_MAX_N
     }
 }
 
-/* The staging of one block's inputs (frames t0 .. t0 + U - 1 of the wave's two streams, both
- * channels: lanes 0-19 / 32-51 load frame i of stream A / B, L and R in 16 bytes) and dither values
- * (its four channels: lanes 0-39 half a dither row each, 16 bytes); frames past T, streams past the
- * batch and channels past n_gen load nothing.  A block is loaded one block before it is stored to
- * LDS and stored one block before it is read, so no per-sample wait reaches global memory -- the
- * per-sample loads they replace ended each block in a full drain (s_waitcnt vmcnt(0)). */
+/* What a lane holds of one block's staging between its global loads and its stores to LDS (frames
+ * t0 .. t0 + U - 1 of the workgroup's two streams: lanes 0-19 / 32-51 frame i of stream A / B, L and R
+ * in 16 bytes; its four channels' dither values: lanes 0-39 half a dither row each, 16 bytes).  The
+ * loads run blocks ahead of the stores (icw_k3c_stage_*), so no per-sample wait reaches global memory. */
 struct IcwRowStage {
     double2 x, d;
 };
-
-/* What a lane stages, fixed for the launch: its source rows at t0 = 0 (the addresses then advance by
- * t0, no per-block 64-bit multiplies), its frame within a block for the t0 + i < T test, whether it
- * loads at all, and its LDS offsets inside one buffer (the buffer's own offset is a scalar) */
-struct IcwRowLane {
-    const double *xp, *dp;
-    size_t dstr;                 /* dither elements per frame: dith_pitch (time-major) or 1 (generator-major) */
-    int xi, di, di1;             /* frame of the x pair; frames of the dither pair's two values */
-    bool xv, dvv;
-    uint32_t xo, dof, d2;        /* LDS byte offsets of the x pair and the dither pair; d2 the second value's in doubles */
-};
-
-/* dither values, 40 lanes x 16 bytes: time-major, lane 2i + h loads channels 2h, 2h + 1 at frame i (LDS rows
- * 2h, 2h + 1); generator-major (dith_gm), lane 10c + p loads frames 2p, 2p + 1 of channel c (LDS row c) */
-__device__ __forceinline__ IcwRowLane icw_rrow_lane(const IcwK3Args &a, int lane)
-{
-    constexpr int U = ICW_MAX_NS_TAPS;
-    IcwRowLane L;
-    const int sb = lane >> 5, i = lane & 31;
-    const int s = blockIdx.x * 2 + sb;
-    L.xi = i;
-    L.xv = i < U && 2 * s < a.n_gen;
-    L.xp = L.xv ? a.pre + (size_t)s * a.pre_stride + (size_t)i * 2 : a.pre;
-    L.xo = (uint32_t)(((2 * sb) * U + (i < U ? i : 0)) * sizeof(double));
-    const int ld = lane < 2 * U ? lane : 0;
-    if (a.dith_gm) {
-        const int ch = ld / (U / 2), p = ld % (U / 2);
-        L.di = 2 * p;
-        L.di1 = 2 * p + 1;
-        L.dvv = a.dith && lane < 2 * U && (int)blockIdx.x * 4 + ch < a.n_gen;
-        L.dp = L.dvv ? a.dith + (size_t)(blockIdx.x * 4 + ch) * a.dith_pitch + 2 * p : a.dith;
-        L.dstr = 1;
-        L.dof = (uint32_t)((ch * U + 2 * p) * sizeof(double));
-        L.d2 = 1;
-    } else {
-        const int tt = ld >> 1, h = ld & 1;
-        L.di = L.di1 = tt;
-        L.dvv = a.dith && lane < 2 * U && (int)blockIdx.x * 4 + 2 * h < a.n_gen;
-        L.dp = L.dvv ? a.dith + (size_t)tt * a.dith_pitch + blockIdx.x * 4 + 2 * h : a.dith;
-        L.dstr = a.dith_pitch;
-        L.dof = (uint32_t)(((2 * h) * U + tt) * sizeof(double));
-        L.d2 = U;
-    }
-    return L;
-}
-
-__device__ __forceinline__ void icw_rrow_stage_load(const IcwK3Args &a, const IcwRowLane &L, int t0, IcwRowStage &st)
-{
-#ifdef ICW_K3R_NOLOAD
-    if (t0 >= 3 * ICW_MAX_NS_TAPS) return;          /* diagnostic build (timing only): no staging loads */
-#endif
-    st.x = make_double2(0.0, 0.0);
-    st.d = make_double2(0.0, 0.0);
-    if (L.xv && t0 + L.xi < a.T) st.x = *(const double2 *)(L.xp + (size_t)t0 * 2);
-    if (L.dvv && t0 + L.di1 < a.T) st.d = *(const double2 *)(L.dp + (size_t)t0 * L.dstr);
-    else if (L.dvv && t0 + L.di < a.T) st.d.x = L.dp[(size_t)t0 * L.dstr];   /* generator-major: the last, odd frame */
-}
-
-/* The inputs go to LDS as x * norm_mul (sound_render.c:754's product, formed here lane-parallel: two
- * multiplies per block instead of one per sample on the chain).  Returns, wave-uniform, whether every
- * staged |x * norm_mul| <= thr (render_consts' spec_thr; NaN fails): the block may run clamp-free.
- * xs / ds: the buffer's x rows [4][U] and dither rows [4][U]. */
-__device__ __forceinline__ bool icw_rrow_stage_store(double (*xs)[ICW_MAX_NS_TAPS], double (*ds)[ICW_MAX_NS_TAPS],
-                                                     int lane, const IcwRowLane &L, const IcwRowStage &st, double nm,
-                                                     double thr)
-{
-    constexpr int U = ICW_MAX_NS_TAPS;
-    const int i = lane & 31;
-    bool ok = true;
-    if (i < U) {
-        const double a = st.x.x * nm, b = st.x.y * nm;
-        double *p = (double *)((char *)&xs[0][0] + L.xo);
-        p[0] = a;
-        p[U] = b;
-        ok = fabs(a) <= thr && fabs(b) <= thr;
-    }
-    if (lane < 2 * U) {
-        double *p = (double *)((char *)&ds[0][0] + L.dof);
-        p[0] = st.d.x;
-        p[L.d2] = st.d.y;
-    }
-    return __all(ok);
-}
 
 /* End of a block of nf samples: clips and peak of the staged q (lane l: samples l, l + 16 of its
  * row), then the block's frames -- lanes 0-31 write stream A's (rows 0, 1), 32-63 stream B's.  The
@@ -3620,186 +3345,11 @@ __device__ __forceinline__ bool icw_rrow_flush(const double (*qs)[ICW_MAX_NS_TAP
     return calm;
 }
 
-/* the flush of a clamp-free block: every |q| < clip_abs, finite -- no clip to count, the integer is the
- * plain conversion (exact below 2^31) + the mid-riser's delta, no clamp, no NaN */
-template <bool MR>
-__device__ __forceinline__ void icw_rrow_flush_fast(const double (*qs)[ICW_MAX_NS_TAPS / 2][16][2], int r, int lr, int lane,
-                                                    const IcwRenderK &k, double &pk, unsigned char *o, int osz)
-{
-    constexpr int U = ICW_MAX_NS_TAPS;
-    __builtin_amdgcn_wave_barrier();
-    /* the four reads first, unconditionally (clamped indices; a lane's second peak sample repeats its
-     * first where lr + 16 >= U, which changes no maximum), so they share one wait */
-    const int f = lane & 31, sb = lane >> 5, fc = f < U ? f : U - 1;
-    const int j1 = lr + 16 < U ? lr + 16 : lr;
-    const double q0 = qs[r][lr >> 1][lr][lr & 1];
-    const double q1 = qs[r][j1 >> 1][lr][j1 & 1];
-    const double ql = qs[2 * sb][fc >> 1][0][fc & 1], qr = qs[2 * sb + 1][fc >> 1][0][fc & 1];
-    pk = icw_vmax_abs(icw_vmax_abs(pk, q0), q1);
-    const int vl = icw_cvt_sat_i32(ql) + (MR && ql < 0.0 ? -1 : 0);
-    const int vr = icw_cvt_sat_i32(qr) + (MR && qr < 0.0 ? -1 : 0);
-    const uint32_t l = (uint32_t)(vl << k.norm_shift);
-    const uint32_t rr = (uint32_t)(vr << k.norm_shift);
-    /* o: this lane's frame in the block's output (null: no frame to write) */
-    if (o) {
-        if (osz == 2) {
-            *(uint32_t *)o = (l & 0xffffu) | (rr << 16);
-        } else {
-            uint16_t *p = (uint16_t *)o;
-            p[0] = (uint16_t)(l & 0xffffu);
-            p[1] = (uint16_t)(((l >> 16) & 0xffu) | ((rr & 0xffu) << 8));
-            p[2] = (uint16_t)((rr >> 8) & 0xffffu);
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-}
-
-template <int KIND, int NN, bool MR>
-__global__ __launch_bounds__(64) void icw_render_row(IcwK3Args a)
-{
-    constexpr int U = ICW_MAX_NS_TAPS;                 /* samples per unrolled block */
-    constexpr int R = KIND == 1 ? U : (KIND == 2 ? 4 : 1);
-    static_assert(U % R == 0, "ring period must divide the unroll");
-    static_assert(U % 2 == 0, "samples go in pairs");
-    __shared__ __attribute__((aligned(16))) double qs[4][U / 2][16][2];   /* q of each sample, every lane its own slots */
-    const int lane = threadIdx.x, r = lane >> 4, lr = lane & 15;
-    const int g0 = blockIdx.x * 4 + r;
-    const bool valid = g0 < a.n_gen;
-    const int g = valid ? g0 : a.n_gen - 1;            /* spare rows run on zeros, store nothing */
-    const IcwRenderK &k = a.rk;
-    double *rs = a.rs + (size_t)g * ICW_RSTATE;
-    double prev_err = rs[1];
-    double E[R], O[R], P[R], P2[R];
-    IcwRowNs c;
-    c.one = 1.0;
-    c.c0 = k.ns_c[0];
-    c.cN = KIND == 2 ? k.ns_c[NN] : 0.0;
-    if constexpr (KIND == 2) {
-        c.pl = lr + 1 < NN ? k.ns_c[lr + 1] : 0.0;
-        c.pl2 = lr + 1 < NN ? k.ns_c[lr + 1 + NN] : 0.0;
-    } else {
-        c.pl = lr + 1 < NN ? k.ns_c[lr + 1] : 0.0;
-        c.pl2 = lr + 17 < NN ? k.ns_c[lr + 17] : 0.0;
-    }
-    /* block start: age i sits in slot (-1 - i) mod R; the products of those ages */
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-        E[(R - 1 - i) % R] = rs[2 + i];
-        O[(R - 1 - i) % R] = rs[2 + U + i];
-    }
-    if constexpr (KIND == 1) {
-#pragma unroll
-        for (int m = 0; m < R; ++m) {
-            P[m] = icw_rmul(c.pl, E[m]);
-            if constexpr (NN > 17) P2[m] = icw_rmul(c.pl2, E[m]);
-        }
-    } else if constexpr (KIND == 2) {
-#pragma unroll
-        for (int m = 0; m < R; ++m) P[m] = icw_rsub(icw_rmul(c.pl, E[m]), icw_rmul(c.pl2, O[(m + R - 1) % R]));
-    }
-    asm volatile("s_nop 1");                           /* VALU write -> DPP read of P / P2 */
-    const int osz = k.is24 ? 3 : 2;
-    /* the wave's two streams (channels 4b..4b+3); a stream past the batch writes nothing */
-    const int sA = blockIdx.x * 2, sB = sA + 1;
-    unsigned char *oA = 2 * sA < a.n_gen ? a.out + (size_t)sA * a.out_stride : nullptr;
-    unsigned char *oB = 2 * sB < a.n_gen ? a.out + (size_t)sB * a.out_stride : nullptr;
-    double *qst = &qs[r][0][lr][0];
-    unsigned clips = 0;
-    double pk = 0.0;
-    const int T = a.T;
-    /* block j's inputs in LDS buffer j & 1: loaded at the end of block j - 3, stored at the end of
-     * block j - 2, read (a block ahead) during block j - 1 */
-    __shared__ __attribute__((aligned(16))) double xsl[2][4][U];
-    __shared__ __attribute__((aligned(16))) double dsl[2][4][U];
-    const double nm = k.norm_mul, thr = k.spec_thr;
-    IcwRowStage stg;
-    const IcwRowLane sl = icw_rrow_lane(a, lane);
-    /* the frame this lane writes in a clamp-free block's flush: frame lane & 31 of stream A / B */
-    unsigned char *const olane = (lane & 31) < U && ((lane >> 5) ? oB : oA) ? ((lane >> 5) ? oB : oA) + (size_t)(lane & 31) * 2 * osz
-                                                                          : nullptr;
-    icw_rrow_stage_load(a, sl, 0, stg);
-    bool x_ok0 = icw_rrow_stage_store(xsl[0], dsl[0], lane, sl, stg, nm, thr);
-    icw_rrow_stage_load(a, sl, U, stg);
-    bool x_ok1 = icw_rrow_stage_store(xsl[1], dsl[1], lane, sl, stg, nm, thr);
-    icw_rrow_stage_load(a, sl, 2 * U, stg);
-    __builtin_amdgcn_wave_barrier();
-    double xin[U], dv[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        xin[j] = xsl[0][r][j];
-        dv[j] = dsl[0][r][j];
-    }
-    /* Clamp-free blocks (render_consts: spec_thr).  A block runs without the clip stage when the block
-     * before it clipped nowhere (every |q| < clip_abs: `calm`) and its own inputs are all within
-     * spec_thr; it then clips nowhere itself, so the next block's history is calm too.  The first block
-     * of a launch starts from a saved history and takes the exact form.  Wave-uniform (__all).
-     * The two forms run in loops of their own, each with its own back edge: with one loop and the form
-     * chosen per block, the register allocation of the two unrolled bodies met at the loop's end, and
-     * every block paid ~80 AGPR / VGPR moves for it (more than the clamp it saved). */
-    bool calm = false;
-    int t = 0, kb = 0;
-    double mq_unused = 0.0;             /* this kernel's calm test is the flush's */
-    /* one block of either form, the staging of block kb + 2 (into the buffer block kb has left), the
-     * block's flush, and block kb + 3 on its way.  The staging comes before the flush: its stores to
-     * LDS wait for the registers loaded one block ago, and on gfx950 that wait (vmcnt) also counts
-     * the global stores issued before it -- after the flush it waited for the block's own output
-     * stores to complete. */
-    auto step = [&](auto fast) {
-        constexpr bool FAST = decltype(fast)::value;
-        const int nb = (kb + 1) & 1;
-        unsigned char *ot0 = oA ? oA + (size_t)t * 2 * osz : nullptr, *ot1 = oB ? oB + (size_t)t * 2 * osz : nullptr;
-        icw_rrow_block<KIND, NN, R, 0, MR, FAST>(xin, dv, prev_err, E, O, P, P2, c, k, qst, &xsl[nb][r][0],
-                                                 &dsl[nb][r][0], mq_unused);
-        x_ok0 = x_ok1;
-        x_ok1 = icw_rrow_stage_store(xsl[kb & 1], dsl[kb & 1], lane, sl, stg, nm, thr);
-        if constexpr (FAST) {
-            icw_rrow_flush_fast<MR>(qs, r, lr, lane, k, pk, olane ? olane + (size_t)t * 2 * osz : nullptr, osz);
-#ifdef ICW_K3R_COUNT
-            if (lr == 0 && valid) atomicAdd(&a.clips[g], 1u);   /* diagnostic build: clamp-free blocks */
-#endif
-        } else {
-            calm = icw_rrow_flush<MR>(qs, r, lr, lane, U, k, clips, pk, ot0, ot1, osz);
-        }
-        icw_rrow_stage_load(a, sl, t + 3 * U, stg);
-        __builtin_amdgcn_wave_barrier();
-        t += U;
-        ++kb;
-    };
-    while (t + U <= T) {
-        while (t + U <= T && !(KIND != 2 && calm && x_ok0)) step(icw_ic<0>());
-        if constexpr (KIND != 2) {
-            while (t + U <= T && x_ok0) step(icw_ic<1>());
-        }
-    }
-    const int rem = T - t;
-    if (rem > 0) {
-        icw_rrow_block_lim<KIND, NN, R, 0, MR>(xin, dv, prev_err, E, O, P, P2, c, k, qst, rem, mq_unused);
-        icw_rrow_flush<MR>(qs, r, lr, lane, rem, k, clips, pk, oA ? oA + (size_t)t * 2 * osz : nullptr,
-                           oB ? oB + (size_t)t * 2 * osz : nullptr, osz);
-        /* back to the block-start mapping: rotate left by rem mod R */
-#pragma unroll
-        for (int q = 1; q < U; ++q)
-            if (q <= rem) { icw_ring_rotate1<R>(E); icw_ring_rotate1<R>(O); }
-    }
-    /* meters: the row's lanes hold disjoint samples */
-#pragma unroll
-    for (int off = 1; off < 16; off <<= 1) {
-        clips += __shfl_xor(clips, off);
-        pk = fmax(pk, __shfl_xor(pk, off));
-    }
-    if (!valid || lr != 0) return;
-    rs[1] = prev_err;
-#pragma unroll
-    for (int i = 0; i < R; ++i) { rs[2 + i] = E[(R - 1 - i) % R]; rs[2 + U + i] = O[(R - 1 - i) % R]; }
-    if (clips) atomicAdd(&a.clips[g], clips);
-    if (pk > 0.0) atomicMax(&a.peak_bits[g], (unsigned long long)__double_as_longlong(pk));
-}
-
 /* ------------------------------------------- render, row broadcast + companion wave (K3c) ------ */
-/* icw_render_row with everything that is not the error-feedback chain moved to a second wave of the
+/* The row render with everything that is not the error-feedback chain on a second wave of the
  * workgroup, which the dispatcher puts on another SIMD of the CU.  A lone wave issues one FP64 op per
- * ~5 cycles, so in K3r every staging load, LDS store, integer conversion, meter update and
- * output store was issue time taken from the chain: 18.9 VALU + 2.5 SALU + 1.8 LDS per sample for a
+ * ~5 cycles, so on one wave every staging load, LDS store, integer conversion, meter update
+ * and output store is issue time taken from the chain: 18.9 VALU + 2.5 SALU + 1.8 LDS per sample for a
  * 16-op chain (MEW44).  Here
  *   wave 0 (chain)      runs only the chain of sound_render.c:754-809 on its four channels: per sample
  *                       the row-uniform chain, one ds_read_b128 per two samples for x and for the
@@ -3819,8 +3369,8 @@ __global__ __launch_bounds__(64) void icw_render_row(IcwK3Args a)
  * the chain itself keeps max |q| in an exact block (one v_max_f64 per sample, only there); a NaN q
  * makes the chain's error, and so prev_ns_err, NaN for good (the shaper's sum of a NaN), which the
  * block-end test also sees; a FIR shaper's NaN is never self-clearing, a flat one has no history.
- * Results are icw_render_row's bit for bit: the same chain code, the same exact flush for every
- * block (a clamp-free block gives the same integers through it: no clip, no NaN). */
+ * Every block goes through the same exact flush (a clamp-free block gives the same integers through
+ * it: no clip, no NaN). */
 #define ICW_K3C_NSB 4                  /* staging buffers (blocks) */
 #define ICW_K3C_NQB 4                  /* q buffers (blocks) */
 #define ICW_K3C_SPIN (1u << 24)        /* spin bound: ~2^24 s_sleep(1), far beyond any healthy wait */
@@ -4189,7 +3739,7 @@ __global__ __launch_bounds__(64) void icw_render_fc(IcwK3Args a)
 extern "C" hipError_t icw_launch_unpack(const IcwK0Args *a, hipStream_t st)
 {
     dim3 grid((a->T + 255) / 256, a->n_streams);
-    hipLaunchKernelGGL(icw_unpack_frames, grid, dim3(256), a->lds_guard, st, *a);
+    hipLaunchKernelGGL(icw_unpack_frames, grid, dim3(256), 0, st, *a);
     return hipGetLastError();
 }
 
@@ -4283,7 +3833,8 @@ static bool fir_sig_known(int sig)
     }
 }
 
-extern "C" hipError_t icw_launch_fir_graph(const IcwFirArgs *f, const IcwK2Args *a, int in_step, hipStream_t st)
+extern "C" hipError_t icw_launch_fir_graph(const IcwFirArgs *f, const IcwK2Args *a, int in_step, int sig_on,
+                                           hipStream_t st)
 {
     if (!fir_ok(f->M, f->nt)) return hipErrorInvalidValue;
     /* the render-only form (icw_fast_render) takes the quantiser from sign_delta alone: mid-riser
@@ -4299,9 +3850,7 @@ extern "C" hipError_t icw_launch_fir_graph(const IcwFirArgs *f, const IcwK2Args 
     /* the signature form takes the tiles before the one holding the block's last frame when every
      * lane of them would take icw_chain_frames' render-only branch: a chain program of a known
      * signature, its rotation factors (if any) from the table, a render here, no pre-render doubles,
-     * no I / Q hand-off, no dither rows.  ICW_FIR_SIG=0: icw_fir_graph for every tile (A/B). */
-    const char *sig_env = getenv("ICW_FIR_SIG");
-    const bool sig_on = !sig_env || atoi(sig_env) != 0;
+     * no I / Q hand-off, no dither rows.  sig_on 0 (IcwTuning.fir_sig): icw_fir_graph for every tile. */
     const int sig = f->sig;
     const bool rot = (sig & ~ICW_SIG_UNIT) != ICW_SIG_M;
     if (sig_on && ICW_CHAIN4 && fir_sig_known(sig) && (rot ? (a->trig && in_step) : !a->trig) && a->do_render &&
@@ -4342,10 +3891,7 @@ static hipError_t launch_k2_t(IcwK2Args a, hipStream_t st)
 template <int RT>
 static hipError_t icw_launch_dither_t(const IcwK3Args *a, hipStream_t st)
 {
-    if (!a->wbuf) {                        /* the one-kernel K3a (ICW_DITHER=coop, A/B) */
-        hipLaunchKernelGGL(icw_dither_coop<RT>, dim3(a->n_gen), dim3(64), 0, st, *a);
-        return hipGetLastError();
-    }
+    if (!a->wbuf) return hipErrorInvalidValue;
     constexpr int W = 2 * (RT == ICW_RENDER_GAUSS ? 12 : (RT == ICW_RENDER_TPDF ? 2 : 1));
     const int chunk = (int)std::min<size_t>((size_t)a->T, a->wcap / W);
     if (chunk <= 0) return hipErrorInvalidValue;
@@ -4373,42 +3919,17 @@ extern "C" hipError_t icw_launch_dither(const IcwK3Args *a, hipStream_t st)
     }
 }
 
-/* the lane-per-channel generator, kept for A/B timing (ICW_DITHER=lane) */
-extern "C" hipError_t icw_launch_dither_lane(const IcwK3Args *a, hipStream_t st)
-{
-    const int blocks = (a->n_gen + 63) / 64;
-    switch (a->rk.render_type) {
-    case ICW_RENDER_RPDF: hipLaunchKernelGGL(icw_dither_gen<ICW_RENDER_RPDF>, dim3(blocks), dim3(64), 0, st, *a); break;
-    case ICW_RENDER_TPDF: hipLaunchKernelGGL(icw_dither_gen<ICW_RENDER_TPDF>, dim3(blocks), dim3(64), 0, st, *a); break;
-    case ICW_RENDER_STPDF: hipLaunchKernelGGL(icw_dither_gen<ICW_RENDER_STPDF>, dim3(blocks), dim3(64), 0, st, *a); break;
-    case ICW_RENDER_GAUSS: hipLaunchKernelGGL(icw_dither_gen<ICW_RENDER_GAUSS>, dim3(blocks), dim3(64), 0, st, *a); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
 template <int KIND, int NN, bool MR>
 static void icw_launch_rr(const IcwK3Args *a, int rb, hipStream_t st)
 {
-    /* K3c (a companion wave beside the chain, 128 threads) or K3r (one wave).  ICW_K3C_LDS (A/B): dynamic
-     * LDS bytes K3c reserves on top of its own, so that fewer other workgroups share its CUs */
-    if (a->comp) {
-        const char *e = getenv("ICW_K3C_LDS");
-        size_t pad = e ? (size_t)atol(e) : 0;
-        if (pad > 150 * 1024) pad = 150 * 1024;
-        if (pad > 64 * 1024)
-            (void)hipFuncSetAttribute((const void *)icw_render_rowc<KIND, NN, MR>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
-        hipLaunchKernelGGL((icw_render_rowc<KIND, NN, MR>), dim3(rb), dim3(128), pad, st, *a);
-    } else {
-        hipLaunchKernelGGL((icw_render_row<KIND, NN, MR>), dim3(rb), dim3(64), 0, st, *a);
-    }
+    /* K3c: a companion wave beside the chain, 128 threads */
+    hipLaunchKernelGGL((icw_render_rowc<KIND, NN, MR>), dim3(rb), dim3(128), 0, st, *a);
 }
 
 template <bool MR>
 static hipError_t icw_launch_render_row(const IcwK3Args *a, int rb, int nn, hipStream_t st)
 {
-    if (a->comp && a->dith && !a->dith_gm) return hipErrorInvalidValue;   /* K3c stages generator-major rows */
+    if (a->dith && !a->dith_gm) return hipErrorInvalidValue;   /* K3c stages generator-major rows */
     if (a->rk.ns_kind == 0) {
         icw_launch_rr<0, 0, MR>(a, rb, st);
     } else if (a->rk.ns_kind == 1) {
@@ -4474,13 +3995,13 @@ extern "C" hipError_t icw_launch_output(const IcwK2Args *a, int nord, int kahan,
 
 extern "C" hipError_t icw_launch_trig_table(const IcwTrigArgs *a, hipStream_t st)
 {
-    hipLaunchKernelGGL(icw_trig_table, dim3((a->T + 255) / 256), dim3(256), a->lds_guard, st, *a);
+    hipLaunchKernelGGL(icw_trig_table, dim3((a->T + 255) / 256), dim3(256), 0, st, *a);
     return hipGetLastError();
 }
 
 extern "C" hipError_t icw_launch_graph_serial(const IcwK4Args *a, hipStream_t st)
 {
-    hipLaunchKernelGGL(icw_graph_serial, dim3((a->n_streams + 63) / 64), dim3(64), a->lds_guard, st, *a);
+    hipLaunchKernelGGL(icw_graph_serial, dim3((a->n_streams + 63) / 64), dim3(64), 0, st, *a);
     return hipGetLastError();
 }
 
@@ -4524,6 +4045,6 @@ extern "C" hipError_t icw_launch_stream1(const IcwS1Args *a, int nord, hipStream
 
 extern "C" hipError_t icw_launch_advance(const IcwAdvArgs *a, hipStream_t st)
 {
-    hipLaunchKernelGGL(icw_advance, dim3((a->n_streams + 63) / 64), dim3(64), a->lds_guard, st, *a);
+    hipLaunchKernelGGL(icw_advance, dim3((a->n_streams + 63) / 64), dim3(64), 0, st, *a);
     return hipGetLastError();
 }

@@ -125,7 +125,7 @@ def test_stream1_path(oracle, icw, rtype, quantz, b24, monkeypatch):
 @pytest.mark.parametrize("path", ["iir", "fir", "stream1"])
 @pytest.mark.parametrize("rtype", DITHERS)
 def test_same_bytes_as_serial_render(oracle, icw, path, rtype, monkeypatch):
-    """ICW_DITH_PAR=0 renders the same configuration through the serial render (K3a + K3r): the bytes
+    """ICW_DITH_PAR=0 renders the same configuration through the serial render (K3a + K3c): the bytes
     and meters are the frame-parallel render's"""
     monkeypatch.setenv("ICW_K1_MODE", "row")
     cfg = flat_cfg(48000, rtype, abi.QUANTZ_MID_RISER, True, False)

@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(autouse=True, params=["plain", "row"])
 def k1_mode(request, monkeypatch):
     """run every case through both shipped forms of the two serial kernels: lane per chain / per
-    render channel (large batches: K1, K3b) and the 16-lane row broadcast (small batches: K1r, K3r;
+    render channel (large batches: K1, K3b) and the 16-lane row broadcast (small batches: K1r, K3c;
     K1r takes Kahan + reject only, other modes fall back to the lane-per-chain kernel)"""
     monkeypatch.setenv("ICW_K1_MODE", request.param)
     monkeypatch.setenv("ICW_RENDER", "serial" if request.param == "plain" else "row")
@@ -384,9 +384,10 @@ def test_meters_and_output_after_device_call_without_sync(oracle, icw):
 @pytest.mark.parametrize("ns", [abi.NSHAPE_FLAT, abi.NSHAPE_FW44, abi.NSHAPE_MEW44, 9, abi.NSHAPE_MAX])
 def test_serial_render_short_and_ragged_calls(oracle, icw, ns):
     """the serial renders over calls shorter than one, two and three 20-sample blocks and around
-    their multiples -- K3r stages a block's inputs in LDS two blocks ahead (its prologue reads past a
-    short call's end, its last block is partial) and rotates the shaper ring by the remainder; three
-    streams leave two spare rows in the second K3r wave; the state carries across the calls"""
+    their multiples -- K3c's companion wave stages a block's inputs in LDS blocks ahead (its loads run
+    past a short call's end, the last block is partial) and the chain rotates the shaper ring by the
+    remainder; three streams leave two spare rows in the second K3c workgroup; the state carries
+    across the calls"""
     cfg = graph.default_config(48000, need24bits=(ns % 2 == 1))
     cfg.render.render_type = abi.RENDER_TPDF
     cfg.render.nshape_type = ns

@@ -1,4 +1,4 @@
-"""GPU parity of K3r's clamp-free blocks (icw_render_row, render_consts' spec_thr).
+"""GPU parity of K3c's clamp-free blocks (icw_render_rowc, render_consts' spec_thr).
 
 The row render runs a 20-sample block without the clip stage when the block before it clipped
 nowhere and the block's own inputs x * norm_mul are all within spec_thr: the error fed back is then
