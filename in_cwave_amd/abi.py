@@ -121,6 +121,12 @@ class BatchStats(C.Structure):
                 ("frames_out", C.c_uint64), ("wall_s", C.c_double), ("io_s", C.c_double)]
 
 
+class CwaveEncOpts(C.Structure):
+    """icw_cwave_enc_opts (include/icw_reader.h)"""
+    _fields_ = [("k_M", C.c_int32), ("align", C.c_int32), ("k_beta", C.c_double), ("cw_format", C.c_uint32),
+                ("block_frames", C.c_int32), ("device", C.c_int32), ("reserved_", C.c_int32)]
+
+
 # every function declared in include/icw.h, icw_amod.h, icw_cwave.h: name -> (restype, argtypes)
 _vp, _sz, _i, _u = C.c_void_p, C.c_size_t, C.c_int, C.c_uint
 SIGNATURES = {
@@ -181,6 +187,11 @@ SIGNATURES = {
                              C.POINTER(C.c_uint32), _u, _i, _vp]),
     "icw_crc32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "icw_cwave_check": (_i, [_vp, C.c_uint64, _u, _i, C.POINTER(C.c_uint32), C.POINTER(_i)]),
+    "icw_cwave_frame_bytes": (_i, [C.c_uint32, C.c_uint32]),
+    "icw_encode_cwave": (_i, [_vp, _i, _i, _vp, _sz, _vp, _sz, _i, C.c_uint32, _u, _vp]),
+    "icw_encode_clipped": (_i, [_vp, _i, _i, C.POINTER(C.c_uint64)]),
+    "icw_cwave_encode_files": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, C.POINTER(CwaveEncOpts),
+                                    C.POINTER(BatchStats), C.POINTER(C.c_uint64), C.POINTER(_i)]),
     "icw_config_load": (_i, [C.c_char_p, _sz, C.POINTER(FileConfig), C.POINTER(_i)]),
     "icw_node_dsp_parse": (_i, [C.c_char_p, C.POINTER(Node), C.c_char_p, _sz]),
     "icw_node_dsp_format": (_i, [C.POINTER(Node), C.c_char_p, C.c_char_p, _sz]),

@@ -305,9 +305,250 @@ int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::v
     return rc;
 }
 
+/* HCWAVE_V2 (cwave.h:48-60), little-endian */
+void cwave_header(unsigned char *h, const icw_cwave_enc_opts &o, uint32_t channels, uint32_t frames, uint32_t rate, uint32_t crc)
+{
+    auto p32 = [](unsigned char *q, uint32_t v) { q[0] = v; q[1] = v >> 8; q[2] = v >> 16; q[3] = v >> 24; };
+    memcpy(h, "cPLXwAVE", 8);
+    p32(h + 8, ICW_CWAVE_HEADER_BYTES);
+    p32(h + 12, 2);
+    p32(h + 16, o.cw_format - ICW_FMT_CW_F64);
+    p32(h + 20, channels);
+    p32(h + 24, frames);
+    p32(h + 28, rate);
+    p32(h + 32, (uint32_t)o.k_M);
+    p32(h + 36, crc);
+    uint64_t b;
+    memcpy(&b, &o.k_beta, 8);
+    p32(h + 40, (uint32_t)b);
+    p32(h + 44, (uint32_t)(b >> 32));
+}
+
+/* One group of WAV files sharing (rate, format, channels) through the CWAVE encoder: one context, one
+ * fresh stream per file, no fades, no tail.  The CRC of every file's data is chained block by block
+ * over the packed frames while they are in HBM (icw_crc32_batch, device pointers). */
+int run_enc_group(std::vector<Job *> &jobs, const icw_cwave_enc_opts &o, icw_batch_stats &st, uint64_t *clipped, int *status)
+{
+    const int S = (int)jobs.size();
+    const icw_wav_info &wi = jobs[0]->info;
+    icw_config cfg;
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.sample_rate = wi.sample_rate;
+    cfg.in_format = wi.fmt;
+    cfg.in_channels = wi.channels;
+    cfg.hilbert_type = 1;
+    cfg.iir_kahan = cfg.iir_subnorm_reject = cfg.frmod_scaled = 1;
+    cfg.seed_left = ICW_SEED_LEFT;
+    cfg.seed_right = ICW_SEED_RIGHT;
+    cfg.render.dth_bits = 1.0;
+    cfg.render.sign_bits16 = 16;
+    cfg.render.sign_bits24 = 24;
+    icw_ctx *ctx = nullptr;
+    int rc = icw_create(&cfg, nullptr, 0, S, o.device, &ctx, nullptr);
+    if (rc != ICW_OK) return rc;
+    std::unique_ptr<icw_ctx, int (*)(icw_ctx *)> guard(ctx, icw_destroy);
+    if ((rc = icw_set_fir_hilbert(ctx, o.k_M, o.k_beta)) != ICW_OK) return rc;
+    const size_t fsz = wi.frame_bytes;
+    const size_t FB = (size_t)icw_cwave_frame_bytes(o.cw_format, wi.channels);
+    const int skip = o.align ? o.k_M / 2 : 0;            /* aligned: the first k_M/2 output frames are dropped */
+    const int B = std::max(o.block_frames > 0 ? o.block_frames : 65536, std::max(skip, 64));
+    int64_t T = 0;
+    for (int s = 0; s < S; ++s) {
+        Job &j = *jobs[s];
+        j.total = j.info.n_samples;                       /* file frames */
+        T = std::max(T, j.total);
+        if ((rc = icw_stream_open(ctx, s, j.info.n_samples + skip, 0, 0, 0, 0, 0)) != ICW_OK) return rc;
+        unsigned char hdr[ICW_CWAVE_HEADER_BYTES];
+        cwave_header(hdr, o, wi.channels, (uint32_t)j.total, wi.sample_rate, 0);
+        if (fwrite(hdr, 1, sizeof(hdr), j.out) != sizeof(hdr)) status[j.idx] = ICW_EINVAL;
+        if (fseeko(j.in, j.info.data_offset, SEEK_SET)) status[j.idx] = ICW_EINVAL;
+    }
+    const size_t in_b = (size_t)S * B * fsz, out_b = (size_t)S * B * FB;
+    unsigned char *hin[2] = {nullptr, nullptr}, *hout[2] = {nullptr, nullptr}, *din[2] = {nullptr, nullptr},
+                  *dout[2] = {nullptr, nullptr};
+    hipStream_t cs = nullptr, ks = nullptr;
+    hipEvent_t h2d[2] = {nullptr, nullptr}, comp[2] = {nullptr, nullptr}, d2h[2] = {nullptr, nullptr};
+    auto cleanup = [&]() {
+        if (cs) (void)hipStreamSynchronize(cs);
+        if (ks) (void)hipStreamSynchronize(ks);
+        for (int p = 0; p < 2; ++p) {
+            if (hin[p]) (void)hipHostFree(hin[p]);
+            if (hout[p]) (void)hipHostFree(hout[p]);
+            if (din[p]) (void)hipFree(din[p]);
+            if (dout[p]) (void)hipFree(dout[p]);
+            for (hipEvent_t e : {h2d[p], comp[p], d2h[p]}) if (e) (void)hipEventDestroy(e);
+        }
+        if (cs) (void)hipStreamDestroy(cs);
+        if (ks) (void)hipStreamDestroy(ks);
+    };
+    bool ok = true;
+    for (int p = 0; p < 2 && ok; ++p) {
+        ok = hipHostMalloc((void **)&hin[p], in_b, hipHostMallocDefault) == hipSuccess &&
+             hipHostMalloc((void **)&hout[p], out_b, hipHostMallocDefault) == hipSuccess &&
+             hipMalloc((void **)&din[p], in_b) == hipSuccess && hipMalloc((void **)&dout[p], out_b) == hipSuccess &&
+             hipEventCreateWithFlags(&h2d[p], hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&comp[p], hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&d2h[p], hipEventDisableTiming) == hipSuccess;
+    }
+    ok = ok && hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) == hipSuccess &&
+         hipStreamCreateWithFlags(&ks, hipStreamNonBlocking) == hipSuccess;
+    if (!ok) { cleanup(); return ICW_ENOMEM; }
+
+    /* the next nfr input frames of every stream into buf: data frames, then the format's zero sample */
+    auto read_frames = [&](unsigned char *buf, int nfr) {
+        const double t0 = now_s();
+        for (int s = 0; s < S; ++s) {
+            Job &j = *jobs[s];
+            unsigned char *row = buf + (size_t)s * B * fsz;
+            const int64_t want = std::min<int64_t>(nfr, std::max<int64_t>(0, j.info.n_samples - j.read));
+            size_t got = 0;
+            if (want > 0 && status[j.idx] == ICW_OK) {
+                got = fread(row, fsz, (size_t)want, j.in);
+                if ((int64_t)got != want) status[j.idx] = ICW_EINVAL;      /* short read: broken file */
+                j.read += (int64_t)got;
+                st.frames_in += got;
+            }
+            memset(row + got * fsz, zero_byte(j.info.fmt), (size_t)(B - (int64_t)got) * fsz);
+        }
+        st.io_s += now_s() - t0;
+    };
+    std::vector<uint32_t> crc(S, 0u);
+    std::vector<uint64_t> off(S), len(S);
+    auto write_block = [&](int k) {
+        const double t0 = now_s();
+        const unsigned char *buf = hout[k & 1];
+        for (int s = 0; s < S; ++s) {
+            Job &j = *jobs[s];
+            const int64_t n = std::min<int64_t>(B, j.total - j.written);
+            if (n <= 0 || status[j.idx] != ICW_OK) continue;
+            if (fwrite(buf + (size_t)s * B * FB, FB, (size_t)n, j.out) != (size_t)n) status[j.idx] = ICW_EINVAL;
+            j.written += n;
+            st.frames_out += (uint64_t)n;
+        }
+        st.io_s += now_s() - t0;
+    };
+
+    /* aligned mode: the k_M/2 frames that are dropped go through first, on their own (so that neither the
+     * CRC nor the clip counts see them) */
+    if (skip) {
+        read_frames(hin[0], skip);
+        if (hipMemcpyAsync(din[0], hin[0], in_b, hipMemcpyHostToDevice, ks) != hipSuccess) rc = ICW_EDEVICE;
+        if (rc == ICW_OK)
+            rc = icw_encode_cwave(ctx, 0, S, din[0], (size_t)B * fsz, dout[0], (size_t)B * FB, skip, o.cw_format,
+                                  ICW_F_DEVICE_PTRS, ks);
+        for (int s = 0; s < S && rc == ICW_OK; ++s) rc = icw_encode_clipped(ctx, s, 1, nullptr);
+    }
+    const int nb = (int)((T + B - 1) / B);
+    if (rc == ICW_OK) read_frames(hin[0], B);
+    for (int k = 0; k < nb && rc == ICW_OK; ++k) {
+        const int p = k & 1;
+        /* H2D(k): d_in[p] was last read by compute(k-2); d_out[p] by D2H(k-2), which compute(k) waits for */
+        if (k >= 2 && (hipStreamWaitEvent(cs, comp[p], 0) != hipSuccess || hipStreamWaitEvent(ks, d2h[p], 0) != hipSuccess))
+            rc = ICW_EDEVICE;
+        if (rc == ICW_OK && (hipMemcpyAsync(din[p], hin[p], in_b, hipMemcpyHostToDevice, cs) != hipSuccess ||
+                             hipEventRecord(h2d[p], cs) != hipSuccess || hipStreamWaitEvent(ks, h2d[p], 0) != hipSuccess))
+            rc = ICW_EDEVICE;
+        if (rc == ICW_OK)
+            rc = icw_encode_cwave(ctx, 0, S, din[p], (size_t)B * fsz, dout[p], (size_t)B * FB, B, o.cw_format,
+                                  ICW_F_DEVICE_PTRS, ks);
+        if (rc == ICW_OK && (hipEventRecord(comp[p], ks) != hipSuccess || hipStreamWaitEvent(cs, comp[p], 0) != hipSuccess ||
+                             hipMemcpyAsync(hout[p], dout[p], out_b, hipMemcpyDeviceToHost, cs) != hipSuccess ||
+                             hipEventRecord(d2h[p], cs) != hipSuccess))
+            rc = ICW_EDEVICE;
+        if (rc != ICW_OK) break;
+        /* this block's part of every file's CRC, from the frames in HBM (returns once the kernel is done) */
+        for (int s = 0; s < S; ++s) {
+            off[s] = (uint64_t)s * B * FB;
+            len[s] = (uint64_t)std::max<int64_t>(0, std::min<int64_t>(B, jobs[s]->total - (int64_t)k * B)) * FB;
+        }
+        if ((rc = icw_crc32_batch(dout[p], off.data(), len.data(), S, crc.data(), crc.data(), ICW_F_DEVICE_PTRS, o.device, ks)) !=
+            ICW_OK)
+            break;
+        if (k + 1 < nb) {
+            if (k >= 1 && hipEventSynchronize(h2d[(k + 1) & 1]) != hipSuccess) { rc = ICW_EDEVICE; break; }
+            read_frames(hin[(k + 1) & 1], B);
+        }
+        if (k >= 1) {
+            if (hipEventSynchronize(d2h[(k - 1) & 1]) != hipSuccess) { rc = ICW_EDEVICE; break; }
+            write_block(k - 1);
+        }
+    }
+    if (rc == ICW_OK && nb >= 1) {
+        if (hipEventSynchronize(d2h[(nb - 1) & 1]) != hipSuccess) rc = ICW_EDEVICE;
+        else write_block(nb - 1);
+    }
+    if (rc == ICW_OK) rc = icw_synchronize(ctx);
+    for (int s = 0; s < S && rc == ICW_OK; ++s) {
+        Job &j = *jobs[s];
+        uint64_t nclip = 0;
+        rc = icw_encode_clipped(ctx, s, 0, &nclip);
+        if (clipped) clipped[j.idx] = nclip;
+        unsigned char hdr[ICW_CWAVE_HEADER_BYTES];
+        cwave_header(hdr, o, wi.channels, (uint32_t)j.total, wi.sample_rate, crc[s]);
+        if (status[j.idx] == ICW_OK && (fseeko(j.out, 0, SEEK_SET) || fwrite(hdr, 1, sizeof(hdr), j.out) != sizeof(hdr)))
+            status[j.idx] = ICW_EINVAL;
+    }
+    cleanup();
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
+
+int icw_cwave_encode_files(const char *const *in_paths, const char *const *out_paths, int n, const icw_cwave_enc_opts *opts,
+                           icw_batch_stats *stats, uint64_t *clipped, int *status)
+{
+    if (!opts || n < 0 || (n > 0 && (!in_paths || !out_paths))) return ICW_EINVAL;
+    const icw_cwave_enc_opts &o = *opts;
+    if (o.k_M < 2 || o.k_M > ICW_FIR_MAX_ORDER || (o.k_M & 1) || !(o.k_beta >= 0.0 && o.k_beta < 1e3) ||
+        o.cw_format < ICW_FMT_CW_F64 || o.cw_format > ICW_FMT_CW_F32 || (o.align != 0 && o.align != 1) || o.block_frames < 0)
+        return ICW_EINVAL;
+    const double t0 = now_s();
+    icw_batch_stats st;
+    memset(&st, 0, sizeof(st));
+    std::vector<int> stat_local(n > 0 ? n : 1, ICW_OK);
+    int *sts = status ? status : stat_local.data();
+    std::vector<Job> jobs(n);
+    std::map<std::tuple<uint32_t, uint32_t, uint32_t>, std::vector<Job *>> groups;
+    for (int i = 0; i < n; ++i) {
+        sts[i] = ICW_OK;
+        if (clipped) clipped[i] = 0;
+        Job &j = jobs[i];
+        j.idx = i;
+        if (!in_paths[i] || !out_paths[i] || icw_wav_parse_file(in_paths[i], &j.info) != ICW_OK ||
+            j.info.fmt >= ICW_FMT_CW_F64 ||                      /* a CWAVE file is analytic already */
+            j.info.n_samples < 2 || j.info.n_samples >= ((int64_t)1 << 32)) {
+            sts[i] = ICW_EINVAL;
+            continue;
+        }
+        if (!(j.in = fopen(in_paths[i], "rb")) || !(j.out = fopen(out_paths[i], "wb"))) {
+            sts[i] = ICW_EINVAL;
+            continue;
+        }
+        setvbuf(j.in, nullptr, _IOFBF, 1 << 20);
+        setvbuf(j.out, nullptr, _IOFBF, 1 << 20);
+        groups[std::make_tuple(j.info.sample_rate, j.info.fmt, j.info.channels)].push_back(&j);
+    }
+    int rc = ICW_OK;
+    for (auto &g : groups) {
+        const int r = run_enc_group(g.second, o, st, clipped, sts);
+        if (r != ICW_OK) {
+            rc = r;
+            for (Job *j : g.second) if (sts[j->idx] == ICW_OK) sts[j->idx] = r;
+        }
+        ++st.n_groups;
+    }
+    for (Job &j : jobs) {
+        if (j.in) fclose(j.in);
+        if (j.out && fclose(j.out) != 0 && sts[j.idx] == ICW_OK) sts[j.idx] = ICW_EINVAL;
+        if (sts[j.idx] == ICW_OK) ++st.n_files;
+        else if (rc == ICW_OK) rc = sts[j.idx];
+    }
+    st.wall_s = now_s() - t0;
+    if (stats) *stats = st;
+    return rc;
+}
 
 int icw_wav_parse_file(const char *path, icw_wav_info *info)
 {

@@ -65,7 +65,15 @@ struct IcwFirArgs {
                                       both output channels are one computation (icw_fir_sig) */
 };
 
-/* Arguments of the call-end bookkeeping kernel: one thread per stream.  During a call every
+/* Arguments of the CWAVE encoder (KFE): KF's, with the packed file frames as the output (xd unused) */
+struct IcwEncArgs {
+    IcwFirArgs f;
+    unsigned char *out;            /* stream s, the block's first frame, at out + s*out_stride */
+    size_t out_stride;
+    unsigned long long *clipped;   /* [n_streams] saturated / NaN int16 samples, accumulated */
+};
+
+/* Arguments of the call-end bookkeeping kernel: one thread per stream. During a call every
  * kernel reads the call-start position / phases / frame counter and adds its block offset; this
  * kernel advances them once, after the last block. */
 struct IcwAdvArgs {

@@ -1,0 +1,204 @@
+/*
+ * icw_encode.hip -- gfx950 (CDNA4) kernel of the CWAVE encoder: the FIR Hilbert converter's analytic
+ * signal as the packed frames of a CWAVE file (include/icw_cwave.h: icw_encode_cwave).
+ *
+ * Built like icw_kernels.hip (`-ffp-contract=off`, no fast-math).  The staging and the sums are the
+ * converter's own (icw_fir_dev.h), so I and Q are bit for bit what KF / KF2 feed the graph.
+ */
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "../../include/icw.h"
+#include "icw_device.h"
+
+#pragma clang fp contract(off)
+
+#include "icw_unpack_dev.h"
+#include "icw_fir_dev.h"
+
+/* KFE: the converter as a CWAVE encoder.  KF's staging and sums (so the same unpack, fades, I and Q,
+ * bit for bit), written as the interleaved frames of a CWAVE file (cwave.h:74-81) instead of the I / Q
+ * rows: per channel `Re Im` as double / int16 / int16 + float / float, stereo Re(L) Im(L) Re(R) Im(R),
+ * mono input one channel.  One workgroup per 2048-frame tile of a stream; a lane converts both channels
+ * of its 8 frames.
+ *
+ * Conversions (the file format has no reference writer; these are the project's definition):
+ *   float   (float)v, round to nearest even;
+ *   int16   rint(v) (ties to even) saturated to [-32768, 32767], NaN -> 0; every saturated or NaN sample
+ *           of a frame inside the block counts in clipped[s];
+ *   double  the bits.
+ *
+ * Byte assembly.  A lane's 8 frames are 8 FB contiguous file bytes (FB = 4 .. 32, always a whole number
+ * CU = FB / 2 of 16-byte units), packed in registers and written over the staged inputs (all read by
+ * then) with ds_write_b128.  Those stores go by groups of 8 consecutive lanes over 32 banks: a lane
+ * stride of an odd number of units puts the 8 lanes on the 8 distinct slots, so an even CU gets one pad
+ * unit per lane (physical unit j + j / CU) and the odd one (CU 3: the 6-byte frame) none.  The tile then
+ * leaves as consecutive 16-byte units, one global_store_dwordx4 per lane and pass; a tile whose first
+ * byte is not 16-byte aligned leaves as dwords funnelled from two LDS words, and only the at most two
+ * partial dwords at its ends as bytes. */
+template <int CWF> struct icw_cw_bytes { static constexpr int value = CWF == 0 ? 16 : CWF == 1 ? 4 : CWF == 2 ? 6 : 8; };
+
+__device__ __forceinline__ uint32_t icw_enc_i16(double v, bool live, unsigned &clip)
+{
+    const double r = __builtin_rint(v);
+    if (r >= -32768.0 && r <= 32767.0) return (uint32_t)(int)r & 0xffffu;
+    if (live) ++clip;
+    return r != r ? 0u : (r < 0.0 ? 0x8000u : 0x7fffu);
+}
+
+template <int CWF, int NC>
+__global__ __launch_bounds__(256) void icw_fir_encode(IcwEncArgs e)
+{
+    extern __shared__ __attribute__((aligned(16))) double xs[];   /* staged inputs (padded); then the frames */
+    __shared__ unsigned nclip;
+    const IcwFirArgs &a = e.f;
+    constexpr int TF = 256 * ICW_FIR_R;
+    constexpr int CB = icw_cw_bytes<CWF>::value, FB = NC * CB;    /* bytes per channel, per frame */
+    constexpr int NW = ICW_FIR_R * FB / 4;                        /* dwords a lane packs */
+    constexpr int CU = FB / 2, PADU = (CU & 1) ? 0 : 1;           /* its 16-byte units, pad units */
+    const int s = blockIdx.y, tid = threadIdx.x;
+    const int tt = blockIdx.x * TF;
+    const int M = a.M, c = M >> 1;
+    const int sh = (8 - ((c - 1) & 7)) & 7;          /* c - 1 + sh = 8 a */
+    const int av = (c - 1 + sh) >> 3;
+    const int nf = min(TF, a.T - tt);
+    const int px = (icw_fir_phys(sh + M + TF + 24) + 2) & ~1;
+    if (tid == 0) nclip = 0u;
+    icw_fir_stage<NC>(a, s, 0, xs, px, tt, TF, sh, tid, 256);
+    icw_ctap *gs = (icw_ctap *)a.g;
+    __syncthreads();
+    uint32_t w[NW];
+    unsigned clip = 0u;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        double q[ICW_FIR_R], vi[ICW_FIR_R];
+        icw_fir_sums(xs + k * px, gs, a.nt, tid, av, sh, c, q);
+#pragma unroll
+        for (int r = 0; r < ICW_FIR_R; ++r) vi[r] = xs[k * px + icw_fir_phys(ICW_FIR_R * tid + r + 8 * av + 1)];
+#pragma unroll
+        for (int r = 0; r < ICW_FIR_R; ++r) {
+            const int o = r * FB + k * CB;               /* byte offset in the lane's run: even, a constant */
+            const bool live = ICW_FIR_R * tid + r < nf;
+            if constexpr (CWF == 0) {
+                const unsigned long long bi = (unsigned long long)__double_as_longlong(vi[r]);
+                const unsigned long long bq = (unsigned long long)__double_as_longlong(q[r]);
+                w[o / 4] = (uint32_t)bi;
+                w[o / 4 + 1] = (uint32_t)(bi >> 32);
+                w[o / 4 + 2] = (uint32_t)bq;
+                w[o / 4 + 3] = (uint32_t)(bq >> 32);
+            } else if constexpr (CWF == 1) {
+                w[o / 4] = icw_enc_i16(vi[r], live, clip) | (icw_enc_i16(q[r], live, clip) << 16);
+            } else if constexpr (CWF == 2) {
+                const uint32_t re = icw_enc_i16(vi[r], live, clip), im = __float_as_uint((float)q[r]);
+                if (o & 2) {                             /* the frame starts in a dword's upper half */
+                    w[o / 4] |= re << 16;
+                    w[o / 4 + 1] = im;
+                } else {
+                    w[o / 4] = re | (im << 16);
+                    w[o / 4 + 1] = im >> 16;
+                }
+            } else {
+                w[o / 4] = __float_as_uint((float)vi[r]);
+                w[o / 4 + 1] = __float_as_uint((float)q[r]);
+            }
+        }
+    }
+    __syncthreads();                                     /* every lane has read its inputs */
+    uint4 *ob = (uint4 *)xs;
+#pragma unroll
+    for (int i = 0; i < CU; ++i) ob[tid * (CU + PADU) + i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+    if (CWF == 1 || CWF == 2) {
+        if (clip) atomicAdd(&nclip, clip);
+    }
+    __syncthreads();
+    if ((CWF == 1 || CWF == 2) && tid == 0 && nclip) atomicAdd(e.clipped + s, (unsigned long long)nclip);
+    unsigned char *dst = e.out + (size_t)s * e.out_stride + (size_t)tt * FB;
+    const int nbytes = nf * FB;
+    const uint32_t *ow = (const uint32_t *)xs;
+    const unsigned char *oc = (const unsigned char *)xs;
+    /* logical 16-byte unit / dword / byte of the tile -> its place in the padded image */
+    auto pu = [](int j) { return j + PADU * (j / CU); };
+    auto pw = [](int j) { return j + 4 * PADU * (j / (4 * CU)); };
+    auto pb = [](int j) { return j + 16 * PADU * (j / (16 * CU)); };
+    if (!((uintptr_t)dst & 15)) {
+        const int nu = nbytes >> 4;
+        uint4 *d4 = (uint4 *)dst;
+        for (int j = tid; j < nu; j += 256) d4[j] = ob[pu(j)];
+        const int rest = nbytes - 16 * nu;               /* < 16, even: the last frames of a short tile */
+        if (tid < rest / 2) {
+            const int j = 16 * nu + 2 * tid;
+            *(unsigned short *)(dst + j) = *(const unsigned short *)(oc + pb(j));
+        }
+    } else {
+        const int b = (int)((uintptr_t)dst & 3);
+        unsigned char *d0 = dst - b;
+        const int nd = (b + nbytes + 3) >> 2;
+        for (int k = tid; k < nd; k += 256) {
+            const int o = 4 * k - b;                     /* the dword's first byte in the tile */
+            if (o >= 0 && o + 4 <= nbytes) {
+                uint32_t v = ow[pw(k)];
+                if (b) v = (ow[pw(k - 1)] >> (8 * (4 - b))) | (v << (8 * b));
+                *(uint32_t *)(d0 + 4 * k) = v;
+            } else {
+                for (int i = 0; i < 4; ++i)
+                    if (o + i >= 0 && o + i < nbytes) d0[4 * k + i] = oc[pb(o + i)];
+            }
+        }
+    }
+}
+
+/* the reader position of the streams an encode call covered (what icw_advance does to it) */
+__global__ __launch_bounds__(64) void icw_pos_advance(long long *pos, int n_streams, long long n)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s < n_streams) pos[s] += n;
+}
+
+/* ---------------------------------------------------------------- launch wrappers ------- */
+/* LDS doubles of one staged channel (the px of the kernels) */
+static size_t enc_px(int M)
+{
+    const int sh = (8 - ((M / 2 - 1) & 7)) & 7;
+    const int nl = sh + M + 256 * ICW_FIR_R + 24;
+    return (size_t)(nl + ICW_FIR_PAD * (nl >> 3) + 2) & ~(size_t)1;
+}
+
+template <int CWF, int NC>
+static hipError_t launch_fir_encode_t(const IcwEncArgs *e, hipStream_t st)
+{
+    constexpr int TF = 256 * ICW_FIR_R;
+    constexpr int CU = NC * icw_cw_bytes<CWF>::value / 2, PADU = (CU & 1) ? 0 : 1;
+    /* the staged channels, or the tile's padded frame image where that is larger (it takes their place) */
+    const size_t lds = std::max((size_t)NC * enc_px(e->f.M) * sizeof(double), (size_t)256 * (CU + PADU) * 16);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    /* LDS above 64 KB per workgroup needs the kernel attribute (gfx950: 160 KB per CU) */
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)icw_fir_encode<CWF, NC>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((icw_fir_encode<CWF, NC>), dim3((e->f.T + TF - 1) / TF, e->f.n_streams), dim3(256), lds, st, *e);
+    return hipGetLastError();
+}
+
+/* KFE of one launch block; cwf = cw_format - ICW_FMT_CW_F64 */
+extern "C" hipError_t icw_launch_fir_encode(const IcwEncArgs *e, int cwf, hipStream_t st)
+{
+    const int M = e->f.M, nt = e->f.nt;
+    if (M < 2 || M > ICW_FIR_MAX_M || (M & 1) || nt < 1 || 2 * nt - 1 > M / 2 || e->f.T <= 0) return hipErrorInvalidValue;
+    const bool st2 = e->f.nch > 1;
+    switch (cwf) {
+    case 0: return st2 ? launch_fir_encode_t<0, 2>(e, st) : launch_fir_encode_t<0, 1>(e, st);
+    case 1: return st2 ? launch_fir_encode_t<1, 2>(e, st) : launch_fir_encode_t<1, 1>(e, st);
+    case 2: return st2 ? launch_fir_encode_t<2, 2>(e, st) : launch_fir_encode_t<2, 1>(e, st);
+    case 3: return st2 ? launch_fir_encode_t<3, 2>(e, st) : launch_fir_encode_t<3, 1>(e, st);
+    }
+    return hipErrorInvalidValue;
+}
+
+extern "C" hipError_t icw_launch_pos_advance(long long *pos, int n_streams, long long n, hipStream_t st)
+{
+    hipLaunchKernelGGL(icw_pos_advance, dim3((n_streams + 63) / 64), dim3(64), 0, st, pos, n_streams, n);
+    return hipGetLastError();
+}

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/icw.h"
+#include "../../include/icw_cwave.h"
 #include "icw_device.h"
 #include "icw_tables.inc"
 #include "icw_tuning.h"
@@ -40,6 +41,8 @@ extern "C" hipError_t icw_launch_fir(const IcwFirArgs *a, hipStream_t st);
 extern "C" hipError_t icw_launch_fir_graph(const IcwFirArgs *f, const IcwK2Args *a, int in_step, int sig_on,
                                            hipStream_t st);
 extern "C" size_t icw_fir_graph_lds(int M, int nt, int nch, int n_regs);
+extern "C" hipError_t icw_launch_fir_encode(const IcwEncArgs *e, int cwf, hipStream_t st);
+extern "C" hipError_t icw_launch_pos_advance(long long *pos, int n_streams, long long n, hipStream_t st);
 
 #define ICW_PI_H (3.1415926535897932384626433832795029)
 
@@ -185,6 +188,7 @@ struct icw_ctx {
     double *d_fir_g = nullptr;
     double *fir_hist[2] = {};
     int fir_par = 0;
+    unsigned long long *enc_clipped = nullptr; /* [streams] icw_encode_cwave: saturated / NaN int16 samples (lazy) */
     unsigned long long *s1_stamps = nullptr;   /* ICW_S1_STAMPS=1: K5 phase stamps, printed per call */
     unsigned long long calls = 0;         /* icw_process_* calls so far (icw_prepare needs a fresh context) */
     /* per-stream state set by an entry point other than a call (stream_open, seek, set_state, the
@@ -774,7 +778,7 @@ bool fir_clear(icw_ctx *c, size_t f, size_t n, hipStream_t st)
 void free_all(icw_ctx *c)
 {
     DevState &s = c->st;
-    void *ptrs[] = {c->s1_stamps, s.mt, s.mt_idx, s.rs, s.lr_equal, s.fes, s.err, s.hist, s.sncnt, s.hq_phase, s.pos, s.fade,
+    void *ptrs[] = {c->enc_clipped, c->s1_stamps, s.mt, s.mt_idx, s.rs, s.lr_equal, s.fes, s.err, s.hist, s.sncnt, s.hq_phase, s.pos, s.fade,
                     s.n_frame, s.bus, s.clips, s.peak_bits, c->d_prog, c->trig, c->d_in, c->d_out, c->d_pre, c->d_xin,
                     c->d_fir_g, c->fir_hist[0], c->fir_hist[1], c->dwords, c->dbk, c->dflag};
     for (void *p : ptrs)
@@ -2166,6 +2170,112 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         c->last_launches[0] = c->last_launches[1] = n_blocks;
     }
     return hipGetLastError() == hipSuccess ? ICW_OK : ICW_EDEVICE;
+}
+
+/* ------------------------------------------------------------- CWAVE encoder (icw_cwave.h) -- */
+int icw_cwave_frame_bytes(uint32_t cw_format, uint32_t channels)
+{
+    if (cw_format < ICW_FMT_CW_F64 || cw_format > ICW_FMT_CW_F32 || channels == 0) return 0;
+    return (int)(fmt_size(cw_format) * (channels > 1 ? 2u : 1u));
+}
+
+/* The FIR converter's analytic signal as packed CWAVE frames (KFE).  The call shares icw_process_streams'
+ * converter state -- the per-stream history (double-buffered by launch block, back in fir_hist[fir_par]
+ * at the end) and the reader position -- and nothing else of the context. */
+int icw_encode_cwave(icw_ctx *c, int first, int count, const void *in, size_t in_stride, void *out, size_t out_stride,
+                     int n_frames, uint32_t cw_format, unsigned flags, void *hip_stream)
+{
+    if (!c || first < 0 || count <= 0 || first + count > c->n_streams || n_frames < 0 || !in || !out ||
+        (flags & ~ICW_F_DEVICE_PTRS))
+        return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const icw_config &cfg = c->cfg;
+    const int FB = icw_cwave_frame_bytes(cw_format, cfg.in_channels);
+    if (cfg.in_format >= ICW_FMT_CW_F64 || c->fir_M <= 0 || FB == 0) return ICW_EINVAL;
+    const unsigned csz = fmt_size(cfg.in_format), fsz = csz * cfg.in_channels;
+    const bool dev = flags & ICW_F_DEVICE_PTRS;
+    const size_t S = (size_t)count, ib = (size_t)n_frames * fsz, ob = (size_t)n_frames * FB;
+    if (!dev && (in_stride < ib || out_stride < ob)) return ICW_EINVAL;
+    if (n_frames == 0) return ICW_OK;
+    if (set_dev(c)) return ICW_EDEVICE;
+    ++c->calls;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    /* a NULL handle with device pointers: the legacy default stream, as in icw_process_streams */
+    const bool legacy = !hip_stream && dev;
+    if (legacy && (hipEventRecord(c->join, nullptr) != hipSuccess || hipStreamWaitEvent(st, c->join, 0) != hipSuccess))
+        return ICW_EDEVICE;
+    if (!c->enc_clipped) {
+        const int rc = dalloc(&c->enc_clipped, (size_t)c->n_streams);
+        if (rc != ICW_OK) {
+            if (c->enc_clipped) (void)hipFree(c->enc_clipped);
+            c->enc_clipped = nullptr;
+            return rc;
+        }
+    }
+    const unsigned char *d_in = (const unsigned char *)in;
+    unsigned char *d_out = (unsigned char *)out;
+    size_t dis = in_stride, dos = out_stride;
+    if (!dev) {
+        dis = ib;
+        dos = (ob + 15) & ~(size_t)15;                     /* every stream's frames 16-byte aligned */
+        if (grow((void **)&c->d_in, &c->d_in_bytes, dis * S) || grow((void **)&c->d_out, &c->d_out_bytes, dos * S + 16))
+            return ICW_ENOMEM;
+        if (hipMemcpy2DAsync(c->d_in, dis, in, in_stride, ib, S, hipMemcpyHostToDevice, st) != hipSuccess) return ICW_EDEVICE;
+        d_in = c->d_in;
+        d_out = c->d_out;
+    }
+    const int Tb = std::min(n_frames, c->tn.block_env ? c->tn.max_block : kMaxFirBlockFrames);
+    const std::vector<std::pair<int, int>> blocks = plan_blocks(n_frames, Tb, 0, 0.0, c->tn.taper_min);
+    const int n_blocks = (int)blocks.size();
+    const size_t f0 = (size_t)first, hrow = 2 * (size_t)c->fir_M;
+    for (int b = 0; b < n_blocks; ++b) {
+        IcwEncArgs e;
+        memset(&e, 0, sizeof(e));
+        e.f.in = d_in + (size_t)blocks[b].first * fsz;
+        e.f.in_stride = dis;
+        e.f.fmt = cfg.in_format;
+        e.f.csz = csz;
+        e.f.fsz = fsz;
+        e.f.nch = cfg.in_channels;
+        e.f.n_streams = count;
+        e.f.T = blocks[b].second;
+        e.f.t0 = blocks[b].first;
+        e.f.pos = c->st.pos + f0;
+        e.f.fade = c->st.fade + f0 * 3;
+        e.f.M = c->fir_M;
+        e.f.nt = c->fir_nt;
+        e.f.g = c->d_fir_g;
+        e.f.hist_in = c->fir_hist[(c->fir_par + b) & 1] + f0 * hrow;
+        e.f.hist_out = c->fir_hist[(c->fir_par + b + 1) & 1] + f0 * hrow;
+        e.out = d_out + (size_t)blocks[b].first * FB;
+        e.out_stride = dos;
+        e.clipped = c->enc_clipped + f0;
+        if (icw_launch_fir_encode(&e, (int)(cw_format - ICW_FMT_CW_F64), st) != hipSuccess) return ICW_EDEVICE;
+    }
+    if ((n_blocks & 1) &&
+        hipMemcpyAsync(c->fir_hist[c->fir_par] + f0 * hrow, c->fir_hist[c->fir_par ^ 1] + f0 * hrow,
+                       S * hrow * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return ICW_EDEVICE;
+    if (icw_launch_pos_advance(c->st.pos + f0, count, (long long)n_frames, st) != hipSuccess) return ICW_EDEVICE;
+    if (legacy && hipStreamSynchronize(st) != hipSuccess) return ICW_EDEVICE;
+    if (!dev && (hipMemcpy2DAsync(out, out_stride, d_out, dos, ob, S, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                 hipStreamSynchronize(st) != hipSuccess))
+        return ICW_EDEVICE;
+    return hipGetLastError() == hipSuccess ? ICW_OK : ICW_EDEVICE;
+}
+
+int icw_encode_clipped(icw_ctx *c, int s, int reset, uint64_t *clipped)
+{
+    if (!c || s < 0 || s >= c->n_streams) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    unsigned long long v = 0;
+    if (c->enc_clipped) {
+        if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+        if (hipMemcpy(&v, c->enc_clipped + s, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return ICW_EDEVICE;
+        if (reset && hipMemset(c->enc_clipped + s, 0, sizeof(v)) != hipSuccess) return ICW_EDEVICE;
+    }
+    if (clipped) *clipped = v;
+    return ICW_OK;
 }
 
 /* Warm-up of a fresh context (include/icw.h): one call of n_frames frames of digital silence through

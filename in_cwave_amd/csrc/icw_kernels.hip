@@ -30,110 +30,7 @@
 #define ICW_PI (3.1415926535897932384626433832795029)
 #define ICW_SQRT2 (1.4142135623730950488016887242097)
 
-/* ------------------------------------------------------------------ input unpack --------- */
-/* xwave_reader.c:205-239 + unpack_lsb.h:53-125 (little-endian, exact conversions) */
-__device__ __forceinline__ double icw_unpack(const unsigned char *p, uint32_t fmt)
-{
-    switch (fmt) {
-    case ICW_FMT_I16: {
-        int v = (int)(short)((unsigned)p[0] | ((unsigned)p[1] << 8));
-        return (double)v;
-    }
-    case ICW_FMT_U8:
-        return 256.0 * (double)((signed char)(unsigned char)(p[0] - 0x80u));
-    case ICW_FMT_I24: {
-        int v = ((int)(((unsigned)p[0] << 8) | ((unsigned)p[1] << 16) | ((unsigned)p[2] << 24))) >> 8;
-        return ((double)v) / 256.0;
-    }
-    case ICW_FMT_I32: {
-        int v = (int)((unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16) | ((unsigned)p[3] << 24));
-        return ((double)v) / 65536.0;
-    }
-    default: {
-        unsigned u = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16) | ((unsigned)p[3] << 24);
-        return 32768.0 * (double)__uint_as_float(u);
-    }
-    }
-}
-
-/* CWAVE unpackers (xwave_reader.c:171-200): no scaling, values already on the 16-bit scale */
-__device__ __forceinline__ uint32_t icw_le32(const unsigned char *p)
-{
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-
-__device__ __forceinline__ void icw_unpack_iq(const unsigned char *p, uint32_t fmt, double &vI, double &vQ)
-{
-    switch (fmt) {
-    case ICW_FMT_CW_F64: {
-        const unsigned long long lo = icw_le32(p), hi = icw_le32(p + 4);
-        const unsigned long long lo2 = icw_le32(p + 8), hi2 = icw_le32(p + 12);
-        vI = __longlong_as_double((long long)(lo | (hi << 32)));
-        vQ = __longlong_as_double((long long)(lo2 | (hi2 << 32)));
-        break;
-    }
-    case ICW_FMT_CW_I16:
-        vI = (double)(short)((unsigned)p[0] | ((unsigned)p[1] << 8));
-        vQ = (double)(short)((unsigned)p[2] | ((unsigned)p[3] << 8));
-        break;
-    case ICW_FMT_CW_I16_F32:
-        vI = (double)(short)((unsigned)p[0] | ((unsigned)p[1] << 8));
-        vQ = (double)__uint_as_float(icw_le32(p + 2));
-        break;
-    default:
-        vI = (double)__uint_as_float(icw_le32(p));
-        vQ = (double)__uint_as_float(icw_le32(p + 4));
-        break;
-    }
-}
-
-/* one sample of format FMT; AL: the address is aligned to the sample's size, so one typed load
- * replaces the byte loads and their shifts */
-template <int FMT, bool AL>
-__device__ __forceinline__ double icw_unpack_f(const unsigned char *p)
-{
-    if constexpr (AL && FMT == ICW_FMT_I16) return (double)*(const short *)p;
-    else if constexpr (AL && FMT == ICW_FMT_I32) return ((double)*(const int *)p) / 65536.0;
-    else if constexpr (AL && FMT == ICW_FMT_F32) return 32768.0 * (double)*(const float *)p;
-    else return icw_unpack(p, FMT);
-}
-
-template <int V> struct icw_ic { static constexpr int value = V; };
-
-/* calls f(icw_ic<FMT>, icw_ic<AL>) for a uniform real format: the unpack specialised once per
- * workgroup instead of a format switch per sample.  al: the OR of the base address and the strides
- * the samples are read at (aligned when its low bits below the sample size are clear) */
-template <typename F>
-__device__ __forceinline__ void icw_fmt_dispatch(uint32_t fmt, uintptr_t al, F &&f)
-{
-    switch (fmt) {
-    case ICW_FMT_I16:
-        if (al & 1) f(icw_ic<ICW_FMT_I16>(), icw_ic<0>());
-        else f(icw_ic<ICW_FMT_I16>(), icw_ic<1>());
-        break;
-    case ICW_FMT_U8: f(icw_ic<ICW_FMT_U8>(), icw_ic<0>()); break;
-    case ICW_FMT_I24: f(icw_ic<ICW_FMT_I24>(), icw_ic<0>()); break;
-    case ICW_FMT_I32:
-        if (al & 3) f(icw_ic<ICW_FMT_I32>(), icw_ic<0>());
-        else f(icw_ic<ICW_FMT_I32>(), icw_ic<1>());
-        break;
-    default:
-        if (al & 3) f(icw_ic<ICW_FMT_F32>(), icw_ic<0>());
-        else f(icw_ic<ICW_FMT_F32>(), icw_ic<1>());
-        break;
-    }
-}
-
-/* fade factor of xwave_unpack_csample (xwave_reader.c:918-936); < 0 means "no fade" */
-__device__ __forceinline__ double icw_fade(long long ix, long long ns, long long fi, long long fo)
-{
-    double fade = -1.0;
-    if (ix < fi)
-        fade = ((double)ix) / ((double)fi);
-    else if (ix > ns - fo && ix < ns)
-        fade = ((double)(ns - ix)) / ((double)fo);
-    return fade;
-}
+#include "icw_unpack_dev.h"
 
 /* input of the I (f=0) / Q (f=1) filter for Hilbert phase k (lpf_hilbert_quad.c:133-151):
  *   I: {x, +0, -x, +0}   Q: {+0, -x, +0, x}.  K0 writes the nonzero values of both into one row per
@@ -207,328 +104,7 @@ __global__ __launch_bounds__(256) void icw_unpack_frames(IcwK0Args a)
     if (t < a.T) icw_unpack_frame(a, t, blockIdx.y);
 }
 
-/* FIR Hilbert converter: real PCM -> the analytic signal a CWAVE file holds (cwave.h:40,56-58:
- * "Hilbert FIR filter order" k_M, "filter parameter" k_beta; the converter itself is not part of
- * in_cwave).  Order M (even, M + 1 taps), centre c = M/2, odd taps only:
- *     I[n] = x[n - c],   Q[n] = sum_{m = 1, 3, .., <= c} g_m * (x[n - c - m] - x[n - c + m])
- * with the sum taken in ascending m as acc = fma(g_m, d_m, acc) from +0.0 -- the oracle's order, so
- * the result is bit-identical.  x is the unpacked, faded input of K0 (xwave_unpack_csample,
- * xwave_reader.c:908-936), mono feeding R with L.
- *
- * Register blocking.  A lane sums 8 consecutive outputs of one channel.  For 8 taps at a time it
- * loads the 22 inputs their left operands span and the 22 of the right ones, then runs the 64
- * subtract + FMA pairs from registers: 44 LDS reads per 64 output-taps instead of 128.  The staged
- * inputs carry one pad double after every 8 (physical index i + i/8), so the 32 lanes of a
- * ds_read_b64 group, 9 doubles apart, hit 64 distinct banks; a staging shift `sh` puts every lane's
- * window at the same phase of that pattern, so all offsets inside a block are immediates.  Taps past
- * the last multiple of 8 run one at a time. */
-#define ICW_FIR_R 8                                  /* outputs per lane */
-#ifndef ICW_FIR_VEC
-#define ICW_FIR_VEC 1                                /* FIR staging: 16-byte loads, one LDS base per thread */
-#endif
-#ifndef ICW_FIR_INTERIOR
-#define ICW_FIR_INTERIOR 1                           /* FIR staging: the interior tiles' short form */
-#endif
-#ifndef ICW_FIR_OCC
-#define ICW_FIR_OCC 4                                /* KF2 workgroups per CU the register budget is sized for */
-#endif
-#ifndef ICW_FIR_CUT
-#define ICW_FIR_CUT 0                                /* diagnostic: 1 no graph, 2 no sums either (VALU by phase) */
-#endif
-#ifndef ICW_FIR_DIAG
-#define ICW_FIR_DIAG 0                               /* diagnostic, not exact: 1 no division slow path, 2 no render */
-#endif
-#ifndef ICW_FIR_STAMPS
-#define ICW_FIR_STAMPS 0                             /* diagnostic: KF2 phase stamps (tools/fir_phases.py) */
-#endif
-#ifndef ICW_CHAIN4
-#define ICW_CHAIN4 1                                 /* KF2: chain programs op by op over a lane's frames */
-#endif
-
-/* The staged inputs carry ICW_FIR_PAD pad doubles after every 8 (physical index i + PAD (i / 8)).  With
- * 2 a lane's window (8 outputs apart: 10 doubles = 20 dwords) starts 16-byte aligned at every lane, and
- * the sums read it two doubles at a time (ds_read_b128, conflict-free over each 16-lane group: 20 l
- * mod 64 covers the 64 banks once), half the LDS instructions of the 1-pad layout's ds_read_b64. */
-#ifndef ICW_FIR_PAD
-#define ICW_FIR_PAD 2
-#endif
-#if ICW_FIR_PAD != 1 && ICW_FIR_PAD != 2
-#error "ICW_FIR_PAD: icw_fir_block's window reads are written for 1 or 2 pad doubles per 8"
-#endif
-#ifndef ICW_SCALAR_UNIT
-#define ICW_SCALAR_UNIT 1                            /* A/B: unit gains / norm_mul tested on scalar flags */
-#endif
-#ifndef ICW_RENDER_SH0
-#define ICW_RENDER_SH0 1                             /* A/B: the render-only form specialised for norm_shift 0 */
-#endif
-__device__ __forceinline__ int icw_fir_phys(int i) { return i + ICW_FIR_PAD * (i >> 3); }
-
-
-/* inputs of NC channels from ch0 for the outputs [tt, tt + nout) of a launch block, at logical
- * index i <-> frame j = tt - M + i - sh (zero outside [-M, T)), channel k at xs + k * px; the
- * history after the block is written by the tile that owns each of its frames.  The stereo form
- * computes a frame's address, validity and fade once for both channels. */
-template <int FMT, bool AL, int NC>
-__device__ __forceinline__ void icw_fir_stage_t(const IcwFirArgs &f, int s, int ch0, double *xs, int px, int tt,
-                                                int nout, int sh, int tid, int nthr)
-{
-    const int T = f.T, M = f.M;
-    const unsigned char *src = f.in + (size_t)s * f.in_stride + (size_t)ch0 * f.csz;
-    const long long p0 = f.pos[s] + f.t0;
-    const long long ns = f.fade[s * 3 + 0], fi = f.fade[s * 3 + 1], fo = f.fade[s * 3 + 2];
-    const double *hin = f.hist_in + ((size_t)s * 2 + ch0) * M;
-    double *hout = f.hist_out + ((size_t)s * 2 + ch0) * M;
-    const bool mono = f.nch == 1;
-    const int nl = sh + M + nout + 24;               /* logical extent: pad, history, tile, margin */
-    const int nf = min(nout, T - tt);
-    /* uniform over the tile: no fade anywhere in the frames it stages (icw_fade returns "none" for
-     * fi <= ix <= ns - fo and for ix >= ns), and whether any staged frame precedes the block (the
-     * history).  The fade's two FP64 divisions and the history loads were computed for every input
-     * and made the staging ~half of the kernel's VALU instructions (r03_c2fir_sq.json). */
-    const long long ja = max(tt - M, 0), jb = (long long)tt + nf - 1;
-    const bool nofade = p0 + ja >= fi && (p0 + jb <= ns - fo || p0 + ja >= ns);
-    const bool need_hist = tt < M + sh;
-    /* 8 consecutive frames per thread and pass, their loads issued together (clamped in range,
-     * selected after): the staging is load-latency bound otherwise */
-    constexpr int V = 8;
-    /* An interior tile of a packed typed format (i16 / i32 / f32, the file frame exactly the computed
-     * channels): a thread's 8 frames are 8 * frame-size contiguous bytes, read by 16-byte loads from
-     * one address, unpacked from the registers (the same conversions as icw_unpack_f), and written to
-     * 8 consecutive LDS doubles per channel (logical 8t..8t+7 sit at physical 9t..9t+7) from one base.
-     * Only the threads at the ends of the staged range select zeros.  With M >= 32 every frame a
-     * thread loads lies in [0, T) (tt >= M + sh, and the last load ends 30 frames past the tile's
-     * outputs, tt + nout <= T - M).  The per-frame address, clamp and select of the general form were
-     * most of the staging's VALU instructions (c2fir: ~150 per wave). */
-    if constexpr (ICW_FIR_VEC && AL && (FMT == ICW_FMT_I16 || FMT == ICW_FMT_I32 || FMT == ICW_FMT_F32)) {
-        constexpr int CS = FMT == ICW_FMT_I16 ? 2 : 4;
-        constexpr int FB = NC * CS;                       /* bytes per frame */
-        constexpr int NW = V * FB / 4;                    /* 32-bit words per thread and pass */
-        const unsigned char *b0 = src + (size_t)(tt - M - sh) * f.fsz;
-        if (nofade && !need_hist && tt + nf <= T - M && M >= 32 && f.fsz == FB && !((uintptr_t)b0 & 15)) {
-            const int lim = sh + M + nf;                  /* logical [sh, lim) holds inputs, the rest zeros */
-            for (int i0 = tid * V; i0 < nl; i0 += nthr * V) {
-                const uint4 *p = (const uint4 *)(b0 + (size_t)i0 * FB);
-                uint32_t w[NW];
-#pragma unroll
-                for (int k = 0; k < NW / 4; ++k) {
-                    const uint4 q4 = p[k];
-                    w[4 * k] = q4.x; w[4 * k + 1] = q4.y; w[4 * k + 2] = q4.z; w[4 * k + 3] = q4.w;
-                }
-                double v[NC][V];
-#pragma unroll
-                for (int e = 0; e < V; ++e) {
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) {
-                        const int si = e * NC + k;            /* sample index in the thread's run */
-                        if constexpr (FMT == ICW_FMT_I16) {
-                            const uint32_t u = w[si >> 1];
-                            v[k][e] = (double)((si & 1) ? ((int)u >> 16) : (int)(short)(u & 0xffffu));
-                        } else if constexpr (FMT == ICW_FMT_I32) {
-                            v[k][e] = ((double)(int)w[si]) / 65536.0;
-                        } else {
-                            v[k][e] = 32768.0 * (double)__uint_as_float(w[si]);
-                        }
-                    }
-                }
-                double *d = xs + icw_fir_phys(i0);
-                if (i0 >= sh && i0 + V <= lim) {
-#pragma unroll
-                    for (int k = 0; k < NC; ++k)
-#pragma unroll
-                        for (int e = 0; e < V; ++e) d[k * px + e] = v[k][e];
-                } else {
-#pragma unroll
-                    for (int e = 0; e < V; ++e) {
-                        const int i = i0 + e;
-                        if (i < nl) {
-#pragma unroll
-                            for (int k = 0; k < NC; ++k) d[k * px + e] = (i >= sh && i < lim) ? v[k][e] : 0.0;
-                        }
-                    }
-                }
-            }
-            return;
-        }
-    }
-    if (ICW_FIR_INTERIOR && NC == 2 && nofade && !need_hist && tt + nf <= T - M) {
-        /* an interior tile (most of them): no fade, no history to read or write -- a frame is its
-         * input inside [tt - M, tt + nf) and zero outside (c2fir +3 %, c4fir +3 %; the mono form
-         * measured 1 % slower with it, so it keeps the general one) */
-        for (int i0 = tid * V; i0 < nl; i0 += nthr * V) {
-            double raw[NC][V];
-#pragma unroll
-            for (int e = 0; e < V; ++e) {
-                const int jr = min(tt - M + i0 + e - sh, T - 1);
-                const unsigned char *p = src + (size_t)jr * f.fsz;
-#pragma unroll
-                for (int k = 0; k < NC; ++k) raw[k][e] = icw_unpack_f<FMT, AL>(p + k * f.csz);
-            }
-#pragma unroll
-            for (int e = 0; e < V; ++e) {
-                const int i = i0 + e;
-                const bool in = i >= sh && i < sh + M + nf;
-                if (i < nl) {
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) xs[k * px + icw_fir_phys(i)] = in ? raw[k][e] : 0.0;
-                }
-            }
-        }
-        return;
-    }
-    for (int i0 = tid * V; i0 < nl; i0 += nthr * V) {
-        double raw[NC][V], his[NC][V];
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            const int j = tt - M + i0 + e - sh;
-            const int jr = min(max(j, 0), T - 1);
-            const unsigned char *p = src + (size_t)jr * f.fsz;
-#pragma unroll
-            for (int k = 0; k < NC; ++k) {
-                raw[k][e] = icw_unpack_f<FMT, AL>(p + k * f.csz);
-                his[k][e] = 0.0;
-            }
-        }
-        if (need_hist) {
-#pragma unroll
-            for (int e = 0; e < V; ++e) {
-                const int h = min(max(tt + i0 + e - sh, 0), M - 1);
-#pragma unroll
-                for (int k = 0; k < NC; ++k) his[k][e] = hin[k * M + h];
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            const int i = i0 + e;
-            const int j = tt - M + i - sh;
-            double v[NC];
-#pragma unroll
-            for (int k = 0; k < NC; ++k) v[k] = 0.0;
-            if (i >= sh && j < tt + nf) {
-                if (j < 0) {
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) v[k] = his[k][e];
-                } else {
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) v[k] = raw[k][e];
-                    if (!nofade) {
-                        const double fd = icw_fade(p0 + j, ns, fi, fo);
-                        if (fd >= 0.0) {
-#pragma unroll
-                            for (int k = 0; k < NC; ++k) v[k] *= fd;
-                        }
-                    }
-                }
-                if (j >= T - M && (j >= tt || tt == 0)) {
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) hout[k * M + j - (T - M)] = v[k];
-                    if (NC == 1 && mono) hout[M + j - (T - M)] = v[0];
-                }
-            }
-            if (i < nl) {
-#pragma unroll
-                for (int k = 0; k < NC; ++k) xs[k * px + icw_fir_phys(i)] = v[k];
-            }
-        }
-    }
-}
-
-/* the staging of NC channels, its format and alignment resolved once (uniform) per workgroup */
-template <int NC>
-__device__ __forceinline__ void icw_fir_stage(const IcwFirArgs &f, int s, int ch0, double *xs, int px, int tt,
-                                              int nout, int sh, int tid, int nthr)
-{
-    const uintptr_t al = (uintptr_t)(f.in + (size_t)s * f.in_stride) | (uintptr_t)f.fsz;
-    icw_fmt_dispatch(f.fmt, al, [&](auto fc, auto ac) {
-        icw_fir_stage_t<decltype(fc)::value, decltype(ac)::value != 0, NC>(f, s, ch0, xs, px, tt, nout, sh, tid,
-                                                                           nthr);
-    });
-}
-
-/* The taps through the constant address space: every lane of a wave reads the same tap, so they
- * come in by scalar loads into SGPRs (the FMA takes one SGPR operand) and leave the LDS pipe to the
- * inputs -- which bounds the sums: 52 -> 44 LDS reads per 8-tap block of a lane's 8 outputs. */
-typedef const __attribute__((address_space(4))) double icw_ctap;
-
-/* one NTAP-tap block (k0 = NTAP b) of a lane's 8 outputs: bl / br = physical index of the first input
- * of the left / right window (both at phase 2 of the pad pattern; NTAP 4 or 8 keeps it there) */
-#ifndef ICW_FIR_NTAP
-#define ICW_FIR_NTAP 8                               /* taps per register block of the sums */
-#endif
-template <int NTAP>
-__device__ __forceinline__ void icw_fir_block(const double *xs, icw_ctap *gs, int k0, int bl, int br,
-                                              double (&acc)[ICW_FIR_R])
-{
-    static_assert(NTAP == 4 || NTAP == 8, "a window step of whole pad groups");
-    constexpr int W = ICW_FIR_R + 2 * NTAP - 2;
-    double L[W], Rt[W], g[NTAP];
-    if constexpr (ICW_FIR_PAD == 2) {
-        /* elements e, e + 1 (e even) never straddle a pad: the window starts at logical phase 2 */
-#pragma unroll
-        for (int e = 0; e < W; e += 2) {
-            const double2 v = *(const double2 *)(xs + bl + e + 2 * ((e + 2) >> 3));
-            L[e] = v.x;
-            L[e + 1] = v.y;
-            asm volatile("" ::: "memory");
-        }
-#pragma unroll
-        for (int e = 0; e < W; e += 2) {
-            const double2 v = *(const double2 *)(xs + br + e + 2 * ((e + 2) >> 3));
-            Rt[e] = v.x;
-            Rt[e + 1] = v.y;
-            asm volatile("" ::: "memory");
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < W; ++e) {
-            L[e] = xs[bl + e + ((e + 2) >> 3)];
-            asm volatile("" ::: "memory");               /* no ds_read2 pairing: 2 x 2 cycles, not 8 */
-        }
-#pragma unroll
-        for (int e = 0; e < W; ++e) {
-            Rt[e] = xs[br + e + ((e + 2) >> 3)];
-            asm volatile("" ::: "memory");
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < NTAP; ++j) g[j] = gs[k0 + j];
-#pragma unroll
-    for (int j = 0; j < NTAP; ++j) {
-#pragma unroll
-        for (int r = 0; r < ICW_FIR_R; ++r)
-            acc[r] = __builtin_fma(g[j], L[r - 2 * j + 2 * NTAP - 2] - Rt[r + 2 * j], acc[r]);
-    }
-}
-
-/* Q of a lane's 8 outputs tt + 8 ll + r; a = (c - 1 + sh) / 8.  The taps in ascending order, in
- * register blocks of ICW_FIR_NTAP, then one by one */
-template <int NB = ICW_FIR_NTAP>
-__device__ __forceinline__ void icw_fir_sums(const double *xs, icw_ctap *gs, int nt, int ll, int a, int sh, int c,
-                                             double (&acc)[ICW_FIR_R])
-{
-#pragma unroll
-    for (int r = 0; r < ICW_FIR_R; ++r) acc[r] = 0.0;
-    const int nb = nt / NB;
-    constexpr int G = 8 + ICW_FIR_PAD;                  /* physical doubles per group of 8 */
-    constexpr int GS = G * NB / 4;                      /* physical step of a window per block */
-    int bl = G * (ll + a - NB / 4) + 2, br = G * (ll + a) + 2;
-#pragma unroll 1
-    for (int b = 0; b < nb; ++b) {
-        icw_fir_block<NB>(xs, gs, NB * b, bl, br, acc);
-        bl -= GS;
-        br += GS;
-    }
-    const int A = 8 * a;
-#pragma unroll 1
-    for (int k = nb * NB; k < nt; ++k) {
-        const double gk = gs[k];
-#pragma unroll
-        for (int r = 0; r < ICW_FIR_R; ++r) {
-            const int li = 8 * ll + A + r - 2 * k, ri = 8 * ll + A + 2 + r + 2 * k;
-            acc[r] = __builtin_fma(gk, xs[icw_fir_phys(li)] - xs[icw_fir_phys(ri)], acc[r]);
-        }
-    }
-    (void)sh; (void)c;
-}
+#include "icw_fir_dev.h"
 
 /* KF: the converter alone, one workgroup per channel and 2048-frame tile of a stream; I / Q rows
  * go out coalesced through LDS to the CWAVE rows K2 reads */

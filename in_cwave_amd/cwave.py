@@ -1,7 +1,9 @@
 """CWAVE file images (cwave.h): header layout HCWAVE_V2 (cwave.h:48-60), magic "cPLXwAVE",
 little-endian fields, data part right after the header.  The writer is what the reference's
 external CWAVE converter produces; n_CRC32 is the CRC-32 of the data part (gui_cwave.c:82-129).
-Used to make test and benchmark inputs; decoding is icw_process_* with ICW_FMT_CW_*."""
+Used to make test and benchmark inputs from I/Q data made elsewhere; decoding is icw_process_* with
+ICW_FMT_CW_*.  The product's own converter from WAV / PCM is lib.cwave_encode_files / Context.encode_cwave
+(icw_cwave_encode_files, icw_encode_cwave)."""
 import struct
 import zlib
 

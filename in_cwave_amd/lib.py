@@ -254,6 +254,36 @@ class Context:
                                              out_stride, n_frames, flags, None, hip_stream),
                "icw_process_streams")
 
+    def encode_cwave(self, inp, n_frames, cw_format=abi.FMT_CW_F64, first=0, count=None, out=None):
+        """icw_encode_cwave, host path: inp uint8 [count, >= n_frames*fsz] through the FIR Hilbert converter
+        (set_fir_hilbert) to packed CWAVE frames, uint8 [count, n_frames * frame bytes].  Advances the
+        converter's history and the reader position like a process call; nothing else."""
+        count = self.n_streams - first if count is None else count
+        inp = np.ascontiguousarray(inp)
+        assert inp.dtype == np.uint8 and inp.shape[0] == count and inp.shape[1] >= n_frames * self.fsz
+        fb = cwave_frame_bytes(cw_format, self.cfg.in_channels)
+        if out is None:
+            out = np.zeros((count, n_frames * fb), dtype=np.uint8)
+        assert out.dtype == np.uint8 and out.shape[0] == count and out.shape[1] >= n_frames * fb
+        in_stride = inp.strides[0] if count > 1 else inp.shape[1]
+        out_stride = out.strides[0] if count > 1 else out.shape[1]
+        _check(self._lib.icw_encode_cwave(self.h, first, count, _ptr(inp), in_stride, _ptr(out), out_stride,
+                                          n_frames, cw_format, 0, None), "icw_encode_cwave")
+        return out
+
+    def encode_cwave_device(self, d_in, in_stride, d_out, out_stride, n_frames, cw_format=abi.FMT_CW_F64,
+                            first=0, count=None, hip_stream=None):
+        """icw_encode_cwave with ICW_F_DEVICE_PTRS (torch tensors / int pointers), stream-ordered"""
+        count = self.n_streams - first if count is None else count
+        _check(self._lib.icw_encode_cwave(self.h, first, count, _ptr(d_in), in_stride, _ptr(d_out), out_stride,
+                                          n_frames, cw_format, abi.F_DEVICE_PTRS, hip_stream), "icw_encode_cwave")
+
+    def encode_clipped(self, s, reset=False):
+        """icw_encode_clipped: saturated / NaN int16 samples stream s has encoded since the last reset"""
+        v = C.c_uint64()
+        _check(self._lib.icw_encode_clipped(self.h, s, 1 if reset else 0, C.byref(v)), "icw_encode_clipped")
+        return v.value
+
     def synchronize(self):
         _check(self._lib.icw_synchronize(self.h), "icw_synchronize")
 
@@ -400,6 +430,26 @@ def transcode_files(cfg, nodes, in_paths, out_paths, fade_in_ms=0, fade_out_ms=0
     status = (C.c_int * max(1, n))()
     rc = load().icw_transcode_files(C.byref(cfg), arr, len(nodes), ins, outs, n, C.byref(o), C.byref(st), status)
     return rc, st, [status[i] for i in range(n)]
+
+
+def cwave_frame_bytes(cw_format, channels):
+    """icw_cwave_frame_bytes: bytes of one CWAVE frame for an input of `channels` channels (0: invalid)"""
+    return int(load().icw_cwave_frame_bytes(cw_format, channels))
+
+
+def cwave_encode_files(in_paths, out_paths, k_M, k_beta=8.0, cw_format=abi.FMT_CW_F64, align=0, block_frames=0,
+                       device=-1):
+    """icw_cwave_encode_files: WAV files to V2 CWAVE files through the FIR Hilbert converter; returns
+    (rc, stats, per-file status, per-file clipped int16 samples)"""
+    n = len(in_paths)
+    ins = (C.c_char_p * max(1, n))(*[str(p).encode() for p in in_paths])
+    outs = (C.c_char_p * max(1, n))(*[str(p).encode() for p in out_paths])
+    o = abi.CwaveEncOpts(k_M, align, k_beta, cw_format, block_frames, device, 0)
+    st = abi.BatchStats()
+    status = (C.c_int * max(1, n))()
+    clipped = (C.c_uint64 * max(1, n))()
+    rc = load().icw_cwave_encode_files(ins, outs, n, C.byref(o), C.byref(st), clipped, status)
+    return rc, st, [status[i] for i in range(n)], [int(clipped[i]) for i in range(n)]
 
 
 def transcode_files_devices(cfg, nodes, in_paths, out_paths, devices, fade_in_ms=0, fade_out_ms=0, sec_align=0,

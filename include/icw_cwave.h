@@ -66,6 +66,42 @@ uint32_t icw_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 int icw_cwave_check(const void *file, uint64_t file_size, unsigned flags, int device, uint32_t *crc,
                     int *crc_ok);
 
+/* ---- CWAVE encoder: real PCM -> the analytic-signal frames a CWAVE file holds ----
+ * The converter is the context's FIR Hilbert (icw_set_fir_hilbert, k_M > 0): the same kernel code
+ * stages and sums, so I[n] = x[n - k_M/2] and Q[n] are bit for bit what icw_process_* feeds the graph.
+ * Frame layout (cwave.h:74-81), per channel Re then Im, stereo Re(L) Im(L) Re(R) Im(R):
+ *   ICW_FMT_CW_F64 16 bytes, ICW_FMT_CW_I16 4, ICW_FMT_CW_I16_F32 6 (float unaligned), ICW_FMT_CW_F32 8.
+ * Mono input gives 1-channel frames; input of 2 or more channels gives 2-channel frames of the first two.
+ * Conversions (the project's definition; the reference ships no converter, so parity is unpinned, like
+ * the FIR converter itself): double = the bits; float = round to nearest even; int16 = round to nearest,
+ * ties to even, saturated to [-32768, 32767], NaN -> 0.
+ * Not covered: an IIR-Hilbert CWAVE (k_M 0), the direct-FFT converter (k_M -1), V1 headers. */
+
+/* bytes of one frame of cw_format for an input of `channels` channels; 0 if either is invalid */
+int icw_cwave_frame_bytes(uint32_t cw_format, uint32_t channels);
+
+/* Encode n_frames frames of streams [first, first + count): stream i's PCM (the context's input
+ * format) at in + i*in_stride, its CWAVE frames to out + i*out_stride.  Pointers, ICW_F_DEVICE_PTRS,
+ * hip_stream and the ordering are those of icw_process_streams (host pointers: the call returns with
+ * `out` filled; device pointers: stream-ordered); long calls run in launch blocks the same way.
+ * For these streams the call advances the FIR history and the reader position (fades included)
+ * exactly as a process call of n_frames would, so two calls equal one and icw_get_state /
+ * icw_set_state carry an encode to another context.  It leaves n_frame, the bus, the IIR Hilbert, the
+ * renders, the dither generators and the meters alone.
+ * Errors: ICW_EINVAL -- nothing ran, no state changed -- for a bad range or pointer, a host stride
+ * shorter than the frames, a flag other than ICW_F_DEVICE_PTRS, a cw_format outside ICW_FMT_CW_*, a
+ * context with CWAVE input (already analytic) or without icw_set_fir_hilbert(k_M > 0).  ICW_ENOMEM /
+ * ICW_EDEVICE: a buffer or a HIP call failed; the streams' state is then unspecified (reset or
+ * icw_set_state them). */
+int icw_encode_cwave(icw_ctx *ctx, int first, int count, const void *in, size_t in_stride_bytes,
+                     void *out, size_t out_stride_bytes, int n_frames, uint32_t cw_format,
+                     unsigned flags, void *hip_stream);
+
+/* Saturated or NaN int16 samples (Re and Im counted separately) stream s has encoded since the count
+ * was last reset; waits for the context's queued work.  reset != 0 clears it after the read.
+ * clipped may be NULL. */
+int icw_encode_clipped(icw_ctx *ctx, int s, int reset, uint64_t *clipped);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,36 @@ int icw_transcode_files(const icw_config *cfg, const icw_node *nodes, int n_node
                         const char *const *out_paths, int n, const icw_batch_opts *opts, icw_batch_stats *stats,
                         int *status);
 
+/* ---- convert: WAV files -> CWAVE files (the external converter cwave.h:56-58 names) ---- */
+typedef struct icw_cwave_enc_opts {
+    int32_t  k_M;                       /* FIR Hilbert order: even, 2 .. ICW_FIR_MAX_ORDER */
+    int32_t  align;                     /* 0: causal (what the in-context converter feeds the graph: file frame n
+                                           holds I = x[n - k_M/2]); 1: delay-compensated (file frame n is centred
+                                           on input frame n) */
+    double   k_beta;                    /* Kaiser window parameter */
+    uint32_t cw_format;                 /* ICW_FMT_CW_* of the output */
+    int32_t  block_frames;              /* frames per stream per GPU block (0: 65536) */
+    int32_t  device;                    /* HIP device, -1: current */
+    int32_t  reserved_;
+} icw_cwave_enc_opts;
+
+/* Encode n WAV files: in_paths[i] -> out_paths[i], a V2 CWAVE file (magic, hsize 48, version 2, format,
+ * channels, n_samples = the input's frames, rate, k_M, k_beta, n_CRC32) of icw_encode_cwave's frames
+ * (icw_cwave.h: layout and conversions).  Files are grouped by (sample rate, format, channels), one
+ * context per group; every file is one fresh stream with no fades and no tail, staged like
+ * icw_transcode_files.  n_CRC32 is computed on the GPU over the packed frames while they are in HBM,
+ * chained block by block (icw_crc32_batch); the host makes no CRC pass.
+ * align = 1 is the causal encode of the input followed by k_M/2 zero frames, with the first k_M/2
+ * output frames dropped (they count neither in the CRC nor in `clipped`).
+ * status (nullable, n entries) gets ICW_OK or the file's error: ICW_EINVAL for a CWAVE input (already
+ * analytic), a WAV icw_wav_parse_file refuses, fewer than 2 frames (the reader would refuse the result),
+ * 2^32 frames or more, or an I/O error; the rest of the batch still completes.  clipped (nullable, n
+ * entries) gets the file's saturated / NaN int16 samples.  Returns ICW_EINVAL for bad options (nothing
+ * runs), else ICW_OK if every file was encoded, else one of the files' errors.
+ * Not covered: an IIR-Hilbert CWAVE (k_M 0), the direct-FFT converter (k_M -1), V1 headers. */
+int icw_cwave_encode_files(const char *const *in_paths, const char *const *out_paths, int n,
+                           const icw_cwave_enc_opts *opts, icw_batch_stats *stats, uint64_t *clipped, int *status);
+
 #ifdef __cplusplus
 }
 #endif
