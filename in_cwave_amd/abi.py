@@ -127,6 +127,13 @@ class CwaveEncOpts(C.Structure):
                 ("block_frames", C.c_int32), ("device", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class CwaveEncIirOpts(C.Structure):
+    """icw_cwave_enc_iir_opts (include/icw_reader.h)"""
+    _fields_ = [("hilbert_type", C.c_uint32), ("iir_kahan", C.c_int32), ("iir_subnorm_reject", C.c_int32),
+                ("cw_format", C.c_uint32), ("block_frames", C.c_int32), ("device", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
 # every function declared in include/icw.h, icw_amod.h, icw_cwave.h: name -> (restype, argtypes)
 _vp, _sz, _i, _u = C.c_void_p, C.c_size_t, C.c_int, C.c_uint
 SIGNATURES = {
@@ -189,9 +196,12 @@ SIGNATURES = {
     "icw_cwave_check": (_i, [_vp, C.c_uint64, _u, _i, C.POINTER(C.c_uint32), C.POINTER(_i)]),
     "icw_cwave_frame_bytes": (_i, [C.c_uint32, C.c_uint32]),
     "icw_encode_cwave": (_i, [_vp, _i, _i, _vp, _sz, _vp, _sz, _i, C.c_uint32, _u, _vp]),
+    "icw_encode_cwave_iir": (_i, [_vp, _i, _i, _vp, _sz, _vp, _sz, _i, C.c_uint32, _u, _vp]),
     "icw_encode_clipped": (_i, [_vp, _i, _i, C.POINTER(C.c_uint64)]),
     "icw_cwave_encode_files": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, C.POINTER(CwaveEncOpts),
                                     C.POINTER(BatchStats), C.POINTER(C.c_uint64), C.POINTER(_i)]),
+    "icw_cwave_encode_files_iir": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, C.POINTER(CwaveEncIirOpts),
+                                        C.POINTER(BatchStats), C.POINTER(C.c_uint64), C.POINTER(_i)]),
     "icw_config_load": (_i, [C.c_char_p, _sz, C.POINTER(FileConfig), C.POINTER(_i)]),
     "icw_node_dsp_parse": (_i, [C.c_char_p, C.POINTER(Node), C.c_char_p, _sz]),
     "icw_node_dsp_format": (_i, [C.POINTER(Node), C.c_char_p, C.c_char_p, _sz]),

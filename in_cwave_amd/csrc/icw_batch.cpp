@@ -305,8 +305,20 @@ int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::v
     return rc;
 }
 
+/* what a group needs of either encoder's options: icw_cwave_enc_opts (the FIR converter), or
+ * icw_cwave_enc_iir_opts (iir: the quadrature IIR; k_M 0, k_beta 0.0, no aligned mode) */
+struct EncSpec {
+    int32_t k_M = 0, align = 0;
+    double k_beta = 0.0;
+    uint32_t cw_format = 0;
+    int32_t block_frames = 0, device = -1;
+    bool iir = false;
+    uint32_t hilbert_type = 1;
+    int32_t iir_kahan = 1, iir_subnorm_reject = 1;
+};
+
 /* HCWAVE_V2 (cwave.h:48-60), little-endian */
-void cwave_header(unsigned char *h, const icw_cwave_enc_opts &o, uint32_t channels, uint32_t frames, uint32_t rate, uint32_t crc)
+void cwave_header(unsigned char *h, const EncSpec &o, uint32_t channels, uint32_t frames, uint32_t rate, uint32_t crc)
 {
     auto p32 = [](unsigned char *q, uint32_t v) { q[0] = v; q[1] = v >> 8; q[2] = v >> 16; q[3] = v >> 24; };
     memcpy(h, "cPLXwAVE", 8);
@@ -327,7 +339,7 @@ void cwave_header(unsigned char *h, const icw_cwave_enc_opts &o, uint32_t channe
 /* One group of WAV files sharing (rate, format, channels) through the CWAVE encoder: one context, one
  * fresh stream per file, no fades, no tail.  The CRC of every file's data is chained block by block
  * over the packed frames while they are in HBM (icw_crc32_batch, device pointers). */
-int run_enc_group(std::vector<Job *> &jobs, const icw_cwave_enc_opts &o, icw_batch_stats &st, uint64_t *clipped, int *status)
+int run_enc_group(std::vector<Job *> &jobs, const EncSpec &o, icw_batch_stats &st, uint64_t *clipped, int *status)
 {
     const int S = (int)jobs.size();
     const icw_wav_info &wi = jobs[0]->info;
@@ -336,8 +348,10 @@ int run_enc_group(std::vector<Job *> &jobs, const icw_cwave_enc_opts &o, icw_bat
     cfg.sample_rate = wi.sample_rate;
     cfg.in_format = wi.fmt;
     cfg.in_channels = wi.channels;
-    cfg.hilbert_type = 1;
-    cfg.iir_kahan = cfg.iir_subnorm_reject = cfg.frmod_scaled = 1;
+    cfg.hilbert_type = o.hilbert_type;
+    cfg.iir_kahan = o.iir_kahan;
+    cfg.iir_subnorm_reject = o.iir_subnorm_reject;
+    cfg.frmod_scaled = 1;
     cfg.seed_left = ICW_SEED_LEFT;
     cfg.seed_right = ICW_SEED_RIGHT;
     cfg.render.dth_bits = 1.0;
@@ -347,7 +361,8 @@ int run_enc_group(std::vector<Job *> &jobs, const icw_cwave_enc_opts &o, icw_bat
     int rc = icw_create(&cfg, nullptr, 0, S, o.device, &ctx, nullptr);
     if (rc != ICW_OK) return rc;
     std::unique_ptr<icw_ctx, int (*)(icw_ctx *)> guard(ctx, icw_destroy);
-    if ((rc = icw_set_fir_hilbert(ctx, o.k_M, o.k_beta)) != ICW_OK) return rc;
+    if (!o.iir && (rc = icw_set_fir_hilbert(ctx, o.k_M, o.k_beta)) != ICW_OK) return rc;
+    const auto encode = o.iir ? icw_encode_cwave_iir : icw_encode_cwave;
     const size_t fsz = wi.frame_bytes;
     const size_t FB = (size_t)icw_cwave_frame_bytes(o.cw_format, wi.channels);
     const int skip = o.align ? o.k_M / 2 : 0;            /* aligned: the first k_M/2 output frames are dropped */
@@ -434,8 +449,7 @@ int run_enc_group(std::vector<Job *> &jobs, const icw_cwave_enc_opts &o, icw_bat
         read_frames(hin[0], skip);
         if (hipMemcpyAsync(din[0], hin[0], in_b, hipMemcpyHostToDevice, ks) != hipSuccess) rc = ICW_EDEVICE;
         if (rc == ICW_OK)
-            rc = icw_encode_cwave(ctx, 0, S, din[0], (size_t)B * fsz, dout[0], (size_t)B * FB, skip, o.cw_format,
-                                  ICW_F_DEVICE_PTRS, ks);
+            rc = encode(ctx, 0, S, din[0], (size_t)B * fsz, dout[0], (size_t)B * FB, skip, o.cw_format, ICW_F_DEVICE_PTRS, ks);
         for (int s = 0; s < S && rc == ICW_OK; ++s) rc = icw_encode_clipped(ctx, s, 1, nullptr);
     }
     const int nb = (int)((T + B - 1) / B);
@@ -449,8 +463,7 @@ int run_enc_group(std::vector<Job *> &jobs, const icw_cwave_enc_opts &o, icw_bat
                              hipEventRecord(h2d[p], cs) != hipSuccess || hipStreamWaitEvent(ks, h2d[p], 0) != hipSuccess))
             rc = ICW_EDEVICE;
         if (rc == ICW_OK)
-            rc = icw_encode_cwave(ctx, 0, S, din[p], (size_t)B * fsz, dout[p], (size_t)B * FB, B, o.cw_format,
-                                  ICW_F_DEVICE_PTRS, ks);
+            rc = encode(ctx, 0, S, din[p], (size_t)B * fsz, dout[p], (size_t)B * FB, B, o.cw_format, ICW_F_DEVICE_PTRS, ks);
         if (rc == ICW_OK && (hipEventRecord(comp[p], ks) != hipSuccess || hipStreamWaitEvent(cs, comp[p], 0) != hipSuccess ||
                              hipMemcpyAsync(hout[p], dout[p], out_b, hipMemcpyDeviceToHost, cs) != hipSuccess ||
                              hipEventRecord(d2h[p], cs) != hipSuccess))
@@ -492,18 +505,10 @@ int run_enc_group(std::vector<Job *> &jobs, const icw_cwave_enc_opts &o, icw_bat
     return rc;
 }
 
-}  // namespace
-
-extern "C" {
-
-int icw_cwave_encode_files(const char *const *in_paths, const char *const *out_paths, int n, const icw_cwave_enc_opts *opts,
-                           icw_batch_stats *stats, uint64_t *clipped, int *status)
+/* icw_cwave_encode_files / icw_cwave_encode_files_iir after their option checks */
+int encode_files(const char *const *in_paths, const char *const *out_paths, int n, const EncSpec &o,
+                        icw_batch_stats *stats, uint64_t *clipped, int *status)
 {
-    if (!opts || n < 0 || (n > 0 && (!in_paths || !out_paths))) return ICW_EINVAL;
-    const icw_cwave_enc_opts &o = *opts;
-    if (o.k_M < 2 || o.k_M > ICW_FIR_MAX_ORDER || (o.k_M & 1) || !(o.k_beta >= 0.0 && o.k_beta < 1e3) ||
-        o.cw_format < ICW_FMT_CW_F64 || o.cw_format > ICW_FMT_CW_F32 || (o.align != 0 && o.align != 1) || o.block_frames < 0)
-        return ICW_EINVAL;
     const double t0 = now_s();
     icw_batch_stats st;
     memset(&st, 0, sizeof(st));
@@ -548,6 +553,47 @@ int icw_cwave_encode_files(const char *const *in_paths, const char *const *out_p
     st.wall_s = now_s() - t0;
     if (stats) *stats = st;
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int icw_cwave_encode_files(const char *const *in_paths, const char *const *out_paths, int n, const icw_cwave_enc_opts *opts,
+                           icw_batch_stats *stats, uint64_t *clipped, int *status)
+{
+    if (!opts || n < 0 || (n > 0 && (!in_paths || !out_paths))) return ICW_EINVAL;
+    const icw_cwave_enc_opts &o = *opts;
+    if (o.k_M < 2 || o.k_M > ICW_FIR_MAX_ORDER || (o.k_M & 1) || !(o.k_beta >= 0.0 && o.k_beta < 1e3) ||
+        o.cw_format < ICW_FMT_CW_F64 || o.cw_format > ICW_FMT_CW_F32 || (o.align != 0 && o.align != 1) || o.block_frames < 0)
+        return ICW_EINVAL;
+    EncSpec e;
+    e.k_M = o.k_M;
+    e.align = o.align;
+    e.k_beta = o.k_beta;
+    e.cw_format = o.cw_format;
+    e.block_frames = o.block_frames;
+    e.device = o.device;
+    return encode_files(in_paths, out_paths, n, e, stats, clipped, status);
+}
+
+int icw_cwave_encode_files_iir(const char *const *in_paths, const char *const *out_paths, int n,
+                               const icw_cwave_enc_iir_opts *opts, icw_batch_stats *stats, uint64_t *clipped, int *status)
+{
+    if (!opts || n < 0 || (n > 0 && (!in_paths || !out_paths))) return ICW_EINVAL;
+    const icw_cwave_enc_iir_opts &o = *opts;
+    if (o.hilbert_type > 5 || (o.iir_kahan != 0 && o.iir_kahan != 1) || (o.iir_subnorm_reject != 0 && o.iir_subnorm_reject != 1) ||
+        o.cw_format < ICW_FMT_CW_F64 || o.cw_format > ICW_FMT_CW_F32 || o.block_frames < 0)
+        return ICW_EINVAL;
+    EncSpec e;
+    e.iir = true;
+    e.hilbert_type = o.hilbert_type;
+    e.iir_kahan = o.iir_kahan;
+    e.iir_subnorm_reject = o.iir_subnorm_reject;
+    e.cw_format = o.cw_format;
+    e.block_frames = o.block_frames;
+    e.device = o.device;
+    return encode_files(in_paths, out_paths, n, e, stats, clipped, status);
 }
 
 int icw_wav_parse_file(const char *path, icw_wav_info *info)

@@ -73,6 +73,16 @@ struct IcwEncArgs {
     unsigned long long *clipped;   /* [n_streams] saturated / NaN int16 samples, accumulated */
 };
 
+/* Arguments of the IIR encoder's packer (KIP): a launch block's `in` rows, as K2 writes them with
+ * iq_out set, to the packed file frames */
+struct IcwPackArgs {
+    const double *iq;              /* [n_streams][T][4] (lI, lQ, rI, rQ) per frame of the block */
+    int32_t n_streams, T;
+    unsigned char *out;            /* stream s, the block's first frame, at out + s*out_stride */
+    size_t out_stride;
+    unsigned long long *clipped;   /* [n_streams] saturated / NaN int16 samples, accumulated */
+};
+
 /* Arguments of the call-end bookkeeping kernel: one thread per stream. During a call every
  * kernel reads the call-start position / phases / frame counter and adds its block offset; this
  * kernel advances them once, after the last block. */

@@ -1,6 +1,7 @@
 /*
- * icw_encode.hip -- gfx950 (CDNA4) kernel of the CWAVE encoder: the FIR Hilbert converter's analytic
- * signal as the packed frames of a CWAVE file (include/icw_cwave.h: icw_encode_cwave).
+ * icw_encode.hip -- gfx950 (CDNA4) kernels of the CWAVE encoders: the FIR Hilbert converter's analytic
+ * signal as the packed frames of a CWAVE file (include/icw_cwave.h: icw_encode_cwave, KFE), and the
+ * packer that does the same to the quadrature IIR's (icw_encode_cwave_iir, KIP).
  *
  * Built like icw_kernels.hip (`-ffp-contract=off`, no fast-math).  The staging and the sums are the
  * converter's own (icw_fir_dev.h), so I and Q are bit for bit what KF / KF2 feed the graph.
@@ -157,6 +158,116 @@ __global__ __launch_bounds__(64) void icw_pos_advance(long long *pos, int n_stre
     if (s < n_streams) pos[s] += n;
 }
 
+/* KIP: the packer of the IIR encoder (icw_encode_cwave_iir).  The quadrature IIR's analytic signal of a
+ * launch block is already in HBM, as the `in` rows K2 writes with iq_out set ([n_streams][T][4]: lI, lQ,
+ * rI, rQ -- the bus-form hand-off); this kernel only converts and interleaves them into KFE's frame
+ * layout with KFE's conversions (icw_enc_i16, icw_cw_bytes).  Mono input: the left converter's pair.
+ *
+ * One workgroup per tile of 1 024 frames of a stream; a lane converts frames tid, tid + 256, .. (its row
+ * reads are two 16-byte loads, consecutive lanes consecutive rows) and writes each frame's FB bytes at
+ * byte t * FB of an unpadded LDS image of the tile.  The image leaves as KFE's tiles do: 16-byte units
+ * where the tile's first byte is 16-byte aligned, else dwords funnelled from two LDS words with the at
+ * most two partial dwords at its ends as bytes.  The kernel runs once per block beside nothing it could
+ * slow down (the recurrence bounds the call), so its LDS stores are left to conflict. */
+#define ICW_PACK_R 4                                     /* frames per lane */
+template <int CWF, int NC>
+__global__ __launch_bounds__(256) void icw_iq_pack(IcwPackArgs a)
+{
+    constexpr int CB = icw_cw_bytes<CWF>::value, FB = NC * CB;    /* bytes per channel, per frame */
+    constexpr int TF = 256 * ICW_PACK_R;
+    /* 16 spare bytes: the funnel's second word may lie past the tile's last byte (its bits are shifted out) */
+    __shared__ __attribute__((aligned(16))) unsigned char img[TF * FB + 16];
+    __shared__ unsigned nclip;
+    const int s = blockIdx.y, tid = threadIdx.x;
+    const int tt = blockIdx.x * TF;
+    const int nf = min(TF, a.T - tt);
+    if (tid == 0) nclip = 0u;
+    const double *rows = a.iq + ((size_t)s * a.T + tt) * 4;
+    unsigned clip = 0u;
+#pragma unroll
+    for (int r = 0; r < ICW_PACK_R; ++r) {
+        const int t = r * 256 + tid;
+        if (t < nf) {
+            double v[2 * NC];
+            const double2 l = *(const double2 *)(rows + (size_t)t * 4);
+            v[0] = l.x;
+            v[1] = l.y;
+            if constexpr (NC == 2) {
+                const double2 rr = *(const double2 *)(rows + (size_t)t * 4 + 2);
+                v[2] = rr.x;
+                v[3] = rr.y;
+            }
+            unsigned char *f = img + t * FB;             /* FB is even; a multiple of 4 but for the 6-byte frame */
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+                if constexpr (CWF == 0) {
+                    *(double2 *)(f + 16 * k) = make_double2(v[2 * k], v[2 * k + 1]);
+                } else if constexpr (CWF == 1) {
+                    const uint32_t re = icw_enc_i16(v[2 * k], true, clip), im = icw_enc_i16(v[2 * k + 1], true, clip);
+                    *(uint32_t *)(f + 4 * k) = re | (im << 16);
+                } else if constexpr (CWF == 2) {
+                    const uint32_t re = icw_enc_i16(v[2 * k], true, clip), im = __float_as_uint((float)v[2 * k + 1]);
+                    unsigned short *h = (unsigned short *)(f + 6 * k);
+                    h[0] = (unsigned short)re;
+                    h[1] = (unsigned short)im;
+                    h[2] = (unsigned short)(im >> 16);
+                } else {
+                    *(uint2 *)(f + 8 * k) = make_uint2(__float_as_uint((float)v[2 * k]), __float_as_uint((float)v[2 * k + 1]));
+                }
+            }
+        }
+    }
+    __syncthreads();                                     /* the image is whole; nclip is zero */
+    if (CWF == 1 || CWF == 2) {
+        if (clip) atomicAdd(&nclip, clip);
+    }
+    unsigned char *dst = a.out + (size_t)s * a.out_stride + (size_t)tt * FB;
+    const int nbytes = nf * FB;
+    const uint32_t *ow = (const uint32_t *)img;
+    if (!((uintptr_t)dst & 15)) {
+        const int nu = nbytes >> 4;
+        uint4 *d4 = (uint4 *)dst;
+        const uint4 *ob = (const uint4 *)img;
+        for (int j = tid; j < nu; j += 256) d4[j] = ob[j];
+        const int rest = nbytes - 16 * nu;               /* < 16, even: the last frames of a short tile */
+        if (tid < rest / 2) {
+            const int j = 16 * nu + 2 * tid;
+            *(unsigned short *)(dst + j) = *(const unsigned short *)(img + j);
+        }
+    } else {
+        const int b = (int)((uintptr_t)dst & 3);
+        unsigned char *d0 = dst - b;
+        const int nd = (b + nbytes + 3) >> 2;
+        for (int k = tid; k < nd; k += 256) {
+            const int o = 4 * k - b;                     /* the dword's first byte in the tile */
+            if (o >= 0 && o + 4 <= nbytes) {
+                uint32_t v = ow[k];
+                if (b) v = (ow[k - 1] >> (8 * (4 - b))) | (v << (8 * b));
+                *(uint32_t *)(d0 + 4 * k) = v;
+            } else {
+                for (int i = 0; i < 4; ++i)
+                    if (o + i >= 0 && o + i < nbytes) d0[4 * k + i] = img[o + i];
+            }
+        }
+    }
+    if (CWF == 1 || CWF == 2) {
+        __syncthreads();
+        if (tid == 0 && nclip) atomicAdd(a.clipped + s, (unsigned long long)nclip);
+    }
+}
+
+/* the reader position and the Hilbert phases of the streams an IIR encode call covered: what icw_advance
+ * does to them, without its frame counter */
+__global__ __launch_bounds__(64) void icw_enc_advance(long long *pos, uint32_t *hq_phase, int n_streams, long long n)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s < n_streams) {
+        pos[s] += n;
+        hq_phase[s * 2 + 0] = (hq_phase[s * 2 + 0] + (unsigned)n) & 3u;
+        hq_phase[s * 2 + 1] = (hq_phase[s * 2 + 1] + (unsigned)n) & 3u;
+    }
+}
+
 /* ---------------------------------------------------------------- launch wrappers ------- */
 /* LDS doubles of one staged channel (the px of the kernels) */
 static size_t enc_px(int M)
@@ -195,6 +306,34 @@ extern "C" hipError_t icw_launch_fir_encode(const IcwEncArgs *e, int cwf, hipStr
     case 3: return st2 ? launch_fir_encode_t<3, 2>(e, st) : launch_fir_encode_t<3, 1>(e, st);
     }
     return hipErrorInvalidValue;
+}
+
+template <int CWF, int NC>
+static hipError_t launch_iq_pack_t(const IcwPackArgs *a, hipStream_t st)
+{
+    constexpr int TF = 256 * ICW_PACK_R;
+    hipLaunchKernelGGL((icw_iq_pack<CWF, NC>), dim3((a->T + TF - 1) / TF, a->n_streams), dim3(256), 0, st, *a);
+    return hipGetLastError();
+}
+
+/* KIP of one launch block; cwf = cw_format - ICW_FMT_CW_F64, nc = channels of the file's frames (1 or 2) */
+extern "C" hipError_t icw_launch_iq_pack(const IcwPackArgs *a, int cwf, int nc, hipStream_t st)
+{
+    if (a->T <= 0 || a->n_streams <= 0 || !a->iq || !a->out || !a->clipped || nc < 1 || nc > 2) return hipErrorInvalidValue;
+    const bool st2 = nc > 1;
+    switch (cwf) {
+    case 0: return st2 ? launch_iq_pack_t<0, 2>(a, st) : launch_iq_pack_t<0, 1>(a, st);
+    case 1: return st2 ? launch_iq_pack_t<1, 2>(a, st) : launch_iq_pack_t<1, 1>(a, st);
+    case 2: return st2 ? launch_iq_pack_t<2, 2>(a, st) : launch_iq_pack_t<2, 1>(a, st);
+    case 3: return st2 ? launch_iq_pack_t<3, 2>(a, st) : launch_iq_pack_t<3, 1>(a, st);
+    }
+    return hipErrorInvalidValue;
+}
+
+extern "C" hipError_t icw_launch_enc_advance(long long *pos, uint32_t *hq_phase, int n_streams, long long n, hipStream_t st)
+{
+    hipLaunchKernelGGL(icw_enc_advance, dim3((n_streams + 63) / 64), dim3(64), 0, st, pos, hq_phase, n_streams, n);
+    return hipGetLastError();
 }
 
 extern "C" hipError_t icw_launch_pos_advance(long long *pos, int n_streams, long long n, hipStream_t st)

@@ -43,6 +43,8 @@ extern "C" hipError_t icw_launch_fir_graph(const IcwFirArgs *f, const IcwK2Args 
 extern "C" size_t icw_fir_graph_lds(int M, int nt, int nch, int n_regs);
 extern "C" hipError_t icw_launch_fir_encode(const IcwEncArgs *e, int cwf, hipStream_t st);
 extern "C" hipError_t icw_launch_pos_advance(long long *pos, int n_streams, long long n, hipStream_t st);
+extern "C" hipError_t icw_launch_iq_pack(const IcwPackArgs *a, int cwf, int nc, hipStream_t st);
+extern "C" hipError_t icw_launch_enc_advance(long long *pos, uint32_t *hq_phase, int n_streams, long long n, hipStream_t st);
 
 #define ICW_PI_H (3.1415926535897932384626433832795029)
 
@@ -2261,6 +2263,181 @@ int icw_encode_cwave(icw_ctx *c, int first, int count, const void *in, size_t in
     if (!dev && (hipMemcpy2DAsync(out, out_stride, d_out, dos, ob, S, hipMemcpyDeviceToHost, st) != hipSuccess ||
                  hipStreamSynchronize(st) != hipSuccess))
         return ICW_EDEVICE;
+    return hipGetLastError() == hipSuccess ? ICW_OK : ICW_EDEVICE;
+}
+
+/* The quadrature IIR converter's analytic signal as packed CWAVE frames.  Per launch block the kernels of
+ * a process call up to the graph -- K0, the K1 the context would pick, K2 with iq_out set (it stops at
+ * the `in` rows: no graph, no render, no meters) -- then the packer KIP.  The recurrence bounds the call
+ * and nothing of a block can start before the block's K1 has ended, so the four run in sequence on the
+ * caller's stream with one scratch set; the call shares icw_process_streams' converter state (rings,
+ * phases, de-subnorm counters, lr_equal) and the reader position, and nothing else of the context. */
+int icw_encode_cwave_iir(icw_ctx *c, int first, int count, const void *in, size_t in_stride, void *out, size_t out_stride,
+                         int n_frames, uint32_t cw_format, unsigned flags, void *hip_stream)
+{
+    if (!c || first < 0 || count <= 0 || first + count > c->n_streams || n_frames < 0 || !in || !out ||
+        (flags & ~ICW_F_DEVICE_PTRS))
+        return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const icw_config &cfg = c->cfg;
+    const int FB = icw_cwave_frame_bytes(cw_format, cfg.in_channels);
+    if (cfg.in_format >= ICW_FMT_CW_F64 || c->fir_M > 0 || FB == 0) return ICW_EINVAL;
+    const unsigned csz = fmt_size(cfg.in_format), nch = cfg.in_channels, fsz = csz * nch;
+    const bool dev = flags & ICW_F_DEVICE_PTRS;
+    const size_t S = (size_t)count, ib = (size_t)n_frames * fsz, ob = (size_t)n_frames * FB;
+    if (!dev && (in_stride < ib || out_stride < ob)) return ICW_EINVAL;
+    if (cfg.fp_check) return ICW_EUNSUPPORTED;             /* FC() arithmetic changes the values */
+    if (n_frames == 0) return ICW_OK;
+    if (set_dev(c)) return ICW_EDEVICE;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    /* the K1 of a process call over these streams (icw_process_streams) */
+    bool dedup = nch == 1 && c->tn.dedup_ok && (c->tn.k1_mode <= 0 || c->tn.k1_mode == 3);
+    for (int i = 0; dedup && i < count; ++i) dedup = c->lr_known[first + i] != 0;
+    const int row_waves = (int)(((dedup ? count : 2L * count) + 3) / 4) * 2;
+    const bool row_ok = cfg.iir_kahan && cfg.iir_subnorm_reject;
+    int k1_mode = c->tn.k1_mode;
+    if (k1_mode < 0) k1_mode = (row_ok && row_waves <= (c->n_cu / 2) * c->tn.k1_wpc) ? 3 : 0;
+    if (k1_mode == 3 && !row_ok) k1_mode = 0;
+    /* launch blocks: uniform (no pipeline to fill or drain), as long as the block scratch allows */
+    const int Tb = std::min(n_frames, c->tn.block_env ? c->tn.max_block : kMaxBlockFrames);
+    const std::vector<std::pair<int, int>> blocks = plan_blocks(n_frames, Tb, 0, 0.0, c->tn.taper_min);
+    const int n_blocks = (int)blocks.size();
+    const int N = c->nord;
+    const size_t w_pitch = (size_t)Tb + N + 1;
+    const size_t x_pitch = ((size_t)Tb + ICW_MAX_IIR_ORDER + 2) & ~(size_t)1;   /* look-ahead pad */
+    if (!c->enc_clipped) {
+        const int rc = dalloc(&c->enc_clipped, (size_t)c->n_streams);
+        if (rc != ICW_OK) {
+            if (c->enc_clipped) (void)hipFree(c->enc_clipped);
+            c->enc_clipped = nullptr;
+            return rc;
+        }
+    }
+    if (grow((void **)&c->w[0], &c->w_bytes[0], S * 4 * w_pitch * sizeof(double)) ||
+        grow((void **)&c->xd[0], &c->xd_bytes[0], S * 4 * x_pitch * sizeof(double)) ||
+        grow((void **)&c->iq[0], &c->iq_bytes[0], S * (size_t)Tb * 4 * sizeof(double)))
+        return ICW_ENOMEM;
+    const unsigned char *d_in = (const unsigned char *)in;
+    unsigned char *d_out = (unsigned char *)out;
+    size_t dis = in_stride, dos = out_stride;
+    if (!dev) {
+        dis = ib;
+        dos = (ob + 15) & ~(size_t)15;                     /* every stream's frames 16-byte aligned */
+        if (grow((void **)&c->d_in, &c->d_in_bytes, dis * S) || grow((void **)&c->d_out, &c->d_out_bytes, dos * S + 16))
+            return ICW_ENOMEM;
+        d_in = c->d_in;
+        d_out = c->d_out;
+    }
+    ++c->calls;
+    c->last_k1 = k1_mode;
+    /* a NULL handle with device pointers: the legacy default stream, as in icw_process_streams */
+    const bool legacy = !hip_stream && dev;
+    if (legacy && (hipEventRecord(c->join, nullptr) != hipSuccess || hipStreamWaitEvent(st, c->join, 0) != hipSuccess))
+        return ICW_EDEVICE;
+    if (!dev && hipMemcpy2DAsync(c->d_in, dis, in, in_stride, ib, S, hipMemcpyHostToDevice, st) != hipSuccess)
+        return ICW_EDEVICE;
+    DevState &ds = c->st;
+    const size_t f0 = (size_t)first;
+    for (int b = 0; b < n_blocks; ++b) {
+        const int t0 = blocks[b].first, T = blocks[b].second;
+        IcwK0Args a0;
+        memset(&a0, 0, sizeof(a0));
+        a0.in = d_in + (size_t)t0 * fsz;
+        a0.in_stride = dis;
+        a0.fmt = cfg.in_format;
+        a0.csz = csz;
+        a0.fsz = fsz;
+        a0.nch = nch;
+        a0.n_streams = count;
+        a0.T = T;
+        a0.t0 = t0;
+        a0.pos = ds.pos + f0;
+        a0.fade = ds.fade + f0 * 3;
+        a0.hq_phase = ds.hq_phase + f0 * 2;
+        a0.xd = c->xd[0];
+        a0.x_pitch = x_pitch;
+        a0.dedup = dedup ? 1 : 0;
+        if (icw_launch_unpack(&a0, st) != hipSuccess) return ICW_EDEVICE;
+
+        IcwK1Args a1;
+        memset(&a1, 0, sizeof(a1));
+        a1.xd = c->xd[0];
+        a1.x_pitch = x_pitch;
+        a1.nch = nch;
+        a1.n_streams = count;
+        a1.n_chains = count * 4;
+        a1.T = T;
+        a1.hist = ds.hist + f0 * 4 * ICW_HIST_PITCH;
+        a1.sncnt = ds.sncnt + f0 * 4;
+        a1.err = ds.err;
+        a1.w = c->w[0];
+        a1.w_pitch = w_pitch;
+        a1.lr_equal = ds.lr_equal + f0 * 2;
+        a1.hq_phase = ds.hq_phase + f0 * 2;
+        a1.t0 = t0;
+        a1.info_dup = c->info_dup[0];
+        memcpy(a1.pc, c->pc, sizeof(a1.pc));
+        a1.wg_waves = (c->tn.k1_wg_env || k1_mode != 3) ? c->tn.k1_wg : 2;
+        a1.dedup = dedup ? 1 : 0;
+        const hipError_t e1 = k1_mode == 3 ? icw_launch_iir_row(&a1, N, cfg.iir_kahan, cfg.iir_subnorm_reject, st)
+                                           : icw_launch_iir_state(&a1, N, cfg.iir_kahan, cfg.iir_subnorm_reject, st);
+        if (e1 != hipSuccess) return ICW_EDEVICE;
+
+        /* K2 up to `in`: the output sums and the fs/4 un-mix, then the rows instead of the graph; it still
+         * counts the block's de-subnorm rejections */
+        IcwK2Args a2;
+        memset(&a2, 0, sizeof(a2));
+        a2.w = c->w[0];
+        a2.w_pitch = w_pitch;
+        a2.n_streams = count;
+        a2.T = T;
+        a2.n_chains = count * 4;
+        a2.nch = nch;
+        a2.t0 = t0;
+        a2.hq_phase = ds.hq_phase + f0 * 2;
+        a2.n_frame = ds.n_frame + f0;
+        a2.ssr = (unsigned long long)cfg.sample_rate * ICW_HZ_SCALE;
+        a2.scaled = cfg.frmod_scaled;
+        a2.sample_rate = cfg.sample_rate;
+        a2.prog = c->d_prog;
+        a2.bus = ds.bus + f0 * ICW_N_INPUTS * 4;
+        a2.do_render = 0;
+        a2.n_regs = c->prog.chain ? 0 : c->prog.n_regs;
+        a2.clips = ds.clips + f0 * 2;
+        a2.peak_bits = ds.peak_bits + f0 * 2;
+        a2.rk = c->rk;
+        memcpy(a2.pc, c->pc, sizeof(a2.pc));
+        memcpy(a2.pd, c->pd, sizeof(a2.pd));
+        a2.d0 = c->d0;
+        a2.info_dup = c->info_dup[0];
+        a2.xin = c->xd[0];
+        a2.x_pitch = x_pitch;
+        a2.iq_out = c->iq[0];
+        a2.sncnt = cfg.iir_subnorm_reject ? ds.sncnt + f0 * 4 : nullptr;
+        if (icw_launch_output(&a2, N, cfg.iir_kahan, st) != hipSuccess) return ICW_EDEVICE;
+
+        IcwPackArgs ap;
+        memset(&ap, 0, sizeof(ap));
+        ap.iq = c->iq[0];
+        ap.n_streams = count;
+        ap.T = T;
+        ap.out = d_out + (size_t)t0 * FB;
+        ap.out_stride = dos;
+        ap.clipped = c->enc_clipped + f0;
+        if (icw_launch_iq_pack(&ap, (int)(cw_format - ICW_FMT_CW_F64), nch > 1 ? 2 : 1, st) != hipSuccess) return ICW_EDEVICE;
+    }
+    if (nch > 1)
+        for (int i = 0; i < count; ++i) c->lr_known[first + i] = 0;   /* stereo: the halves diverge */
+    if (icw_launch_enc_advance(ds.pos + f0, ds.hq_phase + f0 * 2, count, (long long)n_frames, st) != hipSuccess)
+        return ICW_EDEVICE;
+    if (legacy && hipStreamSynchronize(st) != hipSuccess) return ICW_EDEVICE;
+    if (!dev) {
+        if (hipMemcpy2DAsync(out, out_stride, d_out, dos, ob, S, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return ICW_EDEVICE;
+        int e = 0;
+        if (hipMemcpy(&e, ds.err, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess || e) return ICW_EDEVICE;
+    }
     return hipGetLastError() == hipSuccess ? ICW_OK : ICW_EDEVICE;
 }
 

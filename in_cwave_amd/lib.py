@@ -278,6 +278,31 @@ class Context:
         _check(self._lib.icw_encode_cwave(self.h, first, count, _ptr(d_in), in_stride, _ptr(d_out), out_stride,
                                           n_frames, cw_format, abi.F_DEVICE_PTRS, hip_stream), "icw_encode_cwave")
 
+    def encode_cwave_iir(self, inp, n_frames, cw_format=abi.FMT_CW_F64, first=0, count=None, out=None):
+        """icw_encode_cwave_iir, host path: inp uint8 [count, >= n_frames*fsz] through the context's quadrature
+        IIR converter to packed CWAVE frames, uint8 [count, n_frames * frame bytes].  Advances the converters
+        (rings, phases, de-subnorm counters) and the reader position like a process call; nothing else."""
+        count = self.n_streams - first if count is None else count
+        inp = np.ascontiguousarray(inp)
+        assert inp.dtype == np.uint8 and inp.shape[0] == count and inp.shape[1] >= n_frames * self.fsz
+        fb = cwave_frame_bytes(cw_format, self.cfg.in_channels)
+        if out is None:
+            out = np.zeros((count, n_frames * fb), dtype=np.uint8)
+        assert out.dtype == np.uint8 and out.shape[0] == count and out.shape[1] >= n_frames * fb
+        in_stride = inp.strides[0] if count > 1 else inp.shape[1]
+        out_stride = out.strides[0] if count > 1 else out.shape[1]
+        _check(self._lib.icw_encode_cwave_iir(self.h, first, count, _ptr(inp), in_stride, _ptr(out), out_stride,
+                                              n_frames, cw_format, 0, None), "icw_encode_cwave_iir")
+        return out
+
+    def encode_cwave_iir_device(self, d_in, in_stride, d_out, out_stride, n_frames, cw_format=abi.FMT_CW_F64,
+                                first=0, count=None, hip_stream=None):
+        """icw_encode_cwave_iir with ICW_F_DEVICE_PTRS (torch tensors / int pointers), stream-ordered"""
+        count = self.n_streams - first if count is None else count
+        _check(self._lib.icw_encode_cwave_iir(self.h, first, count, _ptr(d_in), in_stride, _ptr(d_out), out_stride,
+                                              n_frames, cw_format, abi.F_DEVICE_PTRS, hip_stream),
+               "icw_encode_cwave_iir")
+
     def encode_clipped(self, s, reset=False):
         """icw_encode_clipped: saturated / NaN int16 samples stream s has encoded since the last reset"""
         v = C.c_uint64()
@@ -449,6 +474,21 @@ def cwave_encode_files(in_paths, out_paths, k_M, k_beta=8.0, cw_format=abi.FMT_C
     status = (C.c_int * max(1, n))()
     clipped = (C.c_uint64 * max(1, n))()
     rc = load().icw_cwave_encode_files(ins, outs, n, C.byref(o), C.byref(st), clipped, status)
+    return rc, st, [status[i] for i in range(n)], [int(clipped[i]) for i in range(n)]
+
+
+def cwave_encode_files_iir(in_paths, out_paths, hilbert_type=1, iir_kahan=1, iir_subnorm_reject=1,
+                           cw_format=abi.FMT_CW_F64, block_frames=0, device=-1):
+    """icw_cwave_encode_files_iir: WAV files to V2 CWAVE files (k_M 0) through the quadrature IIR converter;
+    returns (rc, stats, per-file status, per-file clipped int16 samples)"""
+    n = len(in_paths)
+    ins = (C.c_char_p * max(1, n))(*[str(p).encode() for p in in_paths])
+    outs = (C.c_char_p * max(1, n))(*[str(p).encode() for p in out_paths])
+    o = abi.CwaveEncIirOpts(hilbert_type, iir_kahan, iir_subnorm_reject, cw_format, block_frames, device, 0)
+    st = abi.BatchStats()
+    status = (C.c_int * max(1, n))()
+    clipped = (C.c_uint64 * max(1, n))()
+    rc = load().icw_cwave_encode_files_iir(ins, outs, n, C.byref(o), C.byref(st), clipped, status)
     return rc, st, [status[i] for i in range(n)], [int(clipped[i]) for i in range(n)]
 
 

@@ -66,16 +66,18 @@ uint32_t icw_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 int icw_cwave_check(const void *file, uint64_t file_size, unsigned flags, int device, uint32_t *crc,
                     int *crc_ok);
 
-/* ---- CWAVE encoder: real PCM -> the analytic-signal frames a CWAVE file holds ----
- * The converter is the context's FIR Hilbert (icw_set_fir_hilbert, k_M > 0): the same kernel code
- * stages and sums, so I[n] = x[n - k_M/2] and Q[n] are bit for bit what icw_process_* feeds the graph.
+/* ---- CWAVE encoders: real PCM -> the analytic-signal frames a CWAVE file holds ----
+ * icw_encode_cwave: the converter is the context's FIR Hilbert (icw_set_fir_hilbert, k_M > 0): the same
+ * kernel code stages and sums, so I[n] = x[n - k_M/2] and Q[n] are bit for bit what icw_process_* feeds the graph.
  * Frame layout (cwave.h:74-81), per channel Re then Im, stereo Re(L) Im(L) Re(R) Im(R):
  *   ICW_FMT_CW_F64 16 bytes, ICW_FMT_CW_I16 4, ICW_FMT_CW_I16_F32 6 (float unaligned), ICW_FMT_CW_F32 8.
  * Mono input gives 1-channel frames; input of 2 or more channels gives 2-channel frames of the first two.
  * Conversions (the project's definition; the reference ships no converter, so parity is unpinned, like
  * the FIR converter itself): double = the bits; float = round to nearest even; int16 = round to nearest,
  * ties to even, saturated to [-32768, 32767], NaN -> 0.
- * Not covered: an IIR-Hilbert CWAVE (k_M 0), the direct-FFT converter (k_M -1), V1 headers. */
+ * icw_encode_cwave_iir (below) writes the same frames from the quadrature IIR converter, whose values
+ * are the reference's (hq_rp_process) bit for bit.
+ * Not covered: the direct-FFT converter (k_M -1), V1 headers. */
 
 /* bytes of one frame of cw_format for an input of `channels` channels; 0 if either is invalid */
 int icw_cwave_frame_bytes(uint32_t cw_format, uint32_t channels);
@@ -97,8 +99,31 @@ int icw_encode_cwave(icw_ctx *ctx, int first, int count, const void *in, size_t 
                      void *out, size_t out_stride_bytes, int n_frames, uint32_t cw_format,
                      unsigned flags, void *hip_stream);
 
-/* Saturated or NaN int16 samples (Re and Im counted separately) stream s has encoded since the count
- * was last reset; waits for the context's queued work.  reset != 0 clears it after the read.
+/* The same call through the quadrature half-band IIR converter (hq_rp_process: cfg.hilbert_type 0..5,
+ * iir_kahan, iir_subnorm_reject with its `< 1.0` reject), for a context without icw_set_fir_hilbert: frame n
+ * holds, per channel, exactly the (I, Q) pair icw_process_* feeds the graph at frame n, so a stored file
+ * decoded with cfg.in_format = ICW_FMT_CW_F64 renders what the PCM renders.  Frame layout, conversions,
+ * pointers, ICW_F_DEVICE_PTRS, hip_stream, ordering and launch blocks (ICW_BLOCK) as in icw_encode_cwave.
+ * Per launch block the call runs the process call's own kernels up to the graph (the unpack / fade / fs/4
+ * mix, the recurrence the context would pick for a process call -- ICW_K1_MODE honoured --, the output
+ * sums and un-mix) and a packer.
+ * State: for these streams the IIR delay lines, the Hilbert phases, the de-subnorm counters
+ * (icw_get_meters().desubnorm), the left / right identity flags and the reader position (fades included)
+ * advance exactly as a process call of n_frames would.  n_frame, the bus, the FIR history, the renders,
+ * the dither generators and the clip / peak meters are left alone.  So two calls equal one, icw_get_state /
+ * icw_set_state carry an encode to another context, and a process call after an encode continues the
+ * converters as if the encoded frames had been processed.
+ * Errors: ICW_EINVAL -- nothing ran, no state changed -- for a bad range or pointer, a host stride shorter
+ * than the frames, a flag other than ICW_F_DEVICE_PTRS, a cw_format outside ICW_FMT_CW_*, a context with
+ * CWAVE input, or one with the FIR converter on (icw_set_fir_hilbert(k_M > 0): icw_encode_cwave is its
+ * call).  ICW_EUNSUPPORTED for a cfg.fp_check context (FC() arithmetic changes the values).  ICW_ENOMEM /
+ * ICW_EDEVICE as above. */
+int icw_encode_cwave_iir(icw_ctx *ctx, int first, int count, const void *in, size_t in_stride_bytes,
+                         void *out, size_t out_stride_bytes, int n_frames, uint32_t cw_format,
+                         unsigned flags, void *hip_stream);
+
+/* Saturated or NaN int16 samples (Re and Im counted separately) stream s has encoded, by either
+ * encoder (one counter), since the count was last reset; waits for the context's queued work.  reset != 0 clears it after the read.
  * clipped may be NULL. */
 int icw_encode_clipped(icw_ctx *ctx, int s, int reset, uint64_t *clipped);
 

@@ -96,9 +96,33 @@ typedef struct icw_cwave_enc_opts {
  * 2^32 frames or more, or an I/O error; the rest of the batch still completes.  clipped (nullable, n
  * entries) gets the file's saturated / NaN int16 samples.  Returns ICW_EINVAL for bad options (nothing
  * runs), else ICW_OK if every file was encoded, else one of the files' errors.
- * Not covered: an IIR-Hilbert CWAVE (k_M 0), the direct-FFT converter (k_M -1), V1 headers. */
+ * Not covered: the direct-FFT converter (k_M -1), V1 headers. */
 int icw_cwave_encode_files(const char *const *in_paths, const char *const *out_paths, int n,
                            const icw_cwave_enc_opts *opts, icw_batch_stats *stats, uint64_t *clipped, int *status);
+
+/* ---- convert with the reference's own converter: the quadrature half-band IIR (hq_rp_process) ---- */
+typedef struct icw_cwave_enc_iir_opts {
+    uint32_t hilbert_type;              /* filter type 0 .. 5 (icw_config.hilbert_type) */
+    int32_t  iir_kahan;                 /* 0 / 1: baseline or Kahan sums */
+    int32_t  iir_subnorm_reject;        /* 0 / 1: the `< 1.0` reject */
+    uint32_t cw_format;                 /* ICW_FMT_CW_* of the output */
+    int32_t  block_frames;              /* frames per stream per GPU block (0: 65536) */
+    int32_t  device;                    /* HIP device, -1: current */
+    int32_t  reserved_;
+} icw_cwave_enc_iir_opts;
+
+/* icw_cwave_encode_files through icw_encode_cwave_iir (icw_cwave.h): file frame n holds exactly the (I, Q)
+ * pairs the in-context converter of that type and configuration feeds the graph at frame n, so playing the
+ * .cwave file renders what playing the .wav renders -- the serial IIR is paid once, at the conversion.
+ * Grouping, staging, the n_CRC32 chained on the GPU, per-file status and `clipped` as above; every file is
+ * a fresh stream with no fades and no tail.  There is no aligned mode: the IIR's group delay is not a
+ * constant number of frames.  The header is V2 with hsize 48, n_samples = the input's frames, k_M = 0 and
+ * k_beta = 0.0 -- the reference's reader shows k_M 0 as an unknown converter (gui_cwave.c:164-170) and
+ * plays the file like any other.  Returns ICW_EINVAL for bad options (hilbert_type > 5, a flag that is not
+ * 0 or 1, a cw_format outside ICW_FMT_CW_*, block_frames < 0; nothing runs, nothing is written). */
+int icw_cwave_encode_files_iir(const char *const *in_paths, const char *const *out_paths, int n,
+                               const icw_cwave_enc_iir_opts *opts, icw_batch_stats *stats, uint64_t *clipped,
+                               int *status);
 
 #ifdef __cplusplus
 }
