@@ -147,6 +147,10 @@ SIGNATURES = {
     "icw_set_input": (_i, [_vp, C.c_uint32, C.c_uint32, C.c_uint32]),
     "icw_set_fir_hilbert": (_i, [_vp, C.c_int32, C.c_double]),
     "icw_set_graph": (_i, [_vp, C.POINTER(Node), _i, _i, C.POINTER(_i)]),
+    "icw_set_stream_graph": (_i, [_vp, _i, _i, C.POINTER(Node), _i, _i, C.POINTER(_i)]),
+    "icw_clear_stream_bus_slot": (_i, [_vp, _i, _i, _i]),
+    "icw_stream_graph_count": (_i, [_vp]),
+    "icw_graph_form": (_i, [C.POINTER(Config), C.POINTER(Node), _i, _i]),
     "icw_set_render": (_i, [_vp, C.POINTER(RenderCfg)]),
     "icw_set_outbits": (_i, [_vp, _i]),
     "icw_clear_bus_slot": (_i, [_vp, _i]),
@@ -209,6 +213,9 @@ SIGNATURES = {
     "icw_transcode_files": (_i, [C.POINTER(Config), C.POINTER(Node), _i, C.POINTER(C.c_char_p),
                                  C.POINTER(C.c_char_p), _i, C.POINTER(BatchOpts), C.POINTER(BatchStats),
                                  C.POINTER(_i)]),
+    "icw_transcode_files_lists": (_i, [C.POINTER(Config), C.POINTER(C.POINTER(Node)), C.POINTER(_i), C.POINTER(_i),
+                                       C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, C.POINTER(BatchOpts),
+                                       C.POINTER(BatchStats), C.POINTER(_i)]),
     "icw_group_create": (_i, [C.POINTER(Config), C.POINTER(Node), _i, _i, C.POINTER(_i), _i, C.POINTER(_vp),
                               C.POINTER(_i)]),
     "icw_group_destroy": (_i, [_vp]),

@@ -167,9 +167,17 @@ double now_s()
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+/* icw_transcode_files_lists: file i's own list (indexed like the files), null for the one-list call */
+struct FileLists {
+    const icw_node *const *nodes = nullptr;
+    const int *n_nodes = nullptr;
+    const int *bypass = nullptr;       /* nullable: cfg->bypass_list */
+    bool per_stream = false;           /* the group's lists may differ (all register form) */
+};
+
 /* One group of files sharing (rate, format, channels): one context, one stream per file. */
 int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::vector<Job *> &jobs,
-              const icw_batch_opts &o, icw_batch_stats &st, int *status)
+              const icw_batch_opts &o, icw_batch_stats &st, int *status, const FileLists &fl = FileLists())
 {
     const int S = (int)jobs.size();
     const icw_wav_info &wi = jobs[0]->info;
@@ -177,11 +185,24 @@ int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::v
     cfg.sample_rate = wi.sample_rate;
     cfg.in_format = wi.fmt;
     cfg.in_channels = wi.channels;
+    if (fl.nodes) {
+        /* the context starts on the first file's list; a group of differing lists then gives every
+         * stream its own before the first block */
+        nodes = fl.nodes[jobs[0]->idx];
+        n_nodes = fl.n_nodes[jobs[0]->idx];
+        if (fl.bypass) cfg.bypass_list = fl.bypass[jobs[0]->idx];
+    }
     icw_ctx *ctx = nullptr;
     int accepted = 0;
     int rc = icw_create(&cfg, nodes, n_nodes, S, o.device, &ctx, &accepted);
     if (rc != ICW_OK) return rc;
     std::unique_ptr<icw_ctx, int (*)(icw_ctx *)> guard(ctx, icw_destroy);
+    for (int s = 1; s < S && fl.per_stream; ++s) {
+        const int i = jobs[s]->idx;
+        rc = icw_set_stream_graph(ctx, s, 1, fl.nodes[i], fl.n_nodes[i], fl.bypass ? fl.bypass[i] : cfg0.bypass_list,
+                                  &accepted);
+        if (rc != ICW_OK) return rc;
+    }
     const int rs = icw_render_size(ctx), osz = 2 * rs;
     const size_t fsz = wi.frame_bytes;
     const int B = o.block_frames > 0 ? o.block_frames : 65536;
@@ -664,6 +685,90 @@ int icw_transcode_files(const icw_config *cfg, const icw_node *nodes, int n_node
     int rc = ICW_OK;
     for (auto &g : groups) {
         const int r = run_group(*cfg, nodes, n_nodes, g.second, o, st, sts);
+        if (r != ICW_OK) {
+            rc = r;
+            for (Job *j : g.second) if (sts[j->idx] == ICW_OK) sts[j->idx] = r;
+        }
+        ++st.n_groups;
+    }
+    for (Job &j : jobs) {
+        if (j.in) fclose(j.in);
+        if (j.out && fclose(j.out) != 0 && sts[j.idx] == ICW_OK) sts[j.idx] = ICW_EINVAL;
+        if (sts[j.idx] == ICW_OK) ++st.n_files;
+        else if (rc == ICW_OK) rc = sts[j.idx];
+    }
+    st.wall_s = now_s() - t0;
+    if (stats) *stats = st;
+    return rc;
+}
+
+/* icw_transcode_files with file i's own list (include/icw_reader.h) */
+int icw_transcode_files_lists(const icw_config *cfg, const icw_node *const *nodes, const int *n_nodes,
+                              const int *bypass_list, const char *const *in_paths, const char *const *out_paths, int n,
+                              const icw_batch_opts *opts, icw_batch_stats *stats, int *status)
+{
+    if (!cfg || n < 0 || (n > 0 && (!in_paths || !out_paths || !nodes || !n_nodes))) return ICW_EINVAL;
+    const double t0 = now_s();
+    icw_batch_opts o;
+    memset(&o, 0, sizeof(o));
+    o.device = -1;
+    if (opts) o = *opts;
+    icw_batch_stats st;
+    memset(&st, 0, sizeof(st));
+    std::vector<int> stat_local(n > 0 ? n : 1, ICW_OK);
+    int *sts = status ? status : stat_local.data();
+    std::vector<Job> jobs(n);
+    /* (rate, format, channels, list): -1 for the register-form lists, which share a context whatever
+     * they are; a bus-form list (context-wide only) groups with the files that carry the same one */
+    std::map<std::tuple<uint32_t, uint32_t, uint32_t, int>, std::vector<Job *>> groups;
+    std::vector<int> bus_first;                     /* file index of each distinct bus-form list */
+    auto same = [&](int a, int b) {
+        const int ba = bypass_list ? bypass_list[a] : cfg->bypass_list, bb = bypass_list ? bypass_list[b] : cfg->bypass_list;
+        return n_nodes[a] == n_nodes[b] && !ba == !bb &&
+               (n_nodes[a] == 0 || !memcmp(nodes[a], nodes[b], (size_t)n_nodes[a] * sizeof(icw_node)));
+    };
+    for (int i = 0; i < n; ++i) {
+        sts[i] = ICW_OK;
+        Job &j = jobs[i];
+        j.idx = i;
+        if (n_nodes[i] < 0 || (n_nodes[i] > 0 && !nodes[i])) {
+            sts[i] = ICW_EINVAL;
+            continue;
+        }
+        const int form = icw_graph_form(cfg, nodes[i], n_nodes[i], bypass_list ? bypass_list[i] : cfg->bypass_list);
+        if (form < 0) {
+            sts[i] = form;                          /* ICW_EGRAPH: the rest of the batch goes on */
+            continue;
+        }
+        if (!in_paths[i] || !out_paths[i] || (sts[i] = icw_wav_parse_file(in_paths[i], &j.info)) != ICW_OK) {
+            if (sts[i] == ICW_OK) sts[i] = ICW_EINVAL;
+            continue;
+        }
+        if (!(j.in = fopen(in_paths[i], "rb")) || !(j.out = fopen(out_paths[i], "wb"))) {
+            sts[i] = ICW_EINVAL;
+            continue;
+        }
+        setvbuf(j.in, nullptr, _IOFBF, 1 << 20);
+        setvbuf(j.out, nullptr, _IOFBF, 1 << 20);
+        int key = -1;
+        if (form == 1) {
+            for (size_t k = 0; k < bus_first.size() && key < 0; ++k)
+                if (same(bus_first[k], i)) key = (int)k;
+            if (key < 0) {
+                key = (int)bus_first.size();
+                bus_first.push_back(i);
+            }
+        }
+        groups[std::make_tuple(j.info.sample_rate, j.info.fmt, j.info.channels, key)].push_back(&j);
+    }
+    int rc = ICW_OK;
+    for (auto &g : groups) {
+        FileLists fl;
+        fl.nodes = nodes;
+        fl.n_nodes = n_nodes;
+        fl.bypass = bypass_list;
+        fl.per_stream = std::get<3>(g.first) < 0;
+        const int r = run_group(*cfg, nullptr, 0, g.second, o, st, sts, fl);
         if (r != ICW_OK) {
             rc = r;
             for (Job *j : g.second) if (sts[j->idx] == ICW_OK) sts[j->idx] = r;

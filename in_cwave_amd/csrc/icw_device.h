@@ -281,6 +281,13 @@ struct IcwK2Args {
                                       frame-parallel -- K3a's rnd * dth_mul, generator-major
                                       [n_streams * 2][dith_pitch] (row 2s + ch, frame t of the block) */
     size_t dith_pitch;
+    /* per-stream DSP lists (icw_set_stream_graph); null: every stream runs prog[0] and reads the one
+     * rotation table against stream 0's counter, exactly as before.  [3][n_streams] of the launch:
+     * row 0 the stream's index into prog[], row 1 its slab of the rotation table (-1: its program
+     * has no slab, the factors are computed inline), row 2 that slab's reference stream -- the
+     * stream reads the slab while its call-start counter equals the reference's */
+    const int32_t *prog_id;
+    size_t slab_stride;            /* doubles per slab of trig_tab (slabs share trig_pitch) */
 };
 
 /* Per-frame rotation table (one thread per frame): the Shift / PM factors depend only on the frame
@@ -294,6 +301,11 @@ struct IcwTrigArgs {
     uint32_t sample_rate;
     double *tab;                   /* [T][trig_pitch], rows in icw_trig_index order */
     int32_t perm_q;                /* 0: row t at t; > 0 (KF2): row t at (t & 7) * perm_q + (t >> 3) */
+    /* per-stream DSP lists: one slab per grid row y (null: the one table above).  [2][n_slabs]:
+     * row 0 slab y's index into prog[], row 1 its reference stream (index into n_frame[]) */
+    const int32_t *slabs;
+    int32_t n_slabs;
+    size_t slab_stride;            /* doubles per slab of tab */
 };
 
 

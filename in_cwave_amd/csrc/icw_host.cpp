@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <list>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -115,6 +116,23 @@ struct icw_ctx {
     IcwRenderK rk{};
     IcwProg prog{};
     IcwProg *d_prog = nullptr;
+    /* per-stream DSP lists (icw_set_stream_graph).  While every stream runs one list the table is
+     * empty and nodes / prog / d_prog above are that list, as before.  Otherwise: the distinct
+     * compiled programs (never bus form), the normalised list each came from, every stream's index,
+     * and the table on the device; prog / d_prog then hold entry 0 (is_bus = 0, which is all the
+     * render setters ask of it). */
+    std::vector<IcwProg> progs;
+    std::vector<std::vector<icw_node>> plists;
+    std::vector<int32_t> prog_of;         /* [streams] */
+    IcwProg *d_progs = nullptr;
+    size_t d_progs_cap = 0;               /* entries d_progs has room for */
+    /* a call over streams with different lists: K2's [3][count] selection rows, then the rotation
+     * table's [2][n_slabs] (IcwK2Args.prog_id, IcwTrigArgs.slabs), rebuilt when the lists or the
+     * range change */
+    int32_t *d_pid = nullptr;
+    bool pid_valid = false;
+    int pid_first = 0, pid_count = 0, pid_slabs = 0;
+    IcwProg mix{};                        /* that call's launch configuration: needs_omega, n_trig, chain, n_regs */
     DevState st;
     /* host mirrors of meters that survive "reset" semantics */
     std::vector<double> peak_db;          /* [streams][2] */
@@ -781,7 +799,8 @@ void free_all(icw_ctx *c)
 {
     DevState &s = c->st;
     void *ptrs[] = {c->enc_clipped, c->s1_stamps, s.mt, s.mt_idx, s.rs, s.lr_equal, s.fes, s.err, s.hist, s.sncnt, s.hq_phase, s.pos, s.fade,
-                    s.n_frame, s.bus, s.clips, s.peak_bits, c->d_prog, c->trig, c->d_in, c->d_out, c->d_pre, c->d_xin,
+                    s.n_frame, s.bus, s.clips, s.peak_bits, c->d_prog, c->d_progs, c->d_pid, c->trig, c->d_in, c->d_out,
+                    c->d_pre, c->d_xin,
                     c->d_fir_g, c->fir_hist[0], c->fir_hist[1], c->dwords, c->dbk, c->dflag};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -921,6 +940,168 @@ int apply_graph(icw_ctx *c, std::vector<icw_node> &nv, int bypass, const std::ve
     c->render_state = rstate;
     for (int slot : clears)
         if (clear_slot(c, slot) != ICW_OK) return ICW_EDEVICE;
+    return ICW_OK;
+}
+
+/* ---- per-stream DSP lists (icw_set_stream_graph) ---- */
+
+/* clear_slot for streams [first, first + count) only */
+int clear_slot_range(icw_ctx *c, int first, int count, int slot)
+{
+    if (slot < 0 || slot >= ICW_N_INPUTS || count <= 0) return ICW_OK;
+    const size_t pitch = (size_t)ICW_N_INPUTS * 4 * sizeof(double);
+    return hipMemset2D(c->st.bus + ((size_t)first * ICW_N_INPUTS + (size_t)slot) * 4, pitch, 0, 4 * sizeof(double),
+                       (size_t)count) == hipSuccess ? ICW_OK : ICW_EDEVICE;
+}
+
+/* the position-matched clears of icw_set_graph (include/icw.h): old list o against the new list nv */
+void matched_clears(const std::vector<icw_node> &o, const std::vector<icw_node> &nv, std::vector<int> &clears)
+{
+    for (size_t i = 0; i < o.size(); ++i) {
+        if (plug_slot(o[i]) < 0) continue;
+        if (i >= nv.size() || nv[i].mode != o[i].mode || nv[i].n_out != o[i].n_out) clears.push_back(o[i].n_out);
+    }
+}
+
+/* the normalised list stream s runs */
+const std::vector<icw_node> &stream_list(const icw_ctx *c, int s)
+{
+    return c->progs.empty() ? c->nodes : c->plists[(size_t)c->prog_of[(size_t)s]];
+}
+
+bool same_list(const std::vector<icw_node> &a, const std::vector<icw_node> &b)
+{
+    return a.size() == b.size() && (a.empty() || !memcmp(a.data(), b.data(), a.size() * sizeof(icw_node)));
+}
+
+/* The program table of a per-stream assignment: entry e compiled from lists[e], stream s running
+ * entry of[s].  Entries that compiled to the same program from the same list become one, entries
+ * no stream runs go, and the survivors are numbered in order of their first stream. */
+void prog_table_compact(std::vector<IcwProg> &progs, std::vector<std::vector<icw_node>> &lists,
+                        std::vector<int32_t> &of)
+{
+    std::vector<IcwProg> np;
+    std::vector<std::vector<icw_node>> nl;
+    std::vector<int32_t> map(progs.size(), -1);
+    for (int32_t &e : of) {
+        if (map[(size_t)e] < 0) {
+            size_t k = 0;
+            while (k < np.size() && !(!memcmp(&np[k], &progs[(size_t)e], sizeof(IcwProg)) && same_list(nl[k], lists[(size_t)e]))) ++k;
+            if (k == np.size()) {
+                np.push_back(progs[(size_t)e]);
+                nl.push_back(lists[(size_t)e]);
+            }
+            map[(size_t)e] = (int32_t)k;
+        }
+        e = map[(size_t)e];
+    }
+    progs.swap(np);
+    lists.swap(nl);
+}
+
+/* Install a compacted table (the caller holds c->mu and has waited for the context's work).  The
+ * device copies come first, into memory the running table does not use where the table grows, so a
+ * failed copy leaves the old lists in force on both sides.  One entry: the context is a one-list
+ * context again (prog / d_prog / nodes), and issues the launches it always did. */
+int install_table(icw_ctx *c, std::vector<IcwProg> &progs, std::vector<std::vector<icw_node>> &lists,
+                  std::vector<int32_t> &of)
+{
+    const size_t n = progs.size();
+    IcwProg *fresh = nullptr;
+    if (n > 1) {
+        if (n > c->d_progs_cap && hipMalloc((void **)&fresh, n * sizeof(IcwProg)) != hipSuccess) return ICW_ENOMEM;
+        if (!c->d_pid && dalloc(&c->d_pid, (size_t)c->n_streams * 5) != ICW_OK) {
+            if (fresh) (void)hipFree(fresh);
+            c->d_pid = nullptr;
+            return ICW_ENOMEM;
+        }
+        if (hipMemcpy(fresh ? fresh : c->d_progs, progs.data(), n * sizeof(IcwProg), hipMemcpyHostToDevice) != hipSuccess) {
+            if (fresh) (void)hipFree(fresh);
+            return ICW_EDEVICE;
+        }
+    }
+    /* d_prog follows prog (entry 0): the paths that read the pair (the encoders) see one program */
+    if (hipMemcpy(c->d_prog, &progs[0], sizeof(IcwProg), hipMemcpyHostToDevice) != hipSuccess) {
+        if (fresh) (void)hipFree(fresh);
+        return ICW_EDEVICE;
+    }
+    if (fresh) {
+        if (c->d_progs) (void)hipFree(c->d_progs);
+        c->d_progs = fresh;
+        c->d_progs_cap = n;
+    }
+    c->prog = progs[0];
+    c->nodes = lists[0];
+    c->pid_valid = false;
+    if (n == 1) {
+        c->cfg.bypass_list = progs[0].bypass;
+        c->progs.clear();
+        c->plists.clear();
+        c->prog_of.clear();
+    } else {
+        c->progs.swap(progs);
+        c->plists.swap(lists);
+        c->prog_of.swap(of);
+    }
+    return ICW_OK;
+}
+
+/* A call over streams [first, first + count) that run different lists: K2's selection rows and the
+ * rotation table's slabs on the device, the launch configuration in c->mix.  One slab per program
+ * with an active Shift / PM channel that at least two of the call's streams run, at the counter of
+ * the first of them; a program one stream runs computes its factors inline (the table would do
+ * the same work and add its traffic); a program without Shift / PM reads nothing, so it is marked
+ * as using slab 0 against itself and skips the counter arithmetic. */
+int prepare_mix(icw_ctx *c, int first, int count, hipStream_t st)
+{
+    if (c->pid_valid && c->pid_first == first && c->pid_count == count) return ICW_OK;
+    const size_t n = c->progs.size(), S = (size_t)count;
+    std::vector<int> uses(n, 0), slab(n, -1), ref(n, -1);
+    for (int i = 0; i < count; ++i) {
+        const int e = c->prog_of[(size_t)(first + i)];
+        if (uses[(size_t)e]++ == 0) ref[(size_t)e] = i;
+    }
+    IcwProg &M = c->mix;
+    M.is_bus = 0;
+    M.needs_omega = 0;
+    M.n_trig = 0;
+    M.chain = 1;
+    M.sig = 0;
+    M.n_regs = 0;
+    int n_slabs = 0;
+    std::vector<int32_t> h(S * 5, 0);
+    for (size_t e = 0; e < n; ++e) {
+        if (!uses[e]) continue;
+        const IcwProg &P = c->progs[e];
+        M.needs_omega |= P.needs_omega;
+        if (!P.chain) {
+            M.chain = 0;
+            M.n_regs = std::max(M.n_regs, P.n_regs);
+        }
+        if (P.needs_omega && P.n_trig > 0 && uses[e] >= 2) {
+            slab[e] = n_slabs;
+            h[S * 3 + (size_t)n_slabs] = (int32_t)e;
+            ++n_slabs;
+            M.n_trig = std::max(M.n_trig, P.n_trig);
+        }
+    }
+    for (size_t e = 0, y = 0; e < n; ++e)
+        if (slab[e] >= 0) h[S * 3 + (size_t)n_slabs + y++] = ref[e];
+    for (int i = 0; i < count; ++i) {
+        const size_t e = (size_t)c->prog_of[(size_t)(first + i)];
+        const bool no_trig = !(c->progs[e].needs_omega && c->progs[e].n_trig > 0);
+        h[(size_t)i] = (int32_t)e;
+        h[S + (size_t)i] = no_trig ? 0 : slab[e];
+        h[2 * S + (size_t)i] = no_trig ? i : (slab[e] >= 0 ? ref[e] : i);
+    }
+    /* ordered after the earlier calls on st, which may still read the rows; waited for, since h goes */
+    if (hipMemcpyAsync(c->d_pid, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return ICW_EDEVICE;
+    c->pid_valid = true;
+    c->pid_first = first;
+    c->pid_count = count;
+    c->pid_slabs = n_slabs;
     return ICW_OK;
 }
 
@@ -1162,6 +1343,8 @@ int icw_set_fir_hilbert(icw_ctx *c, int32_t M, double beta)
     if (!c || (M != 0 && (M < 2 || M > ICW_FIR_MAX_ORDER || (M & 1))) || !(beta >= 0.0 && beta < 1e3))
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
+    /* the fused converter takes one list per launch: not beside per-stream lists (include/icw.h) */
+    if (M > 0 && !c->progs.empty()) return ICW_EUNSUPPORTED;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     for (double *&h : c->fir_hist)
         if (h) { (void)hipFree(h); h = nullptr; }
@@ -1240,12 +1423,106 @@ int icw_set_graph(icw_ctx *c, const icw_node *nodes, int n_nodes, int bypass_lis
     /* replace_output_plug (adv_modulator.c:176-209) of the removed / re-plugged nodes, matched by
      * position (include/icw.h): their old output slots read zero from now on */
     std::vector<int> clears;
-    for (size_t i = 0; i < c->nodes.size(); ++i) {
-        const icw_node &o = c->nodes[i];
-        if (o.mode != ICW_MODE_SHIFT && o.mode != ICW_MODE_PM && o.mode != ICW_MODE_MIX) continue;
-        if (i >= nv.size() || nv[i].mode != o.mode || nv[i].n_out != o.n_out) clears.push_back(o.n_out);
+    if (!c->progs.empty()) {
+        /* the streams' lists differ: every one of them is replaced (the table collapses to this list),
+         * each stream's clears matched against its own old list.  A bus-form list is refused here
+         * (include/icw.h): the host collapses with a register-form list first. */
+        icw_config cfg = c->cfg;
+        cfg.bypass_list = bypass_list ? 1 : 0;
+        IcwProg P;
+        int rc = build_prog(cfg, nv, P);
+        if (rc) return rc;
+        if (P.is_bus) return ICW_EUNSUPPORTED;
+        std::vector<std::vector<int>> per(c->plists.size());
+        for (size_t e = 0; e < c->plists.size(); ++e) matched_clears(c->plists[e], nv, per[e]);
+        const std::vector<int32_t> of = c->prog_of;
+        if ((rc = apply_graph(c, nv, cfg.bypass_list, clears)) != ICW_OK) return rc;
+        c->progs.clear();
+        c->plists.clear();
+        c->prog_of.clear();
+        c->pid_valid = false;
+        for (int s = 0; s < c->n_streams; ++s)
+            for (int slot : per[(size_t)of[(size_t)s]])
+                if (clear_slot_range(c, s, 1, slot) != ICW_OK) return ICW_EDEVICE;
+        return ICW_OK;
     }
+    matched_clears(c->nodes, nv, clears);
     return apply_graph(c, nv, bypass_list ? 1 : 0, clears);
+}
+
+/* icw_set_graph for streams [first, first + count) (include/icw.h) */
+int icw_set_stream_graph(icw_ctx *c, int first, int count, const icw_node *nodes, int n_nodes, int bypass_list,
+                         int *accepted)
+{
+    if (!c || first < 0 || count <= 0 || first > c->n_streams - count || n_nodes < 0 || (n_nodes > 0 && !nodes))
+        return ICW_EINVAL;
+    std::vector<icw_node> nv(nodes, nodes + n_nodes);
+    const bool ok = graph_accept(nv);
+    if (accepted) *accepted = ok ? 1 : 0;
+    if (!ok) return ICW_EGRAPH;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+    /* K4 runs one lane per stream on a scalar program and the fused FIR kernels take one signature
+     * per launch: bus-form lists and the FIR converter stay context-wide */
+    if (c->fir_M > 0 || c->prog.is_bus) return ICW_EUNSUPPORTED;
+    icw_config cfg = c->cfg;
+    cfg.bypass_list = bypass_list ? 1 : 0;
+    IcwProg P;
+    int rc = build_prog(cfg, nv, P);
+    if (rc) return rc;
+    if (P.is_bus) return ICW_EUNSUPPORTED;
+    if (!c->tn.chain_ok) P.chain = P.sig = 0;
+    /* the assignment as it is, the new entry for the range, then the table compacted */
+    std::vector<IcwProg> progs = c->progs;
+    std::vector<std::vector<icw_node>> lists = c->plists;
+    std::vector<int32_t> of = c->prog_of;
+    if (progs.empty()) {
+        progs.push_back(c->prog);
+        lists.push_back(c->nodes);
+        of.assign((size_t)c->n_streams, 0);
+    }
+    std::vector<std::vector<int>> per(lists.size());
+    for (size_t e = 0; e < lists.size(); ++e) matched_clears(lists[e], nv, per[e]);
+    const std::vector<int32_t> old_of = of;
+    progs.push_back(P);
+    lists.push_back(nv);
+    for (int s = first; s < first + count; ++s) of[(size_t)s] = (int32_t)progs.size() - 1;
+    prog_table_compact(progs, lists, of);
+    if ((rc = install_table(c, progs, lists, of)) != ICW_OK) return rc;
+    for (int s = first; s < first + count; ++s)
+        for (int slot : per[(size_t)old_of[(size_t)s]])
+            if (clear_slot_range(c, s, 1, slot) != ICW_OK) return ICW_EDEVICE;
+    return ICW_OK;
+}
+
+int icw_clear_stream_bus_slot(icw_ctx *c, int first, int count, int slot)
+{
+    if (!c || first < 0 || count <= 0 || first > c->n_streams - count || slot < 0 || slot >= ICW_N_INPUTS)
+        return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+    return clear_slot_range(c, first, count, slot);
+}
+
+/* host only: the form a list compiles to (include/icw.h) */
+int icw_graph_form(const icw_config *cfg, const icw_node *nodes, int n_nodes, int bypass_list)
+{
+    if (!cfg || n_nodes < 0 || (n_nodes > 0 && !nodes)) return ICW_EINVAL;
+    std::vector<icw_node> nv(nodes, nodes + n_nodes);
+    if (!graph_accept(nv)) return ICW_EGRAPH;
+    icw_config c2 = *cfg;
+    c2.bypass_list = bypass_list ? 1 : 0;
+    std::unique_ptr<IcwProg> P(new IcwProg);
+    const int rc = build_prog(c2, nv, *P);
+    if (rc) return rc;
+    return P->is_bus ? 1 : 0;
+}
+
+int icw_stream_graph_count(const icw_ctx *c)
+{
+    if (!c) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(const_cast<icw_ctx *>(c)->mu);
+    return c->progs.empty() ? 1 : (int)c->progs.size();
 }
 
 /* the list primitives (include/icw.h): the reference's own edits, each with replace_output_plug's
@@ -1254,6 +1531,7 @@ int icw_graph_del_last(icw_ctx *c)
 {
     if (!c) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->progs.empty()) return ICW_EUNSUPPORTED;                 /* no one list to edit (include/icw.h) */
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     if (c->nodes.size() <= 1) return ICW_OK;                        /* am.tail->prev == NULL */
     std::vector<icw_node> nv(c->nodes.begin(), c->nodes.end() - 1);
@@ -1267,6 +1545,7 @@ int icw_graph_del_all(icw_ctx *c)
 {
     if (!c) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->progs.empty()) return ICW_EUNSUPPORTED;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     if (c->nodes.size() <= 1) return ICW_OK;
     std::vector<int> clears;
@@ -1283,6 +1562,7 @@ int icw_graph_add_last(icw_ctx *c, const icw_node *node)
     if (!c || !node) return ICW_EINVAL;
     if (node->mode == ICW_MODE_MASTER) return ICW_EGRAPH;           /* create_node_dsp: NULL */
     std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->progs.empty()) return ICW_EUNSUPPORTED;
     std::vector<icw_node> nv(c->nodes);
     nv.push_back(*node);
     if (!graph_accept(nv)) return ICW_EGRAPH;
@@ -1294,6 +1574,7 @@ int icw_graph_set_output_plug(icw_ctx *c, int index, int n)
 {
     if (!c || n < -1 || n >= ICW_N_INPUTS || n == 0) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->progs.empty()) return ICW_EUNSUPPORTED;
     if (index < 0 || index >= (int)c->nodes.size()) return ICW_EINVAL;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     std::vector<icw_node> nv(c->nodes);
@@ -1439,7 +1720,26 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
      * the block continues as CWAVE input does */
     const bool fir = c->fir_M > 0 && cfg.in_format < ICW_FMT_CW_F64;
     const bool cw = cfg.in_format >= ICW_FMT_CW_F64 || fir;
-    const bool bus = c->prog.is_bus;
+    /* the list of the call's streams: the context's one, the one table entry all of them run, or --
+     * streams with different lists -- the table with K2's per-stream selection (prepare_mix) */
+    const IcwProg *lp = &c->prog, *dP = c->d_prog;
+    bool mix = false;
+    if (!c->progs.empty()) {
+        const int32_t e0 = c->prog_of[(size_t)first];
+        for (int i = 1; i < count && !mix; ++i) mix = c->prog_of[(size_t)(first + i)] != e0;
+        if (mix) {
+            const int rc = prepare_mix(c, first, count, st);
+            if (rc != ICW_OK) return rc;
+            lp = &c->mix;
+            dP = c->d_progs;
+        } else {
+            lp = &c->progs[(size_t)e0];
+            dP = c->d_progs + e0;
+        }
+    }
+    const IcwProg &LP = *lp;
+    const int n_slabs = mix ? c->pid_slabs : 1;
+    const bool bus = LP.is_bus;
     /* mono dedup: every stream of the call known to hold identical left / right converters */
     const bool fcm = c->cfg.fp_check != 0;                /* FP_CHECK: FC() kernels, no shortcuts */
     bool dedup = !cw && !fcm && nch == 1 && c->tn.dedup_ok && (c->tn.k1_mode <= 0 || c->tn.k1_mode == 3);   /* plain / row K1 */
@@ -1464,8 +1764,8 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
      * block scratch and has no recurrence to pipeline against, so its blocks are as long as the
      * scratch bound allows (fewer launches, fewer partly filled waves of workgroups at their ends) */
     const bool fir_fused = fir && c->tn.fir_fuse &&
-                           icw_fir_graph_lds(c->fir_M, c->fir_nt, (int)nch, c->prog.chain ? 0 : c->prog.n_regs) > 0 &&
-                           !c->prog.is_bus;
+                           icw_fir_graph_lds(c->fir_M, c->fir_nt, (int)nch, LP.chain ? 0 : LP.n_regs) > 0 &&
+                           !LP.is_bus;
     /* The row kernel without a serial render (C2) has K2 at ~0.16 of K1r's time per frame: 65 536-frame
      * blocks (a quarter of the launches, of their gaps and prologues) ending in a steep tail
      * (65 536 -> 16 384 -> 4 096 -> 1 024: the drain stays one short K2) measured +0.8 % on C2
@@ -1586,10 +1886,12 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         for (int p = 0; p < n_sets; ++p)
             if (grow((void **)&c->rpre[p], &c->rpre_bytes[p], S * (size_t)Tb * 2 * sizeof(double))) return ICW_ENOMEM;
     /* the shared rotation table pays from two streams on; one stream computes its factors inline */
-    const bool table = c->prog.needs_omega && !bus && c->prog.n_trig > 0 && count > 1;
+    const bool table = LP.needs_omega && !bus && LP.n_trig > 0 && count > 1;
     bool in_step = table;
     for (int i = 1; in_step && i < count; ++i) in_step = c->nf_host[first + i] == c->nf_host[first];
-    if (table && grow((void **)&c->trig, &c->trig_bytes, (size_t)((Tb + 7) & ~7) * 2 * c->prog.n_trig * sizeof(double)))
+    /* per-stream lists: one slab per program that has one (prepare_mix), all of the widest one's pitch */
+    const size_t slab_stride = (size_t)((Tb + 7) & ~7) * 2 * (size_t)LP.n_trig;
+    if (table && grow((void **)&c->trig, &c->trig_bytes, (size_t)n_slabs * slab_stride * sizeof(double)))
         return ICW_ENOMEM;
     if (bus)
         for (int p = 0; p < n_sets; ++p)
@@ -1706,12 +2008,12 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         af.hist_out = c->fir_hist[(c->fir_par + b + 1) & 1] + f0 * hrow;
         af.xd = c->xd[b % n_sets];
         af.x_pitch = x_pitch;
-        af.sig = c->prog.chain ? c->prog.sig : 0;
+        af.sig = LP.chain ? LP.sig : 0;
         {
             /* mono input through a Master-only chain (signature count 1, mode MASTER, chain_in `in`:
              * ICW_SIG_M) whose gains are bit-identical: L and R are one computation */
-            const IcwOp &m = c->prog.ops[0];
-            af.lr_same = nch == 1 && c->prog.chain && (c->prog.sig & ~ICW_SIG_UNIT) == ICW_SIG_M &&
+            const IcwOp &m = LP.ops[0];
+            af.lr_same = nch == 1 && LP.chain && (LP.sig & ~ICW_SIG_UNIT) == ICW_SIG_M &&
                          !memcmp(&m.gain[0], &m.gain[1], sizeof(double)) && m.unit_gain[0] == m.unit_gain[1];
         }
         return af;
@@ -1820,7 +2122,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         a2.ssr = ssr;
         a2.scaled = cfg.frmod_scaled;
         a2.sample_rate = cfg.sample_rate;
-        a2.prog = c->d_prog;
+        a2.prog = dP;
         a2.bus = ds.bus + f0 * ICW_N_INPUTS * 4;
         a2.out = d_out + (size_t)t0 * osz;
         a2.out_stride = dos;
@@ -1832,7 +2134,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
             a2.pre_stride = (size_t)T * 2;
         }
         a2.do_render = c->serial_render ? 0 : 1;
-        a2.n_regs = c->prog.chain ? 0 : c->prog.n_regs;    /* a chain program keeps its values in VGPRs */
+        a2.n_regs = LP.chain ? 0 : LP.n_regs;    /* a chain program keeps its values in VGPRs */
         a2.clips = ds.clips + f0 * 2;
         a2.peak_bits = ds.peak_bits + f0 * 2;
         a2.rk = c->rk;
@@ -1844,7 +2146,11 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         a2.xin = c->xd[p];
         a2.x_pitch = x_pitch;
         if (bus) a2.iq_out = c->iq[p];
-        a2.trig = c->prog.needs_omega;
+        a2.trig = LP.needs_omega;
+        if (mix) {
+            a2.prog_id = c->d_pid;
+            a2.slab_stride = slab_stride;
+        }
         a2.sncnt = (!cw && cfg.iir_subnorm_reject) ? ds.sncnt + f0 * 4 : nullptr;
         a2.fes = fcm ? ds.fes + f0 * 4 * ICW_FES_PITCH : nullptr;
         return a2;
@@ -1919,18 +2225,18 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         a5.adv = adv_args();
         a5.stamps = c->s1_stamps;
         a5.ovl = c->tn.s1_ovl ? 1 : 0;
-        if (c->prog.needs_omega && c->prog.n_trig > 0 && !bus) {
+        if (LP.needs_omega && LP.n_trig > 0 && !bus) {
             /* the one stream's rotation factors, computed by the kernel's idle waves beside the
              * recurrence: the output phase reads them instead of evaluating sin / cos per frame */
-            if (grow((void **)&c->trig, &c->trig_bytes, (size_t)n_frames * 2 * c->prog.n_trig * sizeof(double)))
+            if (grow((void **)&c->trig, &c->trig_bytes, (size_t)n_frames * 2 * LP.n_trig * sizeof(double)))
                 return ICW_ENOMEM;
             IcwTrigArgs &at = a5.trig;
-            at.prog = c->d_prog;
+            at.prog = dP;
             at.n_frame = ds.n_frame + f0;
             at.t0 = 0;
             at.T = n_frames;
             at.scaled = cfg.frmod_scaled;
-            at.trig_pitch = 2 * c->prog.n_trig;
+            at.trig_pitch = 2 * LP.n_trig;
             at.ssr = ssr;
             at.sample_rate = cfg.sample_rate;
             at.tab = c->trig;
@@ -1996,15 +2302,20 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         if (table) {
             IcwTrigArgs at;
             memset(&at, 0, sizeof(at));
-            at.prog = c->d_prog;
+            at.prog = dP;
             at.n_frame = a2.n_frame;
             at.t0 = t0;
             at.T = T;
             at.scaled = cfg.frmod_scaled;
-            at.trig_pitch = 2 * c->prog.n_trig;
+            at.trig_pitch = 2 * LP.n_trig;
             at.ssr = ssr;
             at.sample_rate = cfg.sample_rate;
             at.tab = c->trig;
+            if (mix) {
+                at.slabs = c->d_pid + 3 * (size_t)count;
+                at.n_slabs = n_slabs;
+                at.slab_stride = slab_stride;
+            }
             /* the fused FIR kernel's lanes hold 4 / 8 consecutive frames: rows 8 frames apart */
             at.perm_q = fir_fused ? (T + 7) / 8 : 0;
             /* same stream as K2: the previous block's K2 has read the table before it is rewritten */
@@ -2055,7 +2366,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
             a4.ssr = a2.ssr;
             a4.scaled = a2.scaled;
             a4.sample_rate = a2.sample_rate;
-            a4.prog = c->d_prog;
+            a4.prog = dP;
             a4.bus = a2.bus;
             a4.pre = a2.pre;
             a4.pre_stride = a2.pre_stride;

@@ -559,15 +559,17 @@ __device__ __forceinline__ void icw_frame_store(const IcwK2Args &a, int s, int t
 template <bool TRIG, bool TAB = false, bool DEFER = false>
 __device__ __forceinline__ void icw_frame_graph(const IcwK2Args &a, icw_cprog *P, const IcwRegFile &R, int s,
                                                 int t, const IcwLR &in, bool use_tab, unsigned &clip_l,
-                                                unsigned &clip_r, double &pk_l, double &pk_r, int *dv = nullptr)
+                                                unsigned &clip_r, double &pk_l, double &pk_r, int *dv = nullptr,
+                                                size_t tab_off = 0)
 {
+    /* tab_off: the stream's slab of the rotation table (per-stream lists; 0: the one table) */
     const int T = a.T;
     if (a.iq_out) {
         /* bus-form graph: the serial graph kernel takes it from here (do_render == 0) */
         double *q = a.iq_out + ((size_t)s * T + t) * 4;
         q[0] = in.lre; q[1] = in.lim; q[2] = in.rre; q[3] = in.rim;
     } else {
-        const double *trow = use_tab ? a.trig_tab + icw_trig_index(t, a.trig_perm_q) * a.trig_pitch : nullptr;
+        const double *trow = use_tab ? a.trig_tab + tab_off + icw_trig_index(t, a.trig_perm_q) * a.trig_pitch : nullptr;
         const double omega = (TRIG && !use_tab) ? icw_omega(a.n_frame[s], a.t0 + t, a.scaled, a.ssr, a.sample_rate)
                                                 : 0.0;
         /* DSP list (adv_modulator.c:637-751) */
@@ -584,11 +586,11 @@ __device__ __forceinline__ void icw_frame_graph(const IcwK2Args &a, icw_cprog *P
             double lo[1] = {0.0}, ro[1] = {0.0};
             const uint32_t tro = TRIG ? (uint32_t)(icw_trig_index(t, a.trig_perm_q) * a.trig_pitch) : 0u;
             if (sig == ICW_SIG_M)
-                icw_chain_sig<TRIG, 1, true, ICW_SIG_M, 0>(a, P, t, T, inr, pv, lo, ro, bus_s, last, 0, tro, 0, 0);
+                icw_chain_sig<TRIG, 1, true, ICW_SIG_M, 0>(a, P, t, T, inr, pv, lo, ro, bus_s, last, 0, tro, tab_off, 0);
             else if (sig == ICW_SIG_SM)
-                icw_chain_sig<TRIG, 1, true, ICW_SIG_SM, 0>(a, P, t, T, inr, pv, lo, ro, bus_s, last, 0, tro, 0, 0);
+                icw_chain_sig<TRIG, 1, true, ICW_SIG_SM, 0>(a, P, t, T, inr, pv, lo, ro, bus_s, last, 0, tro, tab_off, 0);
             else
-                icw_chain_sig<TRIG, 1, true, ICW_SIG_PSXM, 0>(a, P, t, T, inr, pv, lo, ro, bus_s, last, 0, tro, 0, 0);
+                icw_chain_sig<TRIG, 1, true, ICW_SIG_PSXM, 0>(a, P, t, T, inr, pv, lo, ro, bus_s, last, 0, tro, tab_off, 0);
             lOut = lo[0];
             rOut = ro[0];
         } else if (P->chain) {
@@ -1257,7 +1259,8 @@ template <int N, bool KAHAN, bool TRIG, bool FCK>
 __device__ __forceinline__ void icw_output_frame(const IcwK2Args &a, icw_cprog *P, const IcwRegFile &R, int s,
                                                  int t, const double *const (&w)[4], bool dup, const double *lc,
                                                  IcwFes (&fes)[2], bool count_sn, unsigned (&sn)[4], bool use_tab,
-                                                 unsigned &clip_l, unsigned &clip_r, double &pk_l, double &pk_r)
+                                                 unsigned &clip_l, unsigned &clip_r, double &pk_l, double &pk_r,
+                                                 size_t tab_off = 0)
 {
     IcwLR in;
     if (a.cw) {
@@ -1300,7 +1303,7 @@ __device__ __forceinline__ void icw_output_frame(const IcwK2Args &a, icw_cprog *
         }
         in.lre = oI[0]; in.lim = oQ[0]; in.rre = oI[1]; in.rim = oQ[1];
     }
-    icw_frame_graph<TRIG>(a, P, R, s, t, in, use_tab, clip_l, clip_r, pk_l, pk_r);
+    icw_frame_graph<TRIG>(a, P, R, s, t, in, use_tab, clip_l, clip_r, pk_l, pk_r, nullptr, tab_off);
 }
 
 /* the workgroup's de-subnorm counts, one atomic per chain (nc chains computed; dup: the right
@@ -1327,11 +1330,14 @@ __device__ __forceinline__ void icw_sn_wg(const IcwK2Args &a, int s, const unsig
  * stream (fewer when a launch would have too few workgroups to spread over the chip).
  * The w window of tile k+1 is loaded into registers while tile k is computed, then written to the
  * other half of a double-buffered LDS window: the global-load latency hides behind FP64 work and
- * the meters reduce once per workgroup.  TRIG = the program has an active Shift / PM node. */
+ * the meters reduce once per workgroup.  TRIG = the program has an active Shift / PM node.
+ * MIX = per-stream DSP lists (a.prog_id): the workgroup's stream picks its program and its slab of
+ * the rotation table once, before the tile loop -- both wave-uniform, the program pointer stays in
+ * the constant address space.  The MIX = false instances are the kernels of a one-list context. */
 #ifndef ICW_K2_MINWG
 #define ICW_K2_MINWG 1
 #endif
-template <int N, bool KAHAN, bool TRIG, bool FCK = false>
+template <int N, bool KAHAN, bool TRIG, bool FCK = false, bool MIX = false>
 __device__ __forceinline__ void icw_output_body(const IcwK2Args &a, int bx, int s, double *lregs)
 {
     constexpr int TILE = ICW_K2_TILE;
@@ -1352,7 +1358,16 @@ __device__ __forceinline__ void icw_output_body(const IcwK2Args &a, int bx, int 
     IcwFes fes[2] = {};
     const int nc = dup ? 2 : 4;
     /* the per-frame rotation table holds this stream's factors when its counter is in step */
-    const bool use_tab = TRIG && a.trig_tab && a.n_frame[s] == a.n_frame[0];
+    bool use_tab = TRIG && a.trig_tab && a.n_frame[s] == a.n_frame[0];
+    icw_cprog *P = icw_prog_c(a.prog);
+    size_t tab_off = 0;
+    if constexpr (MIX) {
+        const __attribute__((address_space(4))) int32_t *id = (const __attribute__((address_space(4))) int32_t *)a.prog_id;
+        P += id[s];
+        const int slab = id[a.n_streams + s];
+        use_tab = TRIG && a.trig_tab && slab >= 0 && a.n_frame[s] == a.n_frame[id[2 * a.n_streams + s]];
+        tab_off = slab >= 0 ? (size_t)slab * a.slab_stride : 0;
+    }
     double pf[4][2];
     auto load_tile = [&](int k) {
         const int tt = tw0 + k * TILE;
@@ -1381,7 +1396,6 @@ __device__ __forceinline__ void icw_output_body(const IcwK2Args &a, int bx, int 
         __syncthreads();
     }
 
-    icw_cprog *P = icw_prog_c(a.prog);
     IcwRegFile R;
     R.base = lregs + tl;
     /* slots read but never written in the frame hold their block-start values */
@@ -1411,8 +1425,12 @@ __device__ __forceinline__ void icw_output_body(const IcwK2Args &a, int bx, int 
         const int zk = a.zero * k;
         if (t < T) {
             const double *const w[4] = {&W[0][tl], &W[1][tl], &W[2][tl], &W[3][tl]};
-            icw_output_frame<N, KAHAN, TRIG, FCK>(a, P, R, s, t, w, dup, lcoef + zk, fes, count_sn, sn, use_tab, clip_l,
-                                                  clip_r, pk_l, pk_r);
+            if constexpr (MIX)
+                icw_output_frame<N, KAHAN, TRIG, FCK>(a, P, R, s, t, w, dup, lcoef + zk, fes, count_sn, sn, use_tab,
+                                                      clip_l, clip_r, pk_l, pk_r, tab_off);
+            else
+                icw_output_frame<N, KAHAN, TRIG, FCK>(a, P, R, s, t, w, dup, lcoef + zk, fes, count_sn, sn, use_tab,
+                                                      clip_l, clip_r, pk_l, pk_r);
         }
         if (more) {
             /* the other half was last read in tile k-1, before the previous barrier */
@@ -1432,11 +1450,11 @@ __device__ __forceinline__ void icw_output_body(const IcwK2Args &a, int bx, int 
     if (a.do_render) icw_meters_wg(a, s, clip_l, clip_r, pk_l, pk_r, red_clip, red_pk);
 }
 
-template <int N, bool KAHAN, bool TRIG, bool FCK = false>
+template <int N, bool KAHAN, bool TRIG, bool FCK = false, bool MIX = false>
 __global__ __launch_bounds__(ICW_K2_TILE, ICW_K2_MINWG) void icw_output(IcwK2Args a)
 {
     extern __shared__ __attribute__((aligned(16))) double lregs[];   /* [n_regs][4][TILE] */
-    icw_output_body<N, KAHAN, TRIG, FCK>(a, blockIdx.x, blockIdx.y, lregs);
+    icw_output_body<N, KAHAN, TRIG, FCK, MIX>(a, blockIdx.x, blockIdx.y, lregs);
 }
 
 /* Fused FIR converter + graph + render (KF2): one workgroup per stream and 1024-frame tile (2048
@@ -1961,11 +1979,21 @@ __global__ __launch_bounds__(256, NC == 2 ? ICW_FIR_SIG_OCC : ICW_FIR_SIG_OCC1) 
  * counter, which all streams of a batch share while they are in step (same call-start counter).
  * One thread per frame evaluates each active channel's factor once (icw_trig, the same code as
  * the inline path); K2 reads the row instead of running fmod / sin / sincos per stream. */
-__device__ __forceinline__ void icw_trig_row(const IcwTrigArgs &a, int t)
+/* y: the slab (per-stream DSP lists, a.slabs: program y's factors at its reference stream's counter) */
+template <bool SLAB = false>
+__device__ __forceinline__ void icw_trig_row(const IcwTrigArgs &a, int t, int y = 0)
 {
     icw_cprog *P = icw_prog_c(a.prog);
-    const double omega = icw_omega(a.n_frame[0], a.t0 + t, a.scaled, a.ssr, a.sample_rate);
-    double *row = a.tab + icw_trig_index(t, a.perm_q) * a.trig_pitch;
+    int ref = 0;
+    double *tab = a.tab;
+    if constexpr (SLAB) {
+        const __attribute__((address_space(4))) int32_t *sl = (const __attribute__((address_space(4))) int32_t *)a.slabs;
+        P += sl[y];
+        ref = sl[a.n_slabs + y];
+        tab += (size_t)y * a.slab_stride;
+    }
+    const double omega = icw_omega(a.n_frame[ref], a.t0 + t, a.scaled, a.ssr, a.sample_rate);
+    double *row = tab + icw_trig_index(t, a.perm_q) * a.trig_pitch;
     for (int oi = 0; oi < P->n_ops; ++oi) {
         icw_cop &op = P->ops[oi];
         if (op.mode != ICW_MODE_SHIFT && op.mode != ICW_MODE_PM) continue;
@@ -1982,7 +2010,9 @@ __device__ __forceinline__ void icw_trig_row(const IcwTrigArgs &a, int t)
 __global__ __launch_bounds__(256) void icw_trig_table(IcwTrigArgs a)
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t < a.T) icw_trig_row(a, t);
+    if (t >= a.T) return;
+    if (a.slabs) icw_trig_row<true>(a, t, blockIdx.y);
+    else icw_trig_row(a, t);
 }
 
 /* ------------------------------------------------------- serial graph kernel (K4) ------ */
@@ -3458,6 +3488,13 @@ static hipError_t launch_k2_t(IcwK2Args a, hipStream_t st)
     const int span = ICW_K2_TILE * tpw;
     dim3 grid((a.T + span - 1) / span, a.n_streams);
     const size_t lds = (size_t)a.n_regs * 4 * ICW_K2_TILE * sizeof(double);
+    if (a.prog_id) {
+        /* per-stream DSP lists: the instances that select the program per workgroup */
+        if (a.fes && !a.cw) hipLaunchKernelGGL((icw_output<N, K, true, true, true>), grid, dim3(ICW_K2_TILE), lds, st, a);
+        else if (a.trig) hipLaunchKernelGGL((icw_output<N, K, true, false, true>), grid, dim3(ICW_K2_TILE), lds, st, a);
+        else hipLaunchKernelGGL((icw_output<N, K, false, false, true>), grid, dim3(ICW_K2_TILE), lds, st, a);
+        return hipGetLastError();
+    }
     if (a.fes && !a.cw) hipLaunchKernelGGL((icw_output<N, K, true, true>), grid, dim3(ICW_K2_TILE), lds, st, a);
     else if (a.trig) hipLaunchKernelGGL((icw_output<N, K, true>), grid, dim3(ICW_K2_TILE), lds, st, a);
     else hipLaunchKernelGGL((icw_output<N, K, false>), grid, dim3(ICW_K2_TILE), lds, st, a);
@@ -3571,7 +3608,7 @@ extern "C" hipError_t icw_launch_output(const IcwK2Args *a, int nord, int kahan,
 
 extern "C" hipError_t icw_launch_trig_table(const IcwTrigArgs *a, hipStream_t st)
 {
-    hipLaunchKernelGGL(icw_trig_table, dim3((a->T + 255) / 256), dim3(256), 0, st, *a);
+    hipLaunchKernelGGL(icw_trig_table, dim3((a->T + 255) / 256, a->slabs ? a->n_slabs : 1), dim3(256), 0, st, *a);
     return hipGetLastError();
 }
 

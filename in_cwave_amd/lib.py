@@ -160,6 +160,29 @@ class Context:
         """mod_context_clear_all_inouts for every stream (icw_clear_bus_slot): slot 0..26 to zero"""
         _check(self._lib.icw_clear_bus_slot(self.h, int(slot)), "icw_clear_bus_slot")
 
+    def set_stream_graph(self, nodes, first=0, count=None, bypass_list=0):
+        """icw_set_stream_graph: the DSP list of streams [first, first + count) for the next calls;
+        returns False when the list is one amod_init would reject (the running lists stay)"""
+        count = self.n_streams - first if count is None else count
+        arr = (abi.Node * max(1, len(nodes)))(*nodes) if nodes else (abi.Node * 1)()
+        acc = C.c_int()
+        rc = self._lib.icw_set_stream_graph(self.h, int(first), int(count), arr, len(nodes), int(bypass_list),
+                                            C.byref(acc))
+        if rc == abi.EGRAPH:
+            return False
+        _check(rc, "icw_set_stream_graph")
+        return True
+
+    def clear_stream_bus_slot(self, slot, first=0, count=None):
+        """icw_clear_stream_bus_slot: bus slot 0..26 of streams [first, first + count) to zero"""
+        count = self.n_streams - first if count is None else count
+        _check(self._lib.icw_clear_stream_bus_slot(self.h, int(first), int(count), int(slot)),
+               "icw_clear_stream_bus_slot")
+
+    def stream_graph_count(self):
+        """icw_stream_graph_count: distinct compiled lists in force (1 on a fresh context)"""
+        return int(self._lib.icw_stream_graph_count(self.h))
+
     def graph_del_last(self):
         """amod_del_lastdsp (icw_graph_del_last): the tail goes, its output slot is cleared"""
         _check(self._lib.icw_graph_del_last(self.h), "icw_graph_del_last")
@@ -212,6 +235,10 @@ class Context:
     def stream_open(self, s, n_samples, fade_in_ms=0, fade_out_ms=0, sec_align=0, clr_nframe=0, clr_hilb=0):
         _check(self._lib.icw_stream_open(self.h, s, n_samples, fade_in_ms, fade_out_ms, sec_align,
                                          clr_nframe, clr_hilb), "icw_stream_open")
+
+    def stream_reset_framecnt(self, s):
+        """mod_context_reset_framecnt (icw_stream_reset_framecnt): stream s's modulator frame counter to 0"""
+        _check(self._lib.icw_stream_reset_framecnt(self.h, int(s)), "icw_stream_reset_framecnt")
 
     def process(self, inp, n_frames, first=0, count=None, want_pre=False, out=None):
         """Host numpy path: inp uint8 [count, >= n_frames*fsz]; returns (out uint8 [count, n_frames*2*rs],
@@ -454,6 +481,30 @@ def transcode_files(cfg, nodes, in_paths, out_paths, fade_in_ms=0, fade_out_ms=0
     st = abi.BatchStats()
     status = (C.c_int * max(1, n))()
     rc = load().icw_transcode_files(C.byref(cfg), arr, len(nodes), ins, outs, n, C.byref(o), C.byref(st), status)
+    return rc, st, [status[i] for i in range(n)]
+
+
+def graph_form(cfg, nodes, bypass_list=0):
+    """icw_graph_form (host only): 0 register form, 1 bus form, abi.EGRAPH a rejected list"""
+    return int(load().icw_graph_form(C.byref(cfg), graph_nodes(nodes), len(nodes), int(bypass_list)))
+
+
+def transcode_files_lists(cfg, node_lists, in_paths, out_paths, bypass_lists=None, fade_in_ms=0, fade_out_ms=0,
+                          sec_align=0, block_frames=0, device=-1):
+    """icw_transcode_files_lists: file i through its own list node_lists[i] (bypass_lists[i] where
+    given); returns (rc, stats, per-file status)"""
+    n = len(in_paths)
+    assert len(node_lists) == n and len(out_paths) == n and (bypass_lists is None or len(bypass_lists) == n)
+    ins = (C.c_char_p * max(1, n))(*[str(p).encode() for p in in_paths])
+    outs = (C.c_char_p * max(1, n))(*[str(p).encode() for p in out_paths])
+    arrs = [graph_nodes(nl) for nl in node_lists]
+    ptrs = (C.POINTER(abi.Node) * max(1, n))(*[C.cast(a, C.POINTER(abi.Node)) for a in arrs])
+    cnt = (C.c_int * max(1, n))(*[len(nl) for nl in node_lists])
+    byp = (C.c_int * max(1, n))(*[int(b) for b in bypass_lists]) if bypass_lists is not None else None
+    o = abi.BatchOpts(fade_in_ms, fade_out_ms, sec_align, block_frames, device, 0)
+    st = abi.BatchStats()
+    status = (C.c_int * max(1, n))()
+    rc = load().icw_transcode_files_lists(C.byref(cfg), ptrs, cnt, byp, ins, outs, n, C.byref(o), C.byref(st), status)
     return rc, st, [status[i] for i in range(n)]
 
 

@@ -245,6 +245,44 @@ int icw_graph_del_all(icw_ctx *ctx);
 int icw_graph_add_last(icw_ctx *ctx, const icw_node *node);
 int icw_graph_set_output_plug(icw_ctx *ctx, int index, int n);
 int icw_set_render(icw_ctx *ctx, const icw_render_cfg *render);
+
+/* Per-stream DSP lists: a batch whose streams each carry their own NODE_DSP settings (Shift
+ * frequency, PM settings, gains, bypass flag) in ONE context, so the batch keeps its width.
+ *   icw_set_stream_graph      icw_set_graph for streams [first, first + count) only: the same
+ *                             normalisation and validation (a list amod_init would reject returns
+ *                             ICW_EGRAPH with *accepted = 0 and the running lists stay), in force
+ *                             from the next call on.  The position-matched bus clearing is applied
+ *                             to those streams only, each against its own old list; bypass_list is
+ *                             per stream.  The context keeps the distinct compiled lists and an
+ *                             index per stream; streams given the same list share one entry, so a
+ *                             call that gives every stream one list leaves a one-list context.
+ *   icw_clear_stream_bus_slot icw_clear_bus_slot for streams [first, first + count) only.
+ *   icw_stream_graph_count    distinct lists in force (1 on a fresh context).
+ * icw_create and icw_set_graph keep their meaning, every stream: on a context whose streams differ,
+ * icw_set_graph replaces all the lists (count back to 1), its clears matched per stream against
+ * that stream's old list.
+ * Limits, each refusal changing nothing:
+ *   ICW_EINVAL        a range outside the context, or nodes == NULL with n_nodes > 0.
+ *   ICW_EUNSUPPORTED  - the new list, or the list in force, compiles to the bus form (a one-frame
+ *                       delay, feedback, more than 16 nodes): the serial graph kernel runs one lane
+ *                       per stream on one program.  Such lists stay context-wide (icw_set_graph);
+ *                     - the FIR converter is on (icw_set_fir_hilbert with k_M > 0);
+ *                     - while the count is above 1: icw_set_fir_hilbert(k_M > 0), icw_set_graph with
+ *                       a bus-form list (collapse with a register-form icw_set_graph first), and the
+ *                       list primitives icw_graph_del_last / _del_all / _add_last / _set_output_plug
+ *                       ("the context's list" is undefined then: edit such streams with
+ *                       icw_set_stream_graph and icw_clear_stream_bus_slot).
+ * FP_CHECK contexts and CWAVE input are served.  Not served: icw_group (its lists stay
+ * context-wide), the icw_amod_* drop-in and the encoders (they run no list).  The state blob does not
+ * carry a list: icw_set_state expects the stream's list to be set as it was. */
+int icw_set_stream_graph(icw_ctx *ctx, int first, int count, const icw_node *nodes, int n_nodes,
+                         int bypass_list, int *accepted);
+int icw_clear_stream_bus_slot(icw_ctx *ctx, int first, int count, int slot);
+int icw_stream_graph_count(const icw_ctx *ctx);
+/* The form a list would compile to, on the host alone (no context, no device): 0 the register form
+ * (icw_set_stream_graph takes it), 1 the bus form (context-wide only), ICW_EGRAPH a list amod_init
+ * or the compiler rejects.  icw_transcode_files_lists sorts its files with it. */
+int icw_graph_form(const icw_config *cfg, const icw_node *nodes, int n_nodes, int bypass_list);
 /* icw_set_outbits <- sound_render_set_outbits (sound_render.c:617-621), which mod_context_fopen
  *                    applies to both renders with the.cfg.need24bits at every track open
  *                    (in_cwave.c:212, 233-234; the GUI flips the flag between tracks,

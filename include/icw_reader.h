@@ -70,6 +70,17 @@ int icw_transcode_files(const icw_config *cfg, const icw_node *nodes, int n_node
                         const char *const *out_paths, int n, const icw_batch_opts *opts, icw_batch_stats *stats,
                         int *status);
 
+/* icw_transcode_files with file i's own DSP list: nodes[i] / n_nodes[i], and bypass_list[i] where
+ * bypass_list is not NULL (else cfg->bypass_list).  The grouping stays by (sample rate, format,
+ * channels): one context per group, every stream given its list through icw_set_stream_graph
+ * before the first block, so files that differ only in their lists keep one batch.  A file whose
+ * list amod_init rejects gets ICW_EGRAPH in status and the rest of the batch completes.  A file
+ * whose list compiles to the bus form (icw_graph_form: context-wide only) runs in a context of the
+ * files of its group that carry the same list; stats->n_groups counts the contexts. */
+int icw_transcode_files_lists(const icw_config *cfg, const icw_node *const *nodes, const int *n_nodes,
+                              const int *bypass_list, const char *const *in_paths, const char *const *out_paths, int n,
+                              const icw_batch_opts *opts, icw_batch_stats *stats, int *status);
+
 /* ---- convert: WAV files -> CWAVE files (the external converter cwave.h:56-58 names) ---- */
 typedef struct icw_cwave_enc_opts {
     int32_t  k_M;                       /* FIR Hilbert order: even, 2 .. ICW_FIR_MAX_ORDER */
