@@ -175,6 +175,187 @@ struct FileLists {
     bool per_stream = false;           /* the group's lists may differ (all register form) */
 };
 
+/* The frame of a many-file call: parse and open every file, group the accepted ones by (rate, format,
+ * channels, key), run each group, close the files and count the results.  accept(i, job) fills the
+ * job's info and returns file i's status (ICW_OK to go on); key(i) is the caller's own part of the
+ * group key, asked once the file is open; run(key, jobs, stats, status) processes one group. */
+template <class Accept, class Key, class Run>
+int for_file_groups(const char *const *in_paths, const char *const *out_paths, int n, icw_batch_stats *stats, int *status,
+                    Accept accept, Key key, Run run)
+{
+    const double t0 = now_s();
+    icw_batch_stats st;
+    memset(&st, 0, sizeof(st));
+    std::vector<int> stat_local(n > 0 ? n : 1, ICW_OK);
+    int *sts = status ? status : stat_local.data();
+    std::vector<Job> jobs(n);
+    std::map<std::tuple<uint32_t, uint32_t, uint32_t, int>, std::vector<Job *>> groups;
+    for (int i = 0; i < n; ++i) {
+        Job &j = jobs[i];
+        j.idx = i;
+        if ((sts[i] = accept(i, j)) != ICW_OK) continue;
+        if (!(j.in = fopen(in_paths[i], "rb")) || !(j.out = fopen(out_paths[i], "wb"))) {
+            sts[i] = ICW_EINVAL;
+            continue;
+        }
+        setvbuf(j.in, nullptr, _IOFBF, 1 << 20);
+        setvbuf(j.out, nullptr, _IOFBF, 1 << 20);
+        groups[std::make_tuple(j.info.sample_rate, j.info.fmt, j.info.channels, key(i))].push_back(&j);
+    }
+    int rc = ICW_OK;
+    for (auto &g : groups) {
+        const int r = run(std::get<3>(g.first), g.second, st, sts);
+        if (r != ICW_OK) {
+            rc = r;
+            for (Job *j : g.second) if (sts[j->idx] == ICW_OK) sts[j->idx] = r;
+        }
+        ++st.n_groups;
+    }
+    for (Job &j : jobs) {
+        if (j.in) fclose(j.in);
+        if (j.out && fclose(j.out) != 0 && sts[j.idx] == ICW_OK) sts[j.idx] = ICW_EINVAL;
+        if (sts[j.idx] == ICW_OK) ++st.n_files;
+        else if (rc == ICW_OK) rc = sts[j.idx];
+    }
+    st.wall_s = now_s() - t0;
+    if (stats) *stats = st;
+    return rc;
+}
+
+/* a file the WAV / CWAVE parser takes: its status, ICW_EINVAL for a missing path */
+int accept_wav(const char *in_path, const char *out_path, icw_wav_info *info)
+{
+    if (!in_path || !out_path) return ICW_EINVAL;
+    return icw_wav_parse_file(in_path, info);
+}
+
+/* One group's file pipeline: pinned double buffers, device double buffers, a copy stream (cs) and a
+ * compute stream (ks).  Block k of B frames per stream is read from the files, copied in, computed,
+ * copied out and written, with the host's file I/O beside the GPU's work on the other buffer. */
+struct GroupPipe {
+    std::vector<Job *> &jobs;
+    icw_batch_stats &st;
+    int *status;
+    const int S, B;
+    const size_t fsz, osz;                /* bytes per input / output frame */
+    const size_t in_b, out_b;
+    unsigned char *hin[2] = {nullptr, nullptr}, *hout[2] = {nullptr, nullptr}, *din[2] = {nullptr, nullptr},
+                  *dout[2] = {nullptr, nullptr};
+    hipStream_t cs = nullptr, ks = nullptr;
+    hipEvent_t h2d[2] = {nullptr, nullptr}, comp[2] = {nullptr, nullptr}, d2h[2] = {nullptr, nullptr};
+
+    GroupPipe(std::vector<Job *> &jobs_, int B_, size_t fsz_, size_t osz_, icw_batch_stats &st_, int *status_)
+        : jobs(jobs_), st(st_), status(status_), S((int)jobs_.size()), B(B_), fsz(fsz_), osz(osz_),
+          in_b((size_t)S * B_ * fsz_), out_b((size_t)S * B_ * osz_) {}
+    GroupPipe(const GroupPipe &) = delete;
+
+    ~GroupPipe()
+    {
+        if (cs) (void)hipStreamSynchronize(cs);
+        if (ks) (void)hipStreamSynchronize(ks);
+        for (int p = 0; p < 2; ++p) {
+            if (hin[p]) (void)hipHostFree(hin[p]);
+            if (hout[p]) (void)hipHostFree(hout[p]);
+            if (din[p]) (void)hipFree(din[p]);
+            if (dout[p]) (void)hipFree(dout[p]);
+            for (hipEvent_t e : {h2d[p], comp[p], d2h[p]}) if (e) (void)hipEventDestroy(e);
+        }
+        if (cs) (void)hipStreamDestroy(cs);
+        if (ks) (void)hipStreamDestroy(ks);
+    }
+
+    bool alloc()
+    {
+        bool ok = true;
+        for (int p = 0; p < 2 && ok; ++p) {
+            ok = hipHostMalloc((void **)&hin[p], in_b, hipHostMallocDefault) == hipSuccess &&
+                 hipHostMalloc((void **)&hout[p], out_b, hipHostMallocDefault) == hipSuccess &&
+                 hipMalloc((void **)&din[p], in_b) == hipSuccess && hipMalloc((void **)&dout[p], out_b) == hipSuccess &&
+                 hipEventCreateWithFlags(&h2d[p], hipEventDisableTiming) == hipSuccess &&
+                 hipEventCreateWithFlags(&comp[p], hipEventDisableTiming) == hipSuccess &&
+                 hipEventCreateWithFlags(&d2h[p], hipEventDisableTiming) == hipSuccess;
+        }
+        return ok && hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) == hipSuccess &&
+               hipStreamCreateWithFlags(&ks, hipStreamNonBlocking) == hipSuccess;
+    }
+
+    /* xwave_read_samples: the next nfr input frames of every stream into buf -- data frames, then the
+     * format's zero sample */
+    void read_frames(unsigned char *buf, int nfr)
+    {
+        const double t0 = now_s();
+        for (int s = 0; s < S; ++s) {
+            Job &j = *jobs[s];
+            unsigned char *row = buf + (size_t)s * B * fsz;
+            const int64_t want = std::min<int64_t>(nfr, std::max<int64_t>(0, j.info.n_samples - j.read));
+            size_t got = 0;
+            if (want > 0 && status[j.idx] == ICW_OK) {
+                got = fread(row, fsz, (size_t)want, j.in);
+                if ((int64_t)got != want) status[j.idx] = ICW_EINVAL;      /* short read: broken file */
+                j.read += (int64_t)got;
+                st.frames_in += got;
+            }
+            memset(row + got * fsz, zero_byte(j.info.fmt), (size_t)(B - (int64_t)got) * fsz);
+        }
+        st.io_s += now_s() - t0;
+    }
+
+    void write_block(int k)
+    {
+        const double t0 = now_s();
+        const unsigned char *buf = hout[k & 1];
+        for (int s = 0; s < S; ++s) {
+            Job &j = *jobs[s];
+            const int64_t n = std::min<int64_t>(B, j.total - j.written);
+            if (n <= 0 || status[j.idx] != ICW_OK) continue;
+            if (fwrite(buf + (size_t)s * B * osz, osz, (size_t)n, j.out) != (size_t)n) status[j.idx] = ICW_EINVAL;
+            j.written += n;
+            st.frames_out += (uint64_t)n;
+        }
+        st.io_s += now_s() - t0;
+    }
+
+    /* nb blocks: compute(p) runs block k from din[p] to dout[p] on ks; after(k, p) follows it once the
+     * block's D2H is queued (the encoder's CRC over the frames in HBM) */
+    template <class Compute, class After>
+    int run(int nb, Compute compute, After after)
+    {
+        int rc = ICW_OK;
+        read_frames(hin[0], B);
+        for (int k = 0; k < nb && rc == ICW_OK; ++k) {
+            const int p = k & 1;
+            /* H2D(k): d_in[p] was last read by compute(k-2); d_out[p] by D2H(k-2), which compute(k) waits for */
+            if (k >= 2 && (hipStreamWaitEvent(cs, comp[p], 0) != hipSuccess || hipStreamWaitEvent(ks, d2h[p], 0) != hipSuccess))
+                rc = ICW_EDEVICE;
+            if (rc == ICW_OK && (hipMemcpyAsync(din[p], hin[p], in_b, hipMemcpyHostToDevice, cs) != hipSuccess ||
+                                 hipEventRecord(h2d[p], cs) != hipSuccess || hipStreamWaitEvent(ks, h2d[p], 0) != hipSuccess))
+                rc = ICW_EDEVICE;
+            if (rc == ICW_OK) rc = compute(p);
+            if (rc == ICW_OK && (hipEventRecord(comp[p], ks) != hipSuccess || hipStreamWaitEvent(cs, comp[p], 0) != hipSuccess ||
+                                 hipMemcpyAsync(hout[p], dout[p], out_b, hipMemcpyDeviceToHost, cs) != hipSuccess ||
+                                 hipEventRecord(d2h[p], cs) != hipSuccess))
+                rc = ICW_EDEVICE;
+            if (rc != ICW_OK) break;
+            if ((rc = after(k, p)) != ICW_OK) break;
+            /* host work overlapping the GPU: read block k+1 (after H2D(k-1) released its buffer),
+             * write block k-1 (after its D2H) */
+            if (k + 1 < nb) {
+                if (k >= 1 && hipEventSynchronize(h2d[(k + 1) & 1]) != hipSuccess) { rc = ICW_EDEVICE; break; }
+                read_frames(hin[(k + 1) & 1], B);
+            }
+            if (k >= 1) {
+                if (hipEventSynchronize(d2h[(k - 1) & 1]) != hipSuccess) { rc = ICW_EDEVICE; break; }
+                write_block(k - 1);
+            }
+        }
+        if (rc == ICW_OK && nb >= 1) {
+            if (hipEventSynchronize(d2h[(nb - 1) & 1]) != hipSuccess) rc = ICW_EDEVICE;
+            else write_block(nb - 1);
+        }
+        return rc;
+    }
+};
+
 /* One group of files sharing (rate, format, channels): one context, one stream per file. */
 int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::vector<Job *> &jobs,
               const icw_batch_opts &o, icw_batch_stats &st, int *status, const FileLists &fl = FileLists())
@@ -224,105 +405,15 @@ int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::v
         if (fwrite(hdr, 1, 44, j.out) != 44) status[j.idx] = ICW_EINVAL;
         if (fseeko(j.in, j.info.data_offset, SEEK_SET)) status[j.idx] = ICW_EINVAL;
     }
-    /* pinned double buffers, device double buffers, a copy stream */
-    const size_t in_b = (size_t)S * B * fsz, out_b = (size_t)S * B * osz;
-    unsigned char *hin[2] = {nullptr, nullptr}, *hout[2] = {nullptr, nullptr}, *din[2] = {nullptr, nullptr},
-                  *dout[2] = {nullptr, nullptr};
-    hipStream_t cs = nullptr, ks = nullptr;
-    hipEvent_t h2d[2] = {nullptr, nullptr}, comp[2] = {nullptr, nullptr}, d2h[2] = {nullptr, nullptr};
-    auto cleanup = [&]() {
-        if (cs) (void)hipStreamSynchronize(cs);
-        if (ks) (void)hipStreamSynchronize(ks);
-        for (int p = 0; p < 2; ++p) {
-            if (hin[p]) (void)hipHostFree(hin[p]);
-            if (hout[p]) (void)hipHostFree(hout[p]);
-            if (din[p]) (void)hipFree(din[p]);
-            if (dout[p]) (void)hipFree(dout[p]);
-            for (hipEvent_t e : {h2d[p], comp[p], d2h[p]}) if (e) (void)hipEventDestroy(e);
-        }
-        if (cs) (void)hipStreamDestroy(cs);
-        if (ks) (void)hipStreamDestroy(ks);
-    };
-    bool ok = true;
-    for (int p = 0; p < 2 && ok; ++p) {
-        ok = hipHostMalloc((void **)&hin[p], in_b, hipHostMallocDefault) == hipSuccess &&
-             hipHostMalloc((void **)&hout[p], out_b, hipHostMallocDefault) == hipSuccess &&
-             hipMalloc((void **)&din[p], in_b) == hipSuccess && hipMalloc((void **)&dout[p], out_b) == hipSuccess &&
-             hipEventCreateWithFlags(&h2d[p], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&comp[p], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&d2h[p], hipEventDisableTiming) == hipSuccess;
-    }
-    ok = ok && hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) == hipSuccess &&
-         hipStreamCreateWithFlags(&ks, hipStreamNonBlocking) == hipSuccess;
-    if (!ok) { cleanup(); return ICW_ENOMEM; }
-
-    const int nb = (int)((T + B - 1) / B);
-    /* xwave_read_samples for block k into hin[k&1]: data frames, then zero samples */
-    auto read_block = [&](int k) {
-        const double t0 = now_s();
-        unsigned char *buf = hin[k & 1];
-        for (int s = 0; s < S; ++s) {
-            Job &j = *jobs[s];
-            unsigned char *row = buf + (size_t)s * B * fsz;
-            const int64_t want = std::min<int64_t>(B, std::max<int64_t>(0, j.info.n_samples - j.read));
-            size_t got = 0;
-            if (want > 0 && status[j.idx] == ICW_OK) {
-                got = fread(row, fsz, (size_t)want, j.in);
-                if ((int64_t)got != want) status[j.idx] = ICW_EINVAL;      /* short read: broken file */
-                j.read += (int64_t)got;
-                st.frames_in += got;
-            }
-            memset(row + got * fsz, zero_byte(j.info.fmt), (size_t)(B - (int64_t)got) * fsz);
-        }
-        st.io_s += now_s() - t0;
-    };
-    auto write_block = [&](int k) {
-        const double t0 = now_s();
-        const unsigned char *buf = hout[k & 1];
-        for (int s = 0; s < S; ++s) {
-            Job &j = *jobs[s];
-            const int64_t n = std::min<int64_t>(B, j.total - j.written);
-            if (n <= 0 || status[j.idx] != ICW_OK) continue;
-            if (fwrite(buf + (size_t)s * B * osz, osz, (size_t)n, j.out) != (size_t)n) status[j.idx] = ICW_EINVAL;
-            j.written += n;
-            st.frames_out += (uint64_t)n;
-        }
-        st.io_s += now_s() - t0;
-    };
-
-    read_block(0);
-    for (int k = 0; k < nb && rc == ICW_OK; ++k) {
-        const int p = k & 1;
-        /* H2D(k): d_in[p] was last read by compute(k-2) */
-        if (k >= 2 && hipStreamWaitEvent(cs, comp[p], 0) != hipSuccess) rc = ICW_EDEVICE;
-        if (rc == ICW_OK && (hipMemcpyAsync(din[p], hin[p], in_b, hipMemcpyHostToDevice, cs) != hipSuccess ||
-                             hipEventRecord(h2d[p], cs) != hipSuccess || hipStreamWaitEvent(ks, h2d[p], 0) != hipSuccess))
-            rc = ICW_EDEVICE;
-        if (rc == ICW_OK)
-            rc = icw_process_streams(ctx, 0, S, din[p], (size_t)B * fsz, dout[p], (size_t)B * osz, B,
-                                     ICW_F_DEVICE_PTRS, nullptr, ks);
-        if (rc == ICW_OK && (hipEventRecord(comp[p], ks) != hipSuccess || hipStreamWaitEvent(cs, comp[p], 0) != hipSuccess ||
-                             hipMemcpyAsync(hout[p], dout[p], out_b, hipMemcpyDeviceToHost, cs) != hipSuccess ||
-                             hipEventRecord(d2h[p], cs) != hipSuccess))
-            rc = ICW_EDEVICE;
-        if (rc != ICW_OK) break;
-        /* host work overlapping the GPU: read block k+1 (after H2D(k-1) released its buffer),
-         * write block k-1 (after its D2H) */
-        if (k + 1 < nb) {
-            if (k >= 1 && hipEventSynchronize(h2d[(k + 1) & 1]) != hipSuccess) { rc = ICW_EDEVICE; break; }
-            read_block(k + 1);
-        }
-        if (k >= 1) {
-            if (hipEventSynchronize(d2h[(k - 1) & 1]) != hipSuccess) { rc = ICW_EDEVICE; break; }
-            write_block(k - 1);
-        }
-    }
-    if (rc == ICW_OK && nb >= 1) {
-        if (hipEventSynchronize(d2h[(nb - 1) & 1]) != hipSuccess) rc = ICW_EDEVICE;
-        else write_block(nb - 1);
-    }
+    GroupPipe pp(jobs, B, fsz, (size_t)osz, st, status);
+    if (!pp.alloc()) return ICW_ENOMEM;
+    rc = pp.run((int)((T + B - 1) / B),
+                [&](int p) {
+                    return icw_process_streams(ctx, 0, S, pp.din[p], (size_t)B * fsz, pp.dout[p], (size_t)B * osz, B,
+                                               ICW_F_DEVICE_PTRS, nullptr, pp.ks);
+                },
+                [](int, int) { return (int)ICW_OK; });
     if (rc == ICW_OK) rc = icw_synchronize(ctx);
-    cleanup();
     return rc;
 }
 
@@ -399,118 +490,34 @@ int run_enc_group(std::vector<Job *> &jobs, const EncSpec &o, icw_batch_stats &s
         if (fwrite(hdr, 1, sizeof(hdr), j.out) != sizeof(hdr)) status[j.idx] = ICW_EINVAL;
         if (fseeko(j.in, j.info.data_offset, SEEK_SET)) status[j.idx] = ICW_EINVAL;
     }
-    const size_t in_b = (size_t)S * B * fsz, out_b = (size_t)S * B * FB;
-    unsigned char *hin[2] = {nullptr, nullptr}, *hout[2] = {nullptr, nullptr}, *din[2] = {nullptr, nullptr},
-                  *dout[2] = {nullptr, nullptr};
-    hipStream_t cs = nullptr, ks = nullptr;
-    hipEvent_t h2d[2] = {nullptr, nullptr}, comp[2] = {nullptr, nullptr}, d2h[2] = {nullptr, nullptr};
-    auto cleanup = [&]() {
-        if (cs) (void)hipStreamSynchronize(cs);
-        if (ks) (void)hipStreamSynchronize(ks);
-        for (int p = 0; p < 2; ++p) {
-            if (hin[p]) (void)hipHostFree(hin[p]);
-            if (hout[p]) (void)hipHostFree(hout[p]);
-            if (din[p]) (void)hipFree(din[p]);
-            if (dout[p]) (void)hipFree(dout[p]);
-            for (hipEvent_t e : {h2d[p], comp[p], d2h[p]}) if (e) (void)hipEventDestroy(e);
-        }
-        if (cs) (void)hipStreamDestroy(cs);
-        if (ks) (void)hipStreamDestroy(ks);
-    };
-    bool ok = true;
-    for (int p = 0; p < 2 && ok; ++p) {
-        ok = hipHostMalloc((void **)&hin[p], in_b, hipHostMallocDefault) == hipSuccess &&
-             hipHostMalloc((void **)&hout[p], out_b, hipHostMallocDefault) == hipSuccess &&
-             hipMalloc((void **)&din[p], in_b) == hipSuccess && hipMalloc((void **)&dout[p], out_b) == hipSuccess &&
-             hipEventCreateWithFlags(&h2d[p], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&comp[p], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&d2h[p], hipEventDisableTiming) == hipSuccess;
-    }
-    ok = ok && hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) == hipSuccess &&
-         hipStreamCreateWithFlags(&ks, hipStreamNonBlocking) == hipSuccess;
-    if (!ok) { cleanup(); return ICW_ENOMEM; }
-
-    /* the next nfr input frames of every stream into buf: data frames, then the format's zero sample */
-    auto read_frames = [&](unsigned char *buf, int nfr) {
-        const double t0 = now_s();
-        for (int s = 0; s < S; ++s) {
-            Job &j = *jobs[s];
-            unsigned char *row = buf + (size_t)s * B * fsz;
-            const int64_t want = std::min<int64_t>(nfr, std::max<int64_t>(0, j.info.n_samples - j.read));
-            size_t got = 0;
-            if (want > 0 && status[j.idx] == ICW_OK) {
-                got = fread(row, fsz, (size_t)want, j.in);
-                if ((int64_t)got != want) status[j.idx] = ICW_EINVAL;      /* short read: broken file */
-                j.read += (int64_t)got;
-                st.frames_in += got;
-            }
-            memset(row + got * fsz, zero_byte(j.info.fmt), (size_t)(B - (int64_t)got) * fsz);
-        }
-        st.io_s += now_s() - t0;
-    };
-    std::vector<uint32_t> crc(S, 0u);
-    std::vector<uint64_t> off(S), len(S);
-    auto write_block = [&](int k) {
-        const double t0 = now_s();
-        const unsigned char *buf = hout[k & 1];
-        for (int s = 0; s < S; ++s) {
-            Job &j = *jobs[s];
-            const int64_t n = std::min<int64_t>(B, j.total - j.written);
-            if (n <= 0 || status[j.idx] != ICW_OK) continue;
-            if (fwrite(buf + (size_t)s * B * FB, FB, (size_t)n, j.out) != (size_t)n) status[j.idx] = ICW_EINVAL;
-            j.written += n;
-            st.frames_out += (uint64_t)n;
-        }
-        st.io_s += now_s() - t0;
-    };
-
+    GroupPipe pp(jobs, B, fsz, FB, st, status);
+    if (!pp.alloc()) return ICW_ENOMEM;
     /* aligned mode: the k_M/2 frames that are dropped go through first, on their own (so that neither the
      * CRC nor the clip counts see them) */
     if (skip) {
-        read_frames(hin[0], skip);
-        if (hipMemcpyAsync(din[0], hin[0], in_b, hipMemcpyHostToDevice, ks) != hipSuccess) rc = ICW_EDEVICE;
+        pp.read_frames(pp.hin[0], skip);
+        if (hipMemcpyAsync(pp.din[0], pp.hin[0], pp.in_b, hipMemcpyHostToDevice, pp.ks) != hipSuccess) rc = ICW_EDEVICE;
         if (rc == ICW_OK)
-            rc = encode(ctx, 0, S, din[0], (size_t)B * fsz, dout[0], (size_t)B * FB, skip, o.cw_format, ICW_F_DEVICE_PTRS, ks);
+            rc = encode(ctx, 0, S, pp.din[0], (size_t)B * fsz, pp.dout[0], (size_t)B * FB, skip, o.cw_format, ICW_F_DEVICE_PTRS, pp.ks);
         for (int s = 0; s < S && rc == ICW_OK; ++s) rc = icw_encode_clipped(ctx, s, 1, nullptr);
+        if (rc != ICW_OK) return rc;
     }
-    const int nb = (int)((T + B - 1) / B);
-    if (rc == ICW_OK) read_frames(hin[0], B);
-    for (int k = 0; k < nb && rc == ICW_OK; ++k) {
-        const int p = k & 1;
-        /* H2D(k): d_in[p] was last read by compute(k-2); d_out[p] by D2H(k-2), which compute(k) waits for */
-        if (k >= 2 && (hipStreamWaitEvent(cs, comp[p], 0) != hipSuccess || hipStreamWaitEvent(ks, d2h[p], 0) != hipSuccess))
-            rc = ICW_EDEVICE;
-        if (rc == ICW_OK && (hipMemcpyAsync(din[p], hin[p], in_b, hipMemcpyHostToDevice, cs) != hipSuccess ||
-                             hipEventRecord(h2d[p], cs) != hipSuccess || hipStreamWaitEvent(ks, h2d[p], 0) != hipSuccess))
-            rc = ICW_EDEVICE;
-        if (rc == ICW_OK)
-            rc = encode(ctx, 0, S, din[p], (size_t)B * fsz, dout[p], (size_t)B * FB, B, o.cw_format, ICW_F_DEVICE_PTRS, ks);
-        if (rc == ICW_OK && (hipEventRecord(comp[p], ks) != hipSuccess || hipStreamWaitEvent(cs, comp[p], 0) != hipSuccess ||
-                             hipMemcpyAsync(hout[p], dout[p], out_b, hipMemcpyDeviceToHost, cs) != hipSuccess ||
-                             hipEventRecord(d2h[p], cs) != hipSuccess))
-            rc = ICW_EDEVICE;
-        if (rc != ICW_OK) break;
-        /* this block's part of every file's CRC, from the frames in HBM (returns once the kernel is done) */
-        for (int s = 0; s < S; ++s) {
-            off[s] = (uint64_t)s * B * FB;
-            len[s] = (uint64_t)std::max<int64_t>(0, std::min<int64_t>(B, jobs[s]->total - (int64_t)k * B)) * FB;
-        }
-        if ((rc = icw_crc32_batch(dout[p], off.data(), len.data(), S, crc.data(), crc.data(), ICW_F_DEVICE_PTRS, o.device, ks)) !=
-            ICW_OK)
-            break;
-        if (k + 1 < nb) {
-            if (k >= 1 && hipEventSynchronize(h2d[(k + 1) & 1]) != hipSuccess) { rc = ICW_EDEVICE; break; }
-            read_frames(hin[(k + 1) & 1], B);
-        }
-        if (k >= 1) {
-            if (hipEventSynchronize(d2h[(k - 1) & 1]) != hipSuccess) { rc = ICW_EDEVICE; break; }
-            write_block(k - 1);
-        }
-    }
-    if (rc == ICW_OK && nb >= 1) {
-        if (hipEventSynchronize(d2h[(nb - 1) & 1]) != hipSuccess) rc = ICW_EDEVICE;
-        else write_block(nb - 1);
-    }
+    std::vector<uint32_t> crc(S, 0u);
+    std::vector<uint64_t> off(S), len(S);
+    rc = pp.run((int)((T + B - 1) / B),
+                [&](int p) {
+                    return encode(ctx, 0, S, pp.din[p], (size_t)B * fsz, pp.dout[p], (size_t)B * FB, B, o.cw_format,
+                                  ICW_F_DEVICE_PTRS, pp.ks);
+                },
+                /* this block's part of every file's CRC, from the frames in HBM (returns once the kernel is done) */
+                [&](int k, int p) {
+                    for (int s = 0; s < S; ++s) {
+                        off[s] = (uint64_t)s * B * FB;
+                        len[s] = (uint64_t)std::max<int64_t>(0, std::min<int64_t>(B, jobs[s]->total - (int64_t)k * B)) * FB;
+                    }
+                    return icw_crc32_batch(pp.dout[p], off.data(), len.data(), S, crc.data(), crc.data(), ICW_F_DEVICE_PTRS,
+                                           o.device, pp.ks);
+                });
     if (rc == ICW_OK) rc = icw_synchronize(ctx);
     for (int s = 0; s < S && rc == ICW_OK; ++s) {
         Job &j = *jobs[s];
@@ -522,58 +529,25 @@ int run_enc_group(std::vector<Job *> &jobs, const EncSpec &o, icw_batch_stats &s
         if (status[j.idx] == ICW_OK && (fseeko(j.out, 0, SEEK_SET) || fwrite(hdr, 1, sizeof(hdr), j.out) != sizeof(hdr)))
             status[j.idx] = ICW_EINVAL;
     }
-    cleanup();
     return rc;
 }
 
 /* icw_cwave_encode_files / icw_cwave_encode_files_iir after their option checks */
 int encode_files(const char *const *in_paths, const char *const *out_paths, int n, const EncSpec &o,
-                        icw_batch_stats *stats, uint64_t *clipped, int *status)
+                 icw_batch_stats *stats, uint64_t *clipped, int *status)
 {
-    const double t0 = now_s();
-    icw_batch_stats st;
-    memset(&st, 0, sizeof(st));
-    std::vector<int> stat_local(n > 0 ? n : 1, ICW_OK);
-    int *sts = status ? status : stat_local.data();
-    std::vector<Job> jobs(n);
-    std::map<std::tuple<uint32_t, uint32_t, uint32_t>, std::vector<Job *>> groups;
-    for (int i = 0; i < n; ++i) {
-        sts[i] = ICW_OK;
-        if (clipped) clipped[i] = 0;
-        Job &j = jobs[i];
-        j.idx = i;
-        if (!in_paths[i] || !out_paths[i] || icw_wav_parse_file(in_paths[i], &j.info) != ICW_OK ||
-            j.info.fmt >= ICW_FMT_CW_F64 ||                      /* a CWAVE file is analytic already */
-            j.info.n_samples < 2 || j.info.n_samples >= ((int64_t)1 << 32)) {
-            sts[i] = ICW_EINVAL;
-            continue;
-        }
-        if (!(j.in = fopen(in_paths[i], "rb")) || !(j.out = fopen(out_paths[i], "wb"))) {
-            sts[i] = ICW_EINVAL;
-            continue;
-        }
-        setvbuf(j.in, nullptr, _IOFBF, 1 << 20);
-        setvbuf(j.out, nullptr, _IOFBF, 1 << 20);
-        groups[std::make_tuple(j.info.sample_rate, j.info.fmt, j.info.channels)].push_back(&j);
-    }
-    int rc = ICW_OK;
-    for (auto &g : groups) {
-        const int r = run_enc_group(g.second, o, st, clipped, sts);
-        if (r != ICW_OK) {
-            rc = r;
-            for (Job *j : g.second) if (sts[j->idx] == ICW_OK) sts[j->idx] = r;
-        }
-        ++st.n_groups;
-    }
-    for (Job &j : jobs) {
-        if (j.in) fclose(j.in);
-        if (j.out && fclose(j.out) != 0 && sts[j.idx] == ICW_OK) sts[j.idx] = ICW_EINVAL;
-        if (sts[j.idx] == ICW_OK) ++st.n_files;
-        else if (rc == ICW_OK) rc = sts[j.idx];
-    }
-    st.wall_s = now_s() - t0;
-    if (stats) *stats = st;
-    return rc;
+    return for_file_groups(
+        in_paths, out_paths, n, stats, status,
+        [&](int i, Job &j) {
+            if (clipped) clipped[i] = 0;
+            if (accept_wav(in_paths[i], out_paths[i], &j.info) != ICW_OK ||
+                j.info.fmt >= ICW_FMT_CW_F64 ||                      /* a CWAVE file is analytic already */
+                j.info.n_samples < 2 || j.info.n_samples >= ((int64_t)1 << 32))
+                return (int)ICW_EINVAL;
+            return (int)ICW_OK;
+        },
+        [](int) { return 0; },
+        [&](int, std::vector<Job *> &g, icw_batch_stats &st, int *sts) { return run_enc_group(g, o, st, clipped, sts); });
 }
 
 }  // namespace
@@ -655,51 +629,15 @@ int icw_transcode_files(const icw_config *cfg, const icw_node *nodes, int n_node
                         int *status)
 {
     if (!cfg || n < 0 || (n > 0 && (!in_paths || !out_paths))) return ICW_EINVAL;
-    const double t0 = now_s();
     icw_batch_opts o;
     memset(&o, 0, sizeof(o));
     o.device = -1;
     if (opts) o = *opts;
-    icw_batch_stats st;
-    memset(&st, 0, sizeof(st));
-    std::vector<int> stat_local(n > 0 ? n : 1, ICW_OK);
-    int *sts = status ? status : stat_local.data();
-    std::vector<Job> jobs(n);
-    std::map<std::tuple<uint32_t, uint32_t, uint32_t>, std::vector<Job *>> groups;
-    for (int i = 0; i < n; ++i) {
-        sts[i] = ICW_OK;
-        Job &j = jobs[i];
-        j.idx = i;
-        if (!in_paths[i] || !out_paths[i] || (sts[i] = icw_wav_parse_file(in_paths[i], &j.info)) != ICW_OK) {
-            if (sts[i] == ICW_OK) sts[i] = ICW_EINVAL;
-            continue;
-        }
-        if (!(j.in = fopen(in_paths[i], "rb")) || !(j.out = fopen(out_paths[i], "wb"))) {
-            sts[i] = ICW_EINVAL;
-            continue;
-        }
-        setvbuf(j.in, nullptr, _IOFBF, 1 << 20);
-        setvbuf(j.out, nullptr, _IOFBF, 1 << 20);
-        groups[std::make_tuple(j.info.sample_rate, j.info.fmt, j.info.channels)].push_back(&j);
-    }
-    int rc = ICW_OK;
-    for (auto &g : groups) {
-        const int r = run_group(*cfg, nodes, n_nodes, g.second, o, st, sts);
-        if (r != ICW_OK) {
-            rc = r;
-            for (Job *j : g.second) if (sts[j->idx] == ICW_OK) sts[j->idx] = r;
-        }
-        ++st.n_groups;
-    }
-    for (Job &j : jobs) {
-        if (j.in) fclose(j.in);
-        if (j.out && fclose(j.out) != 0 && sts[j.idx] == ICW_OK) sts[j.idx] = ICW_EINVAL;
-        if (sts[j.idx] == ICW_OK) ++st.n_files;
-        else if (rc == ICW_OK) rc = sts[j.idx];
-    }
-    st.wall_s = now_s() - t0;
-    if (stats) *stats = st;
-    return rc;
+    return for_file_groups(
+        in_paths, out_paths, n, stats, status,
+        [&](int i, Job &j) { return accept_wav(in_paths[i], out_paths[i], &j.info); },
+        [](int) { return 0; },
+        [&](int, std::vector<Job *> &g, icw_batch_stats &st, int *sts) { return run_group(*cfg, nodes, n_nodes, g, o, st, sts); });
 }
 
 /* icw_transcode_files with file i's own list (include/icw_reader.h) */
@@ -708,82 +646,47 @@ int icw_transcode_files_lists(const icw_config *cfg, const icw_node *const *node
                               const icw_batch_opts *opts, icw_batch_stats *stats, int *status)
 {
     if (!cfg || n < 0 || (n > 0 && (!in_paths || !out_paths || !nodes || !n_nodes))) return ICW_EINVAL;
-    const double t0 = now_s();
     icw_batch_opts o;
     memset(&o, 0, sizeof(o));
     o.device = -1;
     if (opts) o = *opts;
-    icw_batch_stats st;
-    memset(&st, 0, sizeof(st));
-    std::vector<int> stat_local(n > 0 ? n : 1, ICW_OK);
-    int *sts = status ? status : stat_local.data();
-    std::vector<Job> jobs(n);
-    /* (rate, format, channels, list): -1 for the register-form lists, which share a context whatever
+    /* the group key's last part: -1 for the register-form lists, which share a context whatever
      * they are; a bus-form list (context-wide only) groups with the files that carry the same one */
-    std::map<std::tuple<uint32_t, uint32_t, uint32_t, int>, std::vector<Job *>> groups;
+    std::vector<int> form(n > 0 ? n : 1, 0);
     std::vector<int> bus_first;                     /* file index of each distinct bus-form list */
     auto same = [&](int a, int b) {
         const int ba = bypass_list ? bypass_list[a] : cfg->bypass_list, bb = bypass_list ? bypass_list[b] : cfg->bypass_list;
         return n_nodes[a] == n_nodes[b] && !ba == !bb &&
                (n_nodes[a] == 0 || !memcmp(nodes[a], nodes[b], (size_t)n_nodes[a] * sizeof(icw_node)));
     };
-    for (int i = 0; i < n; ++i) {
-        sts[i] = ICW_OK;
-        Job &j = jobs[i];
-        j.idx = i;
-        if (n_nodes[i] < 0 || (n_nodes[i] > 0 && !nodes[i])) {
-            sts[i] = ICW_EINVAL;
-            continue;
-        }
-        const int form = icw_graph_form(cfg, nodes[i], n_nodes[i], bypass_list ? bypass_list[i] : cfg->bypass_list);
-        if (form < 0) {
-            sts[i] = form;                          /* ICW_EGRAPH: the rest of the batch goes on */
-            continue;
-        }
-        if (!in_paths[i] || !out_paths[i] || (sts[i] = icw_wav_parse_file(in_paths[i], &j.info)) != ICW_OK) {
-            if (sts[i] == ICW_OK) sts[i] = ICW_EINVAL;
-            continue;
-        }
-        if (!(j.in = fopen(in_paths[i], "rb")) || !(j.out = fopen(out_paths[i], "wb"))) {
-            sts[i] = ICW_EINVAL;
-            continue;
-        }
-        setvbuf(j.in, nullptr, _IOFBF, 1 << 20);
-        setvbuf(j.out, nullptr, _IOFBF, 1 << 20);
-        int key = -1;
-        if (form == 1) {
-            for (size_t k = 0; k < bus_first.size() && key < 0; ++k)
-                if (same(bus_first[k], i)) key = (int)k;
-            if (key < 0) {
-                key = (int)bus_first.size();
-                bus_first.push_back(i);
+    return for_file_groups(
+        in_paths, out_paths, n, stats, status,
+        [&](int i, Job &j) {
+            if (n_nodes[i] < 0 || (n_nodes[i] > 0 && !nodes[i])) return (int)ICW_EINVAL;
+            form[i] = icw_graph_form(cfg, nodes[i], n_nodes[i], bypass_list ? bypass_list[i] : cfg->bypass_list);
+            if (form[i] < 0) return form[i];            /* ICW_EGRAPH: the rest of the batch goes on */
+            return accept_wav(in_paths[i], out_paths[i], &j.info);
+        },
+        [&](int i) {
+            int key = -1;
+            if (form[i] == 1) {
+                for (size_t k = 0; k < bus_first.size() && key < 0; ++k)
+                    if (same(bus_first[k], i)) key = (int)k;
+                if (key < 0) {
+                    key = (int)bus_first.size();
+                    bus_first.push_back(i);
+                }
             }
-        }
-        groups[std::make_tuple(j.info.sample_rate, j.info.fmt, j.info.channels, key)].push_back(&j);
-    }
-    int rc = ICW_OK;
-    for (auto &g : groups) {
-        FileLists fl;
-        fl.nodes = nodes;
-        fl.n_nodes = n_nodes;
-        fl.bypass = bypass_list;
-        fl.per_stream = std::get<3>(g.first) < 0;
-        const int r = run_group(*cfg, nullptr, 0, g.second, o, st, sts, fl);
-        if (r != ICW_OK) {
-            rc = r;
-            for (Job *j : g.second) if (sts[j->idx] == ICW_OK) sts[j->idx] = r;
-        }
-        ++st.n_groups;
-    }
-    for (Job &j : jobs) {
-        if (j.in) fclose(j.in);
-        if (j.out && fclose(j.out) != 0 && sts[j.idx] == ICW_OK) sts[j.idx] = ICW_EINVAL;
-        if (sts[j.idx] == ICW_OK) ++st.n_files;
-        else if (rc == ICW_OK) rc = sts[j.idx];
-    }
-    st.wall_s = now_s() - t0;
-    if (stats) *stats = st;
-    return rc;
+            return key;
+        },
+        [&](int key, std::vector<Job *> &g, icw_batch_stats &st, int *sts) {
+            FileLists fl;
+            fl.nodes = nodes;
+            fl.n_nodes = n_nodes;
+            fl.bypass = bypass_list;
+            fl.per_stream = key < 0;
+            return run_group(*cfg, nullptr, 0, g, o, st, sts, fl);
+        });
 }
 
 }  /* extern "C" */

@@ -907,9 +907,6 @@ int clear_slot(icw_ctx *c, int slot)
                ? ICW_OK : ICW_EDEVICE;
 }
 
-/* the device's Hilbert phases of streams [first, ...): [stream][L, R] */
-const uint32_t *ds_phase_of(const icw_ctx *c, int first) { return c->st.hq_phase + (size_t)first * 2; }
-
 /* the output slot replace_output_plug clears for node n (adv_modulator.c:180-205): Shift / PM / Mix
  * own one, a Master none (-1) */
 int plug_slot(const icw_node &n)
@@ -961,12 +958,6 @@ void matched_clears(const std::vector<icw_node> &o, const std::vector<icw_node> 
         if (plug_slot(o[i]) < 0) continue;
         if (i >= nv.size() || nv[i].mode != o[i].mode || nv[i].n_out != o[i].n_out) clears.push_back(o[i].n_out);
     }
-}
-
-/* the normalised list stream s runs */
-const std::vector<icw_node> &stream_list(const icw_ctx *c, int s)
-{
-    return c->progs.empty() ? c->nodes : c->plists[(size_t)c->prog_of[(size_t)s]];
 }
 
 bool same_list(const std::vector<icw_node> &a, const std::vector<icw_node> &b)
@@ -1683,405 +1674,99 @@ int icw_set_hilbert_config(icw_ctx *c, int kahan, int subnorm_reject)
 
 int icw_render_size(const icw_ctx *c) { return c ? (c->cfg.need24bits ? 3 : 2) : ICW_EINVAL; }
 
-int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t in_stride, void *out,
-                        size_t out_stride, int n_frames, unsigned flags, void *dbg, void *hip_stream)
-{
-    if (!c || first < 0 || count <= 0 || first + count > c->n_streams || n_frames < 0 || !in || !out)
-        return ICW_EINVAL;
-    if (n_frames == 0) return ICW_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (set_dev(c)) return ICW_EDEVICE;
-    ++c->calls;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    /* A NULL handle with device pointers means the legacy default stream (torch's default stream):
-     * the call starts after the work already queued there, and returns when its results are in
-     * place, so that stream's later work sees them.  The end is a host wait, not an operation on the
-     * null stream: a null-stream wait behind the context's CU-masked streams cost C2 13-25 % (its
-     * implicit synchronisation with every blocking stream serialises the block pipeline). */
-    const bool legacy = !hip_stream && (flags & ICW_F_DEVICE_PTRS);
-    if (legacy && (hipEventRecord(c->join, nullptr) != hipSuccess || hipStreamWaitEvent(st, c->join, 0) != hipSuccess))
-        return ICW_EDEVICE;
-    const icw_config &cfg = c->cfg;
-    const unsigned csz = fmt_size(cfg.in_format);
-    const unsigned nch = cfg.in_channels;
-    const unsigned fsz = csz * nch;
-    const int osz = 2 * (cfg.need24bits ? 3 : 2);
-    const bool dev = flags & ICW_F_DEVICE_PTRS;
-    const bool timing = flags & 4u;
-    /* ICW_F_DEBUG_INPUT: K0's output of every launch block is copied aside (test hook, host dbg) */
-    const bool xin = flags & ICW_F_DEBUG_INPUT;
-    if (xin && (dev || !dbg || (flags & ICW_F_DEBUG_PRE) || c->cfg.in_format >= ICW_FMT_CW_F64 || c->fir_M > 0 ||
-                c->cfg.fp_check))
-        return ICW_EINVAL;
-    const size_t S = (size_t)count;
-    if (!dev && (in_stride < (size_t)n_frames * fsz || out_stride < (size_t)n_frames * osz)) return ICW_EINVAL;
+}  /* extern "C" */
 
-    /* FIR Hilbert converter (icw_set_fir_hilbert): real input becomes complex samples in KF and
-     * the block continues as CWAVE input does */
-    const bool fir = c->fir_M > 0 && cfg.in_format < ICW_FMT_CW_F64;
-    const bool cw = cfg.in_format >= ICW_FMT_CW_F64 || fir;
-    /* the list of the call's streams: the context's one, the one table entry all of them run, or --
-     * streams with different lists -- the table with K2's per-stream selection (prepare_mix) */
-    const IcwProg *lp = &c->prog, *dP = c->d_prog;
+namespace {
+
+/* ---- the call plan ---- */
+
+/* One call's resolved configuration.  It lives on the stack of the entry point, is filled once
+ * (resolve_plan, stage_io, size_scratch, pick_streams; the encoders fill what their kernels read) and
+ * is only read after that.  Its builders are the one place each kernel-argument struct is filled;
+ * the structs are zeroed first and returned by value (the kernels read them whole). */
+struct CallPlan {
+    /* the context, the call's range (count and first also as sizes) and the caller's buffers */
+    icw_ctx *const c;
+    const icw_config &cfg;
+    DevState &ds;
+    const int first, count, n_frames;
+    const size_t S, f0;
+    const void *const in;
+    void *const out, *dbg = nullptr;
+    const size_t in_stride, out_stride;
+    const unsigned flags;
+    const bool dev, legacy;
+    bool timing = false, xin = false;
+    /* the resolved format */
+    unsigned csz = 0, nch = 0, fsz = 0;
+    int osz = 0;
+    unsigned long long ssr = 0;
+    /* the list in use */
+    const IcwProg *lp = nullptr, *dP = nullptr;
     bool mix = false;
-    if (!c->progs.empty()) {
-        const int32_t e0 = c->prog_of[(size_t)first];
-        for (int i = 1; i < count && !mix; ++i) mix = c->prog_of[(size_t)(first + i)] != e0;
-        if (mix) {
-            const int rc = prepare_mix(c, first, count, st);
-            if (rc != ICW_OK) return rc;
-            lp = &c->mix;
-            dP = c->d_progs;
-        } else {
-            lp = &c->progs[(size_t)e0];
-            dP = c->d_progs + e0;
-        }
-    }
-    const IcwProg &LP = *lp;
-    const int n_slabs = mix ? c->pid_slabs : 1;
-    const bool bus = LP.is_bus;
-    /* mono dedup: every stream of the call known to hold identical left / right converters */
-    const bool fcm = c->cfg.fp_check != 0;                /* FP_CHECK: FC() kernels, no shortcuts */
-    bool dedup = !cw && !fcm && nch == 1 && c->tn.dedup_ok && (c->tn.k1_mode <= 0 || c->tn.k1_mode == 3);   /* plain / row K1 */
-    for (int i = 0; dedup && i < count; ++i) dedup = c->lr_known[first + i] != 0;
-    /* K1 variant of this call.  Auto: the row-broadcast kernel (4 chains per wave, ~17 % fewer
-     * instructions per sample) when its waves fit k1_wpc per CU on at most half the chip, else the
-     * lane-per-chain kernel (64 chains per wave).  The row kernel needs Kahan + the reject.  (Round
-     * 1 kept it off with a serial render; with the partition working, C5 gains 9 % from it.) */
-    const int row_waves = (int)(((dedup ? count : 2L * count) + 3) / 4) * 2;
-    const bool row_ok = cfg.iir_kahan && cfg.iir_subnorm_reject;
-    int k1_mode = c->tn.k1_mode;
-    if (k1_mode < 0) k1_mode = (row_ok && row_waves <= (c->n_cu / 2) * c->tn.k1_wpc) ? 3 : 0;
-    if (k1_mode == 3 && !row_ok) k1_mode = 0;
-    if (fcm) k1_mode = ICW_K1_FC;
-    if (!cw) c->last_k1 = k1_mode;
-    /* launch blocks.  The tail taper (plan_blocks) is on by default where it fits: a small batch
-     * (the row kernel K1r) with a serial render -- its drain is the render of the last block, and
-     * the frame-parallel kernels take well under K1r's time per frame (C5: +2 %).  Large batches
-     * keep uniform blocks (K0 + K2 take ~0.9 of K1's time there), ICW_TAPER overrides. */
-    /* FIR converter: fused with the graph and render (KF2, one kernel per block) where its LDS fits;
-     * else KF on its own stream (the caller's: K1's, idle without the IIR) beside K2.  KF2 needs no
-     * block scratch and has no recurrence to pipeline against, so its blocks are as long as the
-     * scratch bound allows (fewer launches, fewer partly filled waves of workgroups at their ends) */
-    const bool fir_fused = fir && c->tn.fir_fuse &&
-                           icw_fir_graph_lds(c->fir_M, c->fir_nt, (int)nch, LP.chain ? 0 : LP.n_regs) > 0 &&
-                           !LP.is_bus;
-    /* The row kernel without a serial render (C2) has K2 at ~0.16 of K1r's time per frame: 65 536-frame
-     * blocks (a quarter of the launches, of their gaps and prologues) ending in a steep tail
-     * (65 536 -> 16 384 -> 4 096 -> 1 024: the drain stays one short K2) measured +0.8 % on C2
-     * (3 170 -> 3 196 Msamples/s; 32 768 with r = 0.5 +0.5 %, 65 536 with no tail +0.5 %). */
-    const bool row_long = !cw && k1_mode == 3 && !c->serial_render && !c->tn.block_env && n_frames >= 4 * kMaxBlockFrames;
-    /* a dithered render with the flat shaper, rendered frame-parallel in the output kernel (K2 / KF2 /
-     * K5) from K3a's dither rows (needs_serial) */
-    const bool dith_par = !c->serial_render && cfg.render.render_type != ICW_RENDER_ROUND;
-    /* (with a dither generator, blocks of kMaxBlockFrames let K3a of the next block run beside KF2) */
-    const bool fir_long = fir_fused && dev && !c->serial_render && !bus && !dith_par;
-    const int Tb = std::min(n_frames, ((fir_fused || row_long) && !c->tn.block_env)
-                                          ? (fir_long ? kMaxFirBlockFrames : kMaxBlockFrames) : c->tn.max_block);
-    const double taper = c->tn.taper >= 0.0 ? c->tn.taper
-                       : (!cw && k1_mode == 3) ? (c->serial_render ? kAutoTaper : (row_long ? kRowTaper : 0.0)) : 0.0;
-    /* the fused FIR converter with a serial render (c5fir): the render of block 0 waits for its
-     * converter and dither alone, so block 0 is short and the next ones ramp up (kFirRenderRamp:
-     * profiles/r04_c5fir_timeline_after.txt had 2.2 ms of fill in a 24.3 ms step) */
-    const bool fir_ramp = fir_fused && c->serial_render && !c->tn.block_env && c->tn.first_block > 0;
-    const std::vector<std::pair<int, int>> blocks =
-        fir_ramp ? plan_blocks(n_frames, Tb, c->tn.first_block_env ? c->tn.first_block : kFirRenderFirst, 0.0, c->tn.taper_min,
-                               c->tn.fir_ramp > 0.0 ? c->tn.fir_ramp : kFirRenderRamp)
-                 : plan_blocks(n_frames, Tb, fir_fused ? 0 : c->tn.first_block, taper, c->tn.taper_min);
-    const int n_blocks = (int)blocks.size();
-    /* K5 (icw_stream1): one stream, one block, the row recurrence, register-form graph, ROUND / flat */
-    const bool s1 = c->tn.stream1 && count == 1 && n_blocks == 1 && !cw && !fcm && k1_mode == 3 && !c->serial_render &&
-                    !bus && n_frames <= ICW_S1_MAX && !xin;
-
-    const unsigned char *d_in;
-    unsigned char *d_out;
-    size_t dis, dos;
-    /* a small host-pointer call stages through pinned memory (asynchronous copies, one wait) */
-    const size_t stage_in = (size_t)n_frames * fsz * S, stage_out = (size_t)n_frames * osz * S;
-    const bool pinned = !dev && stage_in + stage_out + 16 <= kPinnedStage;
-    /* pinned host buffers on a call of several launch blocks: each block's input slice goes in and
-     * its output slice comes out on the copy stream, beside the other blocks' kernels */
-    const bool pipe_io = !dev && !pinned && n_blocks > 1 && !c->tn.serialize && host_pinned(in, c->device) && host_pinned(out, c->device);
-    bool zcopy = false;
-    if (pinned) {
-        if (c->h_stage_bytes < stage_in + stage_out + 16) {
-            if (c->h_stage) (void)hipHostFree(c->h_stage);
-            c->h_stage = nullptr;
-            c->h_stage_bytes = 0;
-            if (hipHostMalloc((void **)&c->h_stage, kPinnedStage, hipHostMallocDefault) != hipSuccess) return ICW_ENOMEM;
-            c->h_stage_bytes = kPinnedStage;
-            void *dp = nullptr;
-            c->h_stage_dev = hipHostGetDevicePointer(&dp, c->h_stage, 0) == hipSuccess ? (unsigned char *)dp : nullptr;
-            if (!c->h_stage_dev) (void)hipGetLastError();
-        }
-        zcopy = c->tn.zero_copy && c->h_stage_dev && !(flags & ICW_F_DEBUG_PRE);
-    }
-    if (dev) {
-        d_in = (const unsigned char *)in;
-        d_out = (unsigned char *)out;
-        dis = in_stride;
-        dos = out_stride;
-    } else {
-        dis = (size_t)n_frames * fsz;
-        dos = (size_t)n_frames * osz;
-        if (grow((void **)&c->d_in, &c->d_in_bytes, dis * S)) return ICW_ENOMEM;
-        if (grow((void **)&c->d_out, &c->d_out_bytes, dos * S + 16)) return ICW_ENOMEM;
-        if (pinned) {
-            for (size_t i = 0; i < S; ++i)
-                memcpy(c->h_stage + i * dis, (const unsigned char *)in + i * in_stride, dis);
-            if (!zcopy && hipMemcpyAsync(c->d_in, c->h_stage, dis * S, hipMemcpyHostToDevice, st) != hipSuccess)
-                return ICW_EDEVICE;
-        } else if (!pipe_io &&
-                   hipMemcpy2DAsync(c->d_in, dis, in, in_stride, dis, S, hipMemcpyHostToDevice, st) != hipSuccess) {
-            return ICW_EDEVICE;
-        }
-        /* zero copy: K0 reads the staged input across PCIe and the last kernel writes the output
-         * (and icw_advance the error flag) straight into the staging buffer -- a few KB, where the
-         * two DMA transfers each cost a setup latency (the 576-frame drop-in) */
-        d_in = zcopy ? c->h_stage_dev : c->d_in;
-        d_out = zcopy ? c->h_stage_dev + stage_in : c->d_out;
-    }
-    /* K5 on the zero-copy buffer: the kernel stores the call's sequence number after its output and
-     * the host polls for it -- no completion signal and no waking of a waiting thread.  The word is
-     * 4-byte aligned inside the output's 16 spare bytes, after the error flag. */
-    const bool s1_poll = s1 && zcopy && c->tn.spin_wait && !timing && !c->s1_stamps;
-    const size_t done_off = ((stage_in + dos * S + sizeof(int) + 3) & ~(size_t)3) - stage_in;
-    uint32_t s1_seq = 0u;
-    if (s1_poll) {
-        if (++c->s1_seq == 0u) ++c->s1_seq;           /* 0 is never a call's number */
-        s1_seq = c->s1_seq;
-        /* the word sits in the reused staging buffer, where an earlier, larger call may have left
-         * input or output bytes that happen to equal this call's number: store a value that cannot
-         * match before the launch (which orders after this store), so the poll sees only the
-         * kernel's own store */
-        __atomic_store_n((uint32_t *)(c->h_stage + stage_in + done_off), ~s1_seq, __ATOMIC_RELEASE);
-    }
-    std::vector<uint32_t> xin_phase;
-    if (xin) {
-        if (grow((void **)&c->d_xin, &c->d_xin_bytes, S * 2 * (size_t)n_frames * sizeof(double))) return ICW_ENOMEM;
-        xin_phase.resize(S * 2);
-        if (hipMemcpyAsync(xin_phase.data(), ds_phase_of(c, first), S * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st) !=
-                hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return ICW_EDEVICE;
-    }
+    int n_slabs = 1;
+    size_t slab_stride = 0;
+    /* the mode flags */
+    bool cw = false, fir = false, fir_fused = false, fir_async = false, bus = false, fcm = false, dedup = false;
+    bool dither = false, dith_par = false, table = false, in_step = false, s1 = false;
+    int k1_mode = 0, row_waves = 0;
+    /* the block plan */
+    std::vector<std::pair<int, int>> blocks;
+    int n_blocks = 0, n_sets = 1, Tb = 0;
+    size_t w_pitch = 0, x_pitch = 0;
+    /* device pointers and strides; the host-pointer paths */
+    const unsigned char *d_in = nullptr;
+    unsigned char *d_out = nullptr;
+    size_t dis = 0, dos = 0;
     double *d_pre = nullptr;
-    if (flags & ICW_F_DEBUG_PRE) {
-        if (!dbg) return ICW_EINVAL;
-        if (dev) d_pre = (double *)dbg;
-        else {
-            if (grow((void **)&c->d_pre, &c->d_pre_bytes, S * (size_t)n_frames * 2 * sizeof(double))) return ICW_ENOMEM;
-            d_pre = c->d_pre;
-        }
+    size_t stage_in = 0, done_off = 0;
+    bool pinned = false, pipe_io = false, zcopy = false, s1_poll = false;
+    uint32_t s1_seq = 0u;
+    std::vector<uint32_t> xin_phase;
+    /* the streams: the caller's (a NULL handle with device pointers is the legacy default stream), then
+     * the pipeline's */
+    const hipStream_t st;
+    hipStream_t sK = nullptr, sA = nullptr, sD = nullptr, sR = nullptr, sF = nullptr, sC = nullptr;
+
+    CallPlan(icw_ctx *c_, int first_, int count_, const void *in_, size_t in_stride_, void *out_, size_t out_stride_,
+             int n_frames_, unsigned flags_, void *hip_stream)
+        : c(c_), cfg(c_->cfg), ds(c_->st), first(first_), count(count_), n_frames(n_frames_), S((size_t)count_), f0((size_t)first_), in(in_), out(out_),
+          in_stride(in_stride_), out_stride(out_stride_), flags(flags_), dev(flags_ & ICW_F_DEVICE_PTRS),
+          legacy(!hip_stream && (flags_ & ICW_F_DEVICE_PTRS)), st(hip_stream ? (hipStream_t)hip_stream : c_->stream) {}
+
+    /* what K0 and the FIR converter take alike: the reader's side of block b */
+    template <class A>
+    void reader_args(A &a, int b) const
+    {
+        a.in = d_in + (size_t)blocks[b].first * fsz;
+        a.in_stride = dis;
+        a.fmt = c->cfg.in_format;
+        a.csz = csz;
+        a.fsz = fsz;
+        a.nch = nch;
+        a.n_streams = count;
+        a.T = blocks[b].second;
+        a.t0 = blocks[b].first;
+        a.pos = c->st.pos + f0;
+        a.fade = c->st.fade + f0 * 3;
     }
 
-    const int N = c->nord;
-    const size_t w_pitch = (size_t)Tb + N + 1;
-    const size_t x_pitch = ((size_t)Tb + ICW_MAX_IIR_ORDER + 2) & ~(size_t)1;   /* look-ahead pad */
-    const int n_sets = std::min(n_blocks, c->tn.max_sets);
-    for (int p = 0; p < n_sets && !fir_fused; ++p) {
-        if (!cw && grow((void **)&c->w[p], &c->w_bytes[p], S * 4 * w_pitch * sizeof(double))) return ICW_ENOMEM;
-        if (grow((void **)&c->xd[p], &c->xd_bytes[p], S * 4 * x_pitch * sizeof(double))) return ICW_ENOMEM;
-    }
-    if (c->serial_render && !d_pre)
-        for (int p = 0; p < n_sets; ++p)
-            if (grow((void **)&c->rpre[p], &c->rpre_bytes[p], S * (size_t)Tb * 2 * sizeof(double))) return ICW_ENOMEM;
-    /* the shared rotation table pays from two streams on; one stream computes its factors inline */
-    const bool table = LP.needs_omega && !bus && LP.n_trig > 0 && count > 1;
-    bool in_step = table;
-    for (int i = 1; in_step && i < count; ++i) in_step = c->nf_host[first + i] == c->nf_host[first];
-    /* per-stream lists: one slab per program that has one (prepare_mix), all of the widest one's pitch */
-    const size_t slab_stride = (size_t)((Tb + 7) & ~7) * 2 * (size_t)LP.n_trig;
-    if (table && grow((void **)&c->trig, &c->trig_bytes, (size_t)n_slabs * slab_stride * sizeof(double)))
-        return ICW_ENOMEM;
-    if (bus)
-        for (int p = 0; p < n_sets; ++p)
-            if (grow((void **)&c->iq[p], &c->iq_bytes[p], S * (size_t)Tb * 4 * sizeof(double))) return ICW_ENOMEM;
-    const bool dither = cfg.render.render_type != ICW_RENDER_ROUND;     /* K3a: serial or frame-parallel render */
-    if (dither)
-        for (int p = 0; p < n_sets; ++p)
-            if (grow((void **)&c->dith[p], &c->dith_bytes[p], S * 2 * (size_t)(Tb + 1) * sizeof(double))) return ICW_ENOMEM;
-    if (dither) {
-        /* chunk rows: 2^26 words (256 MB) shared among the G generators, but never less than 1 024 frames
-         * of the widest draw (GAUSS, 24 words per sample) and never more than the block's.  The floor
-         * wins over the 2^26 share from 2 731 generators on, so the buffer is G * cap <= max(2^26,
-         * 24 576 G) words: 256 MB up to there, 96 KB per generator beyond */
-        const size_t G = S * 2;
-        size_t cap = std::max<size_t>(((size_t)1 << 26) / G, (size_t)24 * 1024);
-        cap = std::min(cap, (size_t)24 * (size_t)(Tb + 1));
-        cap = (cap + 3) & ~(size_t)3;                      /* rows 16-byte aligned */
-        if (grow((void **)&c->dwords, &c->dwords_bytes, G * cap * 4) ||
-            grow((void **)&c->dbk, &c->dbk_bytes, G * ICW_DBK * 4) ||
-            grow((void **)&c->dflag, &c->dflag_bytes, G * 4))
-            return ICW_ENOMEM;
-        c->dwcap = cap;
-    }
-
-    /* Streams.  sK runs the IIR state kernel K1 (the serial, issue-bound one); sA runs the input
-     * prep K0, the output kernel K2 and the serial graph / render; sD the dither generator.  When
-     * K1 needs few CUs (4 waves per CU, one per SIMD) sK is confined to those CUs and sA / sD to
-     * the rest, so the frame-parallel kernels never share a SIMD with a recurrence. */
-    hipStream_t sK = st, sA = c->stream2, sD = c->stream3, sR = c->stream4;
-    /* sF: an unmasked stream for the pipeline's fill and drain under the CU partition -- K0 of the
-     * first block and K2 of the last run while no recurrence does, so they get the whole chip
-     * instead of the partition's share (C3 / C4: the drain was one partitioned K2, ~5 % of a step) */
-    hipStream_t sF = nullptr;
-    /* One launch block: K0 -> K1 -> K2 run in sequence anyway, so everything goes on the caller's
-     * stream -- no cross-stream event waits, which cost the 576-frame drop-in call ~135 us (C1
-     * p50 361 -> 226 us per call). */
-    if (c->tn.serialize || n_blocks == 1) {
-        sA = sD = sR = st;
-    } else if (!cw) {
-        /* plain K1: 128-lane groups of 32 streams (64 with the dedup); the variants: a lane per chain */
-        const int k1_waves = (k1_mode == 0 || k1_mode == ICW_K1_FC) ? ((count + (dedup ? 63 : 31)) / (dedup ? 64 : 32)) * 2
-                           : row_waves;
-        constexpr int kXcd = 8;                               /* MI355X: 8 XCDs */
-        const int k1_cus = ((k1_waves + c->tn.k1_wpc - 1) / c->tn.k1_wpc + kXcd - 1) / kXcd * kXcd;
-        if (c->tn.cu_split && k1_cus * 2 <= c->n_cu) {
-            const CuSplit *cs = cu_split(c, k1_cus);
-            if (!cs) return ICW_EDEVICE;
-            sK = cs->k1;
-            sA = cs->rest;
-            sD = cs->dith;
-            sR = cs->render;
-            if (c->tn.fill_drain) sF = c->stream2;
-        }
-    } else {
-        /* complex input or the FIR converter: no recurrence kernel, so the dither generator runs after
-         * the converter / output kernel on sA, beside the serial render of the previous block on sR.
-         * On its own stream it shared a hardware queue with the render (4 queues per process,
-         * GPU_MAX_HW_QUEUES, streams dealt round-robin): K3a of block b + 1 waited for the render of block b,
-         * 1.2 of every 6.7 ms per c5fir block (profiles/r04_c5fir_timeline.txt).  With a frame-parallel
-         * render (no render stream) it gets a stream of its own, ahead of the converter. */
-        sD = dith_par ? c->stream3 : sA;
-    }
-    hipStream_t sC = pipe_io ? c->stream_io : nullptr;
-    if (pipe_io && (int)c->ev_io.size() < n_blocks) {
-        while ((int)c->ev_io.size() < n_blocks) {
-            hipEvent_t e;
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return ICW_EDEVICE;
-            c->ev_io.push_back(e);
-        }
-    }
-    /* every stream starts after everything already queued on st (inputs, previous calls); a call
-     * whose kernels all run on st (one launch block: the drop-in) records no event -- the marker
-     * packet sat in front of its kernel on the queue */
-    bool other = false;
-    for (hipStream_t x : {sK, sA, sD, sR, sF, sC}) other = other || (x && x != st);
-    if (other && hipEventRecord(c->join, st) != hipSuccess)
-        return ICW_EDEVICE;
-    for (hipStream_t x : {sK, sA, sD, sR, sF, sC})
-        if (x && x != st && hipStreamWaitEvent(x, c->join, 0) != hipSuccess) return ICW_EDEVICE;
-
-    DevState &ds = c->st;
-    const size_t f0 = (size_t)first;
-    if (timing && (int)c->ev.size() < 4 * n_blocks) {
-        while ((int)c->ev.size() < 4 * n_blocks) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return ICW_EDEVICE;
-            c->ev.push_back(e);
-        }
-    }
-    const unsigned long long ssr = (unsigned long long)cfg.sample_rate * ICW_HZ_SCALE;
-
-    const bool fir_async = fir && !fir_fused && sK != sA;
-    /* KF's arguments for launch block b; it reads the history buffer the previous block wrote
-     * (same stream, block order) and writes the other one */
-    auto fir_args = [&](int b) {
-        IcwFirArgs af;
-        memset(&af, 0, sizeof(af));
-        af.in = d_in + (size_t)blocks[b].first * fsz;
-        af.in_stride = dis;
-        af.fmt = cfg.in_format;
-        af.csz = csz;
-        af.fsz = fsz;
-        af.nch = nch;
-        af.n_streams = count;
-        af.T = blocks[b].second;
-        af.t0 = blocks[b].first;
-        af.pos = ds.pos + f0;
-        af.fade = ds.fade + f0 * 3;
-        af.M = c->fir_M;
-        af.nt = c->fir_nt;
-        af.g = c->d_fir_g;
-        const size_t hrow = 2 * (size_t)c->fir_M;
-        af.hist_in = c->fir_hist[(c->fir_par + b) & 1] + f0 * hrow;
-        af.hist_out = c->fir_hist[(c->fir_par + b + 1) & 1] + f0 * hrow;
-        af.xd = c->xd[b % n_sets];
-        af.x_pitch = x_pitch;
-        af.sig = LP.chain ? LP.sig : 0;
-        {
-            /* mono input through a Master-only chain (signature count 1, mode MASTER, chain_in `in`:
-             * ICW_SIG_M) whose gains are bit-identical: L and R are one computation */
-            const IcwOp &m = LP.ops[0];
-            af.lr_same = nch == 1 && LP.chain && (LP.sig & ~ICW_SIG_UNIT) == ICW_SIG_M &&
-                         !memcmp(&m.gain[0], &m.gain[1], sizeof(double)) && m.unit_gain[0] == m.unit_gain[1];
-        }
-        return af;
-    };
-    /* pinned host input: block b's input slice of every stream goes in on the copy stream, and the
-     * stream of the block's first reader (K0, KF or the fused KF2) waits for it */
-    auto io_in = [&](int b, hipStream_t s0) -> int {
-        if (!pipe_io) return ICW_OK;
-        const int t0 = blocks[b].first, T = blocks[b].second;
-        if (hipMemcpy2DAsync(c->d_in + (size_t)t0 * fsz, dis, (const unsigned char *)in + (size_t)t0 * fsz, in_stride,
-                             (size_t)T * fsz, S, hipMemcpyHostToDevice, sC) != hipSuccess ||
-            hipEventRecord(c->ev_io[b], sC) != hipSuccess || hipStreamWaitEvent(s0, c->ev_io[b], 0) != hipSuccess)
-            return ICW_EDEVICE;
-        return ICW_OK;
-    };
-    /* K0 of block b on sA: xd[p] was last read by K1 of block b-2 (and, complex input, by K2 of
-     * block b-2, which precedes it on sA) */
-    auto k0_args = [&](int b) {
-        const int t0 = blocks[b].first, T = blocks[b].second, p = b % n_sets;
+    /* K0 of block b: xd[p] was last read by K1 of block b-2 (and, complex input, by K2 of block
+     * b-2, which precedes it on sA) */
+    IcwK0Args k0_args(int b) const
+    {
         IcwK0Args a0;
         memset(&a0, 0, sizeof(a0));
-        a0.in = d_in + (size_t)t0 * fsz;
-        a0.in_stride = dis;
-        a0.fmt = cfg.in_format;
-        a0.csz = csz;
-        a0.fsz = fsz;
-        a0.nch = nch;
-        a0.n_streams = count;
-        a0.T = T;
-        a0.t0 = t0;
-        a0.pos = ds.pos + f0;
-        a0.fade = ds.fade + f0 * 3;
-        a0.hq_phase = ds.hq_phase + f0 * 2;
-        a0.xd = c->xd[p];
+        reader_args(a0, b);
+        a0.hq_phase = c->st.hq_phase + f0 * 2;
+        a0.xd = c->xd[b % n_sets];
         a0.x_pitch = x_pitch;
         a0.dedup = dedup ? 1 : 0;
         return a0;
-    };
-    auto launch_k0 = [&](int b) -> int {
-        if (fir_fused) return ICW_OK;                   /* KF2 converts inside the block's kernel */
-        const int p = b % n_sets;
-        const IcwK0Args a0 = k0_args(b);
-        if (b >= n_sets && !cw && sK != sA && hipStreamWaitEvent(sA, c->k1done[p], 0) != hipSuccess) return ICW_EDEVICE;
-        hipStream_t s0 = (b == 0 && sF) ? sF : sA;         /* the fill: nothing else runs yet */
-        /* the FIR converter runs on the caller's stream (K1's, idle without the IIR), so KF of the
-         * next block overlaps K2 of this one; it rewrites xd[p] after K2(b - n_sets) has read it */
-        if (fir_async) {
-            s0 = sK;
-            if (b >= n_sets && hipStreamWaitEvent(sK, c->k2done[p], 0) != hipSuccess) return ICW_EDEVICE;
-        }
-        if (io_in(b, s0) != ICW_OK) return ICW_EDEVICE;
-        if (fir) {
-            IcwFirArgs af = fir_args(b);
-            if (timing && hipEventRecord(c->ev[4 * b], s0) != hipSuccess) return ICW_EDEVICE;
-            if (icw_launch_fir(&af, s0) != hipSuccess) return ICW_EDEVICE;
-            if (timing && hipEventRecord(c->ev[4 * b + 1], s0) != hipSuccess) return ICW_EDEVICE;
-        } else if (icw_launch_unpack(&a0, s0) != hipSuccess) {
-            return ICW_EDEVICE;
-        }
-        /* test hook: this block's rows aside before K1 may start (K1 waits for k0done) */
-        if (xin && hipMemcpy2DAsync(c->d_xin + a0.t0, (size_t)n_frames * sizeof(double), a0.xd, x_pitch * sizeof(double),
-                                    (size_t)a0.T * sizeof(double), S * 2, hipMemcpyDeviceToDevice, s0) != hipSuccess)
-            return ICW_EDEVICE;
-        if (hipEventRecord(c->k0done[p], s0) != hipSuccess) return ICW_EDEVICE;
-        return ICW_OK;
-    };
+    }
 
-    auto k1_args = [&](int b) {
+    IcwK1Args k1_args(int b) const
+    {
         const int p = b % n_sets;
         IcwK1Args a1;
         memset(&a1, 0, sizeof(a1));
@@ -2105,8 +1790,10 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         a1.dedup = dedup ? 1 : 0;
         a1.fes = fcm ? ds.fes + f0 * 4 * ICW_FES_PITCH : nullptr;
         return a1;
-    };
-    auto k2_args = [&](int b) {
+    }
+
+    IcwK2Args k2_args(int b) const
+    {
         const int t0 = blocks[b].first, T = blocks[b].second, p = b % n_sets;
         IcwK2Args a2;
         memset(&a2, 0, sizeof(a2));
@@ -2134,7 +1821,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
             a2.pre_stride = (size_t)T * 2;
         }
         a2.do_render = c->serial_render ? 0 : 1;
-        a2.n_regs = LP.chain ? 0 : LP.n_regs;    /* a chain program keeps its values in VGPRs */
+        a2.n_regs = lp->chain ? 0 : lp->n_regs;    /* a chain program keeps its values in VGPRs */
         a2.clips = ds.clips + f0 * 2;
         a2.peak_bits = ds.peak_bits + f0 * 2;
         a2.rk = c->rk;
@@ -2146,7 +1833,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         a2.xin = c->xd[p];
         a2.x_pitch = x_pitch;
         if (bus) a2.iq_out = c->iq[p];
-        a2.trig = LP.needs_omega;
+        a2.trig = lp->needs_omega;
         if (mix) {
             a2.prog_id = c->d_pid;
             a2.slab_stride = slab_stride;
@@ -2154,10 +1841,12 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         a2.sncnt = (!cw && cfg.iir_subnorm_reject) ? ds.sncnt + f0 * 4 : nullptr;
         a2.fes = fcm ? ds.fes + f0 * 4 * ICW_FES_PITCH : nullptr;
         return a2;
-    };
+    }
+
     /* the dither generator's / serial render's arguments for block b */
-    auto k3_args = [&](int b, const IcwK2Args &a2) {
-        const int T = blocks[b].second, p = b % n_sets;
+    IcwK3Args k3_args(int b, const IcwK2Args &a2) const
+    {
+        const int T = blocks[b].second;
         IcwK3Args a3;
         memset(&a3, 0, sizeof(a3));
         a3.pre = a2.pre;
@@ -2180,7 +1869,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         a3.row = c->serial_render && !fcm && (c->tn.render_row == 1 || (c->tn.render_row < 0 && a3.n_gen <= kRowRenderMax)) ? 1 : 0;
         a3.err = ds.err;
         if (dither) {
-            a3.dith = c->dith[p];
+            a3.dith = c->dith[b % n_sets];
             /* the row render and the frame-parallel one read runs of one channel: generator-major
              * [count*2][T rounded up to even] (16-byte pairs); the lane-per-channel renders time-major
              * [T][count*2] */
@@ -2192,8 +1881,81 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
             a3.dbk = c->dbk;
         }
         return a3;
-    };
-    auto adv_args = [&]() {
+    }
+
+    /* the bus-form graph of block b, behind its K2 */
+    IcwK4Args k4_args(int b, const IcwK2Args &a2) const
+    {
+        IcwK4Args a4;
+        memset(&a4, 0, sizeof(a4));
+        a4.iq = c->iq[b % n_sets];
+        a4.n_streams = count;
+        a4.T = blocks[b].second;
+        a4.t0 = blocks[b].first;
+        a4.n_frame = a2.n_frame;
+        a4.ssr = a2.ssr;
+        a4.scaled = a2.scaled;
+        a4.sample_rate = a2.sample_rate;
+        a4.prog = dP;
+        a4.bus = a2.bus;
+        a4.pre = a2.pre;
+        a4.pre_stride = a2.pre_stride;
+        return a4;
+    }
+
+    /* the rotation table of block b: the factors of every active Shift / PM channel per frame */
+    IcwTrigArgs trig_args(int b) const
+    {
+        const int T = blocks[b].second;
+        IcwTrigArgs at;
+        memset(&at, 0, sizeof(at));
+        at.prog = dP;
+        at.n_frame = c->st.n_frame + f0;
+        at.t0 = blocks[b].first;
+        at.T = T;
+        at.scaled = c->cfg.frmod_scaled;
+        at.trig_pitch = 2 * lp->n_trig;
+        at.ssr = ssr;
+        at.sample_rate = c->cfg.sample_rate;
+        at.tab = c->trig;
+        if (mix) {
+            at.slabs = c->d_pid + 3 * (size_t)count;
+            at.n_slabs = n_slabs;
+            at.slab_stride = slab_stride;
+        }
+        /* the fused FIR kernel's lanes hold 4 / 8 consecutive frames: rows 8 frames apart */
+        at.perm_q = fir_fused ? (T + 7) / 8 : 0;
+        return at;
+    }
+
+    /* KF's arguments for launch block b; it reads the history buffer the previous block wrote
+     * (same stream, block order) and writes the other one */
+    IcwFirArgs fir_args(int b) const
+    {
+        IcwFirArgs af;
+        memset(&af, 0, sizeof(af));
+        reader_args(af, b);
+        af.M = c->fir_M;
+        af.nt = c->fir_nt;
+        af.g = c->d_fir_g;
+        const size_t hrow = 2 * (size_t)c->fir_M;
+        af.hist_in = c->fir_hist[(c->fir_par + b) & 1] + f0 * hrow;
+        af.hist_out = c->fir_hist[(c->fir_par + b + 1) & 1] + f0 * hrow;
+        af.xd = c->xd[b % n_sets];
+        af.x_pitch = x_pitch;
+        af.sig = lp->chain ? lp->sig : 0;
+        {
+            /* mono input through a Master-only chain (signature count 1, mode MASTER, chain_in `in`:
+             * ICW_SIG_M) whose gains are bit-identical: L and R are one computation */
+            const IcwOp &m = lp->ops[0];
+            af.lr_same = nch == 1 && lp->chain && (lp->sig & ~ICW_SIG_UNIT) == ICW_SIG_M &&
+                        !memcmp(&m.gain[0], &m.gain[1], sizeof(double)) && m.unit_gain[0] == m.unit_gain[1];
+        }
+        return af;
+    }
+
+    IcwAdvArgs adv_args() const
+    {
         IcwAdvArgs av;
         memset(&av, 0, sizeof(av));
         av.n_streams = count;
@@ -2203,7 +1965,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         av.pos = ds.pos + f0;
         av.n_frame = ds.n_frame + f0;
         av.ssr = ssr;
-        av.scaled = cfg.frmod_scaled;
+        av.scaled = c->cfg.frmod_scaled;
         if (pinned) {
             av.err = ds.err;
             av.err_copy = (int *)(d_out + dos * S);        /* the output buffer has 16 spare bytes */
@@ -2213,73 +1975,547 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
             av.seq = s1_seq;
         }
         return av;
-    };
-    /* K5: a one-stream call of one block (the drop-in's 576-frame calls, playback.c:619) runs its four
-     * kernels as phases of one workgroup (icw_stream1): no launch gaps, one launch per call */
-    if (s1) {
-        IcwS1Args a5;
-        memset(&a5, 0, sizeof(a5));
-        a5.k0 = k0_args(0);
-        a5.k1 = k1_args(0);
-        a5.k2 = k2_args(0);
-        a5.adv = adv_args();
-        a5.stamps = c->s1_stamps;
-        a5.ovl = c->tn.s1_ovl ? 1 : 0;
-        if (LP.needs_omega && LP.n_trig > 0 && !bus) {
-            /* the one stream's rotation factors, computed by the kernel's idle waves beside the
-             * recurrence: the output phase reads them instead of evaluating sin / cos per frame */
-            if (grow((void **)&c->trig, &c->trig_bytes, (size_t)n_frames * 2 * LP.n_trig * sizeof(double)))
-                return ICW_ENOMEM;
-            IcwTrigArgs &at = a5.trig;
-            at.prog = dP;
-            at.n_frame = ds.n_frame + f0;
-            at.t0 = 0;
-            at.T = n_frames;
-            at.scaled = cfg.frmod_scaled;
-            at.trig_pitch = 2 * LP.n_trig;
-            at.ssr = ssr;
-            at.sample_rate = cfg.sample_rate;
-            at.tab = c->trig;
-            a5.has_trig = 1;
-            a5.k2.trig_tab = c->trig;
-            a5.k2.trig_pitch = at.trig_pitch;
+    }
+
+    /* the steps of a call, in the order the entry points take them */
+    void pick_k1();
+    hipError_t launch_k1(const IcwK1Args &a1, hipStream_t s) const;
+    int join_legacy_stream() const;
+    int stage_host_io(size_t in_row, size_t out_row);
+    bool stage_copy_in() const;
+    bool stage_copy_out(size_t row_bytes) const;
+    bool fir_hist_back() const;
+    int enc_format(int FB, bool fir_ok);
+    int enc_buffers(int FB);
+    void set_pitches();
+    void plan_uniform(int max_block);
+    int resolve_plan();
+    int stage_io();
+    int size_scratch();
+    int pick_streams();
+    int run_stream1() const;
+    int io_in(int b, hipStream_t s0) const;
+    int launch_k0(int b) const;
+    int run_blocks() const;
+    int finish_call() const;
+};
+
+
+/* The K1 of a call over the plan's streams of real input (cw, fcm and nch are set): dedup, k1_mode
+ * and row_waves, the row kernel's waves over these streams. */
+void CallPlan::pick_k1()
+{
+    /* mono dedup: every stream of the call known to hold identical left / right converters */
+    dedup = !cw && !fcm && nch == 1 && c->tn.dedup_ok && (c->tn.k1_mode <= 0 || c->tn.k1_mode == 3);   /* plain / row K1 */
+    for (int i = 0; dedup && i < count; ++i) dedup = c->lr_known[first + i] != 0;
+    /* K1 variant of this call.  Auto: the row-broadcast kernel (4 chains per wave, ~17 % fewer
+     * instructions per sample) when its waves fit k1_wpc per CU on at most half the chip, else the
+     * lane-per-chain kernel (64 chains per wave).  The row kernel needs Kahan + the reject.  (Round
+     * 1 kept it off with a serial render; with the partition working, C5 gains 9 % from it.) */
+    row_waves = (int)(((dedup ? count : 2L * count) + 3) / 4) * 2;
+    const bool row_ok = cfg.iir_kahan && cfg.iir_subnorm_reject;
+    k1_mode = c->tn.k1_mode;
+    if (k1_mode < 0) k1_mode = (row_ok && row_waves <= (c->n_cu / 2) * c->tn.k1_wpc) ? 3 : 0;
+    if (k1_mode == 3 && !row_ok) k1_mode = 0;
+    if (fcm) k1_mode = ICW_K1_FC;                  /* FP_CHECK: FC() kernels, no shortcuts */
+}
+
+/* the plan's K1 on stream s */
+hipError_t CallPlan::launch_k1(const IcwK1Args &a1, hipStream_t s) const
+{
+    return k1_mode == ICW_K1_FC ? icw_launch_iir_fc(&a1, c->nord, cfg.iir_kahan, cfg.iir_subnorm_reject, s)
+         : k1_mode == 3         ? icw_launch_iir_row(&a1, c->nord, cfg.iir_kahan, cfg.iir_subnorm_reject, s)
+                                   : icw_launch_iir_state(&a1, c->nord, cfg.iir_kahan, cfg.iir_subnorm_reject, s);
+}
+
+/* ---- what the process call and the encoders share ---- */
+
+/* A NULL handle with device pointers means the legacy default stream (torch's default stream):
+ * the call starts after the work already queued there, and returns when its results are in
+ * place, so that stream's later work sees them.  The end is a host wait, not an operation on the
+ * null stream: a null-stream wait behind the context's CU-masked streams cost C2 13-25 % (its
+ * implicit synchronisation with every blocking stream serialises the block pipeline). */
+int CallPlan::join_legacy_stream() const
+{
+    if (legacy && (hipEventRecord(c->join, nullptr) != hipSuccess || hipStreamWaitEvent(st, c->join, 0) != hipSuccess))
+        return ICW_EDEVICE;
+    return ICW_OK;
+}
+
+/* the encoders' per-stream count of saturated / NaN int16 samples, allocated by the first encode */
+int ensure_enc_clipped(icw_ctx *c)
+{
+    if (c->enc_clipped) return ICW_OK;
+    const int rc = dalloc(&c->enc_clipped, (size_t)c->n_streams);
+    if (rc != ICW_OK) {
+        if (c->enc_clipped) (void)hipFree(c->enc_clipped);
+        c->enc_clipped = nullptr;
+    }
+    return rc;
+}
+
+/* Host pointers: the device staging pair, rows of dis / dos bytes per stream (the output has 16 spare
+ * bytes for the error flag's copy), and the plain 2-D copies of the whole call in and out on st. */
+int CallPlan::stage_host_io(size_t in_row, size_t out_row)
+{
+    if (grow((void **)&c->d_in, &c->d_in_bytes, in_row * S)) return ICW_ENOMEM;
+    if (grow((void **)&c->d_out, &c->d_out_bytes, out_row * S + 16)) return ICW_ENOMEM;
+    d_in = c->d_in;
+    d_out = c->d_out;
+    dis = in_row;
+    dos = out_row;
+    return ICW_OK;
+}
+
+bool CallPlan::stage_copy_in() const
+{
+    return hipMemcpy2DAsync(c->d_in, dis, in, in_stride, dis, S, hipMemcpyHostToDevice, st) == hipSuccess;
+}
+
+bool CallPlan::stage_copy_out(size_t row_bytes) const
+{
+    return hipMemcpy2DAsync(out, out_stride, c->d_out, dos, row_bytes, S, hipMemcpyDeviceToHost, st) == hipSuccess;
+}
+
+/* FIR history: the current rows of every stream stay in fir_hist[fir_par] between calls (a call on
+ * a subset of the streams must not move the others' rows); after an odd number of blocks this
+ * call's rows are in the other buffer and come back */
+bool CallPlan::fir_hist_back() const
+{
+    if (!(n_blocks & 1)) return true;
+    const size_t hrow = 2 * (size_t)c->fir_M;
+    return hipMemcpyAsync(c->fir_hist[c->fir_par] + f0 * hrow, c->fir_hist[c->fir_par ^ 1] + f0 * hrow,
+                          S * hrow * sizeof(double), hipMemcpyDeviceToDevice, st) == hipSuccess;
+}
+
+/* The encoders' format checks (real input, the converter asked for on or off, a CWAVE output format,
+ * strides that hold the call) and their buffers: the caller's device pointers, or the staging pair
+ * with every stream's frames 16-byte aligned.  FB: bytes per output frame. */
+int CallPlan::enc_format(int FB, bool fir_ok)
+{
+    if (cfg.in_format >= ICW_FMT_CW_F64 || !fir_ok || FB == 0) return ICW_EINVAL;
+    csz = fmt_size(cfg.in_format);
+    nch = cfg.in_channels;
+    fsz = csz * nch;
+    if (!dev && (in_stride < (size_t)n_frames * fsz || out_stride < (size_t)n_frames * FB)) return ICW_EINVAL;
+    return ICW_OK;
+}
+
+int CallPlan::enc_buffers(int FB)
+{
+    d_in = (const unsigned char *)in;
+    d_out = (unsigned char *)out;
+    dis = in_stride;
+    dos = out_stride;
+    return dev ? ICW_OK : stage_host_io((size_t)n_frames * fsz, ((size_t)n_frames * FB + 15) & ~(size_t)15);
+}
+
+/* at least n events in v */
+bool grow_events(std::vector<hipEvent_t> &v, int n, unsigned flags)
+{
+    while ((int)v.size() < n) {
+        hipEvent_t e;
+        if (hipEventCreateWithFlags(&e, flags) != hipSuccess) return false;
+        v.push_back(e);
+    }
+    return true;
+}
+
+/* ---- icw_process_streams, step by step ---- */
+
+/* the format, the list and the modes of the call, and its launch blocks */
+int CallPlan::resolve_plan()
+{
+    csz = fmt_size(cfg.in_format);
+    nch = cfg.in_channels;
+    fsz = csz * nch;
+    osz = 2 * (cfg.need24bits ? 3 : 2);
+    ssr = (unsigned long long)cfg.sample_rate * ICW_HZ_SCALE;
+    timing = flags & 4u;
+    /* ICW_F_DEBUG_INPUT: K0's output of every launch block is copied aside (test hook, host dbg) */
+    xin = flags & ICW_F_DEBUG_INPUT;
+    if (xin && (dev || !dbg || (flags & ICW_F_DEBUG_PRE) || cfg.in_format >= ICW_FMT_CW_F64 || c->fir_M > 0 ||
+                   cfg.fp_check))
+        return ICW_EINVAL;
+    if (!dev && (in_stride < (size_t)n_frames * fsz || out_stride < (size_t)n_frames * osz)) return ICW_EINVAL;
+
+    /* FIR Hilbert converter (icw_set_fir_hilbert): real input becomes complex samples in KF and
+     * the block continues as CWAVE input does */
+    fir = c->fir_M > 0 && cfg.in_format < ICW_FMT_CW_F64;
+    cw = cfg.in_format >= ICW_FMT_CW_F64 || fir;
+    /* the list of the call's streams: the context's one, the one table entry all of them run, or --
+     * streams with different lists -- the table with K2's per-stream selection (prepare_mix) */
+    lp = &c->prog;
+    dP = c->d_prog;
+    if (!c->progs.empty()) {
+        const int32_t e0 = c->prog_of[(size_t)first];
+        for (int i = 1; i < count && !mix; ++i) mix = c->prog_of[(size_t)(first + i)] != e0;
+        if (mix) {
+            const int rc = prepare_mix(c, first, count, st);
+            if (rc != ICW_OK) return rc;
+            lp = &c->mix;
+            dP = c->d_progs;
+        } else {
+            lp = &c->progs[(size_t)e0];
+            dP = c->d_progs + e0;
         }
-        if (dith_par) {
-            /* the dithered flat render: K3a of the call's block first, on the same stream */
-            const IcwK3Args a3 = k3_args(0, a5.k2);
-            if (icw_launch_dither(&a3, st) != hipSuccess) return ICW_EDEVICE;
-            a5.k2.dith = a3.dith;
-            a5.k2.dith_pitch = a3.dith_pitch;
+    }
+    const IcwProg &LP = *lp;
+    n_slabs = mix ? c->pid_slabs : 1;
+    bus = LP.is_bus;
+    fcm = cfg.fp_check != 0;
+    pick_k1();
+    if (!cw) c->last_k1 = k1_mode;
+    /* launch blocks.  The tail taper (plan_blocks) is on by default where it fits: a small batch
+     * (the row kernel K1r) with a serial render -- its drain is the render of the last block, and
+     * the frame-parallel kernels take well under K1r's time per frame (C5: +2 %).  Large batches
+     * keep uniform blocks (K0 + K2 take ~0.9 of K1's time there), ICW_TAPER overrides. */
+    /* FIR converter: fused with the graph and render (KF2, one kernel per block) where its LDS fits;
+     * else KF on its own stream (the caller's: K1's, idle without the IIR) beside K2.  KF2 needs no
+     * block scratch and has no recurrence to pipeline against, so its blocks are as long as the
+     * scratch bound allows (fewer launches, fewer partly filled waves of workgroups at their ends) */
+    fir_fused = fir && c->tn.fir_fuse &&
+                   icw_fir_graph_lds(c->fir_M, c->fir_nt, (int)nch, LP.chain ? 0 : LP.n_regs) > 0 && !LP.is_bus;
+    /* The row kernel without a serial render (C2) has K2 at ~0.16 of K1r's time per frame: 65 536-frame
+     * blocks (a quarter of the launches, of their gaps and prologues) ending in a steep tail
+     * (65 536 -> 16 384 -> 4 096 -> 1 024: the drain stays one short K2) measured +0.8 % on C2
+     * (3 170 -> 3 196 Msamples/s; 32 768 with r = 0.5 +0.5 %, 65 536 with no tail +0.5 %). */
+    const bool row_long = !cw && k1_mode == 3 && !c->serial_render && !c->tn.block_env && n_frames >= 4 * kMaxBlockFrames;
+    /* a dithered render with the flat shaper, rendered frame-parallel in the output kernel (K2 / KF2 /
+     * K5) from K3a's dither rows (needs_serial) */
+    dith_par = !c->serial_render && cfg.render.render_type != ICW_RENDER_ROUND;
+    dither = cfg.render.render_type != ICW_RENDER_ROUND;     /* K3a: serial or frame-parallel render */
+    /* (with a dither generator, blocks of kMaxBlockFrames let K3a of the next block run beside KF2) */
+    const bool fir_long = fir_fused && dev && !c->serial_render && !bus && !dith_par;
+    Tb = std::min(n_frames, ((fir_fused || row_long) && !c->tn.block_env)
+                                   ? (fir_long ? kMaxFirBlockFrames : kMaxBlockFrames) : c->tn.max_block);
+    const double taper = c->tn.taper >= 0.0 ? c->tn.taper
+                       : (!cw && k1_mode == 3) ? (c->serial_render ? kAutoTaper : (row_long ? kRowTaper : 0.0)) : 0.0;
+    /* the fused FIR converter with a serial render (c5fir): the render of block 0 waits for its
+     * converter and dither alone, so block 0 is short and the next ones ramp up (kFirRenderRamp:
+     * profiles/r04_c5fir_timeline_after.txt had 2.2 ms of fill in a 24.3 ms step) */
+    const bool fir_ramp = fir_fused && c->serial_render && !c->tn.block_env && c->tn.first_block > 0;
+    blocks = fir_ramp ? plan_blocks(n_frames, Tb, c->tn.first_block_env ? c->tn.first_block : kFirRenderFirst, 0.0,
+                                       c->tn.taper_min, c->tn.fir_ramp > 0.0 ? c->tn.fir_ramp : kFirRenderRamp)
+                         : plan_blocks(n_frames, Tb, fir_fused ? 0 : c->tn.first_block, taper, c->tn.taper_min);
+    n_blocks = (int)blocks.size();
+    /* K5 (icw_stream1): one stream, one block, the row recurrence, register-form graph, ROUND / flat */
+    s1 = c->tn.stream1 && count == 1 && n_blocks == 1 && !cw && !fcm && k1_mode == 3 && !c->serial_render &&
+            !bus && n_frames <= ICW_S1_MAX && !xin;
+    return ICW_OK;
+}
+
+/* where the kernels read the input and write the output: the caller's device buffers, or for host
+ * pointers the staging pair (through pinned memory for a small call, block by block for pinned
+ * caller buffers); the debug hooks' buffers */
+int CallPlan::stage_io()
+{
+    /* a small host-pointer call stages through pinned memory (asynchronous copies, one wait) */
+    stage_in = (size_t)n_frames * fsz * S;
+    const size_t stage_out = (size_t)n_frames * osz * S;
+    pinned = !dev && stage_in + stage_out + 16 <= kPinnedStage;
+    /* pinned host buffers on a call of several launch blocks: each block's input slice goes in and
+     * its output slice comes out on the copy stream, beside the other blocks' kernels */
+    pipe_io = !dev && !pinned && n_blocks > 1 && !c->tn.serialize && host_pinned(in, c->device) &&
+                 host_pinned(out, c->device);
+    if (pinned) {
+        if (c->h_stage_bytes < stage_in + stage_out + 16) {
+            if (c->h_stage) (void)hipHostFree(c->h_stage);
+            c->h_stage = nullptr;
+            c->h_stage_bytes = 0;
+            if (hipHostMalloc((void **)&c->h_stage, kPinnedStage, hipHostMallocDefault) != hipSuccess) return ICW_ENOMEM;
+            c->h_stage_bytes = kPinnedStage;
+            void *dp = nullptr;
+            c->h_stage_dev = hipHostGetDevicePointer(&dp, c->h_stage, 0) == hipSuccess ? (unsigned char *)dp : nullptr;
+            if (!c->h_stage_dev) (void)hipGetLastError();
         }
-        if (timing && hipEventRecord(c->ev[0], st) != hipSuccess) return ICW_EDEVICE;
-        if (icw_launch_stream1(&a5, N, st) != hipSuccess) return ICW_EDEVICE;
-        if (timing && (hipEventRecord(c->ev[1], st) != hipSuccess || hipEventRecord(c->ev[2], st) != hipSuccess ||
-                       hipEventRecord(c->ev[3], st) != hipSuccess))
-            return ICW_EDEVICE;
-        if (!cw && nch > 1) c->lr_known[first] = 0;
+        zcopy = c->tn.zero_copy && c->h_stage_dev && !(flags & ICW_F_DEBUG_PRE);
+    }
+    if (dev) {
+        d_in = (const unsigned char *)in;
+        d_out = (unsigned char *)out;
+        dis = in_stride;
+        dos = out_stride;
     } else {
-    /* n_sets scratch sets (2 by default, ICW_SETS=3): K0 of the first n_sets blocks is queued up
-     * front, K0(b + n_sets) as soon as its xd set is free (below); K1(b + n_sets) reuses the w /
-     * info_dup set that K2(b) read and waits for it.  Three sets measured slower for large
-     * batches (C3: K1 3.96 vs 3.16 ms per launch), so two is the default. */
+        const int rc = stage_host_io((size_t)n_frames * fsz, (size_t)n_frames * osz);
+        if (rc != ICW_OK) return rc;
+        if (pinned) {
+            for (size_t i = 0; i < S; ++i)
+                memcpy(c->h_stage + i * dis, (const unsigned char *)in + i * in_stride, dis);
+            if (!zcopy && hipMemcpyAsync(c->d_in, c->h_stage, dis * S, hipMemcpyHostToDevice, st) != hipSuccess)
+                return ICW_EDEVICE;
+        } else if (!pipe_io && !stage_copy_in()) {
+            return ICW_EDEVICE;
+        }
+        /* zero copy: K0 reads the staged input across PCIe and the last kernel writes the output
+         * (and icw_advance the error flag) straight into the staging buffer -- a few KB, where the
+         * two DMA transfers each cost a setup latency (the 576-frame drop-in) */
+        if (zcopy) {
+            d_in = c->h_stage_dev;
+            d_out = c->h_stage_dev + stage_in;
+        }
+    }
+    /* K5 on the zero-copy buffer: the kernel stores the call's sequence number after its output and
+     * the host polls for it -- no completion signal and no waking of a waiting thread.  The word is
+     * 4-byte aligned inside the output's 16 spare bytes, after the error flag. */
+    s1_poll = s1 && zcopy && c->tn.spin_wait && !timing && !c->s1_stamps;
+    done_off = ((stage_in + dos * S + sizeof(int) + 3) & ~(size_t)3) - stage_in;
+    if (s1_poll) {
+        if (++c->s1_seq == 0u) ++c->s1_seq;           /* 0 is never a call's number */
+        s1_seq = c->s1_seq;
+        /* the word sits in the reused staging buffer, where an earlier, larger call may have left
+         * input or output bytes that happen to equal this call's number: store a value that cannot
+         * match before the launch (which orders after this store), so the poll sees only the
+         * kernel's own store */
+        __atomic_store_n((uint32_t *)(c->h_stage + stage_in + done_off), ~s1_seq, __ATOMIC_RELEASE);
+    }
+    if (xin) {
+        if (grow((void **)&c->d_xin, &c->d_xin_bytes, S * 2 * (size_t)n_frames * sizeof(double))) return ICW_ENOMEM;
+        xin_phase.resize(S * 2);
+        /* the device's Hilbert phases of the call's streams: [stream][L, R] */
+        if (hipMemcpyAsync(xin_phase.data(), c->st.hq_phase + f0 * 2, S * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                           st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return ICW_EDEVICE;
+    }
+    if (flags & ICW_F_DEBUG_PRE) {
+        if (!dbg) return ICW_EINVAL;
+        if (dev) d_pre = (double *)dbg;
+        else {
+            if (grow((void **)&c->d_pre, &c->d_pre_bytes, S * (size_t)n_frames * 2 * sizeof(double))) return ICW_ENOMEM;
+            d_pre = c->d_pre;
+        }
+    }
+    return ICW_OK;
+}
+
+/* row pitches of the block scratch for blocks of at most Tb frames */
+void CallPlan::set_pitches()
+{
+    w_pitch = (size_t)Tb + c->nord + 1;
+    x_pitch = ((size_t)Tb + ICW_MAX_IIR_ORDER + 2) & ~(size_t)1;   /* look-ahead pad */
+}
+
+/* The encoders' plan: uniform launch blocks of at most max_block frames (no pipeline to fill or drain,
+ * so as long as the scratch allows) on one scratch set, and the context's own list rather than a
+ * per-stream table entry -- the encoders stop before the graph and read only its register count. */
+void CallPlan::plan_uniform(int max_block)
+{
+    lp = &c->prog;
+    dP = c->d_prog;
+    ssr = (unsigned long long)c->cfg.sample_rate * ICW_HZ_SCALE;
+    Tb = std::min(n_frames, c->tn.block_env ? c->tn.max_block : max_block);
+    blocks = plan_blocks(n_frames, Tb, 0, 0.0, c->tn.taper_min);
+    n_blocks = (int)blocks.size();
+    n_sets = 1;
+    set_pitches();
+}
+
+/* the block scratch of the call's n_sets sets (icw_prepare relies on this order of growth) */
+int CallPlan::size_scratch()
+{
+    const IcwProg &LP = *lp;
+    set_pitches();
+    n_sets = std::min(n_blocks, c->tn.max_sets);
+    for (int p = 0; p < n_sets && !fir_fused; ++p) {
+        if (!cw && grow((void **)&c->w[p], &c->w_bytes[p], S * 4 * w_pitch * sizeof(double))) return ICW_ENOMEM;
+        if (grow((void **)&c->xd[p], &c->xd_bytes[p], S * 4 * x_pitch * sizeof(double))) return ICW_ENOMEM;
+    }
+    if (c->serial_render && !d_pre)
+        for (int p = 0; p < n_sets; ++p)
+            if (grow((void **)&c->rpre[p], &c->rpre_bytes[p], S * (size_t)Tb * 2 * sizeof(double))) return ICW_ENOMEM;
+    /* the shared rotation table pays from two streams on; one stream computes its factors inline */
+    table = LP.needs_omega && !bus && LP.n_trig > 0 && count > 1;
+    in_step = table;
+    for (int i = 1; in_step && i < count; ++i) in_step = c->nf_host[first + i] == c->nf_host[first];
+    /* per-stream lists: one slab per program that has one (prepare_mix), all of the widest one's pitch */
+    slab_stride = (size_t)((Tb + 7) & ~7) * 2 * (size_t)LP.n_trig;
+    if (table && grow((void **)&c->trig, &c->trig_bytes, (size_t)n_slabs * slab_stride * sizeof(double)))
+        return ICW_ENOMEM;
+    if (bus)
+        for (int p = 0; p < n_sets; ++p)
+            if (grow((void **)&c->iq[p], &c->iq_bytes[p], S * (size_t)Tb * 4 * sizeof(double))) return ICW_ENOMEM;
+    if (dither)
+        for (int p = 0; p < n_sets; ++p)
+            if (grow((void **)&c->dith[p], &c->dith_bytes[p], S * 2 * (size_t)(Tb + 1) * sizeof(double))) return ICW_ENOMEM;
+    if (dither) {
+        /* chunk rows: 2^26 words (256 MB) shared among the G generators, but never less than 1 024 frames
+         * of the widest draw (GAUSS, 24 words per sample) and never more than the block's.  The floor
+         * wins over the 2^26 share from 2 731 generators on, so the buffer is G * cap <= max(2^26,
+         * 24 576 G) words: 256 MB up to there, 96 KB per generator beyond */
+        const size_t G = S * 2;
+        size_t cap = std::max<size_t>(((size_t)1 << 26) / G, (size_t)24 * 1024);
+        cap = std::min(cap, (size_t)24 * (size_t)(Tb + 1));
+        cap = (cap + 3) & ~(size_t)3;                      /* rows 16-byte aligned */
+        if (grow((void **)&c->dwords, &c->dwords_bytes, G * cap * 4) ||
+            grow((void **)&c->dbk, &c->dbk_bytes, G * ICW_DBK * 4) ||
+            grow((void **)&c->dflag, &c->dflag_bytes, G * 4))
+            return ICW_ENOMEM;
+        c->dwcap = cap;
+    }
+    return ICW_OK;
+}
+
+/* Streams.  sK runs the IIR state kernel K1 (the serial, issue-bound one); sA runs the input
+ * prep K0, the output kernel K2 and the serial graph / render; sD the dither generator.  When
+ * K1 needs few CUs (4 waves per CU, one per SIMD) sK is confined to those CUs and sA / sD to
+ * the rest, so the frame-parallel kernels never share a SIMD with a recurrence. */
+int CallPlan::pick_streams()
+{
+    sK = st;
+    sA = c->stream2;
+    sD = c->stream3;
+    sR = c->stream4;
+    /* One launch block: K0 -> K1 -> K2 run in sequence anyway, so everything goes on the caller's
+     * stream -- no cross-stream event waits, which cost the 576-frame drop-in call ~135 us (C1
+     * p50 361 -> 226 us per call). */
+    if (c->tn.serialize || n_blocks == 1) {
+        sA = sD = sR = st;
+    } else if (!cw) {
+        /* plain K1: 128-lane groups of 32 streams (64 with the dedup); the variants: a lane per chain */
+        const int k1_waves = (k1_mode == 0 || k1_mode == ICW_K1_FC)
+                                 ? ((count + (dedup ? 63 : 31)) / (dedup ? 64 : 32)) * 2 : row_waves;
+        constexpr int kXcd = 8;                               /* MI355X: 8 XCDs */
+        const int k1_cus = ((k1_waves + c->tn.k1_wpc - 1) / c->tn.k1_wpc + kXcd - 1) / kXcd * kXcd;
+        if (c->tn.cu_split && k1_cus * 2 <= c->n_cu) {
+            const CuSplit *cs = cu_split(c, k1_cus);
+            if (!cs) return ICW_EDEVICE;
+            sK = cs->k1;
+            sA = cs->rest;
+            sD = cs->dith;
+            sR = cs->render;
+            /* sF: an unmasked stream for the pipeline's fill and drain under the CU partition -- K0 of the
+             * first block and K2 of the last run while no recurrence does, so they get the whole chip
+             * instead of the partition's share (C3 / C4: the drain was one partitioned K2, ~5 % of a step) */
+            if (c->tn.fill_drain) sF = c->stream2;
+        }
+    } else {
+        /* complex input or the FIR converter: no recurrence kernel, so the dither generator runs after
+         * the converter / output kernel on sA, beside the serial render of the previous block on sR.
+         * On its own stream it shared a hardware queue with the render (4 queues per process,
+         * GPU_MAX_HW_QUEUES, streams dealt round-robin): K3a of block b + 1 waited for the render of block b,
+         * 1.2 of every 6.7 ms per c5fir block (profiles/r04_c5fir_timeline.txt).  With a frame-parallel
+         * render (no render stream) it gets a stream of its own, ahead of the converter. */
+        sD = dith_par ? c->stream3 : sA;
+    }
+    sC = pipe_io ? c->stream_io : nullptr;
+    if (pipe_io && !grow_events(c->ev_io, n_blocks, hipEventDisableTiming)) return ICW_EDEVICE;
+    /* every stream starts after everything already queued on st (inputs, previous calls); a call
+     * whose kernels all run on st (one launch block: the drop-in) records no event -- the marker
+     * packet sat in front of its kernel on the queue */
+    bool other = false;
+    for (hipStream_t x : {sK, sA, sD, sR, sF, sC}) other = other || (x && x != st);
+    if (other && hipEventRecord(c->join, st) != hipSuccess)
+        return ICW_EDEVICE;
+    for (hipStream_t x : {sK, sA, sD, sR, sF, sC})
+        if (x && x != st && hipStreamWaitEvent(x, c->join, 0) != hipSuccess) return ICW_EDEVICE;
+
+    if (timing && !grow_events(c->ev, 4 * n_blocks, hipEventDefault)) return ICW_EDEVICE;
+    fir_async = fir && !fir_fused && sK != sA;
+    return ICW_OK;
+}
+
+/* K5: a one-stream call of one block (the drop-in's 576-frame calls, playback.c:619) runs its four
+ * kernels as phases of one workgroup (icw_stream1): no launch gaps, one launch per call */
+int CallPlan::run_stream1() const
+{
+    const IcwProg &LP = *lp;
+    IcwS1Args a5;
+    memset(&a5, 0, sizeof(a5));
+    a5.k0 = k0_args(0);
+    a5.k1 = k1_args(0);
+    a5.k2 = k2_args(0);
+    a5.adv = adv_args();
+    a5.stamps = c->s1_stamps;
+    a5.ovl = c->tn.s1_ovl ? 1 : 0;
+    if (LP.needs_omega && LP.n_trig > 0 && !bus) {
+        /* the one stream's rotation factors, computed by the kernel's idle waves beside the
+         * recurrence: the output phase reads them instead of evaluating sin / cos per frame */
+        if (grow((void **)&c->trig, &c->trig_bytes, (size_t)n_frames * 2 * LP.n_trig * sizeof(double)))
+            return ICW_ENOMEM;
+        a5.trig = trig_args(0);
+        a5.has_trig = 1;
+        a5.k2.trig_tab = c->trig;
+        a5.k2.trig_pitch = a5.trig.trig_pitch;
+    }
+    if (dith_par) {
+        /* the dithered flat render: K3a of the call's block first, on the same stream */
+        const auto a3 = k3_args(0, a5.k2);
+        if (icw_launch_dither(&a3, st) != hipSuccess) return ICW_EDEVICE;
+        a5.k2.dith = a3.dith;
+        a5.k2.dith_pitch = a3.dith_pitch;
+    }
+    if (timing && hipEventRecord(c->ev[0], st) != hipSuccess) return ICW_EDEVICE;
+    if (icw_launch_stream1(&a5, c->nord, st) != hipSuccess) return ICW_EDEVICE;
+    if (timing && (hipEventRecord(c->ev[1], st) != hipSuccess || hipEventRecord(c->ev[2], st) != hipSuccess ||
+                      hipEventRecord(c->ev[3], st) != hipSuccess))
+        return ICW_EDEVICE;
+    if (!cw && nch > 1) c->lr_known[first] = 0;
+    return ICW_OK;
+}
+
+/* pinned host input: block b's input slice of every stream goes in on the copy stream, and the
+ * stream of the block's first reader (K0, KF or the fused KF2) waits for it */
+int CallPlan::io_in(int b, hipStream_t s0) const
+{
+    if (!pipe_io) return ICW_OK;
+    const int t0 = blocks[b].first, T = blocks[b].second;
+    if (hipMemcpy2DAsync(c->d_in + (size_t)t0 * fsz, dis, (const unsigned char *)in + (size_t)t0 * fsz,
+                         in_stride, (size_t)T * fsz, S, hipMemcpyHostToDevice, sC) != hipSuccess ||
+        hipEventRecord(c->ev_io[b], sC) != hipSuccess || hipStreamWaitEvent(s0, c->ev_io[b], 0) != hipSuccess)
+        return ICW_EDEVICE;
+    return ICW_OK;
+}
+
+/* K0 (or the unfused converter KF) of block b */
+int CallPlan::launch_k0(int b) const
+{
+    if (fir_fused) return ICW_OK;                   /* KF2 converts inside the block's kernel */
+    const int p = b % n_sets;
+    const auto a0 = k0_args(b);
+    if (b >= n_sets && !cw && sK != sA && hipStreamWaitEvent(sA, c->k1done[p], 0) != hipSuccess) return ICW_EDEVICE;
+    hipStream_t s0 = (b == 0 && sF) ? sF : sA;         /* the fill: nothing else runs yet */
+    /* the FIR converter runs on the caller's stream (K1's, idle without the IIR), so KF of the
+     * next block overlaps K2 of this one; it rewrites xd[p] after K2(b - n_sets) has read it */
+    if (fir_async) {
+        s0 = sK;
+        if (b >= n_sets && hipStreamWaitEvent(sK, c->k2done[p], 0) != hipSuccess) return ICW_EDEVICE;
+    }
+    if (io_in(b, s0) != ICW_OK) return ICW_EDEVICE;
+    if (fir) {
+        const auto af = fir_args(b);
+        if (timing && hipEventRecord(c->ev[4 * b], s0) != hipSuccess) return ICW_EDEVICE;
+        if (icw_launch_fir(&af, s0) != hipSuccess) return ICW_EDEVICE;
+        if (timing && hipEventRecord(c->ev[4 * b + 1], s0) != hipSuccess) return ICW_EDEVICE;
+    } else if (icw_launch_unpack(&a0, s0) != hipSuccess) {
+        return ICW_EDEVICE;
+    }
+    /* test hook: this block's rows aside before K1 may start (K1 waits for k0done) */
+    if (xin && hipMemcpy2DAsync(c->d_xin + a0.t0, (size_t)n_frames * sizeof(double), a0.xd, x_pitch * sizeof(double),
+                                   (size_t)a0.T * sizeof(double), S * 2, hipMemcpyDeviceToDevice, s0) != hipSuccess)
+        return ICW_EDEVICE;
+    if (hipEventRecord(c->k0done[p], s0) != hipSuccess) return ICW_EDEVICE;
+    return ICW_OK;
+}
+
+/* The block pipeline.  n_sets scratch sets (2 by default, ICW_SETS=3): K0 of the first n_sets blocks
+ * is queued up front, K0(b + n_sets) as soon as its xd set is free (below); K1(b + n_sets) reuses the
+ * w / info_dup set that K2(b) read and waits for it.  Three sets measured slower for large
+ * batches (C3: K1 3.96 vs 3.16 ms per launch), so two is the default. */
+int CallPlan::run_blocks() const
+{
     int rc0 = ICW_OK;
     for (int b = 0; b < n_sets; ++b)
         if ((rc0 = launch_k0(b)) != ICW_OK) return rc0;
     for (int b = 0; b < n_blocks; ++b) {
-        const int t0 = blocks[b].first;
-        const int T = blocks[b].second;
-        const int p = b % n_sets;
+        const int t0 = blocks[b].first, T = blocks[b].second, p = b % n_sets;
 
         if (!cw) {
-            const IcwK1Args a1 = k1_args(b);
+            const auto a1 = k1_args(b);
             /* K0(b) done, and K2(b-2), the last reader of w[p] / info_dup[p] */
             if (sK != sA && hipStreamWaitEvent(sK, c->k0done[p], 0) != hipSuccess) return ICW_EDEVICE;
             if (b >= n_sets && sK != sA && hipStreamWaitEvent(sK, c->k2done[p], 0) != hipSuccess) return ICW_EDEVICE;
             if (timing && hipEventRecord(c->ev[4 * b], sK) != hipSuccess) return ICW_EDEVICE;
-            const hipError_t e1 = k1_mode == ICW_K1_FC ? icw_launch_iir_fc(&a1, N, cfg.iir_kahan, cfg.iir_subnorm_reject, sK)
-                                : k1_mode == 3 ? icw_launch_iir_row(&a1, N, cfg.iir_kahan, cfg.iir_subnorm_reject, sK)
-                                               : icw_launch_iir_state(&a1, N, cfg.iir_kahan, cfg.iir_subnorm_reject, sK);
-            if (e1 != hipSuccess) return ICW_EDEVICE;
+            if (launch_k1(a1, sK) != hipSuccess) return ICW_EDEVICE;
             if (timing && hipEventRecord(c->ev[4 * b + 1], sK) != hipSuccess) return ICW_EDEVICE;
             if (hipEventRecord(c->k1done[p], sK) != hipSuccess) return ICW_EDEVICE;
             if (sK != sA && hipStreamWaitEvent(sA, c->k1done[p], 0) != hipSuccess) return ICW_EDEVICE;
@@ -2298,26 +2534,9 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         if (drain && (hipStreamWaitEvent(sF, c->k1done[p], 0) != hipSuccess ||
                       (b >= 1 && hipStreamWaitEvent(sF, c->k2done[(b - 1) % n_sets], 0) != hipSuccess)))
             return ICW_EDEVICE;
-        IcwK2Args a2 = k2_args(b);
+        auto a2 = k2_args(b);
         if (table) {
-            IcwTrigArgs at;
-            memset(&at, 0, sizeof(at));
-            at.prog = dP;
-            at.n_frame = a2.n_frame;
-            at.t0 = t0;
-            at.T = T;
-            at.scaled = cfg.frmod_scaled;
-            at.trig_pitch = 2 * LP.n_trig;
-            at.ssr = ssr;
-            at.sample_rate = cfg.sample_rate;
-            at.tab = c->trig;
-            if (mix) {
-                at.slabs = c->d_pid + 3 * (size_t)count;
-                at.n_slabs = n_slabs;
-                at.slab_stride = slab_stride;
-            }
-            /* the fused FIR kernel's lanes hold 4 / 8 consecutive frames: rows 8 frames apart */
-            at.perm_q = fir_fused ? (T + 7) / 8 : 0;
+            const auto at = trig_args(b);
             /* same stream as K2: the previous block's K2 has read the table before it is rewritten */
             if (icw_launch_trig_table(&at, s2) != hipSuccess) return ICW_EDEVICE;
             a2.trig_tab = c->trig;
@@ -2331,7 +2550,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
             /* K3a of this block on its own stream (it depends only on the generators' state, so it runs
              * ahead, beside the converter / output kernel of the block before); dith[p] was last read
              * by the output kernel of block b - n_sets */
-            const IcwK3Args a3 = k3_args(b, a2);
+            const auto a3 = k3_args(b, a2);
             if (b >= n_sets && sD != s2 && hipStreamWaitEvent(sD, c->k2done[p], 0) != hipSuccess) return ICW_EDEVICE;
             const hipError_t ed = icw_launch_dither(&a3, sD);
             if (ed != hipSuccess || hipEventRecord(c->ditdone[p], sD) != hipSuccess ||
@@ -2342,38 +2561,25 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         }
         if (timing && hipEventRecord(c->ev[4 * b + 2], s2) != hipSuccess) return ICW_EDEVICE;
         if (fir_fused) {
-            const IcwFirArgs af = fir_args(b);
+            const auto af = fir_args(b);
             if (io_in(b, s2) != ICW_OK) return ICW_EDEVICE;
             if (timing && hipEventRecord(c->ev[4 * b], s2) != hipSuccess) return ICW_EDEVICE;
             if (icw_launch_fir_graph(&af, &a2, in_step, c->tn.fir_sig, s2) != hipSuccess) return ICW_EDEVICE;
             if (timing && hipEventRecord(c->ev[4 * b + 1], s2) != hipSuccess) return ICW_EDEVICE;
         } else {
             if (fir_async && hipStreamWaitEvent(s2, c->k0done[p], 0) != hipSuccess) return ICW_EDEVICE;
-            if (icw_launch_output(&a2, N, cfg.iir_kahan, s2) != hipSuccess) return ICW_EDEVICE;
+            if (icw_launch_output(&a2, c->nord, cfg.iir_kahan, s2) != hipSuccess) return ICW_EDEVICE;
         }
         if (hipEventRecord(c->k2done[p], s2) != hipSuccess) return ICW_EDEVICE;
         /* the serial part (K4, K3b) on sR after K2(b): it then overlaps K2(b+1) instead of
          * delaying it on sA */
         if (c->serial_render && sR != s2 && hipStreamWaitEvent(sR, c->k2done[p], 0) != hipSuccess) return ICW_EDEVICE;
         if (bus) {
-            IcwK4Args a4;
-            memset(&a4, 0, sizeof(a4));
-            a4.iq = c->iq[p];
-            a4.n_streams = count;
-            a4.T = T;
-            a4.t0 = t0;
-            a4.n_frame = a2.n_frame;
-            a4.ssr = a2.ssr;
-            a4.scaled = a2.scaled;
-            a4.sample_rate = a2.sample_rate;
-            a4.prog = dP;
-            a4.bus = a2.bus;
-            a4.pre = a2.pre;
-            a4.pre_stride = a2.pre_stride;
+            const auto a4 = k4_args(b, a2);
             if (icw_launch_graph_serial(&a4, sR) != hipSuccess) return ICW_EDEVICE;
         }
         if (c->serial_render) {
-            IcwK3Args a3 = k3_args(b, a2);
+            const auto a3 = k3_args(b, a2);
             if (dither) {
                 /* K3a for this block on its own stream: dith[p] was last read by K3b of block b-2 */
                 if (b >= n_sets && sD != sR && hipStreamWaitEvent(sD, c->k3done[p], 0) != hipSuccess) return ICW_EDEVICE;
@@ -2389,8 +2595,8 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         if (pipe_io) {
             /* this block's output slice, once its last writer (K2, or the serial render) is done */
             if (hipStreamWaitEvent(sC, c->serial_render ? c->k3done[p] : c->k2done[p], 0) != hipSuccess ||
-                hipMemcpy2DAsync((unsigned char *)out + (size_t)t0 * osz, out_stride, d_out + (size_t)t0 * osz, dos,
-                                 (size_t)T * osz, S, hipMemcpyDeviceToHost, sC) != hipSuccess)
+                hipMemcpy2DAsync((unsigned char *)out + (size_t)t0 * osz, out_stride, d_out + (size_t)t0 * osz,
+                                 dos, (size_t)T * osz, S, hipMemcpyDeviceToHost, sC) != hipSuccess)
                 return ICW_EDEVICE;
         }
         /* complex input: K0(b + n_sets) reuses xd[p], which K2(b) read */
@@ -2403,27 +2609,25 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
     for (hipStream_t x : {sK, sA, sD, sR, sF, sC})
         if (x && x != st && (hipEventRecord(c->join, x) != hipSuccess || hipStreamWaitEvent(st, c->join, 0) != hipSuccess))
             return ICW_EDEVICE;
-    /* FIR history: the current rows of every stream stay in fir_hist[fir_par] between calls (a call on
-     * a subset of the streams must not move the others' rows); after an odd number of blocks this
-     * call's rows are in the other buffer and come back */
-    if (fir && (n_blocks & 1)) {
-        const size_t hrow = 2 * (size_t)c->fir_M;
-        if (hipMemcpyAsync(c->fir_hist[c->fir_par] + f0 * hrow, c->fir_hist[c->fir_par ^ 1] + f0 * hrow,
-                           S * hrow * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
-            return ICW_EDEVICE;
-    }
-        const IcwAdvArgs av = adv_args();
-        if (icw_launch_advance(&av, st) != hipSuccess) return ICW_EDEVICE;
-    }   /* !s1 */
+    if (fir && !fir_hist_back()) return ICW_EDEVICE;
+    const auto av = adv_args();
+    if (icw_launch_advance(&av, st) != hipSuccess) return ICW_EDEVICE;
+    return ICW_OK;
+}
+
+/* after the kernels: the host mirror of the frame counters, the results back to host pointers, the
+ * debug hooks' copies, stamps and timing */
+int CallPlan::finish_call() const
+{
     for (int i = 0; i < count; ++i) {   /* icw_advance's arithmetic */
         unsigned long long &v = c->nf_host[first + i];
-        v = cfg.frmod_scaled ? (v + (unsigned long long)n_frames) % ssr : v + (unsigned long long)n_frames;
+        v = c->cfg.frmod_scaled ? (v + (unsigned long long)n_frames) % ssr : v + (unsigned long long)n_frames;
     }
     if (legacy && hipStreamSynchronize(st) != hipSuccess) return ICW_EDEVICE;
     if (!dev) {
         unsigned char *h_out = pinned ? c->h_stage + stage_in : nullptr;
         if (pinned ? (!zcopy && hipMemcpyAsync(h_out, d_out, dos * S + sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess)
-                   : (!pipe_io && hipMemcpy2DAsync(out, out_stride, d_out, dos, dos, S, hipMemcpyDeviceToHost, st) != hipSuccess))
+                      : (!pipe_io && !stage_copy_out(dos)))
             return ICW_EDEVICE;
         if (d_pre && hipMemcpyAsync(dbg, d_pre, S * (size_t)n_frames * 2 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
             return ICW_EDEVICE;
@@ -2436,13 +2640,13 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
         int e = 0;
         if (pinned) {
             if (s1_poll ? !poll_done((const uint32_t *)(h_out + done_off), s1_seq, st)
-                        : hipStreamSynchronize(st) != hipSuccess)
+                           : hipStreamSynchronize(st) != hipSuccess)
                 return ICW_EDEVICE;
             memcpy(&e, h_out + dos * S, sizeof(int));     /* the flag icw_advance copied */
             for (size_t i = 0; i < S; ++i) memcpy((unsigned char *)out + i * out_stride, h_out + i * dos, dos);
         } else {
             if (hipStreamSynchronize(st) != hipSuccess) return ICW_EDEVICE;
-            if (hipMemcpy(&e, ds.err, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return ICW_EDEVICE;
+            if (hipMemcpy(&e, c->st.err, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return ICW_EDEVICE;
         }
         if (e) return ICW_EDEVICE;
         if (xin) {
@@ -2485,6 +2689,32 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
     return hipGetLastError() == hipSuccess ? ICW_OK : ICW_EDEVICE;
 }
 
+}  // namespace
+
+extern "C" {
+
+int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t in_stride, void *out,
+                        size_t out_stride, int n_frames, unsigned flags, void *dbg, void *hip_stream)
+{
+    if (!c || first < 0 || count <= 0 || first + count > c->n_streams || n_frames < 0 || !in || !out)
+        return ICW_EINVAL;
+    if (n_frames == 0) return ICW_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (set_dev(c)) return ICW_EDEVICE;
+    ++c->calls;
+    CallPlan pl(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
+    pl.dbg = dbg;
+    int rc;
+    if ((rc = pl.join_legacy_stream()) != ICW_OK) return rc;
+    if ((rc = pl.resolve_plan()) != ICW_OK) return rc;
+    if ((rc = pl.stage_io()) != ICW_OK) return rc;
+    if ((rc = pl.size_scratch()) != ICW_OK) return rc;
+    if ((rc = pl.pick_streams()) != ICW_OK) return rc;
+    if ((rc = pl.s1 ? pl.run_stream1() : pl.run_blocks()) != ICW_OK) return rc;
+    return pl.finish_call();
+}
+
+
 /* ------------------------------------------------------------- CWAVE encoder (icw_cwave.h) -- */
 int icw_cwave_frame_bytes(uint32_t cw_format, uint32_t channels)
 {
@@ -2502,78 +2732,37 @@ int icw_encode_cwave(icw_ctx *c, int first, int count, const void *in, size_t in
         (flags & ~ICW_F_DEVICE_PTRS))
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    const icw_config &cfg = c->cfg;
-    const int FB = icw_cwave_frame_bytes(cw_format, cfg.in_channels);
-    if (cfg.in_format >= ICW_FMT_CW_F64 || c->fir_M <= 0 || FB == 0) return ICW_EINVAL;
-    const unsigned csz = fmt_size(cfg.in_format), fsz = csz * cfg.in_channels;
-    const bool dev = flags & ICW_F_DEVICE_PTRS;
-    const size_t S = (size_t)count, ib = (size_t)n_frames * fsz, ob = (size_t)n_frames * FB;
-    if (!dev && (in_stride < ib || out_stride < ob)) return ICW_EINVAL;
+    const int FB = icw_cwave_frame_bytes(cw_format, c->cfg.in_channels);
+    CallPlan pl(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
+    int rc;
+    if ((rc = pl.enc_format(FB, c->fir_M > 0)) != ICW_OK) return rc;
     if (n_frames == 0) return ICW_OK;
     if (set_dev(c)) return ICW_EDEVICE;
     ++c->calls;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    /* a NULL handle with device pointers: the legacy default stream, as in icw_process_streams */
-    const bool legacy = !hip_stream && dev;
-    if (legacy && (hipEventRecord(c->join, nullptr) != hipSuccess || hipStreamWaitEvent(st, c->join, 0) != hipSuccess))
-        return ICW_EDEVICE;
-    if (!c->enc_clipped) {
-        const int rc = dalloc(&c->enc_clipped, (size_t)c->n_streams);
-        if (rc != ICW_OK) {
-            if (c->enc_clipped) (void)hipFree(c->enc_clipped);
-            c->enc_clipped = nullptr;
-            return rc;
-        }
-    }
-    const unsigned char *d_in = (const unsigned char *)in;
-    unsigned char *d_out = (unsigned char *)out;
-    size_t dis = in_stride, dos = out_stride;
-    if (!dev) {
-        dis = ib;
-        dos = (ob + 15) & ~(size_t)15;                     /* every stream's frames 16-byte aligned */
-        if (grow((void **)&c->d_in, &c->d_in_bytes, dis * S) || grow((void **)&c->d_out, &c->d_out_bytes, dos * S + 16))
-            return ICW_ENOMEM;
-        if (hipMemcpy2DAsync(c->d_in, dis, in, in_stride, ib, S, hipMemcpyHostToDevice, st) != hipSuccess) return ICW_EDEVICE;
-        d_in = c->d_in;
-        d_out = c->d_out;
-    }
-    const int Tb = std::min(n_frames, c->tn.block_env ? c->tn.max_block : kMaxFirBlockFrames);
-    const std::vector<std::pair<int, int>> blocks = plan_blocks(n_frames, Tb, 0, 0.0, c->tn.taper_min);
-    const int n_blocks = (int)blocks.size();
-    const size_t f0 = (size_t)first, hrow = 2 * (size_t)c->fir_M;
-    for (int b = 0; b < n_blocks; ++b) {
+    if ((rc = pl.join_legacy_stream()) != ICW_OK) return rc;
+    if ((rc = ensure_enc_clipped(c)) != ICW_OK) return rc;
+    if ((rc = pl.enc_buffers(FB)) != ICW_OK) return rc;
+    if (!pl.dev && !pl.stage_copy_in()) return ICW_EDEVICE;
+    pl.plan_uniform(kMaxFirBlockFrames);
+    for (int b = 0; b < pl.n_blocks; ++b) {
         IcwEncArgs e;
         memset(&e, 0, sizeof(e));
-        e.f.in = d_in + (size_t)blocks[b].first * fsz;
-        e.f.in_stride = dis;
-        e.f.fmt = cfg.in_format;
-        e.f.csz = csz;
-        e.f.fsz = fsz;
-        e.f.nch = cfg.in_channels;
-        e.f.n_streams = count;
-        e.f.T = blocks[b].second;
-        e.f.t0 = blocks[b].first;
-        e.f.pos = c->st.pos + f0;
-        e.f.fade = c->st.fade + f0 * 3;
-        e.f.M = c->fir_M;
-        e.f.nt = c->fir_nt;
-        e.f.g = c->d_fir_g;
-        e.f.hist_in = c->fir_hist[(c->fir_par + b) & 1] + f0 * hrow;
-        e.f.hist_out = c->fir_hist[(c->fir_par + b + 1) & 1] + f0 * hrow;
-        e.out = d_out + (size_t)blocks[b].first * FB;
-        e.out_stride = dos;
-        e.clipped = c->enc_clipped + f0;
-        if (icw_launch_fir_encode(&e, (int)(cw_format - ICW_FMT_CW_F64), st) != hipSuccess) return ICW_EDEVICE;
+        e.f = pl.fir_args(b);
+        /* KFE packs frames instead of writing K2's rows, and no graph follows it: no row buffer, no
+         * chain signature */
+        e.f.xd = nullptr;
+        e.f.x_pitch = 0;
+        e.f.sig = 0;
+        e.f.lr_same = 0;
+        e.out = pl.d_out + (size_t)pl.blocks[b].first * FB;
+        e.out_stride = pl.dos;
+        e.clipped = c->enc_clipped + pl.f0;
+        if (icw_launch_fir_encode(&e, (int)(cw_format - ICW_FMT_CW_F64), pl.st) != hipSuccess) return ICW_EDEVICE;
     }
-    if ((n_blocks & 1) &&
-        hipMemcpyAsync(c->fir_hist[c->fir_par] + f0 * hrow, c->fir_hist[c->fir_par ^ 1] + f0 * hrow,
-                       S * hrow * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return ICW_EDEVICE;
-    if (icw_launch_pos_advance(c->st.pos + f0, count, (long long)n_frames, st) != hipSuccess) return ICW_EDEVICE;
-    if (legacy && hipStreamSynchronize(st) != hipSuccess) return ICW_EDEVICE;
-    if (!dev && (hipMemcpy2DAsync(out, out_stride, d_out, dos, ob, S, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                 hipStreamSynchronize(st) != hipSuccess))
-        return ICW_EDEVICE;
+    if (!pl.fir_hist_back()) return ICW_EDEVICE;
+    if (icw_launch_pos_advance(c->st.pos + pl.f0, count, (long long)n_frames, pl.st) != hipSuccess) return ICW_EDEVICE;
+    if (pl.legacy && hipStreamSynchronize(pl.st) != hipSuccess) return ICW_EDEVICE;
+    if (!pl.dev && (!pl.stage_copy_out((size_t)n_frames * FB) || hipStreamSynchronize(pl.st) != hipSuccess)) return ICW_EDEVICE;
     return hipGetLastError() == hipSuccess ? ICW_OK : ICW_EDEVICE;
 }
 
@@ -2592,160 +2781,65 @@ int icw_encode_cwave_iir(icw_ctx *c, int first, int count, const void *in, size_
     std::lock_guard<std::mutex> lk(c->mu);
     const icw_config &cfg = c->cfg;
     const int FB = icw_cwave_frame_bytes(cw_format, cfg.in_channels);
-    if (cfg.in_format >= ICW_FMT_CW_F64 || c->fir_M > 0 || FB == 0) return ICW_EINVAL;
-    const unsigned csz = fmt_size(cfg.in_format), nch = cfg.in_channels, fsz = csz * nch;
-    const bool dev = flags & ICW_F_DEVICE_PTRS;
-    const size_t S = (size_t)count, ib = (size_t)n_frames * fsz, ob = (size_t)n_frames * FB;
-    if (!dev && (in_stride < ib || out_stride < ob)) return ICW_EINVAL;
-    if (cfg.fp_check) return ICW_EUNSUPPORTED;             /* FC() arithmetic changes the values */
+    CallPlan pl(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
+    int rc;
+    if ((rc = pl.enc_format(FB, c->fir_M <= 0)) != ICW_OK) return rc;
+    const size_t S = pl.S;
+    /* FC() arithmetic changes the values: refused, so K1 / K2 take no census (fes null, fcm false) */
+    if (cfg.fp_check) return ICW_EUNSUPPORTED;
     if (n_frames == 0) return ICW_OK;
     if (set_dev(c)) return ICW_EDEVICE;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    /* the K1 of a process call over these streams (icw_process_streams) */
-    bool dedup = nch == 1 && c->tn.dedup_ok && (c->tn.k1_mode <= 0 || c->tn.k1_mode == 3);
-    for (int i = 0; dedup && i < count; ++i) dedup = c->lr_known[first + i] != 0;
-    const int row_waves = (int)(((dedup ? count : 2L * count) + 3) / 4) * 2;
-    const bool row_ok = cfg.iir_kahan && cfg.iir_subnorm_reject;
-    int k1_mode = c->tn.k1_mode;
-    if (k1_mode < 0) k1_mode = (row_ok && row_waves <= (c->n_cu / 2) * c->tn.k1_wpc) ? 3 : 0;
-    if (k1_mode == 3 && !row_ok) k1_mode = 0;
-    /* launch blocks: uniform (no pipeline to fill or drain), as long as the block scratch allows */
-    const int Tb = std::min(n_frames, c->tn.block_env ? c->tn.max_block : kMaxBlockFrames);
-    const std::vector<std::pair<int, int>> blocks = plan_blocks(n_frames, Tb, 0, 0.0, c->tn.taper_min);
-    const int n_blocks = (int)blocks.size();
-    const int N = c->nord;
-    const size_t w_pitch = (size_t)Tb + N + 1;
-    const size_t x_pitch = ((size_t)Tb + ICW_MAX_IIR_ORDER + 2) & ~(size_t)1;   /* look-ahead pad */
-    if (!c->enc_clipped) {
-        const int rc = dalloc(&c->enc_clipped, (size_t)c->n_streams);
-        if (rc != ICW_OK) {
-            if (c->enc_clipped) (void)hipFree(c->enc_clipped);
-            c->enc_clipped = nullptr;
-            return rc;
-        }
-    }
-    if (grow((void **)&c->w[0], &c->w_bytes[0], S * 4 * w_pitch * sizeof(double)) ||
-        grow((void **)&c->xd[0], &c->xd_bytes[0], S * 4 * x_pitch * sizeof(double)) ||
-        grow((void **)&c->iq[0], &c->iq_bytes[0], S * (size_t)Tb * 4 * sizeof(double)))
+    /* the K1 of a process call over these streams */
+    pl.pick_k1();
+    pl.plan_uniform(kMaxBlockFrames);
+    if ((rc = ensure_enc_clipped(c)) != ICW_OK) return rc;
+    if (grow((void **)&c->w[0], &c->w_bytes[0], S * 4 * pl.w_pitch * sizeof(double)) ||
+        grow((void **)&c->xd[0], &c->xd_bytes[0], S * 4 * pl.x_pitch * sizeof(double)) ||
+        grow((void **)&c->iq[0], &c->iq_bytes[0], S * (size_t)pl.Tb * 4 * sizeof(double)))
         return ICW_ENOMEM;
-    const unsigned char *d_in = (const unsigned char *)in;
-    unsigned char *d_out = (unsigned char *)out;
-    size_t dis = in_stride, dos = out_stride;
-    if (!dev) {
-        dis = ib;
-        dos = (ob + 15) & ~(size_t)15;                     /* every stream's frames 16-byte aligned */
-        if (grow((void **)&c->d_in, &c->d_in_bytes, dis * S) || grow((void **)&c->d_out, &c->d_out_bytes, dos * S + 16))
-            return ICW_ENOMEM;
-        d_in = c->d_in;
-        d_out = c->d_out;
-    }
+    if ((rc = pl.enc_buffers(FB)) != ICW_OK) return rc;
+    /* counted only now that the allocations succeeded: an early ICW_ENOMEM leaves icw_prepare usable */
     ++c->calls;
-    c->last_k1 = k1_mode;
-    /* a NULL handle with device pointers: the legacy default stream, as in icw_process_streams */
-    const bool legacy = !hip_stream && dev;
-    if (legacy && (hipEventRecord(c->join, nullptr) != hipSuccess || hipStreamWaitEvent(st, c->join, 0) != hipSuccess))
-        return ICW_EDEVICE;
-    if (!dev && hipMemcpy2DAsync(c->d_in, dis, in, in_stride, ib, S, hipMemcpyHostToDevice, st) != hipSuccess)
-        return ICW_EDEVICE;
-    DevState &ds = c->st;
-    const size_t f0 = (size_t)first;
-    for (int b = 0; b < n_blocks; ++b) {
-        const int t0 = blocks[b].first, T = blocks[b].second;
-        IcwK0Args a0;
-        memset(&a0, 0, sizeof(a0));
-        a0.in = d_in + (size_t)t0 * fsz;
-        a0.in_stride = dis;
-        a0.fmt = cfg.in_format;
-        a0.csz = csz;
-        a0.fsz = fsz;
-        a0.nch = nch;
-        a0.n_streams = count;
-        a0.T = T;
-        a0.t0 = t0;
-        a0.pos = ds.pos + f0;
-        a0.fade = ds.fade + f0 * 3;
-        a0.hq_phase = ds.hq_phase + f0 * 2;
-        a0.xd = c->xd[0];
-        a0.x_pitch = x_pitch;
-        a0.dedup = dedup ? 1 : 0;
-        if (icw_launch_unpack(&a0, st) != hipSuccess) return ICW_EDEVICE;
-
-        IcwK1Args a1;
-        memset(&a1, 0, sizeof(a1));
-        a1.xd = c->xd[0];
-        a1.x_pitch = x_pitch;
-        a1.nch = nch;
-        a1.n_streams = count;
-        a1.n_chains = count * 4;
-        a1.T = T;
-        a1.hist = ds.hist + f0 * 4 * ICW_HIST_PITCH;
-        a1.sncnt = ds.sncnt + f0 * 4;
-        a1.err = ds.err;
-        a1.w = c->w[0];
-        a1.w_pitch = w_pitch;
-        a1.lr_equal = ds.lr_equal + f0 * 2;
-        a1.hq_phase = ds.hq_phase + f0 * 2;
-        a1.t0 = t0;
-        a1.info_dup = c->info_dup[0];
-        memcpy(a1.pc, c->pc, sizeof(a1.pc));
-        a1.wg_waves = (c->tn.k1_wg_env || k1_mode != 3) ? c->tn.k1_wg : 2;
-        a1.dedup = dedup ? 1 : 0;
-        const hipError_t e1 = k1_mode == 3 ? icw_launch_iir_row(&a1, N, cfg.iir_kahan, cfg.iir_subnorm_reject, st)
-                                           : icw_launch_iir_state(&a1, N, cfg.iir_kahan, cfg.iir_subnorm_reject, st);
-        if (e1 != hipSuccess) return ICW_EDEVICE;
-
+    c->last_k1 = pl.k1_mode;
+    if ((rc = pl.join_legacy_stream()) != ICW_OK) return rc;
+    if (!pl.dev && !pl.stage_copy_in()) return ICW_EDEVICE;
+    const DevState &ds = c->st;
+    for (int b = 0; b < pl.n_blocks; ++b) {
+        const auto a0 = pl.k0_args(b);
+        if (icw_launch_unpack(&a0, pl.st) != hipSuccess) return ICW_EDEVICE;
+        const auto a1 = pl.k1_args(b);
+        if (pl.launch_k1(a1, pl.st) != hipSuccess) return ICW_EDEVICE;
         /* K2 up to `in`: the output sums and the fs/4 un-mix, then the rows instead of the graph; it still
          * counts the block's de-subnorm rejections */
-        IcwK2Args a2;
-        memset(&a2, 0, sizeof(a2));
-        a2.w = c->w[0];
-        a2.w_pitch = w_pitch;
-        a2.n_streams = count;
-        a2.T = T;
-        a2.n_chains = count * 4;
-        a2.nch = nch;
-        a2.t0 = t0;
-        a2.hq_phase = ds.hq_phase + f0 * 2;
-        a2.n_frame = ds.n_frame + f0;
-        a2.ssr = (unsigned long long)cfg.sample_rate * ICW_HZ_SCALE;
-        a2.scaled = cfg.frmod_scaled;
-        a2.sample_rate = cfg.sample_rate;
-        a2.prog = c->d_prog;
-        a2.bus = ds.bus + f0 * ICW_N_INPUTS * 4;
+        auto a2 = pl.k2_args(b);
+        a2.iq_out = c->iq[0];      /* the rows go out although the list is not bus form: K2 ends there */
+        /* nothing is rendered: no output bytes, no pre-render rows.  With do_render 0 and iq_out set K2
+         * returns after the rows, so what the builder filled of the render (rk, clips, peak_bits) is unread */
         a2.do_render = 0;
-        a2.n_regs = c->prog.chain ? 0 : c->prog.n_regs;
-        a2.clips = ds.clips + f0 * 2;
-        a2.peak_bits = ds.peak_bits + f0 * 2;
-        a2.rk = c->rk;
-        memcpy(a2.pc, c->pc, sizeof(a2.pc));
-        memcpy(a2.pd, c->pd, sizeof(a2.pd));
-        a2.d0 = c->d0;
-        a2.info_dup = c->info_dup[0];
-        a2.xin = c->xd[0];
-        a2.x_pitch = x_pitch;
-        a2.iq_out = c->iq[0];
-        a2.sncnt = cfg.iir_subnorm_reject ? ds.sncnt + f0 * 4 : nullptr;
-        if (icw_launch_output(&a2, N, cfg.iir_kahan, st) != hipSuccess) return ICW_EDEVICE;
+        a2.out = nullptr;
+        a2.out_stride = 0;
+        a2.pre = nullptr;
+        a2.pre_stride = 0;
+        a2.trig = 0;               /* no graph runs, so no rotation factors whatever the list holds */
+        if (icw_launch_output(&a2, c->nord, cfg.iir_kahan, pl.st) != hipSuccess) return ICW_EDEVICE;
 
         IcwPackArgs ap;
         memset(&ap, 0, sizeof(ap));
         ap.iq = c->iq[0];
         ap.n_streams = count;
-        ap.T = T;
-        ap.out = d_out + (size_t)t0 * FB;
-        ap.out_stride = dos;
-        ap.clipped = c->enc_clipped + f0;
-        if (icw_launch_iq_pack(&ap, (int)(cw_format - ICW_FMT_CW_F64), nch > 1 ? 2 : 1, st) != hipSuccess) return ICW_EDEVICE;
+        ap.T = pl.blocks[b].second;
+        ap.out = pl.d_out + (size_t)pl.blocks[b].first * FB;
+        ap.out_stride = pl.dos;
+        ap.clipped = c->enc_clipped + pl.f0;
+        if (icw_launch_iq_pack(&ap, (int)(cw_format - ICW_FMT_CW_F64), pl.nch > 1 ? 2 : 1, pl.st) != hipSuccess) return ICW_EDEVICE;
     }
-    if (nch > 1)
+    if (pl.nch > 1)
         for (int i = 0; i < count; ++i) c->lr_known[first + i] = 0;   /* stereo: the halves diverge */
-    if (icw_launch_enc_advance(ds.pos + f0, ds.hq_phase + f0 * 2, count, (long long)n_frames, st) != hipSuccess)
+    if (icw_launch_enc_advance(ds.pos + pl.f0, ds.hq_phase + pl.f0 * 2, count, (long long)n_frames, pl.st) != hipSuccess)
         return ICW_EDEVICE;
-    if (legacy && hipStreamSynchronize(st) != hipSuccess) return ICW_EDEVICE;
-    if (!dev) {
-        if (hipMemcpy2DAsync(out, out_stride, d_out, dos, ob, S, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            return ICW_EDEVICE;
+    if (pl.legacy && hipStreamSynchronize(pl.st) != hipSuccess) return ICW_EDEVICE;
+    if (!pl.dev) {
+        if (!pl.stage_copy_out((size_t)n_frames * FB) || hipStreamSynchronize(pl.st) != hipSuccess) return ICW_EDEVICE;
         int e = 0;
         if (hipMemcpy(&e, ds.err, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess || e) return ICW_EDEVICE;
     }
