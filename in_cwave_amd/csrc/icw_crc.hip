@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "icw_crc.h"
+#include "icw_launch.h"
 
 #define ICW_CRC_POLY 0xEDB88320u
 

@@ -13,8 +13,7 @@
 
 #include "../../include/icw_cwave.h"
 #include "icw_crc.h"
-
-extern "C" hipError_t icw_launch_crc32(const IcwCrcArgs *a, uint64_t max_cells, int n_cu, hipStream_t st);
+#include "icw_launch.h"
 
 namespace {
 

@@ -1,6 +1,6 @@
 /*
- * icw_device.h -- data structures shared by the host orchestration (icw_host.cpp) and the
- * gfx950 kernels (icw_kernels.hip).  Plain structs passed by value as kernel arguments or
+ * icw_device.h -- data structures shared by the host orchestration (icw_context.cpp, icw_host.cpp) and the
+ * gfx950 kernels (icw_kernels.hip, icw_render.hip).  Plain structs passed by value as kernel arguments or
  * placed in device memory; no HIP types.
  */
 #ifndef ICW_DEVICE_H_

@@ -18,6 +18,7 @@
 
 #include "../../include/icw.h"
 #include "icw_device.h"
+#include "icw_launch.h"
 
 #pragma clang fp contract(off)
 

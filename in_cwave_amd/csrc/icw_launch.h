@@ -1,0 +1,49 @@
+/*
+ * icw_launch.h -- internal: every kernel launcher of the library, declared once.  The .hip file that
+ * defines a launcher and the host file that calls it both include this, so a changed parameter
+ * list is a compile error instead of garbage in a kernel's arguments (the launchers are extern "C").
+ */
+#ifndef ICW_LAUNCH_H
+#define ICW_LAUNCH_H
+
+#include <hip/hip_runtime_api.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "icw_crc.h"
+#include "icw_device.h"
+
+extern "C" {
+
+/* icw_kernels.hip */
+hipError_t icw_launch_unpack(const IcwK0Args *a, hipStream_t st);
+hipError_t icw_launch_output(const IcwK2Args *a, int nord, int kahan, hipStream_t st);
+hipError_t icw_launch_trig_table(const IcwTrigArgs *a, hipStream_t st);
+hipError_t icw_launch_graph_serial(const IcwK4Args *a, hipStream_t st);
+hipError_t icw_launch_advance(const IcwAdvArgs *a, hipStream_t st);
+hipError_t icw_launch_stream1(const IcwS1Args *a, int nord, hipStream_t st);
+hipError_t icw_launch_fir(const IcwFirArgs *a, hipStream_t st);
+hipError_t icw_launch_fir_graph(const IcwFirArgs *f, const IcwK2Args *a, int in_step, int sig_on, hipStream_t st);
+size_t icw_fir_graph_lds(int M, int nt, int nch, int n_regs);
+
+/* icw_render.hip */
+hipError_t icw_launch_render(const IcwK3Args *a, hipStream_t st);
+hipError_t icw_launch_dither(const IcwK3Args *a, hipStream_t st);
+
+/* icw_iir.hip */
+hipError_t icw_launch_iir_state(const IcwK1Args *a, int nord, int kahan, int subn, hipStream_t st);
+hipError_t icw_launch_iir_row(const IcwK1Args *a, int nord, int kahan, int subn, hipStream_t st);
+hipError_t icw_launch_iir_fc(const IcwK1Args *a, int nord, int kahan, int subn, hipStream_t st);
+
+/* icw_encode.hip */
+hipError_t icw_launch_fir_encode(const IcwEncArgs *e, int cwf, hipStream_t st);
+hipError_t icw_launch_pos_advance(long long *pos, int n_streams, long long n, hipStream_t st);
+hipError_t icw_launch_iq_pack(const IcwPackArgs *a, int cwf, int nc, hipStream_t st);
+hipError_t icw_launch_enc_advance(long long *pos, uint32_t *hq_phase, int n_streams, long long n, hipStream_t st);
+
+/* icw_crc.hip */
+hipError_t icw_launch_crc32(const IcwCrcArgs *a, uint64_t max_cells, int n_cu, hipStream_t st);
+
+}  /* extern "C" */
+
+#endif

@@ -24,7 +24,7 @@ CALLS = (317, 400)          # two calls: state carried across a call boundary
 
 
 def bus_form(nodes, bypass):
-    """the host's choice (icw_host.cpp compile_graph): a slot read before its writer runs in the
+    """the host's choice (icw_graph_compile.cpp compile_graph): a slot read before its writer runs in the
     tail -> head order is a one-frame delay, and the register program holds <= 16 ops, 8 regs"""
     if bypass:
         return False

@@ -1,5 +1,5 @@
 // cumask_probe.hip -- where do the workgroups of a CU-masked stream run?  (diagnostic tool)
-// Builds the same masks as icw_host.cpp cu_split (K1 on every (n / k)-th CU bit, the rest on the
+// Builds the same masks as icw_context.cpp cu_split (K1 on every (n / k)-th CU bit, the rest on the
 // complement), launches one-wave workgroups on each stream and records HW_REG_XCC_ID and
 // HW_REG_HW_ID (SE, SH, CU, SIMD) per workgroup.
 //   hipcc --offload-arch=gfx950 -O2 -o tools/cumask_probe tools/cumask_probe.hip
@@ -71,7 +71,7 @@ int main(int argc, char **argv)
     for (int cu = 0; cu < k; ++cu) ml[cu / 32] |= 1u << (cu % 32);
     hipStream_t sl;
     hipExtStreamCreateWithCUMask(&sl, words, ml.data());
-    // icw_host.cpp layout: bit b -> XCC b % 8; per XCC k/8 CUs at evenly spaced in-XCC indices
+    // icw_context.cpp layout: bit b -> XCC b % 8; per XCC k/8 CUs at evenly spaced in-XCC indices
     std::vector<uint32_t> mx(words, 0u), mxr(words, 0u);
     const int per = k / 8, step = (n / 8) / (per > 0 ? per : 1);
     for (int i = 0; i < k; ++i) { int b = (i % 8) + 8 * ((i / 8) * step); mx[b / 32] |= 1u << (b % 32); }
