@@ -1,6 +1,6 @@
 /*
  * icw_device.h -- data structures shared by the host orchestration (icw_context.cpp, icw_host.cpp) and the
- * gfx950 kernels (icw_kernels.hip, icw_render.hip).  Plain structs passed by value as kernel arguments or
+ * gfx950 kernels (the .hip units).  Plain structs passed by value as kernel arguments or
  * placed in device memory; no HIP types.
  */
 #ifndef ICW_DEVICE_H_
@@ -185,13 +185,18 @@ struct IcwProg {
 /* Chain-program signatures compiled straight (IcwProg.sig: the op count in bits 0-3, then per op in
  * execution order (tail first) 4 bits: mode | chain_in << 2).  Each is one of the BASELINE graphs:
  * Master on `in` (C3 / C5), Shift -> Master (C1 / C2), PM -> Shift -> Mix(in + B) -> Master (C4).  Any
- * other chain runs the generic op loop (icw_chain_sig, icw_kernels.hip). */
+ * other chain runs the generic op loop (icw_chain_sig, icw_graph_dev.h). */
 #define ICW_SIG_M    0x41
 #define ICW_SIG_SM   0x852
 #define ICW_SIG_PSXM 0x8F964
 /* flag: every op but the Master has gain 1.0 on both channels (the BASELINE lists' Shift / PM / Mix,
  * DEF_GAIN_MOD in_cwave.h:166), so the render-only form skips those multiplies at compile time */
 #define ICW_SIG_UNIT (1 << 30)
+/* the signatures with code of their own, once: ALIAS(sig) names one that runs the code of the X(sig) after it */
+#define ICW_SIG_LIST(ALIAS, X)                                                            \
+    ALIAS(ICW_SIG_M) X(ICW_SIG_M | ICW_SIG_UNIT)                                          \
+    X(ICW_SIG_SM) X(ICW_SIG_SM | ICW_SIG_UNIT)                                            \
+    X(ICW_SIG_PSXM) X(ICW_SIG_PSXM | ICW_SIG_UNIT)
 
 /* Render constants computed on the host by the sound_render_recalc arithmetic
  * (sound_render.c:499-581), so pow() runs once on the CPU exactly as in the reference. */

@@ -51,6 +51,49 @@ __device__ __forceinline__ uint32_t icw_enc_i16(double v, bool live, unsigned &c
     return r != r ? 0u : (r < 0.0 ? 0x8000u : 0x7fffu);
 }
 
+/* A tile's byte image in LDS to its place dst in the file rows: consecutive 16-byte units where dst is
+ * 16-byte aligned (the at most 14 bytes after the last whole unit of a short tile as halfwords), else dwords
+ * funnelled from two LDS words with the at most two partial dwords at the ends as bytes.  PADU pad units
+ * after every CU units of the image (KFE's lane stride, below; 0: the image is the tile's bytes).  The
+ * caller's buffer reaches 16 bytes past the image's last byte: the funnel reads a second word there (its bits
+ * are shifted out) -- KFE's staging area is larger, KIP declares the 16 spare bytes. */
+template <int PADU, int CU>
+__device__ __forceinline__ void icw_tile_out(unsigned char *dst, int nbytes, const void *lds_image, int tid)
+{
+    const uint4 *ob = (const uint4 *)lds_image;
+    const uint32_t *ow = (const uint32_t *)lds_image;
+    const unsigned char *oc = (const unsigned char *)lds_image;
+    /* logical 16-byte unit / dword / byte of the tile -> its place in the padded image */
+    auto pu = [](int j) { return j + PADU * (j / CU); };
+    auto pw = [](int j) { return j + 4 * PADU * (j / (4 * CU)); };
+    auto pb = [](int j) { return j + 16 * PADU * (j / (16 * CU)); };
+    if (!((uintptr_t)dst & 15)) {
+        const int nu = nbytes >> 4;
+        uint4 *d4 = (uint4 *)dst;
+        for (int j = tid; j < nu; j += 256) d4[j] = ob[pu(j)];
+        const int rest = nbytes - 16 * nu;               /* < 16, even: the last frames of a short tile */
+        if (tid < rest / 2) {
+            const int j = 16 * nu + 2 * tid;
+            *(unsigned short *)(dst + j) = *(const unsigned short *)(oc + pb(j));
+        }
+    } else {
+        const int b = (int)((uintptr_t)dst & 3);
+        unsigned char *d0 = dst - b;
+        const int nd = (b + nbytes + 3) >> 2;
+        for (int k = tid; k < nd; k += 256) {
+            const int o = 4 * k - b;                     /* the dword's first byte in the tile */
+            if (o >= 0 && o + 4 <= nbytes) {
+                uint32_t v = ow[pw(k)];
+                if (b) v = (ow[pw(k - 1)] >> (8 * (4 - b))) | (v << (8 * b));
+                *(uint32_t *)(d0 + 4 * k) = v;
+            } else {
+                for (int i = 0; i < 4; ++i)
+                    if (o + i >= 0 && o + i < nbytes) d0[4 * k + i] = oc[pb(o + i)];
+            }
+        }
+    }
+}
+
 template <int CWF, int NC>
 __global__ __launch_bounds__(256) void icw_fir_encode(IcwEncArgs e)
 {
@@ -64,10 +107,9 @@ __global__ __launch_bounds__(256) void icw_fir_encode(IcwEncArgs e)
     const int s = blockIdx.y, tid = threadIdx.x;
     const int tt = blockIdx.x * TF;
     const int M = a.M, c = M >> 1;
-    const int sh = (8 - ((c - 1) & 7)) & 7;          /* c - 1 + sh = 8 a */
-    const int av = (c - 1 + sh) >> 3;
+    const int sh = icw_fir_sh(c), av = icw_fir_av(c, sh);   /* c - 1 + sh = 8 av */
     const int nf = min(TF, a.T - tt);
-    const int px = (icw_fir_phys(sh + M + TF + 24) + 2) & ~1;
+    const int px = icw_fir_px(sh, M, TF);
     if (tid == 0) nclip = 0u;
     icw_fir_stage<NC>(a, s, 0, xs, px, tt, TF, sh, tid, 256);
     icw_ctap *gs = (icw_ctap *)a.g;
@@ -119,44 +161,7 @@ __global__ __launch_bounds__(256) void icw_fir_encode(IcwEncArgs e)
     if ((CWF == 1 || CWF == 2) && tid == 0 && nclip) atomicAdd(e.clipped + s, (unsigned long long)nclip);
     unsigned char *dst = e.out + (size_t)s * e.out_stride + (size_t)tt * FB;
     const int nbytes = nf * FB;
-    const uint32_t *ow = (const uint32_t *)xs;
-    const unsigned char *oc = (const unsigned char *)xs;
-    /* logical 16-byte unit / dword / byte of the tile -> its place in the padded image */
-    auto pu = [](int j) { return j + PADU * (j / CU); };
-    auto pw = [](int j) { return j + 4 * PADU * (j / (4 * CU)); };
-    auto pb = [](int j) { return j + 16 * PADU * (j / (16 * CU)); };
-    if (!((uintptr_t)dst & 15)) {
-        const int nu = nbytes >> 4;
-        uint4 *d4 = (uint4 *)dst;
-        for (int j = tid; j < nu; j += 256) d4[j] = ob[pu(j)];
-        const int rest = nbytes - 16 * nu;               /* < 16, even: the last frames of a short tile */
-        if (tid < rest / 2) {
-            const int j = 16 * nu + 2 * tid;
-            *(unsigned short *)(dst + j) = *(const unsigned short *)(oc + pb(j));
-        }
-    } else {
-        const int b = (int)((uintptr_t)dst & 3);
-        unsigned char *d0 = dst - b;
-        const int nd = (b + nbytes + 3) >> 2;
-        for (int k = tid; k < nd; k += 256) {
-            const int o = 4 * k - b;                     /* the dword's first byte in the tile */
-            if (o >= 0 && o + 4 <= nbytes) {
-                uint32_t v = ow[pw(k)];
-                if (b) v = (ow[pw(k - 1)] >> (8 * (4 - b))) | (v << (8 * b));
-                *(uint32_t *)(d0 + 4 * k) = v;
-            } else {
-                for (int i = 0; i < 4; ++i)
-                    if (o + i >= 0 && o + i < nbytes) d0[4 * k + i] = oc[pb(o + i)];
-            }
-        }
-    }
-}
-
-/* the reader position of the streams an encode call covered (what icw_advance does to it) */
-__global__ __launch_bounds__(64) void icw_pos_advance(long long *pos, int n_streams, long long n)
-{
-    const int s = blockIdx.x * 64 + threadIdx.x;
-    if (s < n_streams) pos[s] += n;
+    icw_tile_out<PADU, CU>(dst, nbytes, xs, tid);
 }
 
 /* KIP: the packer of the IIR encoder (icw_encode_cwave_iir).  The quadrature IIR's analytic signal of a
@@ -224,67 +229,35 @@ __global__ __launch_bounds__(256) void icw_iq_pack(IcwPackArgs a)
     }
     unsigned char *dst = a.out + (size_t)s * a.out_stride + (size_t)tt * FB;
     const int nbytes = nf * FB;
-    const uint32_t *ow = (const uint32_t *)img;
-    if (!((uintptr_t)dst & 15)) {
-        const int nu = nbytes >> 4;
-        uint4 *d4 = (uint4 *)dst;
-        const uint4 *ob = (const uint4 *)img;
-        for (int j = tid; j < nu; j += 256) d4[j] = ob[j];
-        const int rest = nbytes - 16 * nu;               /* < 16, even: the last frames of a short tile */
-        if (tid < rest / 2) {
-            const int j = 16 * nu + 2 * tid;
-            *(unsigned short *)(dst + j) = *(const unsigned short *)(img + j);
-        }
-    } else {
-        const int b = (int)((uintptr_t)dst & 3);
-        unsigned char *d0 = dst - b;
-        const int nd = (b + nbytes + 3) >> 2;
-        for (int k = tid; k < nd; k += 256) {
-            const int o = 4 * k - b;                     /* the dword's first byte in the tile */
-            if (o >= 0 && o + 4 <= nbytes) {
-                uint32_t v = ow[k];
-                if (b) v = (ow[k - 1] >> (8 * (4 - b))) | (v << (8 * b));
-                *(uint32_t *)(d0 + 4 * k) = v;
-            } else {
-                for (int i = 0; i < 4; ++i)
-                    if (o + i >= 0 && o + i < nbytes) d0[4 * k + i] = img[o + i];
-            }
-        }
-    }
+    icw_tile_out<0, 1>(dst, nbytes, img, tid);
     if (CWF == 1 || CWF == 2) {
         __syncthreads();
         if (tid == 0 && nclip) atomicAdd(a.clipped + s, (unsigned long long)nclip);
     }
 }
 
-/* the reader position and the Hilbert phases of the streams an IIR encode call covered: what icw_advance
- * does to them, without its frame counter */
+/* the reader position and (IIR encoder; the FIR one passes no hq_phase) the Hilbert phases of the streams an
+ * encode call covered: what icw_advance does to them, without its frame counter */
 __global__ __launch_bounds__(64) void icw_enc_advance(long long *pos, uint32_t *hq_phase, int n_streams, long long n)
 {
     const int s = blockIdx.x * 64 + threadIdx.x;
     if (s < n_streams) {
         pos[s] += n;
-        hq_phase[s * 2 + 0] = (hq_phase[s * 2 + 0] + (unsigned)n) & 3u;
-        hq_phase[s * 2 + 1] = (hq_phase[s * 2 + 1] + (unsigned)n) & 3u;
+        if (hq_phase) {
+            hq_phase[s * 2 + 0] = (hq_phase[s * 2 + 0] + (unsigned)n) & 3u;
+            hq_phase[s * 2 + 1] = (hq_phase[s * 2 + 1] + (unsigned)n) & 3u;
+        }
     }
 }
 
 /* ---------------------------------------------------------------- launch wrappers ------- */
-/* LDS doubles of one staged channel (the px of the kernels) */
-static size_t enc_px(int M)
-{
-    const int sh = (8 - ((M / 2 - 1) & 7)) & 7;
-    const int nl = sh + M + 256 * ICW_FIR_R + 24;
-    return (size_t)(nl + ICW_FIR_PAD * (nl >> 3) + 2) & ~(size_t)1;
-}
-
 template <int CWF, int NC>
 static hipError_t launch_fir_encode_t(const IcwEncArgs *e, hipStream_t st)
 {
     constexpr int TF = 256 * ICW_FIR_R;
     constexpr int CU = NC * icw_cw_bytes<CWF>::value / 2, PADU = (CU & 1) ? 0 : 1;
     /* the staged channels, or the tile's padded frame image where that is larger (it takes their place) */
-    const size_t lds = std::max((size_t)NC * enc_px(e->f.M) * sizeof(double), (size_t)256 * (CU + PADU) * 16);
+    const size_t lds = std::max((size_t)NC * icw_fir_px(e->f.M, TF) * sizeof(double), (size_t)256 * (CU + PADU) * 16);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     /* LDS above 64 KB per workgroup needs the kernel attribute (gfx950: 160 KB per CU) */
     if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)icw_fir_encode<CWF, NC>,
@@ -294,19 +267,27 @@ static hipError_t launch_fir_encode_t(const IcwEncArgs *e, hipStream_t st)
     return hipGetLastError();
 }
 
+/* f(icw_ic<cwf>, icw_ic<channels>) for a CWAVE format cwf = cw_format - ICW_FMT_CW_F64 of 1 or 2 channels */
+template <class F>
+static hipError_t enc_dispatch(int cwf, bool st2, F &&f)
+{
+    switch (cwf) {
+    case 0: return st2 ? f(icw_ic<0>{}, icw_ic<2>{}) : f(icw_ic<0>{}, icw_ic<1>{});
+    case 1: return st2 ? f(icw_ic<1>{}, icw_ic<2>{}) : f(icw_ic<1>{}, icw_ic<1>{});
+    case 2: return st2 ? f(icw_ic<2>{}, icw_ic<2>{}) : f(icw_ic<2>{}, icw_ic<1>{});
+    case 3: return st2 ? f(icw_ic<3>{}, icw_ic<2>{}) : f(icw_ic<3>{}, icw_ic<1>{});
+    }
+    return hipErrorInvalidValue;
+}
+
 /* KFE of one launch block; cwf = cw_format - ICW_FMT_CW_F64 */
 extern "C" hipError_t icw_launch_fir_encode(const IcwEncArgs *e, int cwf, hipStream_t st)
 {
     const int M = e->f.M, nt = e->f.nt;
     if (M < 2 || M > ICW_FIR_MAX_M || (M & 1) || nt < 1 || 2 * nt - 1 > M / 2 || e->f.T <= 0) return hipErrorInvalidValue;
-    const bool st2 = e->f.nch > 1;
-    switch (cwf) {
-    case 0: return st2 ? launch_fir_encode_t<0, 2>(e, st) : launch_fir_encode_t<0, 1>(e, st);
-    case 1: return st2 ? launch_fir_encode_t<1, 2>(e, st) : launch_fir_encode_t<1, 1>(e, st);
-    case 2: return st2 ? launch_fir_encode_t<2, 2>(e, st) : launch_fir_encode_t<2, 1>(e, st);
-    case 3: return st2 ? launch_fir_encode_t<3, 2>(e, st) : launch_fir_encode_t<3, 1>(e, st);
-    }
-    return hipErrorInvalidValue;
+    return enc_dispatch(cwf, e->f.nch > 1, [&](auto fc, auto nc) {
+        return launch_fir_encode_t<decltype(fc)::value, decltype(nc)::value>(e, st);
+    });
 }
 
 template <int CWF, int NC>
@@ -321,24 +302,13 @@ static hipError_t launch_iq_pack_t(const IcwPackArgs *a, hipStream_t st)
 extern "C" hipError_t icw_launch_iq_pack(const IcwPackArgs *a, int cwf, int nc, hipStream_t st)
 {
     if (a->T <= 0 || a->n_streams <= 0 || !a->iq || !a->out || !a->clipped || nc < 1 || nc > 2) return hipErrorInvalidValue;
-    const bool st2 = nc > 1;
-    switch (cwf) {
-    case 0: return st2 ? launch_iq_pack_t<0, 2>(a, st) : launch_iq_pack_t<0, 1>(a, st);
-    case 1: return st2 ? launch_iq_pack_t<1, 2>(a, st) : launch_iq_pack_t<1, 1>(a, st);
-    case 2: return st2 ? launch_iq_pack_t<2, 2>(a, st) : launch_iq_pack_t<2, 1>(a, st);
-    case 3: return st2 ? launch_iq_pack_t<3, 2>(a, st) : launch_iq_pack_t<3, 1>(a, st);
-    }
-    return hipErrorInvalidValue;
+    return enc_dispatch(cwf, nc > 1, [&](auto fc, auto ncc) {
+        return launch_iq_pack_t<decltype(fc)::value, decltype(ncc)::value>(a, st);
+    });
 }
 
 extern "C" hipError_t icw_launch_enc_advance(long long *pos, uint32_t *hq_phase, int n_streams, long long n, hipStream_t st)
 {
     hipLaunchKernelGGL(icw_enc_advance, dim3((n_streams + 63) / 64), dim3(64), 0, st, pos, hq_phase, n_streams, n);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t icw_launch_pos_advance(long long *pos, int n_streams, long long n, hipStream_t st)
-{
-    hipLaunchKernelGGL(icw_pos_advance, dim3((n_streams + 63) / 64), dim3(64), 0, st, pos, n_streams, n);
     return hipGetLastError();
 }

@@ -1,7 +1,8 @@
 /*
  * icw_fir_dev.h -- device code of the FIR Hilbert converter shared by its kernels (KF, KF2 and the
- * CWAVE encoder KFE): the staging of a tile's inputs in LDS and the register-blocked tap sums.
- * Included after icw_unpack_dev.h.
+ * CWAVE encoder KFE): the tile geometry, the staging of a tile's inputs in LDS, the register-blocked tap
+ * sums, the packing and the store of a lane's rendered frames, and the dispatch on a chain signature.
+ * Included after icw_device.h and icw_unpack_dev.h.
  */
 #ifndef ICW_FIR_DEV_H_
 #define ICW_FIR_DEV_H_
@@ -60,8 +61,16 @@
 #ifndef ICW_RENDER_SH0
 #define ICW_RENDER_SH0 1                             /* A/B: the render-only form specialised for norm_shift 0 */
 #endif
-__device__ __forceinline__ int icw_fir_phys(int i) { return i + ICW_FIR_PAD * (i >> 3); }
+__host__ __device__ __forceinline__ constexpr int icw_fir_phys(int i) { return i + ICW_FIR_PAD * (i >> 3); }
 
+/* Tile geometry, for the kernels and for the launchers' LDS sizes alike.  Order M, centre c = M / 2:
+ *   sh  staging shift, c - 1 + sh = 8 av: every lane's window starts at the same phase of the pad pattern;
+ *   px  doubles of one staged channel of a TF-frame tile (pad, history, tile, margin), even, so the next
+ *       channel's row stays 16-byte aligned. */
+__host__ __device__ __forceinline__ constexpr int icw_fir_sh(int c) { return (8 - ((c - 1) & 7)) & 7; }
+__host__ __device__ __forceinline__ constexpr int icw_fir_av(int c, int sh) { return (c - 1 + sh) >> 3; }
+__host__ __device__ __forceinline__ constexpr int icw_fir_px(int sh, int M, int TF) { return (icw_fir_phys(sh + M + TF + 24) + 2) & ~1; }
+__host__ __device__ __forceinline__ constexpr int icw_fir_px(int M, int TF) { return icw_fir_px(icw_fir_sh(M >> 1), M, TF); }
 
 /* inputs of NC channels from ch0 for the outputs [tt, tt + nout) of a launch block, at logical
  * index i <-> frame j = tt - M + i - sh (zero outside [-M, T)), channel k at xs + k * px; the
@@ -327,6 +336,74 @@ __device__ __forceinline__ void icw_fir_sums(const double *xs, icw_ctap *gs, int
         }
     }
     (void)sh; (void)c;
+}
+
+/* Two rendered stereo frames as they lie in the output: 16-bit l0 r0 l1 r1 in two dwords, 24-bit in three.
+ * The depth B24 is a template parameter here and in icw_store_packed, and every index into a lane's packed
+ * words w is a constant once the callers' loops are unrolled: with a runtime depth flag the compiler merged
+ * the two packings' stores into one store at a selected index, which put w in scratch -- c3fir wrote 6.3 GB
+ * per launch against 4.3 GB of output (profiles/r05_c3fir_pmc.json). */
+template <bool B24>
+__device__ __forceinline__ void icw_pack2(int l0, int r0, int l1, int r1, unsigned *w)
+{
+    if constexpr (B24) {
+        const unsigned a0 = (unsigned)l0 & 0xffffffu, b0 = (unsigned)r0 & 0xffffffu;
+        const unsigned a1 = (unsigned)l1 & 0xffffffu, b1 = (unsigned)r1 & 0xffffffu;
+        w[0] = a0 | (b0 << 24);
+        w[1] = (b0 >> 8) | (a1 << 16);
+        w[2] = (a1 >> 16) | (b1 << 8);
+    } else {
+        w[0] = ((unsigned)l0 & 0xffffu) | ((unsigned)r0 << 16);
+        w[1] = ((unsigned)l1 & 0xffffu) | ((unsigned)r1 << 16);
+    }
+}
+#define ICW_PACK2_WORDS(B24) ((B24) ? 3 : 2)         /* dwords icw_pack2 writes */
+
+/* The first nv of a lane's NFR (4 or 8) packed frames w to their place p in the output row: 16-byte (16-bit)
+ * / 8-byte (24-bit) stores when p is so aligned and nv == NFR, else dwords (16-bit; p is dword-aligned for
+ * every output the library lays out itself) or bytes (24-bit; byte i of the packed run is byte i of the
+ * output). */
+template <bool B24, int NFR, int NW>
+__device__ __forceinline__ void icw_store_packed(unsigned char *p, const unsigned (&w)[NW], int nv)
+{
+    static_assert((NFR == 4 || NFR == 8) && NW >= NFR / 2 * ICW_PACK2_WORDS(B24), "w holds the NFR frames");
+    if constexpr (B24) {
+        if (nv == NFR && !((uintptr_t)p & 7)) {
+            uint2 *q2 = (uint2 *)p;
+#pragma unroll
+            for (int i = 0; i < NFR * 6 / 8; ++i) q2[i] = make_uint2(w[2 * i], w[2 * i + 1]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < NFR * 6; ++i)
+                if (i < nv * 6) p[i] = (unsigned char)(w[i >> 2] >> (8 * (i & 3)));
+        }
+    } else {
+        unsigned *d = (unsigned *)p;
+        if (nv == NFR && !((uintptr_t)p & 15)) {
+#pragma unroll
+            for (int i = 0; i < NFR; i += 4) *(uint4 *)(d + i) = make_uint4(w[i], w[i + 1], w[i + 2], w[i + 3]);
+        } else {
+#pragma unroll
+            for (int r = 0; r < NFR; ++r)
+                if (r < nv) d[r] = w[r];
+        }
+    }
+}
+
+/* A runtime signature as the compile-time constant of its specialised code (ICW_SIG_LIST, icw_device.h:
+ * the Master signature without the unit flag runs the code of the one with it -- it has no other op whose
+ * gain the flag could skip): f(icw_ic<SIG>) for a listed one, false for any other. */
+template <class F>
+__host__ __device__ __forceinline__ bool icw_sig_dispatch(int sig, F &&f)
+{
+    switch (sig) {
+#define ICW_SIG_ALIAS_(S) case (S):
+#define ICW_SIG_CASE_(S) case (S): f(icw_ic<(S)>{}); return true;
+        ICW_SIG_LIST(ICW_SIG_ALIAS_, ICW_SIG_CASE_)
+#undef ICW_SIG_ALIAS_
+#undef ICW_SIG_CASE_
+    default: return false;
+    }
 }
 
 #endif /* ICW_FIR_DEV_H_ */

@@ -1238,7 +1238,7 @@ int icw_encode_cwave(icw_ctx *c, int first, int count, const void *in, size_t in
         if (icw_launch_fir_encode(&e, (int)(cw_format - ICW_FMT_CW_F64), pl.st) != hipSuccess) return ICW_EDEVICE;
     }
     if (!pl.fir_hist_back()) return ICW_EDEVICE;
-    if (icw_launch_pos_advance(c->st.pos + pl.f0, count, (long long)n_frames, pl.st) != hipSuccess) return ICW_EDEVICE;
+    if (icw_launch_enc_advance(c->st.pos + pl.f0, nullptr, count, (long long)n_frames, pl.st) != hipSuccess) return ICW_EDEVICE;
     if (pl.legacy && hipStreamSynchronize(pl.st) != hipSuccess) return ICW_EDEVICE;
     if (!pl.dev && (!pl.stage_copy_out((size_t)n_frames * FB) || hipStreamSynchronize(pl.st) != hipSuccess)) return ICW_EDEVICE;
     return hipGetLastError() == hipSuccess ? ICW_OK : ICW_EDEVICE;

@@ -22,6 +22,8 @@ hipError_t icw_launch_trig_table(const IcwTrigArgs *a, hipStream_t st);
 hipError_t icw_launch_graph_serial(const IcwK4Args *a, hipStream_t st);
 hipError_t icw_launch_advance(const IcwAdvArgs *a, hipStream_t st);
 hipError_t icw_launch_stream1(const IcwS1Args *a, int nord, hipStream_t st);
+
+/* icw_fir.hip */
 hipError_t icw_launch_fir(const IcwFirArgs *a, hipStream_t st);
 hipError_t icw_launch_fir_graph(const IcwFirArgs *f, const IcwK2Args *a, int in_step, int sig_on, hipStream_t st);
 size_t icw_fir_graph_lds(int M, int nt, int nch, int n_regs);
@@ -37,8 +39,8 @@ hipError_t icw_launch_iir_fc(const IcwK1Args *a, int nord, int kahan, int subn, 
 
 /* icw_encode.hip */
 hipError_t icw_launch_fir_encode(const IcwEncArgs *e, int cwf, hipStream_t st);
-hipError_t icw_launch_pos_advance(long long *pos, int n_streams, long long n, hipStream_t st);
 hipError_t icw_launch_iq_pack(const IcwPackArgs *a, int cwf, int nc, hipStream_t st);
+/* hq_phase: null for the FIR encoder (the reader position alone) */
 hipError_t icw_launch_enc_advance(long long *pos, uint32_t *hq_phase, int n_streams, long long n, hipStream_t st);
 
 /* icw_crc.hip */

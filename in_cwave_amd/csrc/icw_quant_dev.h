@@ -1,6 +1,6 @@
 /*
- * icw_quant_dev.h -- device helpers that icw_kernels.hip (the elementwise render inside the output
- * kernels) and icw_render.hip (the serial and row renders) share: the quantiser steps of
+ * icw_quant_dev.h -- device helpers that icw_graph_dev.h (the elementwise render inside K2 and
+ * KF2) and icw_render.hip (the serial and row renders) share: the quantiser steps of
  * sound_render_value and the single-instruction conversions and maxima they use.  Include after
  * <hip/hip_runtime.h> and icw_device.h, under `#pragma clang fp contract(off)`.
  */

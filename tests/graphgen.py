@@ -88,7 +88,7 @@ def random_config(rng):
 # The host compiles a *chain* (every op reads only `in` and / or the op just before it) with no channel
 # exchange, no I/Q inversion, both channels of every Shift / PM rotating and a Master summing re + im
 # into a signature (icw_graph_compile.cpp compile_graph, IcwProg.sig); the three BASELINE structures among them
-# run specialised code (ICW_SIG_M / _SM / _PSXM, icw_kernels.hip), and KF2 runs those in the render-only
+# run specialised code (ICW_SIG_M / _SM / _PSXM, icw_graph_dev.h), and KF2 runs those in the render-only
 # form (icw_sig_fast) when a call asks for no pre-render doubles.  Structures, as (mode, reads) per op
 # in execution order (tail first); reads: 1 = in, 2 = the previous op, 3 = both.
 SIG_STRUCTS = {

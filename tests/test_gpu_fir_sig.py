@@ -1,4 +1,4 @@
-"""GPU parity of KF2's signature form (icw_fir_sig in icw_kernels.hip): the tiles of a launch block
+"""GPU parity of KF2's signature form (icw_fir_sig in icw_fir.hip): the tiles of a launch block
 before the one holding its last frame go through a kernel holding only the staging, the sums, the
 render-only signature pass and the meters, and icw_fir_graph takes the rest (icw_launch_fir_graph,
 IcwFirArgs.tile0).  Calls of lengths around the tile size (1024 stereo / 2048 mono frames: no tile for

@@ -1,5 +1,5 @@
 """GPU parity of the render-only form of the specialised chain programs (icw_sig_fast in
-icw_kernels.hip, KF2): calls that ask for no pre-render doubles run the BASELINE graphs' signatures
+icw_graph_dev.h, KF2): calls that ask for no pre-render doubles run the BASELINE graphs' signatures
 without the reference's leading `0.0 +` per op input, with the division by SQRT2 tested once per op
 and the render's clip stage as a saturating conversion + integer clamp.  Its rendered bytes and
 meters must be the oracle's, and the exact form's (the same call asking for the doubles), for both

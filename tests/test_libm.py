@@ -42,7 +42,7 @@ def test_checker_detects_variant_mix(tmp_path):
 
 
 def test_div_sqrt2_hard_cases():
-    """icw_div_sqrt2 (icw_kernels.hip): dsp_master's x / SQRT2 (adv_modulator.c:498-501) as
+    """icw_div_sqrt2 (icw_graph_dev.h): dsp_master's x / SQRT2 (adv_modulator.c:498-501) as
     q0 = RN(x r), e = RN(x - q0 c), q = RN(q0 + e r) with r = RN(1/c).  Its error is below 2^-51 ulp,
     so it can miss RN(x/c) only where x/c is that close to a rounding midpoint: for c = C 2^-52
     (C odd) those significands X solve (2M + 1) C - 2^s X = k, s = 53 (X >= C) or 54 (X < C), odd
