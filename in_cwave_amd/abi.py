@@ -7,6 +7,7 @@ MAX_IIR_ORDER = 20
 
 # status codes
 OK, EINVAL, ENOMEM, EDEVICE, EGRAPH, EUNSUPPORTED = 0, -1, -2, -3, -4, -5
+HZ_SCALE, MAX_FS_SRC = 1000, 2000000   # ICW_HZ_SCALE, ICW_MAX_FS_SRC
 
 # node modes / master outputs / channel exchange (in_cwave.h:152-287)
 MODE_MASTER, MODE_SHIFT, MODE_PM, MODE_MIX = 0, 1, 2, 3
@@ -111,6 +112,10 @@ class WavInfo(C.Structure):
                 ("htype", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+# icw_batch_opts.reserved_ is the flags word (0: today's grouping, one context per input format)
+BATCH_MERGE_INPUTS = 1   # ICW_BATCH_MERGE_INPUTS: all real-input files in one context per device
+
+
 class BatchOpts(C.Structure):
     _fields_ = [("fade_in_ms", C.c_uint32), ("fade_out_ms", C.c_uint32), ("sec_align", C.c_uint32),
                 ("block_frames", C.c_int32), ("device", C.c_int32), ("reserved_", C.c_int32)]
@@ -145,6 +150,8 @@ SIGNATURES = {
     "icw_stream_reset_framecnt": (_i, [_vp, _i]),
     "icw_stream_seek": (_i, [_vp, _i, C.c_int64]),
     "icw_set_input": (_i, [_vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "icw_set_stream_input": (_i, [_vp, _i, _i, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "icw_stream_input_count": (_i, [_vp]),
     "icw_set_fir_hilbert": (_i, [_vp, C.c_int32, C.c_double]),
     "icw_set_graph": (_i, [_vp, C.POINTER(Node), _i, _i, C.POINTER(_i)]),
     "icw_set_stream_graph": (_i, [_vp, _i, _i, C.POINTER(Node), _i, _i, C.POINTER(_i)]),
@@ -190,6 +197,7 @@ SIGNATURES = {
     "icw_get_state": (_i, [_vp, _i, _vp, _sz]),
     "icw_set_state": (_i, [_vp, _i, _vp, _sz]),
     "icw_last_timing": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
+    "icw_last_k0_timing": (_i, [_vp, C.POINTER(C.c_double)]),
     "icw_last_k1_kernel": (_i, [_vp]),
     "icw_get_fp_census": (_i, [_vp, _i, _i, C.POINTER(C.c_uint32)]),
     "icw_cwave_parse": (_i, [_vp, _sz, C.c_int64, C.POINTER(CwaveHeader), C.POINTER(C.c_uint32),

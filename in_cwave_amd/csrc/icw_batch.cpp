@@ -179,9 +179,11 @@ struct FileLists {
  * channels, key), run each group, close the files and count the results.  accept(i, job) fills the
  * job's info and returns file i's status (ICW_OK to go on); key(i) is the caller's own part of the
  * group key, asked once the file is open; run(key, jobs, stats, status) processes one group. */
+/* merge (ICW_BATCH_MERGE_INPUTS): the real-input files group by the key alone -- one context whose
+ * streams each get their own input (icw_set_stream_input); CWAVE files keep the grouping above. */
 template <class Accept, class Key, class Run>
 int for_file_groups(const char *const *in_paths, const char *const *out_paths, int n, icw_batch_stats *stats, int *status,
-                    Accept accept, Key key, Run run)
+                    Accept accept, Key key, Run run, bool merge = false)
 {
     const double t0 = now_s();
     icw_batch_stats st;
@@ -200,7 +202,8 @@ int for_file_groups(const char *const *in_paths, const char *const *out_paths, i
         }
         setvbuf(j.in, nullptr, _IOFBF, 1 << 20);
         setvbuf(j.out, nullptr, _IOFBF, 1 << 20);
-        groups[std::make_tuple(j.info.sample_rate, j.info.fmt, j.info.channels, key(i))].push_back(&j);
+        if (merge && j.info.fmt < ICW_FMT_CW_F64) groups[std::make_tuple(0u, 0u, 0u, key(i))].push_back(&j);
+        else groups[std::make_tuple(j.info.sample_rate, j.info.fmt, j.info.channels, key(i))].push_back(&j);
     }
     int rc = ICW_OK;
     for (auto &g : groups) {
@@ -237,7 +240,7 @@ struct GroupPipe {
     icw_batch_stats &st;
     int *status;
     const int S, B;
-    const size_t fsz, osz;                /* bytes per input / output frame */
+    const size_t fsz, osz;                /* bytes per input frame (the group's widest: the rows' pitch) / output frame */
     const size_t in_b, out_b;
     unsigned char *hin[2] = {nullptr, nullptr}, *hout[2] = {nullptr, nullptr}, *din[2] = {nullptr, nullptr},
                   *dout[2] = {nullptr, nullptr};
@@ -287,15 +290,16 @@ struct GroupPipe {
         for (int s = 0; s < S; ++s) {
             Job &j = *jobs[s];
             unsigned char *row = buf + (size_t)s * B * fsz;
+            const size_t jf = j.info.frame_bytes;                          /* the file's own frame (<= fsz) */
             const int64_t want = std::min<int64_t>(nfr, std::max<int64_t>(0, j.info.n_samples - j.read));
             size_t got = 0;
             if (want > 0 && status[j.idx] == ICW_OK) {
-                got = fread(row, fsz, (size_t)want, j.in);
+                got = fread(row, jf, (size_t)want, j.in);
                 if ((int64_t)got != want) status[j.idx] = ICW_EINVAL;      /* short read: broken file */
                 j.read += (int64_t)got;
                 st.frames_in += got;
             }
-            memset(row + got * fsz, zero_byte(j.info.fmt), (size_t)(B - (int64_t)got) * fsz);
+            memset(row + got * jf, zero_byte(j.info.fmt), (size_t)(B - (int64_t)got) * jf);
         }
         st.io_s += now_s() - t0;
     }
@@ -356,7 +360,8 @@ struct GroupPipe {
     }
 };
 
-/* One group of files sharing (rate, format, channels): one context, one stream per file. */
+/* One group of files: one context, one stream per file.  The files share (rate, format, channels), or
+ * (ICW_BATCH_MERGE_INPUTS) every stream gets its own file's input before the first block. */
 int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::vector<Job *> &jobs,
               const icw_batch_opts &o, icw_batch_stats &st, int *status, const FileLists &fl = FileLists())
 {
@@ -384,8 +389,15 @@ int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::v
                                   &accepted);
         if (rc != ICW_OK) return rc;
     }
+    size_t fsz = wi.frame_bytes;
+    for (int s = 1; s < S; ++s) {
+        const icw_wav_info &ji = jobs[s]->info;
+        fsz = std::max<size_t>(fsz, ji.frame_bytes);
+        if ((ji.sample_rate != wi.sample_rate || ji.fmt != wi.fmt || ji.channels != wi.channels) &&
+            (rc = icw_set_stream_input(ctx, s, 1, ji.sample_rate, ji.fmt, ji.channels)) != ICW_OK)
+            return rc;
+    }
     const int rs = icw_render_size(ctx), osz = 2 * rs;
-    const size_t fsz = wi.frame_bytes;
     const int B = o.block_frames > 0 ? o.block_frames : 65536;
     int64_t T = 0;
     for (int s = 0; s < S; ++s) {
@@ -393,7 +405,7 @@ int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::v
         /* xwave_reader_create's virtual zero tail (xwave_reader.c:688-697) */
         int64_t tail = 0;
         if (o.sec_align) {
-            const int64_t mt = (int64_t)wi.sample_rate * (int64_t)o.sec_align, fr = j.info.n_samples % mt;
+            const int64_t mt = (int64_t)j.info.sample_rate * (int64_t)o.sec_align, fr = j.info.n_samples % mt;
             tail = fr ? mt - fr : 0;
         }
         j.total = j.info.n_samples + tail;
@@ -401,7 +413,7 @@ int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::v
         if ((rc = icw_stream_open(ctx, s, j.info.n_samples, o.fade_in_ms, o.fade_out_ms, o.sec_align, 0, 0)) != ICW_OK)
             return rc;
         unsigned char hdr[44];
-        wav_header(hdr, wi.sample_rate, rs, (uint64_t)j.total);
+        wav_header(hdr, j.info.sample_rate, rs, (uint64_t)j.total);
         if (fwrite(hdr, 1, 44, j.out) != 44) status[j.idx] = ICW_EINVAL;
         if (fseeko(j.in, j.info.data_offset, SEEK_SET)) status[j.idx] = ICW_EINVAL;
     }
@@ -637,7 +649,8 @@ int icw_transcode_files(const icw_config *cfg, const icw_node *nodes, int n_node
         in_paths, out_paths, n, stats, status,
         [&](int i, Job &j) { return accept_wav(in_paths[i], out_paths[i], &j.info); },
         [](int) { return 0; },
-        [&](int, std::vector<Job *> &g, icw_batch_stats &st, int *sts) { return run_group(*cfg, nodes, n_nodes, g, o, st, sts); });
+        [&](int, std::vector<Job *> &g, icw_batch_stats &st, int *sts) { return run_group(*cfg, nodes, n_nodes, g, o, st, sts); },
+        (o.reserved_ & ICW_BATCH_MERGE_INPUTS) != 0);
 }
 
 /* icw_transcode_files with file i's own list (include/icw_reader.h) */
@@ -686,7 +699,8 @@ int icw_transcode_files_lists(const icw_config *cfg, const icw_node *const *node
             fl.bypass = bypass_list;
             fl.per_stream = key < 0;
             return run_group(*cfg, nullptr, 0, g, o, st, sts, fl);
-        });
+        },
+        (o.reserved_ & ICW_BATCH_MERGE_INPUTS) != 0);
 }
 
 }  /* extern "C" */

@@ -145,7 +145,7 @@ void free_all(icw_ctx *c)
 {
     DevState &s = c->st;
     void *ptrs[] = {c->enc_clipped, c->s1_stamps, s.mt, s.mt_idx, s.rs, s.lr_equal, s.fes, s.err, s.hist, s.sncnt, s.hq_phase, s.pos, s.fade,
-                    s.n_frame, s.bus, s.clips, s.peak_bits, c->d_prog, c->d_progs, c->d_pid, c->trig, c->d_in, c->d_out,
+                    s.n_frame, s.bus, s.clips, s.peak_bits, c->d_prog, c->d_progs, c->d_pid, c->d_inputs, c->trig, c->d_in, c->d_out,
                     c->d_pre, c->d_xin,
                     c->d_fir_g, c->fir_hist[0], c->fir_hist[1], c->dwords, c->dbk, c->dflag};
     for (void *p : ptrs)
@@ -165,6 +165,7 @@ void free_all(icw_ctx *c)
     if (c->join) (void)hipEventDestroy(c->join);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     for (auto e : c->ev) (void)hipEventDestroy(e);
+    for (auto e : c->ev_k0) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
 }
 
@@ -272,6 +273,9 @@ int apply_graph(icw_ctx *c, std::vector<icw_node> &nv, int bypass, const std::ve
     c->cfg.bypass_list = cfg.bypass_list;
     c->nodes = nv;
     c->prog = P;
+    /* a one-list context with per-stream inputs launches from c->mix and the selection rows, both
+     * built from this list (prepare_mix): they are rebuilt by the next call */
+    c->pid_valid = false;
     c->serial_render = serial;
     c->render_state = rstate;
     for (int slot : clears)
@@ -331,7 +335,7 @@ int install_table(icw_ctx *c, std::vector<IcwProg> &progs, std::vector<std::vect
     IcwProg *fresh = nullptr;
     if (n > 1) {
         if (n > c->d_progs_cap && hipMalloc((void **)&fresh, n * sizeof(IcwProg)) != hipSuccess) return ICW_ENOMEM;
-        if (!c->d_pid && dalloc(&c->d_pid, (size_t)c->n_streams * 5) != ICW_OK) {
+        if (!c->d_pid && dalloc(&c->d_pid, (size_t)c->n_streams * kPidWords) != ICW_OK) {
             if (fresh) (void)hipFree(fresh);
             c->d_pid = nullptr;
             return ICW_ENOMEM;
@@ -365,6 +369,37 @@ int install_table(icw_ctx *c, std::vector<IcwProg> &progs, std::vector<std::vect
         c->prog_of.swap(of);
     }
     return ICW_OK;
+}
+
+/* ---- per-stream inputs (icw_set_stream_input) ---- */
+
+IcwInDesc make_input(uint32_t sample_rate, uint32_t fmt, uint32_t channels)
+{
+    IcwInDesc d;
+    memset(&d, 0, sizeof(d));
+    d.fmt = fmt;
+    d.csz = fmt_size(fmt);
+    d.fsz = d.csz * channels;
+    d.nch = channels;
+    d.sample_rate = sample_rate;
+    d.ssr = (unsigned long long)sample_rate * ICW_HZ_SCALE;
+    return d;
+}
+
+bool same_input(const IcwInDesc &a, const IcwInDesc &b)
+{
+    return a.fmt == b.fmt && a.nch == b.nch && a.sample_rate == b.sample_rate;
+}
+
+int count_inputs(const std::vector<IcwInDesc> &v)
+{
+    std::vector<const IcwInDesc *> seen;
+    for (const IcwInDesc &d : v) {
+        size_t k = 0;
+        while (k < seen.size() && !same_input(*seen[k], d)) ++k;
+        if (k == seen.size()) seen.push_back(&d);
+    }
+    return (int)seen.size();
 }
 
 }  // namespace
@@ -470,6 +505,7 @@ int icw_create(const icw_config *cfg, const icw_node *nodes, int n_nodes, int n_
     c->peak_db.assign(S * 2, ICW_SR_ZERO_SIGNAL_DB);
     c->lr_known.assign(S, 1);
     c->nf_host.assign(S, 0ull);
+    c->inputs.assign(S, make_input(cfg->sample_rate, cfg->in_format, cfg->in_channels));
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, c->device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
@@ -533,8 +569,11 @@ int icw_stream_open(icw_ctx *c, int s, int64_t n_samples, uint32_t fade_in, uint
 {
     if (!c || s < 0 || s >= c->n_streams || n_samples < 0) return ICW_EINVAL;
     (void)sec_align;   /* the virtual zero tail is produced by the reader (xwave_read_samples) */
-    long long nfi = (long long)(((uint64_t)fade_in * (uint64_t)c->cfg.sample_rate) / 1000ULL);
-    long long nfo = (long long)(((uint64_t)fade_out * (uint64_t)c->cfg.sample_rate) / 1000ULL);
+    std::lock_guard<std::mutex> lk(c->mu);
+    /* the fades at the stream's own rate (icw_set_stream_input; the context's while the inputs are one) */
+    const uint64_t rate = c->inputs[(size_t)s].sample_rate;
+    long long nfi = (long long)(((uint64_t)fade_in * rate) / 1000ULL);
+    long long nfo = (long long)(((uint64_t)fade_out * rate) / 1000ULL);
     if (nfi + nfo >= n_samples) {
         if (n_samples < 300LL) nfi = nfo = 0;
         else {
@@ -542,7 +581,6 @@ int icw_stream_open(icw_ctx *c, int s, int64_t n_samples, uint32_t fade_in, uint
             if (nfo) nfo = n_samples / 3;
         }
     }
-    std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c)) return ICW_EDEVICE;
     long long fd[3] = {(long long)n_samples, nfi, nfo};
     c->touched = true;
@@ -606,7 +644,7 @@ int icw_set_fir_hilbert(icw_ctx *c, int32_t M, double beta)
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     /* the fused converter takes one list per launch: not beside per-stream lists (include/icw.h) */
-    if (M > 0 && !c->progs.empty()) return ICW_EUNSUPPORTED;
+    if (M > 0 && (!c->progs.empty() || c->n_inputs > 1)) return ICW_EUNSUPPORTED;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     for (double *&h : c->fir_hist)
         if (h) { (void)hipFree(h); h = nullptr; }
@@ -667,7 +705,60 @@ int icw_set_input(icw_ctx *c, uint32_t sample_rate, uint32_t fmt, uint32_t chann
     c->cfg.sample_rate = sample_rate;
     c->cfg.in_format = fmt;
     c->cfg.in_channels = channels;
+    /* every stream: a context whose streams differed is a one-input context again */
+    c->inputs.assign((size_t)c->n_streams, make_input(sample_rate, fmt, channels));
+    c->pid_valid = false;                 /* the selection rows carry the rate and the channels */
+    c->n_inputs = 1;
     return ICW_OK;
+}
+
+/* icw_set_input for streams [first, first + count) (include/icw.h) */
+int icw_set_stream_input(icw_ctx *c, int first, int count, uint32_t sample_rate, uint32_t fmt, uint32_t channels)
+{
+    if (!c || first < 0 || count <= 0 || first > c->n_streams - count || sample_rate == 0 ||
+        sample_rate > ICW_MAX_FS_SRC || fmt > ICW_FMT_CW_F32 || channels == 0)
+        return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    /* whether K1 runs at all is a per-call decision, and the FIR converter's kernels take one format per
+     * launch: CWAVE input and the converter stay context-wide */
+    if (fmt >= ICW_FMT_CW_F64 || c->cfg.in_format >= ICW_FMT_CW_F64 || c->fir_M > 0) return ICW_EUNSUPPORTED;
+    if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+    std::vector<IcwInDesc> nv = c->inputs;
+    for (int s = first; s < first + count; ++s) nv[(size_t)s] = make_input(sample_rate, fmt, channels);
+    const int n = count_inputs(nv);
+    if (n > 1) {
+        /* the device table first: a failed allocation or copy leaves the old inputs in force */
+        IcwInDesc *fresh = nullptr;
+        if (!c->d_inputs && hipMalloc((void **)&fresh, nv.size() * sizeof(IcwInDesc)) != hipSuccess) return ICW_ENOMEM;
+        if (!c->d_pid && dalloc(&c->d_pid, (size_t)c->n_streams * kPidWords) != ICW_OK) {
+            if (fresh) (void)hipFree(fresh);
+            if (c->d_pid) (void)hipFree(c->d_pid);
+            c->d_pid = nullptr;
+            return ICW_ENOMEM;
+        }
+        if (hipMemcpy(fresh ? fresh : c->d_inputs, nv.data(), nv.size() * sizeof(IcwInDesc), hipMemcpyHostToDevice) !=
+            hipSuccess) {
+            if (fresh) (void)hipFree(fresh);
+            return ICW_EDEVICE;
+        }
+        if (fresh) c->d_inputs = fresh;
+    } else {
+        /* one input again, whichever call gave it: the context-wide one */
+        c->cfg.sample_rate = sample_rate;
+        c->cfg.in_format = fmt;
+        c->cfg.in_channels = channels;
+    }
+    c->inputs.swap(nv);
+    c->n_inputs = n;
+    c->pid_valid = false;
+    return ICW_OK;
+}
+
+int icw_stream_input_count(const icw_ctx *c)
+{
+    if (!c) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(const_cast<icw_ctx *>(c)->mu);
+    return c->n_inputs;
 }
 
 /* Live edits: what the reference's GUI thread changes while a decode thread runs
@@ -1161,6 +1252,13 @@ int icw_last_timing(icw_ctx *c, double ms[2], int launches[2])
     ms[1] = c->last_ms[1];
     launches[0] = c->last_launches[0];
     launches[1] = c->last_launches[1];
+    return ICW_OK;
+}
+
+int icw_last_k0_timing(icw_ctx *c, double *ms)
+{
+    if (!c || !ms) return ICW_EINVAL;
+    *ms = c->last_k0_ms;
     return ICW_OK;
 }
 

@@ -32,6 +32,9 @@ constexpr int kFirRenderFirst = 2048;
  * and two ~12 us gaps beside its 0.26 ms kernel, 13 % of a c2fir step */
 constexpr int kMaxFirBlockFrames = 1 << 20;
 constexpr int kRowRenderMax = 2048;          /* channels up to which the render runs a row per channel */
+/* int32 words of d_pid per stream of the context: a call's 5 selection rows [5][count] and the
+ * rotation table's [3][n_slabs], n_slabs <= count / 2 (a slab needs two streams) */
+constexpr size_t kPidWords = 7;
 constexpr size_t kPinnedStage = 1u << 20;   /* host-pointer calls up to this size stage through pinned memory */
 
 /* internal types and helpers, shared between the library's objects and not with its users: hidden,
@@ -87,13 +90,20 @@ struct icw_ctx {
     std::vector<int32_t> prog_of;         /* [streams] */
     IcwProg *d_progs = nullptr;
     size_t d_progs_cap = 0;               /* entries d_progs has room for */
-    /* a call over streams with different lists: K2's [3][count] selection rows, then the rotation
-     * table's [2][n_slabs] (IcwK2Args.prog_id, IcwTrigArgs.slabs), rebuilt when the lists or the
-     * range change */
+    /* a call over streams with different lists or inputs: K2's [5][count] selection rows, then the
+     * rotation table's [3][n_slabs] (IcwK2Args.prog_id, IcwTrigArgs.slabs), rebuilt when the lists, the
+     * inputs or the range change */
     int32_t *d_pid = nullptr;
     bool pid_valid = false;
     int pid_first = 0, pid_count = 0, pid_slabs = 0;
     IcwProg mix{};                        /* that call's launch configuration: needs_omega, n_trig, chain, n_regs */
+    /* per-stream inputs (icw_set_stream_input): every stream's descriptor, always filled, and the number
+     * of distinct ones.  While that is 1, cfg.sample_rate / in_format / in_channels are the one input, as
+     * before; above 1 the device table [n_streams] holds the descriptors (it is allocated by the first
+     * assignment that needs it) and cfg keeps the input last given context-wide. */
+    std::vector<IcwInDesc> inputs;        /* [streams] */
+    int n_inputs = 1;
+    IcwInDesc *d_inputs = nullptr;
     DevState st;
     /* host mirrors of meters that survive "reset" semantics */
     std::vector<double> peak_db;          /* [streams][2] */
@@ -158,6 +168,8 @@ struct icw_ctx {
     uint32_t mt_seed_state[2][624];       /* seeded MT19937 states for L / R (mtrnd_init_seed) */
     hipStream_t stream = nullptr;
     std::vector<hipEvent_t> ev;
+    std::vector<hipEvent_t> ev_k0;        /* ICW_F_TIMING: a pair around K0 of each launch block */
+    double last_k0_ms = 0.0;
     int n_cu = 256;
     double last_ms[2]{};
     int last_launches[2]{};

@@ -20,6 +20,16 @@
 
 struct IcwProg;
 
+/* One stream's input (icw_set_stream_input): a row of the context's device table [n_streams], kept
+ * while the streams' inputs differ.  A call over streams with different inputs hands the table to
+ * the kernels that read the format (K0) or the rate (K4, icw_advance); K2 and the rotation table get
+ * the rate and the channels in their per-call selection rows (IcwK2Args.prog_id). */
+struct IcwInDesc {
+    uint32_t fmt, csz, fsz, nch;   /* real sample format, channel/frame bytes, channels */
+    uint32_t sample_rate, pad_;
+    unsigned long long ssr;        /* sample_rate * ICW_HZ_SCALE */
+};
+
 /* Arguments of the input prep kernel (one thread = one frame). */
 struct IcwK0Args {
     const unsigned char *in;       /* stream s at in + s*in_stride */
@@ -34,6 +44,14 @@ struct IcwK0Args {
     double *xd;                    /* [n_chains][x_pitch]: each chain's own filter input sequence;
                                       complex input: rows s*4 + ch*2 + {0: I, 1: Q} hold the samples */
     size_t x_pitch;
+};
+
+/* K0 over streams with different inputs (icw_unpack_frames_mixed): workgroup column y takes fmt, csz,
+ * fsz and nch from desc[y]; k0.in is the call's first frame (the block offset t0 is applied with the
+ * stream's own frame size) and k0's own four format fields are unused. */
+struct IcwK0MixArgs {
+    IcwK0Args k0;
+    const IcwInDesc *desc;         /* [n_streams] of the launch */
 };
 
 /* Arguments of the FIR Hilbert converter kernels (KF / KF2, the CWAVE converter of cwave.h:40,56-58:
@@ -100,6 +118,12 @@ struct IcwAdvArgs {
     uint32_t seq;                  /* after the output and the flag, so the host can poll for it */
 };
 
+/* the same over streams with different inputs: every stream's counter wraps at its own ssr (desc[s]) */
+struct IcwAdvMixArgs {
+    IcwAdvArgs adv;
+    const IcwInDesc *desc;         /* [n_streams] of the launch */
+};
+
 /* Arguments of the serial graph kernel (bus form; one lane = one stream, loops over frames). */
 struct IcwK4Args {
     const double *iq;              /* [n_streams][T][4] `in` per frame (lre, lim, rre, rim) */
@@ -113,6 +137,7 @@ struct IcwK4Args {
     double *bus;                   /* [n_streams][27][4] */
     double *pre;                   /* [n_streams][pre_stride] (lOut, rOut) per frame */
     size_t pre_stride;
+    const IcwInDesc *desc;         /* streams with different inputs: [n_streams], each stream's own rate */
 };
 
 /* Arguments of the IIR state kernel (one lane = one DF-II chain). */
@@ -286,11 +311,13 @@ struct IcwK2Args {
                                       frame-parallel -- K3a's rnd * dth_mul, generator-major
                                       [n_streams * 2][dith_pitch] (row 2s + ch, frame t of the block) */
     size_t dith_pitch;
-    /* per-stream DSP lists (icw_set_stream_graph); null: every stream runs prog[0] and reads the one
-     * rotation table against stream 0's counter, exactly as before.  [3][n_streams] of the launch:
-     * row 0 the stream's index into prog[], row 1 its slab of the rotation table (-1: its program
+    /* per-stream DSP lists (icw_set_stream_graph) and per-stream inputs (icw_set_stream_input); null:
+     * every stream runs prog[0] at the call's rate and channels and reads the one rotation table
+     * against stream 0's counter, exactly as before.  [5][n_streams] of the launch: row 0 the
+     * stream's index into prog[], row 1 its slab of the rotation table (-1: its (program, rate) pair
      * has no slab, the factors are computed inline), row 2 that slab's reference stream -- the
-     * stream reads the slab while its call-start counter equals the reference's */
+     * stream reads the slab while its call-start counter equals the reference's -- row 3 the
+     * stream's sample rate, row 4 its channels (they replace sample_rate / ssr / nch above) */
     const int32_t *prog_id;
     size_t slab_stride;            /* doubles per slab of trig_tab (slabs share trig_pitch) */
 };
@@ -306,8 +333,9 @@ struct IcwTrigArgs {
     uint32_t sample_rate;
     double *tab;                   /* [T][trig_pitch], rows in icw_trig_index order */
     int32_t perm_q;                /* 0: row t at t; > 0 (KF2): row t at (t & 7) * perm_q + (t >> 3) */
-    /* per-stream DSP lists: one slab per grid row y (null: the one table above).  [2][n_slabs]:
-     * row 0 slab y's index into prog[], row 1 its reference stream (index into n_frame[]) */
+    /* per-stream DSP lists / inputs: one slab per grid row y (null: the one table above).
+     * [3][n_slabs]: row 0 slab y's index into prog[], row 1 its reference stream (index into
+     * n_frame[]), row 2 its sample rate (replaces sample_rate / ssr above) */
     const int32_t *slabs;
     int32_t n_slabs;
     size_t slab_stride;            /* doubles per slab of tab */

@@ -194,6 +194,12 @@ __device__ __forceinline__ size_t icw_trig_index(int t, int perm_q)
     return perm_q ? (size_t)(t & 7) * (size_t)perm_q + (size_t)(t >> 3) : (size_t)t;
 }
 
+/* one stream's own rate, where the streams of a launch differ (icw_set_stream_input) */
+struct IcwRate {
+    unsigned long long ssr;
+    uint32_t sample_rate;
+};
+
 /* rotate (re,im) by e^{j phi} given cos/sin (adv_modulator.c:546-547, 576-577) */
 __device__ __forceinline__ void icw_rot(double re, double im, double cs, double sn, double &ore, double &oim)
 {
@@ -335,13 +341,14 @@ __device__ __forceinline__ void icw_frame_store(const IcwK2Args &a, int s, int t
 
 /* (K2 keeps the exact form for every frame: its render-only form, KF2's icw_sig_fast per frame,
  * measured C3 -0.3 %, C4 -0.5 % on one box -- K2 runs beside the recurrence, which bounds C3 / C4) */
-template <bool TRIG, bool TAB = false, bool DEFER = false>
+template <bool TRIG, bool TAB = false, bool DEFER = false, bool RATE = false>
 __device__ __forceinline__ void icw_frame_graph(const IcwK2Args &a, icw_cprog *P, const IcwRegFile &R, int s,
                                                 int t, const IcwLR &in, bool use_tab, unsigned &clip_l,
                                                 unsigned &clip_r, double &pk_l, double &pk_r, int *dv = nullptr,
-                                                size_t tab_off = 0)
+                                                size_t tab_off = 0, const IcwRate *rt = nullptr)
 {
-    /* tab_off: the stream's slab of the rotation table (per-stream lists; 0: the one table) */
+    /* tab_off: the stream's slab of the rotation table (per-stream lists; 0: the one table);
+     * rt: the stream's own rate, read by the RATE instances only (per-stream inputs) */
     const int T = a.T;
     if (a.iq_out) {
         /* bus-form graph: the serial graph kernel takes it from here (do_render == 0) */
@@ -349,8 +356,11 @@ __device__ __forceinline__ void icw_frame_graph(const IcwK2Args &a, icw_cprog *P
         q[0] = in.lre; q[1] = in.lim; q[2] = in.rre; q[3] = in.rim;
     } else {
         const double *trow = use_tab ? a.trig_tab + tab_off + icw_trig_index(t, a.trig_perm_q) * a.trig_pitch : nullptr;
-        const double omega = (TRIG && !use_tab) ? icw_omega(a.n_frame[s], a.t0 + t, a.scaled, a.ssr, a.sample_rate)
-                                                : 0.0;
+        double omega;
+        if constexpr (RATE)
+            omega = (TRIG && !use_tab) ? icw_omega(a.n_frame[s], a.t0 + t, a.scaled, rt->ssr, rt->sample_rate) : 0.0;
+        else
+            omega = (TRIG && !use_tab) ? icw_omega(a.n_frame[s], a.t0 + t, a.scaled, a.ssr, a.sample_rate) : 0.0;
         /* DSP list (adv_modulator.c:637-751) */
         /* persistent bus at the block's last frame: slot 0 = in, then each written slot's
          * final value from the op that writes it (compile_graph: op.wb_slot) */

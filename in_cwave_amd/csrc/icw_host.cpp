@@ -97,53 +97,73 @@ bool poll_done(const uint32_t *flag, uint32_t seq, hipStream_t st)
     }
 }
 
-/* A call over streams [first, first + count) that run different lists: K2's selection rows and the
- * rotation table's slabs on the device, the launch configuration in c->mix.  One slab per program
- * with an active Shift / PM channel that at least two of the call's streams run, at the counter of
- * the first of them; a program one stream runs computes its factors inline (the table would do
- * the same work and add its traffic); a program without Shift / PM reads nothing, so it is marked
- * as using slab 0 against itself and skips the counter arithmetic. */
+/* A call over streams [first, first + count) that run different lists or have different inputs: K2's
+ * selection rows and the rotation table's slabs on the device, the launch configuration in c->mix.
+ * The factors depend on the list, the counter and the rate, so the slabs are keyed by (list, rate):
+ * one slab per pair with an active Shift / PM channel that at least two of the call's streams
+ * share, at the counter of the first of them; a pair one stream has computes its factors inline
+ * (the table would do the same work and add its traffic); a program without Shift / PM reads
+ * nothing, so it is marked as using slab 0 against itself and skips the counter arithmetic.  A
+ * context with one list is a one-entry program table (c->prog / c->d_prog). */
 int prepare_mix(icw_ctx *c, int first, int count, hipStream_t st)
 {
     if (c->pid_valid && c->pid_first == first && c->pid_count == count) return ICW_OK;
-    const size_t n = c->progs.size(), S = (size_t)count;
-    std::vector<int> uses(n, 0), slab(n, -1), ref(n, -1);
+    const size_t S = (size_t)count;
+    const bool one = c->progs.empty();
+    struct Pair {
+        int32_t e;
+        uint32_t rate;
+        int uses, ref, slab;
+    };
+    std::vector<Pair> pairs;
+    std::vector<size_t> pair_of(S);
     for (int i = 0; i < count; ++i) {
-        const int e = c->prog_of[(size_t)(first + i)];
-        if (uses[(size_t)e]++ == 0) ref[(size_t)e] = i;
+        const int32_t e = one ? 0 : c->prog_of[(size_t)(first + i)];
+        const uint32_t rate = c->inputs[(size_t)(first + i)].sample_rate;
+        size_t k = 0;
+        while (k < pairs.size() && !(pairs[k].e == e && pairs[k].rate == rate)) ++k;
+        if (k == pairs.size()) pairs.push_back(Pair{e, rate, 0, i, -1});
+        ++pairs[k].uses;
+        pair_of[(size_t)i] = k;
     }
     IcwProg &M = c->mix;
-    M.is_bus = 0;
+    M.is_bus = one ? c->prog.is_bus : 0;
     M.needs_omega = 0;
     M.n_trig = 0;
     M.chain = 1;
     M.sig = 0;
     M.n_regs = 0;
     int n_slabs = 0;
-    std::vector<int32_t> h(S * 5, 0);
-    for (size_t e = 0; e < n; ++e) {
-        if (!uses[e]) continue;
-        const IcwProg &P = c->progs[e];
+    for (Pair &q : pairs) {
+        const IcwProg &P = one ? c->prog : c->progs[(size_t)q.e];
         M.needs_omega |= P.needs_omega;
         if (!P.chain) {
             M.chain = 0;
             M.n_regs = std::max(M.n_regs, P.n_regs);
         }
-        if (P.needs_omega && P.n_trig > 0 && uses[e] >= 2) {
-            slab[e] = n_slabs;
-            h[S * 3 + (size_t)n_slabs] = (int32_t)e;
-            ++n_slabs;
+        if (P.needs_omega && P.n_trig > 0 && !P.is_bus && q.uses >= 2) {
+            q.slab = n_slabs++;
             M.n_trig = std::max(M.n_trig, P.n_trig);
         }
     }
-    for (size_t e = 0, y = 0; e < n; ++e)
-        if (slab[e] >= 0) h[S * 3 + (size_t)n_slabs + y++] = ref[e];
+    /* [5][count] selection rows, then [3][n_slabs] (n_slabs <= count / 2: kPidWords per stream hold both) */
+    std::vector<int32_t> h(S * 5 + (size_t)n_slabs * 3, 0);
+    for (const Pair &q : pairs)
+        if (q.slab >= 0) {
+            int32_t *sl = h.data() + S * 5;
+            sl[q.slab] = q.e;
+            sl[n_slabs + q.slab] = q.ref;
+            sl[2 * n_slabs + q.slab] = (int32_t)q.rate;
+        }
     for (int i = 0; i < count; ++i) {
-        const size_t e = (size_t)c->prog_of[(size_t)(first + i)];
-        const bool no_trig = !(c->progs[e].needs_omega && c->progs[e].n_trig > 0);
-        h[(size_t)i] = (int32_t)e;
-        h[S + (size_t)i] = no_trig ? 0 : slab[e];
-        h[2 * S + (size_t)i] = no_trig ? i : (slab[e] >= 0 ? ref[e] : i);
+        const Pair &q = pairs[pair_of[(size_t)i]];
+        const IcwProg &P = one ? c->prog : c->progs[(size_t)q.e];
+        const bool no_trig = !(P.needs_omega && P.n_trig > 0);
+        h[(size_t)i] = q.e;
+        h[S + (size_t)i] = no_trig ? 0 : q.slab;
+        h[2 * S + (size_t)i] = no_trig ? i : (q.slab >= 0 ? q.ref : i);
+        h[3 * S + (size_t)i] = (int32_t)q.rate;
+        h[4 * S + (size_t)i] = (int32_t)c->inputs[(size_t)(first + i)].nch;
     }
     /* ordered after the earlier calls on st, which may still read the rows; waited for, since h goes */
     if (hipMemcpyAsync(c->d_pid, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess ||
@@ -175,7 +195,12 @@ struct CallPlan {
     const unsigned flags;
     const bool dev, legacy;
     bool timing = false, xin = false;
-    /* the resolved format */
+    /* the resolved input: the one every stream of the call has, or (mixin, icw_set_stream_input) streams
+     * with different inputs -- then fsz is the widest frame, nch the most channels, and the kernels
+     * take each stream's own from the context's table dD or the selection rows */
+    unsigned fmt = 0, rate = 0;
+    bool mixin = false;
+    const IcwInDesc *dD = nullptr;
     unsigned csz = 0, nch = 0, fsz = 0;
     int osz = 0;
     unsigned long long ssr = 0;
@@ -216,9 +241,9 @@ struct CallPlan {
     template <class A>
     void reader_args(A &a, int b) const
     {
-        a.in = d_in + (size_t)blocks[b].first * fsz;
+        a.in = d_in + (mixin ? 0 : (size_t)blocks[b].first * fsz);   /* mixin: K0 applies the offset per stream */
         a.in_stride = dis;
-        a.fmt = c->cfg.in_format;
+        a.fmt = fmt;
         a.csz = csz;
         a.fsz = fsz;
         a.nch = nch;
@@ -286,7 +311,7 @@ struct CallPlan {
         a2.n_frame = ds.n_frame + f0;
         a2.ssr = ssr;
         a2.scaled = cfg.frmod_scaled;
-        a2.sample_rate = cfg.sample_rate;
+        a2.sample_rate = rate;
         a2.prog = dP;
         a2.bus = ds.bus + f0 * ICW_N_INPUTS * 4;
         a2.out = d_out + (size_t)t0 * osz;
@@ -378,6 +403,7 @@ struct CallPlan {
         a4.bus = a2.bus;
         a4.pre = a2.pre;
         a4.pre_stride = a2.pre_stride;
+        a4.desc = dD;
         return a4;
     }
 
@@ -394,10 +420,10 @@ struct CallPlan {
         at.scaled = c->cfg.frmod_scaled;
         at.trig_pitch = 2 * lp->n_trig;
         at.ssr = ssr;
-        at.sample_rate = c->cfg.sample_rate;
+        at.sample_rate = rate;
         at.tab = c->trig;
         if (mix) {
-            at.slabs = c->d_pid + 3 * (size_t)count;
+            at.slabs = c->d_pid + 5 * (size_t)count;
             at.n_slabs = n_slabs;
             at.slab_stride = slab_stride;
         }
@@ -572,7 +598,9 @@ bool CallPlan::fir_hist_back() const
 int CallPlan::enc_format(int FB, bool fir_ok)
 {
     if (cfg.in_format >= ICW_FMT_CW_F64 || !fir_ok || FB == 0) return ICW_EINVAL;
-    csz = fmt_size(cfg.in_format);
+    fmt = cfg.in_format;
+    rate = cfg.sample_rate;
+    csz = fmt_size(fmt);
     nch = cfg.in_channels;
     fsz = csz * nch;
     if (!dev && (in_stride < (size_t)n_frames * fsz || out_stride < (size_t)n_frames * FB)) return ICW_EINVAL;
@@ -604,39 +632,59 @@ bool grow_events(std::vector<hipEvent_t> &v, int n, unsigned flags)
 /* the format, the list and the modes of the call, and its launch blocks */
 int CallPlan::resolve_plan()
 {
-    csz = fmt_size(cfg.in_format);
-    nch = cfg.in_channels;
-    fsz = csz * nch;
+    /* the input of the call's streams: the one all of them have, resolved here (the launches are
+     * then those of a one-input context), or the table */
+    const IcwInDesc &d0 = c->inputs[f0];
+    fmt = d0.fmt;
+    rate = d0.sample_rate;
+    csz = d0.csz;
+    nch = d0.nch;
+    fsz = d0.fsz;
+    for (int i = 1; i < count; ++i) {
+        const IcwInDesc &d = c->inputs[f0 + (size_t)i];
+        if (d.fmt != fmt || d.nch != d0.nch || d.sample_rate != rate) mixin = true;
+        fsz = std::max(fsz, d.fsz);
+        nch = std::max(nch, d.nch);
+    }
+    if (mixin) dD = c->d_inputs + f0;
     osz = 2 * (cfg.need24bits ? 3 : 2);
-    ssr = (unsigned long long)cfg.sample_rate * ICW_HZ_SCALE;
+    ssr = (unsigned long long)rate * ICW_HZ_SCALE;
     timing = flags & 4u;
     /* ICW_F_DEBUG_INPUT: K0's output of every launch block is copied aside (test hook, host dbg) */
     xin = flags & ICW_F_DEBUG_INPUT;
-    if (xin && (dev || !dbg || (flags & ICW_F_DEBUG_PRE) || cfg.in_format >= ICW_FMT_CW_F64 || c->fir_M > 0 ||
+    if (xin && c->n_inputs > 1) return ICW_EUNSUPPORTED;
+    if (xin && (dev || !dbg || (flags & ICW_F_DEBUG_PRE) || fmt >= ICW_FMT_CW_F64 || c->fir_M > 0 ||
                    cfg.fp_check))
         return ICW_EINVAL;
-    if (!dev && (in_stride < (size_t)n_frames * fsz || out_stride < (size_t)n_frames * osz)) return ICW_EINVAL;
+    /* every stream's row holds the call's frames at the widest frame of the call (mixin: K0 reads by
+     * the table, so the bound is checked for device pointers too) */
+    if ((!dev || mixin) && in_stride < (size_t)n_frames * fsz) return ICW_EINVAL;
+    if (!dev && out_stride < (size_t)n_frames * osz) return ICW_EINVAL;
 
     /* FIR Hilbert converter (icw_set_fir_hilbert): real input becomes complex samples in KF and
      * the block continues as CWAVE input does */
-    fir = c->fir_M > 0 && cfg.in_format < ICW_FMT_CW_F64;
-    cw = cfg.in_format >= ICW_FMT_CW_F64 || fir;
+    fir = c->fir_M > 0 && fmt < ICW_FMT_CW_F64;
+    cw = fmt >= ICW_FMT_CW_F64 || fir;
     /* the list of the call's streams: the context's one, the one table entry all of them run, or --
-     * streams with different lists -- the table with K2's per-stream selection (prepare_mix) */
+     * streams with different lists or inputs -- the table with K2's per-stream selection (prepare_mix;
+     * a one-list context is a one-entry table) */
     lp = &c->prog;
     dP = c->d_prog;
+    mix = mixin;
     if (!c->progs.empty()) {
         const int32_t e0 = c->prog_of[(size_t)first];
         for (int i = 1; i < count && !mix; ++i) mix = c->prog_of[(size_t)(first + i)] != e0;
-        if (mix) {
-            const int rc = prepare_mix(c, first, count, st);
-            if (rc != ICW_OK) return rc;
-            lp = &c->mix;
-            dP = c->d_progs;
-        } else {
+        if (!mix) {
             lp = &c->progs[(size_t)e0];
             dP = c->d_progs + e0;
+        } else {
+            dP = c->d_progs;
         }
+    }
+    if (mix) {
+        const int rc = prepare_mix(c, first, count, st);
+        if (rc != ICW_OK) return rc;
+        lp = &c->mix;
     }
     const IcwProg &LP = *lp;
     n_slabs = mix ? c->pid_slabs : 1;
@@ -694,8 +742,8 @@ int CallPlan::stage_io()
     pinned = !dev && stage_in + stage_out + 16 <= kPinnedStage;
     /* pinned host buffers on a call of several launch blocks: each block's input slice goes in and
      * its output slice comes out on the copy stream, beside the other blocks' kernels */
-    pipe_io = !dev && !pinned && n_blocks > 1 && !c->tn.serialize && host_pinned(in, c->device) &&
-                 host_pinned(out, c->device);
+    pipe_io = !dev && !pinned && n_blocks > 1 && !c->tn.serialize && !mixin && host_pinned(in, c->device) &&
+                 host_pinned(out, c->device);       /* (mixin: a block's slice differs per stream, one copy up front) */
     if (pinned) {
         if (c->h_stage_bytes < stage_in + stage_out + 16) {
             if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -887,7 +935,8 @@ int CallPlan::pick_streams()
     for (hipStream_t x : {sK, sA, sD, sR, sF, sC})
         if (x && x != st && hipStreamWaitEvent(x, c->join, 0) != hipSuccess) return ICW_EDEVICE;
 
-    if (timing && !grow_events(c->ev, 4 * n_blocks, hipEventDefault)) return ICW_EDEVICE;
+    if (timing && (!grow_events(c->ev, 4 * n_blocks, hipEventDefault) || !grow_events(c->ev_k0, 2 * n_blocks, hipEventDefault)))
+        return ICW_EDEVICE;
     fir_async = fir && !fir_fused && sK != sA;
     return ICW_OK;
 }
@@ -964,8 +1013,18 @@ int CallPlan::launch_k0(int b) const
         if (timing && hipEventRecord(c->ev[4 * b], s0) != hipSuccess) return ICW_EDEVICE;
         if (icw_launch_fir(&af, s0) != hipSuccess) return ICW_EDEVICE;
         if (timing && hipEventRecord(c->ev[4 * b + 1], s0) != hipSuccess) return ICW_EDEVICE;
-    } else if (icw_launch_unpack(&a0, s0) != hipSuccess) {
-        return ICW_EDEVICE;
+    } else {
+        if (timing && hipEventRecord(c->ev_k0[2 * b], s0) != hipSuccess) return ICW_EDEVICE;
+        if (mixin) {
+            IcwK0MixArgs m;
+            memset(&m, 0, sizeof(m));
+            m.k0 = a0;
+            m.desc = dD;
+            if (icw_launch_unpack_mixed(&m, s0) != hipSuccess) return ICW_EDEVICE;
+        } else if (icw_launch_unpack(&a0, s0) != hipSuccess) {
+            return ICW_EDEVICE;
+        }
+        if (timing && hipEventRecord(c->ev_k0[2 * b + 1], s0) != hipSuccess) return ICW_EDEVICE;
     }
     /* test hook: this block's rows aside before K1 may start (K1 waits for k0done) */
     if (xin && hipMemcpy2DAsync(c->d_xin + a0.t0, (size_t)n_frames * sizeof(double), a0.xd, x_pitch * sizeof(double),
@@ -1081,7 +1140,8 @@ int CallPlan::run_blocks() const
         if (cw && b + n_sets < n_blocks && (rc0 = launch_k0(b + n_sets)) != ICW_OK) return rc0;
     }
     if (!cw && nch > 1)
-        for (int i = 0; i < count; ++i) c->lr_known[first + i] = 0;   /* stereo: the halves diverge */
+        for (int i = 0; i < count; ++i)
+            if (c->inputs[f0 + (size_t)i].nch > 1) c->lr_known[first + i] = 0;   /* stereo: the halves diverge */
     /* join: the caller's stream continues after every kernel of the call, then the call-start
      * position / phases / frame counters advance (icw_advance) */
     for (hipStream_t x : {sK, sA, sD, sR, sF, sC})
@@ -1089,7 +1149,15 @@ int CallPlan::run_blocks() const
             return ICW_EDEVICE;
     if (fir && !fir_hist_back()) return ICW_EDEVICE;
     const auto av = adv_args();
-    if (icw_launch_advance(&av, st) != hipSuccess) return ICW_EDEVICE;
+    if (mixin) {
+        IcwAdvMixArgs m;
+        memset(&m, 0, sizeof(m));
+        m.adv = av;
+        m.desc = dD;
+        if (icw_launch_advance_mixed(&m, st) != hipSuccess) return ICW_EDEVICE;
+    } else if (icw_launch_advance(&av, st) != hipSuccess) {
+        return ICW_EDEVICE;
+    }
     return ICW_OK;
 }
 
@@ -1099,7 +1167,8 @@ int CallPlan::finish_call() const
 {
     for (int i = 0; i < count; ++i) {   /* icw_advance's arithmetic */
         unsigned long long &v = c->nf_host[first + i];
-        v = c->cfg.frmod_scaled ? (v + (unsigned long long)n_frames) % ssr : v + (unsigned long long)n_frames;
+        const unsigned long long wrap = c->inputs[f0 + (size_t)i].ssr;    /* the stream's own (ssr while they are one) */
+        v = c->cfg.frmod_scaled ? (v + (unsigned long long)n_frames) % wrap : v + (unsigned long long)n_frames;
     }
     if (legacy && hipStreamSynchronize(st) != hipSuccess) return ICW_EDEVICE;
     if (!dev) {
@@ -1160,6 +1229,14 @@ int CallPlan::finish_call() const
             m1 += x;
             m2 += y;
         }
+        /* K0 of every launch block (a K5 call and the FIR converter launch none) */
+        double m0 = 0;
+        for (int b = 0; b < n_blocks && !s1 && !fir; ++b) {
+            float x = 0;
+            if (hipEventElapsedTime(&x, c->ev_k0[2 * b], c->ev_k0[2 * b + 1]) != hipSuccess) return ICW_EDEVICE;
+            m0 += x;
+        }
+        c->last_k0_ms = m0;
         c->last_ms[0] = m1;
         c->last_ms[1] = m2;
         c->last_launches[0] = c->last_launches[1] = n_blocks;
@@ -1210,6 +1287,7 @@ int icw_encode_cwave(icw_ctx *c, int first, int count, const void *in, size_t in
         (flags & ~ICW_F_DEVICE_PTRS))
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
+    if (c->n_inputs > 1) return ICW_EUNSUPPORTED;        /* per-stream inputs: the encoders take one (include/icw.h) */
     const int FB = icw_cwave_frame_bytes(cw_format, c->cfg.in_channels);
     CallPlan pl(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
     int rc;
@@ -1257,6 +1335,7 @@ int icw_encode_cwave_iir(icw_ctx *c, int first, int count, const void *in, size_
         (flags & ~ICW_F_DEVICE_PTRS))
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
+    if (c->n_inputs > 1) return ICW_EUNSUPPORTED;        /* per-stream inputs: the encoders take one (include/icw.h) */
     const icw_config &cfg = c->cfg;
     const int FB = icw_cwave_frame_bytes(cw_format, cfg.in_channels);
     CallPlan pl(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
@@ -1359,10 +1438,13 @@ int icw_prepare(icw_ctx *c, int n_frames)
             grow((void **)&c->d_out, &c->d_out_bytes, (size_t)n_frames * osz * S + 16))
             return ICW_ENOMEM;
     }
-    const unsigned fsz = fmt_size(c->cfg.in_format) * c->cfg.in_channels;
-    const size_t osz = 2 * (size_t)(c->cfg.need24bits ? 3 : 2);
-    std::vector<unsigned char> in((size_t)n_frames * fsz * S, 0), out((size_t)n_frames * osz * S);
-    if (c->cfg.in_format == ICW_FMT_U8) std::fill(in.begin(), in.end(), (unsigned char)0x80);   /* u8 silence */
+    /* rows of the widest frame among the streams' inputs (one input: the context's frame) */
+    unsigned fsz = 0;
+    for (const IcwInDesc &d : c->inputs) fsz = std::max(fsz, d.fsz);
+    const size_t osz = 2 * (size_t)(c->cfg.need24bits ? 3 : 2), row = (size_t)n_frames * fsz;
+    std::vector<unsigned char> in(row * S, 0), out((size_t)n_frames * osz * S);
+    for (size_t i = 0; i < S; ++i)
+        if (c->inputs[i].fmt == ICW_FMT_U8) std::fill(in.begin() + i * row, in.begin() + (i + 1) * row, (unsigned char)0x80);   /* u8 silence */
     int rc = icw_process_streams(c, 0, (int)S, in.data(), (size_t)n_frames * fsz, out.data(), (size_t)n_frames * osz,
                                  n_frames, 0u, nullptr, nullptr);
     if (rc == ICW_OK) rc = icw_stream_init(c, 0, (int)S);

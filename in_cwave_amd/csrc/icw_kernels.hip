@@ -105,6 +105,25 @@ __global__ __launch_bounds__(256) void icw_unpack_frames(IcwK0Args a)
     if (t < a.T) icw_unpack_frame(a, t, blockIdx.y);
 }
 
+/* K0 over streams with different inputs (icw_set_stream_input).  The workgroup column is one stream,
+ * so its descriptor is wave-uniform: read through the constant address space (as K2's prog_id rows)
+ * it comes in by scalar loads, the format dispatch stays a uniform branch and fmt / csz / fsz / nch
+ * stay in SGPRs.  The frame's own code is icw_unpack_frame's, on the stream's frame size and row
+ * address (the aligned / unaligned choice included).  Real formats only (the host checks). */
+__global__ __launch_bounds__(256) void icw_unpack_frames_mixed(IcwK0MixArgs m)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int s = blockIdx.y;
+    const __attribute__((address_space(4))) IcwInDesc *d = (const __attribute__((address_space(4))) IcwInDesc *)m.desc + s;
+    IcwK0Args a = m.k0;
+    a.fmt = d->fmt;
+    a.csz = d->csz;
+    a.fsz = d->fsz;
+    a.nch = d->nch;
+    a.in += (size_t)a.t0 * a.fsz;      /* the block's first frame of this stream */
+    if (t < a.T) icw_unpack_frame(a, t, s);
+}
+
 #include "icw_fir_dev.h"
 #include "icw_graph_dev.h"
 
@@ -112,12 +131,12 @@ __global__ __launch_bounds__(256) void icw_unpack_frames(IcwK0Args a)
 /* One frame of K2: the four chains' output sums from their w rows (w[c]: the row at the frame's
  * window, w[c][N] the state after the frame), the de-subnorm counts, the fs/4 un-mix, then the
  * frame graph.  dup: mono input with bit-identical converters, chains 2-3 are copies of 0-1. */
-template <int N, bool KAHAN, bool TRIG, bool FCK>
+template <int N, bool KAHAN, bool TRIG, bool FCK, bool RATE = false>
 __device__ __forceinline__ void icw_output_frame(const IcwK2Args &a, icw_cprog *P, const IcwRegFile &R, int s,
                                                  int t, const double *const (&w)[4], bool dup, const double *lc,
                                                  IcwFes (&fes)[2], bool count_sn, unsigned (&sn)[4], bool use_tab,
                                                  unsigned &clip_l, unsigned &clip_r, double &pk_l, double &pk_r,
-                                                 size_t tab_off = 0)
+                                                 size_t tab_off = 0, const IcwRate *rt = nullptr)
 {
     IcwLR in;
     if (a.cw) {
@@ -160,7 +179,10 @@ __device__ __forceinline__ void icw_output_frame(const IcwK2Args &a, icw_cprog *
         }
         in.lre = oI[0]; in.lim = oQ[0]; in.rre = oI[1]; in.rim = oQ[1];
     }
-    icw_frame_graph<TRIG>(a, P, R, s, t, in, use_tab, clip_l, clip_r, pk_l, pk_r, nullptr, tab_off);
+    if constexpr (RATE)
+        icw_frame_graph<TRIG, false, false, true>(a, P, R, s, t, in, use_tab, clip_l, clip_r, pk_l, pk_r, nullptr, tab_off, rt);
+    else
+        icw_frame_graph<TRIG>(a, P, R, s, t, in, use_tab, clip_l, clip_r, pk_l, pk_r, nullptr, tab_off);
 }
 
 /* the workgroup's de-subnorm counts, one atomic per chain (nc chains computed; dup: the right
@@ -194,6 +216,14 @@ __device__ __forceinline__ void icw_sn_wg(const IcwK2Args &a, int s, const unsig
 #ifndef ICW_K2_MINWG
 #define ICW_K2_MINWG 1
 #endif
+/* the stream's channels: the call's, or (MIX) its own from the selection rows */
+template <bool MIX>
+__device__ __forceinline__ int icw_stream_nch(const IcwK2Args &a, int s)
+{
+    if constexpr (MIX) return ((const __attribute__((address_space(4))) int32_t *)a.prog_id)[4 * a.n_streams + s];
+    else return a.nch;
+}
+
 template <int N, bool KAHAN, bool TRIG, bool FCK = false, bool MIX = false>
 __device__ __forceinline__ void icw_output_body(const IcwK2Args &a, int bx, int s, double *lregs)
 {
@@ -210,8 +240,15 @@ __device__ __forceinline__ void icw_output_body(const IcwK2Args &a, int bx, int 
 
     /* mono input, converters bit-identical at block start (K1's flag) and in phase: the right
      * filter outputs are copies of the left ones this block */
-    const bool dup = !FCK && !a.cw && a.nch == 1 && a.info_dup && a.info_dup[s * 2] && a.info_dup[s * 2 + 1] &&
+    const bool dup = !FCK && !a.cw && icw_stream_nch<MIX>(a, s) == 1 && a.info_dup && a.info_dup[s * 2] && a.info_dup[s * 2 + 1] &&
                      a.hq_phase[s * 2] == a.hq_phase[s * 2 + 1];
+    [[maybe_unused]] IcwRate rt;
+    if constexpr (MIX) {
+        /* the stream's own rate from the selection rows (it replaces a.ssr / a.sample_rate) */
+        const __attribute__((address_space(4))) int32_t *id = (const __attribute__((address_space(4))) int32_t *)a.prog_id;
+        rt.sample_rate = (uint32_t)id[3 * a.n_streams + s];
+        rt.ssr = (unsigned long long)rt.sample_rate * ICW_HZ_SCALE;
+    }
     IcwFes fes[2] = {};
     const int nc = dup ? 2 : 4;
     /* the per-frame rotation table holds this stream's factors when its counter is in step */
@@ -283,8 +320,8 @@ __device__ __forceinline__ void icw_output_body(const IcwK2Args &a, int bx, int 
         if (t < T) {
             const double *const w[4] = {&W[0][tl], &W[1][tl], &W[2][tl], &W[3][tl]};
             if constexpr (MIX)
-                icw_output_frame<N, KAHAN, TRIG, FCK>(a, P, R, s, t, w, dup, lcoef + zk, fes, count_sn, sn, use_tab,
-                                                      clip_l, clip_r, pk_l, pk_r, tab_off);
+                icw_output_frame<N, KAHAN, TRIG, FCK, true>(a, P, R, s, t, w, dup, lcoef + zk, fes, count_sn, sn, use_tab,
+                                                            clip_l, clip_r, pk_l, pk_r, tab_off, &rt);
             else
                 icw_output_frame<N, KAHAN, TRIG, FCK>(a, P, R, s, t, w, dup, lcoef + zk, fes, count_sn, sn, use_tab,
                                                       clip_l, clip_r, pk_l, pk_r);
@@ -325,13 +362,17 @@ __device__ __forceinline__ void icw_trig_row(const IcwTrigArgs &a, int t, int y 
     icw_cprog *P = icw_prog_c(a.prog);
     int ref = 0;
     double *tab = a.tab;
+    [[maybe_unused]] uint32_t rate = 0;
     if constexpr (SLAB) {
         const __attribute__((address_space(4))) int32_t *sl = (const __attribute__((address_space(4))) int32_t *)a.slabs;
         P += sl[y];
         ref = sl[a.n_slabs + y];
+        rate = (uint32_t)sl[2 * a.n_slabs + y];      /* the slab's own rate: slabs are keyed by (list, rate) */
         tab += (size_t)y * a.slab_stride;
     }
-    const double omega = icw_omega(a.n_frame[ref], a.t0 + t, a.scaled, a.ssr, a.sample_rate);
+    double omega;
+    if constexpr (SLAB) omega = icw_omega(a.n_frame[ref], a.t0 + t, a.scaled, (unsigned long long)rate * ICW_HZ_SCALE, rate);
+    else omega = icw_omega(a.n_frame[ref], a.t0 + t, a.scaled, a.ssr, a.sample_rate);
     double *row = tab + icw_trig_index(t, a.perm_q) * a.trig_pitch;
     for (int oi = 0; oi < P->n_ops; ++oi) {
         icw_cop &op = P->ops[oi];
@@ -360,6 +401,9 @@ __global__ __launch_bounds__(256) void icw_trig_table(IcwTrigArgs a)
  * (adv_modulator.c:636-751) with the 27-slot bus of the stream held in LDS, one lane per stream,
  * frames in order.  `in` comes from the output kernel (Hilbert or complex input), lOut/rOut go
  * to the serial render kernel. */
+/* MIXIN: streams with different inputs -- each lane takes its stream's own rate from a.desc (a
+ * lane-varying load, once per launch) */
+template <bool MIXIN>
 __global__ __launch_bounds__(64) void icw_graph_serial(IcwK4Args a)
 {
     __shared__ double bus[ICW_N_INPUTS * 4][64];
@@ -370,10 +414,16 @@ __global__ __launch_bounds__(64) void icw_graph_serial(IcwK4Args a)
     for (int k = 0; k < ICW_N_INPUTS * 4; ++k) bus[k][lane] = gb[k];
     icw_cprog *P = icw_prog_c(a.prog);
     const unsigned long long n0 = a.n_frame[s];
+    unsigned long long ssr = a.ssr;
+    uint32_t rate = a.sample_rate;
+    if constexpr (MIXIN) {
+        ssr = a.desc[s].ssr;
+        rate = a.desc[s].sample_rate;
+    }
     const double *iq = a.iq + (size_t)s * a.T * 4;
     double *pre = a.pre + (size_t)s * a.pre_stride;
     for (int t = 0; t < a.T; ++t) {
-        const double omega = P->needs_omega ? icw_omega(n0, a.t0 + t, a.scaled, a.ssr, a.sample_rate) : 0.0;
+        const double omega = P->needs_omega ? icw_omega(n0, a.t0 + t, a.scaled, ssr, rate) : 0.0;
         bus[0][lane] = iq[(size_t)t * 4 + 0];
         bus[1][lane] = iq[(size_t)t * 4 + 1];
         bus[2][lane] = iq[(size_t)t * 4 + 2];
@@ -423,6 +473,15 @@ __global__ __launch_bounds__(64) void icw_advance(IcwAdvArgs a)
 {
     const int s = blockIdx.x * 64 + threadIdx.x;
     if (s < a.n_streams) icw_advance_stream(a, s);
+}
+
+__global__ __launch_bounds__(64) void icw_advance_mixed(IcwAdvMixArgs m)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= m.adv.n_streams) return;
+    IcwAdvArgs a = m.adv;
+    a.ssr = m.desc[s].ssr;             /* the stream's own wrap (a lane-varying load) */
+    icw_advance_stream(a, s);
 }
 
 /* K5's overlapped form (a.ovl, the launcher checks that the rows fit in LDS): after K0, waves 0-1
@@ -593,6 +652,14 @@ extern "C" hipError_t icw_launch_unpack(const IcwK0Args *a, hipStream_t st)
     return hipGetLastError();
 }
 
+extern "C" hipError_t icw_launch_unpack_mixed(const IcwK0MixArgs *a, hipStream_t st)
+{
+    if (!a->desc) return hipErrorInvalidValue;
+    dim3 grid((a->k0.T + 255) / 256, a->k0.n_streams);
+    hipLaunchKernelGGL(icw_unpack_frames_mixed, grid, dim3(256), 0, st, *a);
+    return hipGetLastError();
+}
+
 template <int N, bool K>
 static hipError_t launch_k2_t(IcwK2Args a, hipStream_t st)
 {
@@ -637,7 +704,8 @@ extern "C" hipError_t icw_launch_trig_table(const IcwTrigArgs *a, hipStream_t st
 
 extern "C" hipError_t icw_launch_graph_serial(const IcwK4Args *a, hipStream_t st)
 {
-    hipLaunchKernelGGL(icw_graph_serial, dim3((a->n_streams + 63) / 64), dim3(64), 0, st, *a);
+    if (a->desc) hipLaunchKernelGGL(icw_graph_serial<true>, dim3((a->n_streams + 63) / 64), dim3(64), 0, st, *a);
+    else hipLaunchKernelGGL(icw_graph_serial<false>, dim3((a->n_streams + 63) / 64), dim3(64), 0, st, *a);
     return hipGetLastError();
 }
 
@@ -682,5 +750,12 @@ extern "C" hipError_t icw_launch_stream1(const IcwS1Args *a, int nord, hipStream
 extern "C" hipError_t icw_launch_advance(const IcwAdvArgs *a, hipStream_t st)
 {
     hipLaunchKernelGGL(icw_advance, dim3((a->n_streams + 63) / 64), dim3(64), 0, st, *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t icw_launch_advance_mixed(const IcwAdvMixArgs *a, hipStream_t st)
+{
+    if (!a->desc) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(icw_advance_mixed, dim3((a->adv.n_streams + 63) / 64), dim3(64), 0, st, *a);
     return hipGetLastError();
 }

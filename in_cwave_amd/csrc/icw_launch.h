@@ -17,10 +17,12 @@ extern "C" {
 
 /* icw_kernels.hip */
 hipError_t icw_launch_unpack(const IcwK0Args *a, hipStream_t st);
+hipError_t icw_launch_unpack_mixed(const IcwK0MixArgs *a, hipStream_t st);
 hipError_t icw_launch_output(const IcwK2Args *a, int nord, int kahan, hipStream_t st);
 hipError_t icw_launch_trig_table(const IcwTrigArgs *a, hipStream_t st);
 hipError_t icw_launch_graph_serial(const IcwK4Args *a, hipStream_t st);
 hipError_t icw_launch_advance(const IcwAdvArgs *a, hipStream_t st);
+hipError_t icw_launch_advance_mixed(const IcwAdvMixArgs *a, hipStream_t st);
 hipError_t icw_launch_stream1(const IcwS1Args *a, int nord, hipStream_t st);
 
 /* icw_fir.hip */

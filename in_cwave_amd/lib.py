@@ -113,6 +113,7 @@ class Context:
         self.n_streams = n_streams
         self.render_size = lib.icw_render_size(h)
         self.fsz = abi.FMT_BYTES[cfg.in_format] * cfg.in_channels
+        self.stream_fsz = [self.fsz] * n_streams       # every stream's own frame bytes (set_stream_input)
 
     def close(self):
         if self.h:
@@ -133,6 +134,28 @@ class Context:
         """a new track's sample format for every stream (icw_set_input)"""
         _check(self._lib.icw_set_input(self.h, sample_rate, fmt, channels), "icw_set_input")
         self.fsz = abi.FMT_BYTES[fmt] * channels
+        self.stream_fsz = [self.fsz] * self.n_streams
+
+    def set_stream_input(self, sample_rate, fmt, channels, first=0, count=None):
+        """icw_set_stream_input: the input of streams [first, first + count) for the next calls.  A call's
+        rows then hold each stream's frames at its own frame size (stream_fsz), in rows as wide as the
+        call's widest stream needs.  fsz is the streams' common frame size: while they differ it keeps its
+        last value, and the helpers size their rows by call_fsz()."""
+        count = self.n_streams - first if count is None else count
+        _check(self._lib.icw_set_stream_input(self.h, int(first), int(count), sample_rate, fmt, channels),
+               "icw_set_stream_input")
+        self.stream_fsz[first:first + count] = [abi.FMT_BYTES[fmt] * channels] * count
+        if len(set(self.stream_fsz)) == 1:
+            self.fsz = self.stream_fsz[0]
+
+    def stream_input_count(self):
+        """icw_stream_input_count: distinct inputs in force (1 on a fresh context)"""
+        return int(self._lib.icw_stream_input_count(self.h))
+
+    def call_fsz(self, first=0, count=None):
+        """the widest frame among streams [first, first + count): what a call's input rows are sized by"""
+        count = self.n_streams - first if count is None else count
+        return max(self.stream_fsz[first:first + count])
 
     def set_fir_hilbert(self, order, beta=8.0):
         """icw_set_fir_hilbert: real input through the FIR Hilbert converter (order k_M, Kaiser
@@ -245,7 +268,7 @@ class Context:
         pre float64 [count, n_frames, 2] or None).  out: a preallocated output array (reused)."""
         count = self.n_streams - first if count is None else count
         inp = np.ascontiguousarray(inp)
-        assert inp.dtype == np.uint8 and inp.shape[0] == count and inp.shape[1] >= n_frames * self.fsz
+        assert inp.dtype == np.uint8 and inp.shape[0] == count and inp.shape[1] >= n_frames * self.call_fsz(first, count)
         osz = 2 * self.render_size
         if out is None:
             out = np.zeros((count, n_frames * osz), dtype=np.uint8)
@@ -265,7 +288,7 @@ class Context:
         the unpacked, faded samples K0 hands the Hilbert converters (pre-Hilbert, R = L for mono)"""
         count = self.n_streams - first if count is None else count
         inp = np.ascontiguousarray(inp)
-        assert inp.dtype == np.uint8 and inp.shape[0] == count and inp.shape[1] >= n_frames * self.fsz
+        assert inp.dtype == np.uint8 and inp.shape[0] == count and inp.shape[1] >= n_frames * self.call_fsz(first, count)
         out = np.zeros((count, n_frames * 2 * self.render_size), dtype=np.uint8)
         x = np.zeros((count, n_frames, 2), dtype=np.float64)
         in_stride = inp.strides[0] if count > 1 else inp.shape[1]
@@ -287,7 +310,7 @@ class Context:
         converter's history and the reader position like a process call; nothing else."""
         count = self.n_streams - first if count is None else count
         inp = np.ascontiguousarray(inp)
-        assert inp.dtype == np.uint8 and inp.shape[0] == count and inp.shape[1] >= n_frames * self.fsz
+        assert inp.dtype == np.uint8 and inp.shape[0] == count and inp.shape[1] >= n_frames * self.call_fsz(first, count)
         fb = cwave_frame_bytes(cw_format, self.cfg.in_channels)
         if out is None:
             out = np.zeros((count, n_frames * fb), dtype=np.uint8)
@@ -311,7 +334,7 @@ class Context:
         (rings, phases, de-subnorm counters) and the reader position like a process call; nothing else."""
         count = self.n_streams - first if count is None else count
         inp = np.ascontiguousarray(inp)
-        assert inp.dtype == np.uint8 and inp.shape[0] == count and inp.shape[1] >= n_frames * self.fsz
+        assert inp.dtype == np.uint8 and inp.shape[0] == count and inp.shape[1] >= n_frames * self.call_fsz(first, count)
         fb = cwave_frame_bytes(cw_format, self.cfg.in_channels)
         if out is None:
             out = np.zeros((count, n_frames * fb), dtype=np.uint8)
@@ -370,6 +393,12 @@ class Context:
     def last_k1_kernel(self):
         """ICW_K1_* of the last real-input call: 0 lane-per-chain, 1 pair, 2 MFMA, 3 row broadcast"""
         return int(self._lib.icw_last_k1_kernel(self.h))
+
+    def last_k0_ms(self):
+        """icw_last_k0_timing: K0's time in the last timed call, summed over its launch blocks"""
+        v = C.c_double()
+        _check(self._lib.icw_last_k0_timing(self.h, C.byref(v)), "icw_last_k0_timing")
+        return v.value
 
     def last_timing(self):
         ms = (C.c_double * 2)()
@@ -471,13 +500,15 @@ def wav_parse_file(path):
 
 
 def transcode_files(cfg, nodes, in_paths, out_paths, fade_in_ms=0, fade_out_ms=0, sec_align=0,
-                    block_frames=0, device=-1):
-    """icw_transcode_files: many files through the GPU path; returns (stats, per-file status)"""
+                    block_frames=0, device=-1, merge_inputs=False):
+    """icw_transcode_files: many files through the GPU path; returns (stats, per-file status).
+    merge_inputs: ICW_BATCH_MERGE_INPUTS, all real-input files in one context"""
     n = len(in_paths)
     ins = (C.c_char_p * max(1, n))(*[str(p).encode() for p in in_paths])
     outs = (C.c_char_p * max(1, n))(*[str(p).encode() for p in out_paths])
     arr = graph_nodes(nodes)
-    o = abi.BatchOpts(fade_in_ms, fade_out_ms, sec_align, block_frames, device, 0)
+    o = abi.BatchOpts(fade_in_ms, fade_out_ms, sec_align, block_frames, device,
+                      abi.BATCH_MERGE_INPUTS if merge_inputs else 0)
     st = abi.BatchStats()
     status = (C.c_int * max(1, n))()
     rc = load().icw_transcode_files(C.byref(cfg), arr, len(nodes), ins, outs, n, C.byref(o), C.byref(st), status)
@@ -490,7 +521,7 @@ def graph_form(cfg, nodes, bypass_list=0):
 
 
 def transcode_files_lists(cfg, node_lists, in_paths, out_paths, bypass_lists=None, fade_in_ms=0, fade_out_ms=0,
-                          sec_align=0, block_frames=0, device=-1):
+                          sec_align=0, block_frames=0, device=-1, merge_inputs=False):
     """icw_transcode_files_lists: file i through its own list node_lists[i] (bypass_lists[i] where
     given); returns (rc, stats, per-file status)"""
     n = len(in_paths)
@@ -501,7 +532,8 @@ def transcode_files_lists(cfg, node_lists, in_paths, out_paths, bypass_lists=Non
     ptrs = (C.POINTER(abi.Node) * max(1, n))(*[C.cast(a, C.POINTER(abi.Node)) for a in arrs])
     cnt = (C.c_int * max(1, n))(*[len(nl) for nl in node_lists])
     byp = (C.c_int * max(1, n))(*[int(b) for b in bypass_lists]) if bypass_lists is not None else None
-    o = abi.BatchOpts(fade_in_ms, fade_out_ms, sec_align, block_frames, device, 0)
+    o = abi.BatchOpts(fade_in_ms, fade_out_ms, sec_align, block_frames, device,
+                      abi.BATCH_MERGE_INPUTS if merge_inputs else 0)
     st = abi.BatchStats()
     status = (C.c_int * max(1, n))()
     rc = load().icw_transcode_files_lists(C.byref(cfg), ptrs, cnt, byp, ins, outs, n, C.byref(o), C.byref(st), status)
@@ -544,13 +576,14 @@ def cwave_encode_files_iir(in_paths, out_paths, hilbert_type=1, iir_kahan=1, iir
 
 
 def transcode_files_devices(cfg, nodes, in_paths, out_paths, devices, fade_in_ms=0, fade_out_ms=0, sec_align=0,
-                            block_frames=0):
+                            block_frames=0, merge_inputs=False):
     """icw_transcode_files_devices: the files split over `devices` (one host thread each)"""
     n = len(in_paths)
     ins = (C.c_char_p * max(1, n))(*[str(p).encode() for p in in_paths])
     outs = (C.c_char_p * max(1, n))(*[str(p).encode() for p in out_paths])
     arr = graph_nodes(nodes)
-    o = abi.BatchOpts(fade_in_ms, fade_out_ms, sec_align, block_frames, -1, 0)
+    o = abi.BatchOpts(fade_in_ms, fade_out_ms, sec_align, block_frames, -1,
+                      abi.BATCH_MERGE_INPUTS if merge_inputs else 0)
     dv = (C.c_int * len(devices))(*devices)
     st = abi.BatchStats()
     status = (C.c_int * max(1, n))()

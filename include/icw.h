@@ -185,6 +185,39 @@ int icw_stream_seek(icw_ctx *ctx, int s, int64_t frame_pos);
  * channels; applies to every stream of the context */
 int icw_set_input(icw_ctx *ctx, uint32_t sample_rate, uint32_t fmt, uint32_t channels);
 
+/* Per-stream inputs: a batch whose streams each read their own track format (mod_context_fopen
+ * builds a reader per file) -- rate, sample format, channels -- in ONE context, so a library that
+ * mixes 44.1 / 48 / 96 kHz, 16 / 24 bit / float and mono / stereo keeps the batch width.
+ *   icw_set_stream_input      icw_set_input for streams [first, first + count) only, in force from
+ *                             the next call on (the context's work is waited for).  Streams given
+ *                             the same input share it: giving every stream one input leaves a
+ *                             one-input context, which issues the launches it always did.
+ *   icw_stream_input_count    distinct inputs in force (1 on a fresh context).
+ * icw_create and icw_set_input keep their meaning, every stream: icw_set_input on a context whose
+ * streams differ collapses it to one input.
+ * A call's input layout: stream s starts at in + s*in_stride_bytes, as ever, and its frames have that
+ * stream's own frame size; in_stride_bytes must hold n_frames frames of every stream of the call
+ * (device pointers included), else ICW_EINVAL.  Host staging rows are sized by the call's widest frame.
+ * A call whose streams all share one input is resolved on the host and runs the kernels of a
+ * one-input context; only a call over differing inputs takes the table-reading kernel instances.
+ * icw_stream_open takes its fades at stream s's own rate.  The five real formats, 1 or >= 2 channels,
+ * any rate up to ICW_MAX_FS_SRC; host and device pointers; icw_process_batch and icw_process_streams;
+ * register-form and bus-form lists, per-stream lists in the same context, every render, FP_CHECK.
+ * Limits, each refusal changing nothing:
+ *   ICW_EINVAL        a range outside the context, rate 0 or above ICW_MAX_FS_SRC, channels 0, fmt
+ *                     out of range.
+ *   ICW_EUNSUPPORTED  - a CWAVE format (fmt >= ICW_FMT_CW_F64), or a context whose input is CWAVE:
+ *                       whether the quadrature IIR runs at all is decided per call;
+ *                     - the FIR converter is on (icw_set_fir_hilbert with k_M > 0);
+ *                     - while the count is above 1: icw_set_fir_hilbert(k_M > 0), icw_encode_cwave and
+ *                       icw_encode_cwave_iir, and ICW_F_DEBUG_INPUT.
+ * Not served: icw_group and the icw_amod_* drop-in (their input stays context-wide).  The state blob
+ * does not carry the input, as it does not carry the list: icw_set_state expects the stream's input to
+ * be set as it was. */
+int icw_set_stream_input(icw_ctx *ctx, int first, int count, uint32_t sample_rate, uint32_t fmt,
+                         uint32_t channels);
+int icw_stream_input_count(const icw_ctx *ctx);
+
 /* Live parameter changes (the GUI thread edits the DSP list, the renders and the
  * Hilbert converters while a decode thread runs).  Each applies to every stream of the context from
  * the next call on; a call already queued finishes with the old parameters.  Per-stream state
@@ -372,6 +405,9 @@ int icw_set_state(icw_ctx *ctx, int s, const void *blob, size_t size);
  * kernels ran on (bench.py roofline).  ms[0] = IIR state kernel total, ms[1] = output kernel
  * total, launches[0..1] = launch counts. */
 int icw_last_timing(icw_ctx *ctx, double ms[2], int launches[2]);
+/* The same for the input prep kernel K0 of that call, summed over its launch blocks (0 for a one-stream
+ * call that ran as one kernel, and under the FIR converter, whose kernel is ms[0] above). */
+int icw_last_k0_timing(icw_ctx *ctx, double *ms);
 
 /* IIR state kernel (the serial recurrence) the last real-input icw_process_* call ran: ICW_K1_*.
  * The host picks the row-broadcast kernel for small batches (its waves fit two per CU on half

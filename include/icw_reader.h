@@ -50,8 +50,16 @@ typedef struct icw_batch_opts {
     uint32_t sec_align;                 /* SEC_ALIGN: virtual zero tail to a multiple of it, s */
     int32_t  block_frames;              /* frames per stream per GPU block (0: 65536) */
     int32_t  device;                    /* HIP device, -1: current */
-    int32_t  reserved_;
+    int32_t  reserved_;                 /* flags word, ICW_BATCH_* (the member keeps its name; 0: the grouping below) */
 } icw_batch_opts;
+
+/* icw_batch_opts.reserved_ bits.  ICW_BATCH_MERGE_INPUTS: icw_transcode_files, _lists and _devices put
+ * all real-input (WAV / RWAVE) files into ONE context per device, whatever their rate, format and
+ * channels -- every stream gets its file's input through icw_set_stream_input (and its list where
+ * lists differ) -- so a library of mixed formats keeps the batch width.  CWAVE files keep the grouping
+ * by (rate, format, channels), a bus-form list still runs in a context of the files that carry the
+ * same list, fades and tails are per file at the file's rate, and stats->n_groups counts contexts. */
+#define ICW_BATCH_MERGE_INPUTS 1
 
 typedef struct icw_batch_stats {
     int32_t  n_files, n_groups;         /* files transcoded; contexts used (one per input format) */
