@@ -139,6 +139,20 @@ class CwaveEncIirOpts(C.Structure):
                 ("reserved_", C.c_int32)]
 
 
+FFT_MAX_LOG2 = 27       # ICW_FFT_MAX_LOG2: the direct-FFT encoder's longest transform, 2^27 points
+FFT_PASS_LOG2 = 7       # the default (and largest) cap of a pass's sub-transform
+
+
+class FftEncOpts(C.Structure):
+    """icw_fft_enc_opts (include/icw_cwave.h)"""
+    _fields_ = [("device", C.c_int32), ("max_pass_log2", C.c_int32)]
+
+
+class CwaveEncFftOpts(C.Structure):
+    """icw_cwave_enc_fft_opts (include/icw_reader.h)"""
+    _fields_ = [("cw_format", C.c_uint32), ("device", C.c_int32), ("max_bytes", C.c_uint64)]
+
+
 # every function declared in include/icw.h, icw_amod.h, icw_cwave.h: name -> (restype, argtypes)
 _vp, _sz, _i, _u = C.c_void_p, C.c_size_t, C.c_int, C.c_uint
 SIGNATURES = {
@@ -213,6 +227,14 @@ SIGNATURES = {
     "icw_cwave_encode_files": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, C.POINTER(CwaveEncOpts),
                                     C.POINTER(BatchStats), C.POINTER(C.c_uint64), C.POINTER(_i)]),
     "icw_cwave_encode_files_iir": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, C.POINTER(CwaveEncIirOpts),
+                                        C.POINTER(BatchStats), C.POINTER(C.c_uint64), C.POINTER(_i)]),
+    "icw_encode_cwave_fft": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _i, C.c_uint32, C.c_uint32, _vp,
+                                  C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint64), _u,
+                                  C.POINTER(FftEncOpts), _vp]),
+    "icw_encode_cwave_fft_workspace": (_sz, [C.POINTER(C.c_uint64), _i, C.c_uint32]),
+    "icw_encode_cwave_fft_passes": (_i, [C.c_uint64, C.c_int32]),
+    "icw_encode_cwave_fft_last_ms": (_i, [C.POINTER(C.c_double), _i]),
+    "icw_cwave_encode_files_fft": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, C.POINTER(CwaveEncFftOpts),
                                         C.POINTER(BatchStats), C.POINTER(C.c_uint64), C.POINTER(_i)]),
     "icw_config_load": (_i, [C.c_char_p, _sz, C.POINTER(FileConfig), C.POINTER(_i)]),
     "icw_node_dsp_parse": (_i, [C.c_char_p, C.POINTER(Node), C.c_char_p, _sz]),

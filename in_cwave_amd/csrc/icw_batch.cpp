@@ -429,8 +429,9 @@ int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::v
     return rc;
 }
 
-/* what a group needs of either encoder's options: icw_cwave_enc_opts (the FIR converter), or
- * icw_cwave_enc_iir_opts (iir: the quadrature IIR; k_M 0, k_beta 0.0, no aligned mode) */
+/* what a group needs of an encoder's options: icw_cwave_enc_opts (the FIR converter),
+ * icw_cwave_enc_iir_opts (iir: the quadrature IIR; k_M 0, k_beta 0.0, no aligned mode), or
+ * icw_cwave_enc_fft_opts (the direct FFT: k_M -1, k_beta 0.0, whole tracks within max_bytes) */
 struct EncSpec {
     int32_t k_M = 0, align = 0;
     double k_beta = 0.0;
@@ -439,6 +440,7 @@ struct EncSpec {
     bool iir = false;
     uint32_t hilbert_type = 1;
     int32_t iir_kahan = 1, iir_subnorm_reject = 1;
+    uint64_t max_bytes = 0;
 };
 
 /* HCWAVE_V2 (cwave.h:48-60), little-endian */
@@ -562,9 +564,110 @@ int encode_files(const char *const *in_paths, const char *const *out_paths, int 
         [&](int, std::vector<Job *> &g, icw_batch_stats &st, int *sts) { return run_enc_group(g, o, st, clipped, sts); });
 }
 
+/* One group of WAV files sharing (format, channels) through the direct-FFT encoder: whole tracks, no blocks.
+ * The files are packed, in order, into calls whose device working set (PCM, transforms, frames) fits
+ * o.max_bytes; a file that alone exceeds it runs alone.  Per call: read the files, one copy in,
+ * icw_encode_cwave_fft and icw_crc32_batch on the frames in HBM (device pointers), one copy out, write. */
+int run_fft_group(std::vector<Job *> &jobs, const EncSpec &o, icw_batch_stats &st, uint64_t *clipped, int *status)
+{
+    const icw_wav_info &wi = jobs[0]->info;
+    const size_t fsz = wi.frame_bytes, FB = (size_t)icw_cwave_frame_bytes(o.cw_format, wi.channels);
+    const uint64_t budget = o.max_bytes ? o.max_bytes : (uint64_t)16 << 30;
+    auto al16 = [](uint64_t v) { return (v + 15) & ~(uint64_t)15; };
+    if (o.device >= 0 && hipSetDevice(o.device) != hipSuccess) return ICW_EDEVICE;
+    icw_fft_enc_opts fo = {o.device, 0};
+    for (size_t k0 = 0; k0 < jobs.size();) {
+        std::vector<uint64_t> nfr, ioff, ooff, len;
+        uint64_t need = 0, in_b = 0, out_b = 0;
+        size_t k1 = k0;
+        for (; k1 < jobs.size(); ++k1) {
+            const uint64_t N = (uint64_t)jobs[k1]->info.n_samples;
+            const uint64_t cost = icw_encode_cwave_fft_workspace(&N, 1, wi.channels) + al16(N * fsz) + al16(N * FB);
+            if (k1 > k0 && need + cost > budget) break;
+            need += cost;
+            nfr.push_back(N);
+            ioff.push_back(in_b);
+            ooff.push_back(out_b);
+            len.push_back(N * FB);
+            in_b += al16(N * fsz);
+            out_b += al16(N * FB);
+        }
+        const int cnt = (int)(k1 - k0);
+        std::vector<unsigned char> hin(in_b), hout(out_b);
+        double t0 = now_s();
+        for (int k = 0; k < cnt; ++k) {
+            Job &j = *jobs[k0 + k];
+            if (fseeko(j.in, j.info.data_offset, SEEK_SET) || fread(hin.data() + ioff[k], fsz, nfr[k], j.in) != nfr[k])
+                status[j.idx] = ICW_EINVAL;                /* short read: broken file */
+            else
+                st.frames_in += nfr[k];
+        }
+        st.io_s += now_s() - t0;
+        unsigned char *din = nullptr, *dout = nullptr;
+        int rc = ICW_OK;
+        if (hipMalloc((void **)&din, in_b) != hipSuccess || hipMalloc((void **)&dout, out_b) != hipSuccess) rc = ICW_ENOMEM;
+        if (rc == ICW_OK && hipMemcpy(din, hin.data(), in_b, hipMemcpyHostToDevice) != hipSuccess) rc = ICW_EDEVICE;
+        std::vector<uint64_t> clip(cnt, 0);
+        std::vector<uint32_t> crc(cnt, 0u);
+        if (rc == ICW_OK)
+            rc = icw_encode_cwave_fft(din, ioff.data(), nfr.data(), cnt, wi.fmt, wi.channels, dout, ooff.data(), o.cw_format,
+                                      clip.data(), ICW_F_DEVICE_PTRS, &fo, nullptr);
+        if (rc == ICW_OK)
+            rc = icw_crc32_batch(dout, ooff.data(), len.data(), cnt, nullptr, crc.data(), ICW_F_DEVICE_PTRS, o.device, nullptr);
+        if (rc == ICW_OK && hipMemcpy(hout.data(), dout, out_b, hipMemcpyDeviceToHost) != hipSuccess) rc = ICW_EDEVICE;
+        if (din) (void)hipFree(din);
+        if (dout) (void)hipFree(dout);
+        if (rc != ICW_OK) return rc;
+        t0 = now_s();
+        for (int k = 0; k < cnt; ++k) {
+            Job &j = *jobs[k0 + k];
+            if (status[j.idx] != ICW_OK) continue;
+            unsigned char hdr[ICW_CWAVE_HEADER_BYTES];
+            cwave_header(hdr, o, wi.channels, (uint32_t)nfr[k], j.info.sample_rate, crc[k]);
+            if (fwrite(hdr, 1, sizeof(hdr), j.out) != sizeof(hdr) || fwrite(hout.data() + ooff[k], FB, nfr[k], j.out) != nfr[k]) {
+                status[j.idx] = ICW_EINVAL;
+                continue;
+            }
+            if (clipped) clipped[j.idx] = clip[k];
+            j.total = j.written = (int64_t)nfr[k];
+            st.frames_out += nfr[k];
+        }
+        st.io_s += now_s() - t0;
+        k0 = k1;
+    }
+    return ICW_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int icw_cwave_encode_files_fft(const char *const *in_paths, const char *const *out_paths, int n,
+                               const icw_cwave_enc_fft_opts *opts, icw_batch_stats *stats, uint64_t *clipped, int *status)
+{
+    if (!opts || n < 0 || (n > 0 && (!in_paths || !out_paths))) return ICW_EINVAL;
+    if (opts->cw_format < ICW_FMT_CW_F64 || opts->cw_format > ICW_FMT_CW_F32) return ICW_EINVAL;
+    EncSpec e;
+    e.k_M = -1;
+    e.cw_format = opts->cw_format;
+    e.device = opts->device;
+    e.max_bytes = opts->max_bytes;
+    /* the groups: (format, channels) alone -- the rate only goes into the header */
+    std::vector<int> shape(n > 0 ? n : 1, 0);
+    return for_file_groups(
+        in_paths, out_paths, n, stats, status,
+        [&](int i, Job &j) {
+            if (clipped) clipped[i] = 0;
+            if (accept_wav(in_paths[i], out_paths[i], &j.info) != ICW_OK || j.info.fmt >= ICW_FMT_CW_F64 || j.info.n_samples < 2)
+                return (int)ICW_EINVAL;
+            if (j.info.n_samples > ((int64_t)1 << ICW_FFT_MAX_LOG2)) return (int)ICW_EUNSUPPORTED;
+            shape[i] = (int)(j.info.fmt * 16 + j.info.channels);
+            return (int)ICW_OK;
+        },
+        [&](int i) { return shape[i]; },
+        [&](int, std::vector<Job *> &g, icw_batch_stats &st, int *sts) { return run_fft_group(g, e, st, clipped, sts); },
+        true);
+}
 
 int icw_cwave_encode_files(const char *const *in_paths, const char *const *out_paths, int n, const icw_cwave_enc_opts *opts,
                            icw_batch_stats *stats, uint64_t *clipped, int *status)

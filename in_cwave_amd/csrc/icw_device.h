@@ -101,6 +101,29 @@ struct IcwPackArgs {
     unsigned long long *clipped;   /* [n_streams] saturated / NaN int16 samples, accumulated */
 };
 
+/* The direct-FFT encoder (icw_fft.hip, KX): one track of a call */
+struct IcwFftTrack {
+    uint64_t in_off, out_off;      /* byte offsets of the track's PCM in `in` and of its frames in `out` */
+    uint64_t ws_off;               /* the track's first complex point in the workspace */
+    uint32_t n, pad_;              /* frames */
+};
+
+/* Arguments of one pass over the tracks of one transform length 2^logP */
+struct IcwFftArgs {
+    const unsigned char *in;
+    unsigned char *out;
+    double *ws;                    /* the transforms, in place: 2^logP points (re, im) per track; 16-byte aligned */
+    const IcwFftTrack *tracks;     /* the launch's tracks (blockIdx.y) */
+    unsigned long long *clipped;   /* one counter per track of `tracks` */
+    uint32_t fmt, channels, cwf;   /* the PCM's format and channels; cw_format - ICW_FMT_CW_F64 */
+    int32_t logP, l, logR, logC;   /* sub-transforms of 2^l points at stride 2^logR, 2^logC columns per workgroup */
+    int32_t kind;                  /* ICW_FFT_FWD / _MID / _INV */
+    int32_t first, last;           /* the pass loads the PCM / writes the file frames */
+};
+#define ICW_FFT_FWD 0              /* sub-transforms, then the twiddles W_(2^(l+logR))^(n2 k1) */
+#define ICW_FFT_MID 1              /* the last forward pass (stride 1), the multiplier m / P, the first inverse pass */
+#define ICW_FFT_INV 2              /* the conjugate twiddles, then the inverse sub-transforms */
+
 /* Arguments of the call-end bookkeeping kernel: one thread per stream. During a call every
  * kernel reads the call-start position / phases / frame counter and adds its block offset; this
  * kernel advances them once, after the last block. */

@@ -20,6 +20,7 @@
 
 #include "icw_unpack_dev.h"
 #include "icw_fir_dev.h"
+#include "icw_cwpack_dev.h"
 
 /* KFE: the converter as a CWAVE encoder.  KF's staging and sums (so the same unpack, fades, I and Q,
  * bit for bit), written as the interleaved frames of a CWAVE file (cwave.h:74-81) instead of the I / Q
@@ -41,16 +42,6 @@
  * leaves as consecutive 16-byte units, one global_store_dwordx4 per lane and pass; a tile whose first
  * byte is not 16-byte aligned leaves as dwords funnelled from two LDS words, and only the at most two
  * partial dwords at its ends as bytes. */
-template <int CWF> struct icw_cw_bytes { static constexpr int value = CWF == 0 ? 16 : CWF == 1 ? 4 : CWF == 2 ? 6 : 8; };
-
-__device__ __forceinline__ uint32_t icw_enc_i16(double v, bool live, unsigned &clip)
-{
-    const double r = __builtin_rint(v);
-    if (r >= -32768.0 && r <= 32767.0) return (uint32_t)(int)r & 0xffffu;
-    if (live) ++clip;
-    return r != r ? 0u : (r < 0.0 ? 0x8000u : 0x7fffu);
-}
-
 /* A tile's byte image in LDS to its place dst in the file rows: consecutive 16-byte units where dst is
  * 16-byte aligned (the at most 14 bytes after the last whole unit of a short tile as halfwords), else dwords
  * funnelled from two LDS words with the at most two partial dwords at the ends as bytes.  PADU pad units

@@ -45,6 +45,9 @@ hipError_t icw_launch_iq_pack(const IcwPackArgs *a, int cwf, int nc, hipStream_t
 /* hq_phase: null for the FIR encoder (the reader position alone) */
 hipError_t icw_launch_enc_advance(long long *pos, uint32_t *hq_phase, int n_streams, long long n, hipStream_t st);
 
+/* icw_fft.hip: one pass of the direct-FFT encoder over n_tracks tracks of one transform length */
+hipError_t icw_launch_fft_pass(const IcwFftArgs *a, int n_tracks, hipStream_t st);
+
 /* icw_crc.hip */
 hipError_t icw_launch_crc32(const IcwCrcArgs *a, uint64_t max_cells, int n_cu, hipStream_t st);
 

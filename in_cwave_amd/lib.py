@@ -575,6 +575,70 @@ def cwave_encode_files_iir(in_paths, out_paths, hilbert_type=1, iir_kahan=1, iir
     return rc, st, [status[i] for i in range(n)], [int(clipped[i]) for i in range(n)]
 
 
+def _u64(values):
+    return (C.c_uint64 * max(1, len(values)))(*[int(v) for v in values])
+
+
+def encode_cwave_fft_passes(n_frames, max_pass_log2=0):
+    """icw_encode_cwave_fft_passes: passes per transform direction of a track of n_frames frames"""
+    k = int(load().icw_encode_cwave_fft_passes(int(n_frames), int(max_pass_log2)))
+    if k < 0:
+        _check(k, "icw_encode_cwave_fft_passes")
+    return k
+
+
+def encode_cwave_fft_workspace(n_frames, channels=2):
+    """icw_encode_cwave_fft_workspace: device working-set bytes of a call over tracks of n_frames[i] frames"""
+    return int(load().icw_encode_cwave_fft_workspace(_u64(n_frames), len(n_frames), channels))
+
+
+def encode_cwave_fft(tracks, fmt, channels, cw_format=abi.FMT_CW_F64, max_pass_log2=0, device=-1):
+    """icw_encode_cwave_fft, host pointers: tracks is a list of uint8 arrays of whole PCM tracks (format fmt,
+    `channels` interleaved channels) that go through the direct-FFT converter in ONE call.  Returns (list of
+    uint8 arrays of packed CWAVE frames, list of clipped int16 samples)."""
+    fsz = abi.FMT_BYTES[fmt] * channels
+    fb = cwave_frame_bytes(cw_format, channels)
+    tracks = [np.ascontiguousarray(t, dtype=np.uint8).reshape(-1) for t in tracks]
+    nfr = [t.size // fsz for t in tracks]
+    inp = np.concatenate(tracks) if tracks else np.zeros(1, np.uint8)
+    ioff = np.concatenate([[0], np.cumsum([t.size for t in tracks])])[:-1] if tracks else []
+    ooff = np.concatenate([[0], np.cumsum([n * fb for n in nfr])])[:-1] if tracks else []
+    out = np.zeros(max(1, sum(nfr) * fb), dtype=np.uint8)
+    clipped = _u64([0] * len(tracks))
+    o = abi.FftEncOpts(device, max_pass_log2)
+    _check(load().icw_encode_cwave_fft(_ptr(inp), _u64(ioff), _u64(nfr), len(tracks), fmt, channels, _ptr(out), _u64(ooff),
+                                       cw_format, clipped, 0, C.byref(o), None), "icw_encode_cwave_fft")
+    return ([out[int(b):int(b) + n * fb].copy() for b, n in zip(ooff, nfr)], [int(clipped[i]) for i in range(len(tracks))])
+
+
+def encode_cwave_fft_device(d_in, in_offsets, n_frames, fmt, channels, d_out, out_offsets, cw_format=abi.FMT_CW_F64,
+                            max_pass_log2=0, device=-1, hip_stream=None):
+    """icw_encode_cwave_fft with ICW_F_DEVICE_PTRS (torch tensors / int pointers): track i's PCM at
+    d_in + in_offsets[i], its frames to d_out + out_offsets[i].  Returns the clipped counts; the call has
+    waited for hip_stream."""
+    n = len(n_frames)
+    clipped = _u64([0] * n)
+    o = abi.FftEncOpts(device, max_pass_log2)
+    _check(load().icw_encode_cwave_fft(_ptr(d_in), _u64(in_offsets), _u64(n_frames), n, fmt, channels, _ptr(d_out),
+                                       _u64(out_offsets), cw_format, clipped, abi.F_DEVICE_PTRS, C.byref(o), hip_stream),
+           "icw_encode_cwave_fft")
+    return [int(clipped[i]) for i in range(n)]
+
+
+def cwave_encode_files_fft(in_paths, out_paths, cw_format=abi.FMT_CW_F64, device=-1, max_bytes=0):
+    """icw_cwave_encode_files_fft: WAV files to V2 CWAVE files (k_M -1) through the direct-FFT converter; returns
+    (rc, stats, per-file status, per-file clipped int16 samples)"""
+    n = len(in_paths)
+    ins = (C.c_char_p * max(1, n))(*[str(p).encode() for p in in_paths])
+    outs = (C.c_char_p * max(1, n))(*[str(p).encode() for p in out_paths])
+    o = abi.CwaveEncFftOpts(cw_format, device, max_bytes)
+    st = abi.BatchStats()
+    status = (C.c_int * max(1, n))()
+    clipped = (C.c_uint64 * max(1, n))()
+    rc = load().icw_cwave_encode_files_fft(ins, outs, n, C.byref(o), C.byref(st), clipped, status)
+    return rc, st, [status[i] for i in range(n)], [int(clipped[i]) for i in range(n)]
+
+
 def transcode_files_devices(cfg, nodes, in_paths, out_paths, devices, fade_in_ms=0, fade_out_ms=0, sec_align=0,
                             block_frames=0, merge_inputs=False):
     """icw_transcode_files_devices: the files split over `devices` (one host thread each)"""

@@ -76,8 +76,9 @@ int icw_cwave_check(const void *file, uint64_t file_size, unsigned flags, int de
  * the FIR converter itself): double = the bits; float = round to nearest even; int16 = round to nearest,
  * ties to even, saturated to [-32768, 32767], NaN -> 0.
  * icw_encode_cwave_iir (below) writes the same frames from the quadrature IIR converter, whose values
- * are the reference's (hq_rp_process) bit for bit.
- * Not covered: the direct-FFT converter (k_M -1), V1 headers. */
+ * are the reference's (hq_rp_process) bit for bit.  icw_encode_cwave_fft (at the end) writes them from the
+ * direct-FFT converter (k_M -1): the Hilbert transform of the whole track.
+ * Not covered: V1 headers. */
 
 /* bytes of one frame of cw_format for an input of `channels` channels; 0 if either is invalid */
 int icw_cwave_frame_bytes(uint32_t cw_format, uint32_t channels);
@@ -126,6 +127,63 @@ int icw_encode_cwave_iir(icw_ctx *ctx, int first, int count, const void *in, siz
  * encoder (one counter), since the count was last reset; waits for the context's queued work.  reset != 0 clears it after the read.
  * clipped may be NULL. */
 int icw_encode_clipped(icw_ctx *ctx, int s, int reset, uint64_t *clipped);
+
+/* ---- the direct-FFT converter (k_M = -1, cwave.h:40,56; gui_cwave.c:159-170): whole-track analytic signal ----
+ * Definition (the project's: the reference ships no converter, so parity is unpinned).  For one
+ * channel of one track x[0..N) -- the reader's unpacked doubles on the 16-bit scale, no fades, no tail, a
+ * fresh stream, as in the other two encoders --
+ *   P = the smallest power of two >= max(N, 2); x zero-padded to P;
+ *   Q = Re( IDFT_P( m[k] * DFT_P(x)[k] ) ),  m[k] = -j for 0 < k < P/2, +j for k > P/2, m[0] = m[P/2] = 0,
+ *   DFT the forward transform sum x[n] e^(-2 pi j k n / P), IDFT its inverse with the factor 1/P
+ * (scipy.signal.hilbert(x, P).imag; x = A cos(theta) gives Q = A sin(theta), so I + jQ rotates positively).
+ * File frame n < N holds I[n] = x[n], the unpacked sample itself bit for bit (never the transform's round
+ * trip), and Q[n].  Frame layout, mono / stereo rules and conversions are icw_encode_cwave's (above).
+ * There is no design parameter, no transition band at DC or Nyquist and no group delay.
+ * The bytes of a track depend only on that track and on opts->max_pass_log2: not on what else is in the
+ * call, nor on the pointer kind.  The transform is a multi-pass radix-2 FP64 FFT on the GPU; a stereo pair
+ * runs as one complex transform (L + jR), a mono track carries a zero imaginary part.
+ *
+ * Limits: 2 <= N <= P <= 2^ICW_FFT_MAX_LOG2.  The working set is 16 bytes per point of P in HBM: 2 GiB for
+ * a track of the largest P (icw_encode_cwave_fft_workspace gives a call's figure). */
+#define ICW_FFT_MAX_LOG2 27
+
+typedef struct icw_fft_enc_opts {
+    int32_t device;         /* HIP device, -1: current */
+    int32_t max_pass_log2;  /* 0: default; 2..: cap of a pass's sub-transform, 2^cap points (tests; values above
+                               the default's 7 mean the default) */
+} icw_fft_enc_opts;
+
+/* Encode n tracks in one call: track i's PCM (format fmt, `channels` interleaved channels, n_frames[i] frames) at
+ * in + in_offsets[i], its CWAVE frames of cw_format to out + out_offsets[i] (n_frames[i] *
+ * icw_cwave_frame_bytes(cw_format, channels) bytes; any alignment).  Tracks of different lengths run in one
+ * call.  flags: 0 -- in / out are host pointers, staged through the device -- or ICW_F_DEVICE_PTRS.  Either way
+ * the call returns with `out` filled (it waits for hip_stream, on which its work is queued).  clipped
+ * (nullable host array, n entries) gets every track's saturated / NaN int16 samples.  opts may be NULL
+ * (device -1, default passes).
+ * Errors, all found on the host before the device is touched, nothing run: ICW_EINVAL for a null pointer,
+ * n < 0, a CWAVE fmt, channels 0, a cw_format outside ICW_FMT_CW_*, a track of fewer than 2 frames, a flag
+ * other than ICW_F_DEVICE_PTRS, max_pass_log2 negative or 1; then ICW_EUNSUPPORTED for a track of more than
+ * 2^ICW_FFT_MAX_LOG2 frames.  ICW_ENOMEM / ICW_EDEVICE: a buffer or a HIP call failed. */
+int icw_encode_cwave_fft(const void *in, const uint64_t *in_offsets, const uint64_t *n_frames, int n,
+                         uint32_t fmt, uint32_t channels, void *out, const uint64_t *out_offsets,
+                         uint32_t cw_format, uint64_t *clipped, unsigned flags, const icw_fft_enc_opts *opts,
+                         void *hip_stream);
+
+/* working-set bytes the call needs on the device beside in and out: 16 bytes per point of every track's P
+ * (a complex double; mono tracks carry a zero imaginary part, so `channels` does not change it) and 40 bytes
+ * of bookkeeping per track.  A host-pointer call stages in and out on the device on top of it.  0 for
+ * arguments icw_encode_cwave_fft refuses. */
+size_t icw_encode_cwave_fft_workspace(const uint64_t *n_frames, int n, uint32_t channels);
+
+/* passes per transform direction of a track of n_frames frames at this max_pass_log2 (host arithmetic): a
+ * call runs 2 * passes - 1 kernels over such a track (the last forward and the first inverse pass are one).
+ * ICW_EINVAL / ICW_EUNSUPPORTED as icw_encode_cwave_fft. */
+int icw_encode_cwave_fft_passes(uint64_t n_frames, int32_t max_pass_log2);
+
+/* Measurement hook (tools/fft_encode_rate.py): with ICW_FFT_TIMING=1 in the environment a call records every
+ * kernel launch between two HIP events; this returns the number of launches of the process's last such call
+ * and copies up to `max` of their times in ms, in launch order, to ms (nullable). */
+int icw_encode_cwave_fft_last_ms(double *ms, int max);
 
 #ifdef __cplusplus
 }

@@ -115,7 +115,7 @@ typedef struct icw_cwave_enc_opts {
  * 2^32 frames or more, or an I/O error; the rest of the batch still completes.  clipped (nullable, n
  * entries) gets the file's saturated / NaN int16 samples.  Returns ICW_EINVAL for bad options (nothing
  * runs), else ICW_OK if every file was encoded, else one of the files' errors.
- * Not covered: the direct-FFT converter (k_M -1), V1 headers. */
+ * Not covered: V1 headers. */
 int icw_cwave_encode_files(const char *const *in_paths, const char *const *out_paths, int n,
                            const icw_cwave_enc_opts *opts, icw_batch_stats *stats, uint64_t *clipped, int *status);
 
@@ -141,6 +141,27 @@ typedef struct icw_cwave_enc_iir_opts {
  * 0 or 1, a cw_format outside ICW_FMT_CW_*, block_frames < 0; nothing runs, nothing is written). */
 int icw_cwave_encode_files_iir(const char *const *in_paths, const char *const *out_paths, int n,
                                const icw_cwave_enc_iir_opts *opts, icw_batch_stats *stats, uint64_t *clipped,
+                               int *status);
+
+/* ---- convert with the direct-FFT converter (k_M = -1): the Hilbert transform of the whole track ---- */
+typedef struct icw_cwave_enc_fft_opts {
+    uint32_t cw_format;                 /* ICW_FMT_CW_* of the output */
+    int32_t  device;                    /* HIP device, -1: current */
+    uint64_t max_bytes;                 /* device working-set budget of one call (PCM + transforms + frames);
+                                           0: 16 GiB */
+} icw_cwave_enc_fft_opts;
+
+/* icw_cwave_encode_files through icw_encode_cwave_fft (icw_cwave.h: the definition): file frame n holds
+ * I = the input's sample n and Q = the Hilbert transform of the whole zero-padded track at n -- no filter
+ * order, no transition band, no delay.  The header is V2 with hsize 48, n_samples = the input's frames,
+ * k_M = -1 ("direct FFT", gui_cwave.c:159-170) and k_beta = 0.0; n_CRC32 is computed on the GPU over the packed
+ * frames while they are in HBM (icw_crc32_batch).  Tracks are whole: files are grouped by (format, channels)
+ * -- the rate plays no part -- and packed, in order, into calls whose working set fits max_bytes (a file
+ * that alone exceeds it runs alone).  Per-file status and `clipped` as above, and ICW_EUNSUPPORTED for a
+ * track of more than 2^ICW_FFT_MAX_LOG2 frames; the rest of the batch still completes.  Returns ICW_EINVAL
+ * for bad options (a cw_format outside ICW_FMT_CW_*; nothing runs, nothing is written). */
+int icw_cwave_encode_files_fft(const char *const *in_paths, const char *const *out_paths, int n,
+                               const icw_cwave_enc_fft_opts *opts, icw_batch_stats *stats, uint64_t *clipped,
                                int *status);
 
 #ifdef __cplusplus
