@@ -112,6 +112,7 @@ class WavInfo(C.Structure):
                 ("htype", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+FIR_MAX_ORDER = 4096     # ICW_FIR_MAX_ORDER: largest k_M of icw_set_fir_hilbert / icw_transcode_files_fir
 # icw_batch_opts.reserved_ is the flags word (0: today's grouping, one context per input format)
 BATCH_MERGE_INPUTS = 1   # ICW_BATCH_MERGE_INPUTS: all real-input files in one context per device
 
@@ -167,6 +168,7 @@ SIGNATURES = {
     "icw_set_stream_input": (_i, [_vp, _i, _i, C.c_uint32, C.c_uint32, C.c_uint32]),
     "icw_stream_input_count": (_i, [_vp]),
     "icw_set_fir_hilbert": (_i, [_vp, C.c_int32, C.c_double]),
+    "icw_enable_stream_fir": (_i, [_vp, _i]),
     "icw_set_graph": (_i, [_vp, C.POINTER(Node), _i, _i, C.POINTER(_i)]),
     "icw_set_stream_graph": (_i, [_vp, _i, _i, C.POINTER(Node), _i, _i, C.POINTER(_i)]),
     "icw_clear_stream_bus_slot": (_i, [_vp, _i, _i, _i]),
@@ -246,6 +248,9 @@ SIGNATURES = {
     "icw_transcode_files_lists": (_i, [C.POINTER(Config), C.POINTER(C.POINTER(Node)), C.POINTER(_i), C.POINTER(_i),
                                        C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, C.POINTER(BatchOpts),
                                        C.POINTER(BatchStats), C.POINTER(_i)]),
+    "icw_transcode_files_fir": (_i, [C.POINTER(Config), C.POINTER(C.POINTER(Node)), C.POINTER(_i), C.POINTER(_i),
+                                     C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, C.c_int32, C.c_double,
+                                     C.POINTER(BatchOpts), C.POINTER(BatchStats), C.POINTER(_i)]),
     "icw_group_create": (_i, [C.POINTER(Config), C.POINTER(Node), _i, _i, C.POINTER(_i), _i, C.POINTER(_vp),
                               C.POINTER(_i)]),
     "icw_group_destroy": (_i, [_vp]),

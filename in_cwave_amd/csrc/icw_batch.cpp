@@ -173,6 +173,8 @@ struct FileLists {
     const int *n_nodes = nullptr;
     const int *bypass = nullptr;       /* nullable: cfg->bypass_list */
     bool per_stream = false;           /* the group's lists may differ (all register form) */
+    int32_t k_M = 0;                   /* icw_transcode_files_fir: the FIR converter for real-input groups (0: the IIR) */
+    double k_beta = 0.0;
 };
 
 /* The frame of a many-file call: parse and open every file, group the accepted ones by (rate, format,
@@ -383,6 +385,10 @@ int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::v
     int rc = icw_create(&cfg, nodes, n_nodes, S, o.device, &ctx, &accepted);
     if (rc != ICW_OK) return rc;
     std::unique_ptr<icw_ctx, int (*)(icw_ctx *)> guard(ctx, icw_destroy);
+    /* a CWAVE group is analytic already: the converter is for real input */
+    if (fl.k_M > 0 && wi.fmt < ICW_FMT_CW_F64 &&
+        ((rc = icw_enable_stream_fir(ctx, 1)) != ICW_OK || (rc = icw_set_fir_hilbert(ctx, fl.k_M, fl.k_beta)) != ICW_OK))
+        return rc;
     for (int s = 1; s < S && fl.per_stream; ++s) {
         const int i = jobs[s]->idx;
         rc = icw_set_stream_graph(ctx, s, 1, fl.nodes[i], fl.n_nodes[i], fl.bypass ? fl.bypass[i] : cfg0.bypass_list,
@@ -756,10 +762,12 @@ int icw_transcode_files(const icw_config *cfg, const icw_node *nodes, int n_node
         (o.reserved_ & ICW_BATCH_MERGE_INPUTS) != 0);
 }
 
-/* icw_transcode_files with file i's own list (include/icw_reader.h) */
-int icw_transcode_files_lists(const icw_config *cfg, const icw_node *const *nodes, const int *n_nodes,
-                              const int *bypass_list, const char *const *in_paths, const char *const *out_paths, int n,
-                              const icw_batch_opts *opts, icw_batch_stats *stats, int *status)
+namespace {
+
+/* icw_transcode_files_lists, with the FIR converter (k_M > 0) on every context of real-input files */
+int transcode_lists(const icw_config *cfg, const icw_node *const *nodes, const int *n_nodes, const int *bypass_list,
+                    const char *const *in_paths, const char *const *out_paths, int n, int32_t k_M, double k_beta,
+                    const icw_batch_opts *opts, icw_batch_stats *stats, int *status)
 {
     if (!cfg || n < 0 || (n > 0 && (!in_paths || !out_paths || !nodes || !n_nodes))) return ICW_EINVAL;
     icw_batch_opts o;
@@ -801,9 +809,31 @@ int icw_transcode_files_lists(const icw_config *cfg, const icw_node *const *node
             fl.n_nodes = n_nodes;
             fl.bypass = bypass_list;
             fl.per_stream = key < 0;
+            fl.k_M = k_M;
+            fl.k_beta = k_beta;
             return run_group(*cfg, nullptr, 0, g, o, st, sts, fl);
         },
         (o.reserved_ & ICW_BATCH_MERGE_INPUTS) != 0);
+}
+
+}  // namespace
+
+/* icw_transcode_files with file i's own list (include/icw_reader.h) */
+int icw_transcode_files_lists(const icw_config *cfg, const icw_node *const *nodes, const int *n_nodes,
+                              const int *bypass_list, const char *const *in_paths, const char *const *out_paths, int n,
+                              const icw_batch_opts *opts, icw_batch_stats *stats, int *status)
+{
+    return transcode_lists(cfg, nodes, n_nodes, bypass_list, in_paths, out_paths, n, 0, 0.0, opts, stats, status);
+}
+
+/* the same through the FIR converter (include/icw_reader.h); icw_set_fir_hilbert's own checks first, so a
+ * bad order or window parameter opens no file */
+int icw_transcode_files_fir(const icw_config *cfg, const icw_node *const *nodes, const int *n_nodes,
+                            const int *bypass_list, const char *const *in_paths, const char *const *out_paths, int n,
+                            int32_t k_M, double k_beta, const icw_batch_opts *opts, icw_batch_stats *stats, int *status)
+{
+    if (k_M < 2 || k_M > ICW_FIR_MAX_ORDER || (k_M & 1) || !(k_beta >= 0.0 && k_beta < 1e3)) return ICW_EINVAL;
+    return transcode_lists(cfg, nodes, n_nodes, bypass_list, in_paths, out_paths, n, k_M, k_beta, opts, stats, status);
 }
 
 }  /* extern "C" */

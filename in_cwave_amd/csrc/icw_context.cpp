@@ -643,9 +643,11 @@ int icw_set_fir_hilbert(icw_ctx *c, int32_t M, double beta)
     if (!c || (M != 0 && (M < 2 || M > ICW_FIR_MAX_ORDER || (M & 1))) || !(beta >= 0.0 && beta < 1e3))
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    /* the fused converter takes one list per launch: not beside per-stream lists (include/icw.h) */
-    if (M > 0 && (!c->progs.empty() || c->n_inputs > 1)) return ICW_EUNSUPPORTED;
+    /* beside per-stream lists or inputs only once the host has asked for it (icw_enable_stream_fir): the
+     * converter's kernels then run their per-stream form */
+    if (M > 0 && !c->fir_streams && (!c->progs.empty() || c->n_inputs > 1)) return ICW_EUNSUPPORTED;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+    c->pid_valid = false;                 /* with the converter on, every (list, rate) pair has a slab */
     for (double *&h : c->fir_hist)
         if (h) { (void)hipFree(h); h = nullptr; }
     if (c->d_fir_g) { (void)hipFree(c->d_fir_g); c->d_fir_g = nullptr; }
@@ -672,6 +674,17 @@ int icw_set_fir_hilbert(icw_ctx *c, int32_t M, double beta)
     bool ok = fir_clear(c, 0, (size_t)c->n_streams, c->stream);
     ok &= hipStreamSynchronize(c->stream) == hipSuccess;
     return ok ? ICW_OK : ICW_EDEVICE;
+}
+
+/* per-stream lists and inputs beside the FIR converter, on or off (include/icw.h) */
+int icw_enable_stream_fir(icw_ctx *c, int on)
+{
+    if (!c) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    /* off while the two are in force together would leave a state the setters refuse to build */
+    if (!on && c->fir_M > 0 && (!c->progs.empty() || c->n_inputs > 1)) return ICW_EUNSUPPORTED;
+    c->fir_streams = on != 0;
+    return ICW_OK;
 }
 
 int icw_stream_reset_framecnt(icw_ctx *c, int s)
@@ -719,9 +732,10 @@ int icw_set_stream_input(icw_ctx *c, int first, int count, uint32_t sample_rate,
         sample_rate > ICW_MAX_FS_SRC || fmt > ICW_FMT_CW_F32 || channels == 0)
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    /* whether K1 runs at all is a per-call decision, and the FIR converter's kernels take one format per
-     * launch: CWAVE input and the converter stay context-wide */
-    if (fmt >= ICW_FMT_CW_F64 || c->cfg.in_format >= ICW_FMT_CW_F64 || c->fir_M > 0) return ICW_EUNSUPPORTED;
+    /* whether K1 runs at all is a per-call decision: CWAVE input stays context-wide.  The FIR converter
+     * is context-wide too; it reads every stream's own real format once icw_enable_stream_fir said so */
+    if (fmt >= ICW_FMT_CW_F64 || c->cfg.in_format >= ICW_FMT_CW_F64 || (c->fir_M > 0 && !c->fir_streams))
+        return ICW_EUNSUPPORTED;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     std::vector<IcwInDesc> nv = c->inputs;
     for (int s = first; s < first + count; ++s) nv[(size_t)s] = make_input(sample_rate, fmt, channels);
@@ -815,9 +829,9 @@ int icw_set_stream_graph(icw_ctx *c, int first, int count, const icw_node *nodes
     if (!ok) return ICW_EGRAPH;
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
-    /* K4 runs one lane per stream on a scalar program and the fused FIR kernels take one signature
-     * per launch: bus-form lists and the FIR converter stay context-wide */
-    if (c->fir_M > 0 || c->prog.is_bus) return ICW_EUNSUPPORTED;
+    /* K4 runs one lane per stream on a scalar program: bus-form lists stay context-wide; the FIR
+     * converter serves per-stream lists once icw_enable_stream_fir said so */
+    if ((c->fir_M > 0 && !c->fir_streams) || c->prog.is_bus) return ICW_EUNSUPPORTED;
     icw_config cfg = c->cfg;
     cfg.bypass_list = bypass_list ? 1 : 0;
     IcwProg P;

@@ -32,9 +32,13 @@ constexpr int kFirRenderFirst = 2048;
  * and two ~12 us gaps beside its 0.26 ms kernel, 13 % of a c2fir step */
 constexpr int kMaxFirBlockFrames = 1 << 20;
 constexpr int kRowRenderMax = 2048;          /* channels up to which the render runs a row per channel */
-/* int32 words of d_pid per stream of the context: a call's 5 selection rows [5][count] and the
- * rotation table's [3][n_slabs], n_slabs <= count / 2 (a slab needs two streams) */
-constexpr size_t kPidWords = 7;
+/* int32 words of d_pid per stream of the context: a call's 5 selection rows [5][count], the FIR
+ * converter's stream map [count] and the rotation table's [3][n_slabs], n_slabs <= count (with the FIR
+ * converter on every (list, rate) pair has a slab; without it a slab needs two streams) */
+constexpr size_t kPidWords = 9;
+/* doubles of rotation table a call over per-stream lists may ask for with the FIR converter's long
+ * blocks (2 GB): every (list, rate) pair has a slab there, so the launch blocks shorten instead */
+constexpr size_t kMaxMixTabDoubles = (size_t)1 << 28;
 constexpr size_t kPinnedStage = 1u << 20;   /* host-pointer calls up to this size stage through pinned memory */
 
 /* internal types and helpers, shared between the library's objects and not with its users: hidden,
@@ -96,6 +100,12 @@ struct icw_ctx {
     int32_t *d_pid = nullptr;
     bool pid_valid = false;
     int pid_first = 0, pid_count = 0, pid_slabs = 0;
+    /* the same call with the FIR converter on (KF2's per-stream form): the streams by channel class --
+     * the map row lists the mono ones, then the stereo ones -- what the launcher needs of each class
+     * (in_step is the call's), and the host's copy of rows 1 and 2 for the in-step test */
+    bool pid_fir = false;
+    IcwFirClass pid_cls[2] = {};
+    std::vector<int32_t> pid_map, pid_slab, pid_ref;
     IcwProg mix{};                        /* that call's launch configuration: needs_omega, n_trig, chain, n_regs */
     /* per-stream inputs (icw_set_stream_input): every stream's descriptor, always filled, and the number
      * of distinct ones.  While that is 1, cfg.sample_rate / in_format / in_channels are the one input, as
@@ -181,6 +191,9 @@ struct icw_ctx {
     double *d_fir_g = nullptr;
     double *fir_hist[2] = {};
     int fir_par = 0;
+    /* icw_enable_stream_fir: per-stream lists and inputs are served beside the converter.  Off on a fresh
+     * context, where the three setters keep the refusals they always had */
+    bool fir_streams = false;
     unsigned long long *enc_clipped = nullptr; /* [streams] icw_encode_cwave: saturated / NaN int16 samples (lazy) */
     unsigned long long *s1_stamps = nullptr;   /* ICW_S1_STAMPS=1: K5 phase stamps, printed per call */
     unsigned long long calls = 0;         /* icw_process_* calls so far (icw_prepare needs a fresh context) */

@@ -81,6 +81,25 @@ struct IcwFirArgs {
     int32_t tile0;                 /* KF2: index of the first tile icw_fir_graph's grid covers (set by the launcher) */
     int32_t lr_same;               /* KF2, mono input: a Master-only chain whose two gains are the same double, so
                                       both output channels are one computation (icw_fir_sig) */
+    /* the per-stream instances only (streams with different lists or inputs; the others never read these):
+     * desc -- nullable [n_streams of the call]: the stream's own fmt / csz / fsz / nch replace the four
+     * above, and `in` is the call's first frame (the block offset t0 is applied with the stream's own
+     * frame size, as icw_unpack_frames_mixed does); map -- nullable: workgroup column x runs stream
+     * map[x] of the call (a launch covers one channel class, IcwFirClass) */
+    const IcwInDesc *desc;
+    const int32_t *map;
+};
+
+/* One channel class of a FIR call over streams with different lists or inputs (icw_launch_fir_graph_mix):
+ * the computed channels, and with them the tile, are compile-time in KF2, so the mono streams and the
+ * stereo streams of the call are launched apart, each through its stream map. */
+struct IcwFirClass {
+    const int32_t *map;            /* [n] the class's streams, as indices into the call's range */
+    int32_t n, nch;                /* streams; 1: mono, 2: stereo */
+    int32_t sig;                   /* the chain signature every stream's program has (0: they differ, or not a chain) */
+    int32_t lr_same;               /* mono: IcwFirArgs.lr_same holds for every stream */
+    int32_t trig;                  /* some stream's program has an active Shift / PM node */
+    int32_t in_step;               /* every stream is in step with its slab's reference stream */
 };
 
 /* Arguments of the CWAVE encoder (KFE): KF's, with the packed file frames as the output (xd unused) */

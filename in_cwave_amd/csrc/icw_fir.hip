@@ -25,13 +25,38 @@
 #include "icw_fir_dev.h"
 #include "icw_graph_dev.h"
 
+/* The per-stream form of the FIR kernels (PS; streams with different lists or inputs, as K2's MIX): the
+ * workgroup is one stream, so what it selects is wave-uniform and comes in by scalar loads through the
+ * constant address space.  The PS = false instances are the kernels of a one-list, one-input call. */
+typedef const __attribute__((address_space(4))) int32_t icw_csel;
+
+/* the stream's own input replaces the launch's: format, sizes, channels, and the block offset at its own
+ * frame size (icw_unpack_frames_mixed); a null table leaves the launch's one input */
+__device__ __forceinline__ void icw_fir_own_input(IcwFirArgs &f, int s)
+{
+    if (f.desc) {
+        const __attribute__((address_space(4))) IcwInDesc *d = (const __attribute__((address_space(4))) IcwInDesc *)f.desc + s;
+        f.fmt = d->fmt;
+        f.csz = d->csz;
+        f.fsz = d->fsz;
+        f.nch = d->nch;
+        f.in += (size_t)f.t0 * f.fsz;
+    }
+}
+
 /* KF: the converter alone, one workgroup per channel and 2048-frame tile of a stream; I / Q rows
  * go out coalesced through LDS to the CWAVE rows K2 reads */
-__global__ __launch_bounds__(256) void icw_fir_hilbert(IcwFirArgs a)
+template <bool PS>
+__device__ __forceinline__ void icw_fir_hilbert_body(IcwFirArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double xs[];   /* staged inputs (padded), taps, Q */
     constexpr int TF = 256 * ICW_FIR_R;
     const int ch = blockIdx.y, s = blockIdx.z;
+    if constexpr (PS) {
+        /* the grid has the widest stream's channels: a mono stream's second column has nothing to do */
+        icw_fir_own_input(a, s);
+        if (ch >= (a.nch > 1 ? 2 : 1)) return;
+    }
     const int tt = blockIdx.x * TF;
     const int M = a.M, c = M >> 1;
     const int sh = icw_fir_sh(c), av = icw_fir_av(c, sh);   /* c - 1 + sh = 8 av */
@@ -58,6 +83,17 @@ __global__ __launch_bounds__(256) void icw_fir_hilbert(IcwFirArgs a)
             rowQ[f + 2 * a.x_pitch] = vq;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void icw_fir_hilbert(IcwFirArgs a)
+{
+    icw_fir_hilbert_body<false>(a);
+}
+
+/* KF over streams with different inputs (a.desc); K2's MIX instances take the rows from there */
+__global__ __launch_bounds__(256) void icw_fir_hilbert_mixed(IcwFirArgs a)
+{
+    icw_fir_hilbert_body<true>(a);
 }
 
 /* Fused FIR converter + graph + render (KF2): one workgroup per stream and 1024-frame tile (2048
@@ -104,7 +140,8 @@ template <bool TRIG, int SIG, bool ROWP, bool B24>
 __device__ __forceinline__ void icw_mono_passes(const IcwK2Args &a, icw_cprog *P, int s, int t0, int nv,
                                                 const double (&vi)[ICW_FIR_R], const double (&q)[ICW_FIR_R],
                                                 unsigned &clip_l, unsigned &clip_r, double &pk_l, double &pk_r,
-                                                unsigned (&w)[ICW_FIR_R / 2 * 3], uint32_t tro_lane, size_t pq)
+                                                unsigned (&w)[ICW_FIR_R / 2 * 3], uint32_t tro_lane, size_t pq,
+                                                size_t tab_off = 0)
 {
 #pragma unroll
     for (int hh = 0; hh < ICW_FIR_R; hh += 2) {
@@ -117,19 +154,19 @@ __device__ __forceinline__ void icw_mono_passes(const IcwK2Args &a, icw_cprog *P
         int dv[2][2];
         const int n2 = min(2, max(nv - hh, 0));
         if constexpr (!ROWP)
-            icw_chain_frames<TRIG, 2>(a, P, s, t0 + hh, n2, in2, clip_l, clip_r, pk_l, pk_r, dv);
+            icw_chain_frames<TRIG, 2>(a, P, s, t0 + hh, n2, in2, clip_l, clip_r, pk_l, pk_r, dv, 0, tab_off);
         else if constexpr (SIG != 0)
             icw_chain_frames<TRIG, 2, true, SIG>(a, P, s, t0 + hh, n2, in2, clip_l, clip_r, pk_l, pk_r, dv, tro_lane,
-                                                 (size_t)hh * pq, pq);
+                                                 (size_t)hh * pq + tab_off, pq);
         else
             icw_chain_frames<TRIG, 2, true>(a, P, s, t0 + hh, n2, in2, clip_l, clip_r, pk_l, pk_r, dv, tro_lane,
-                                            (size_t)hh * pq, pq);
+                                            (size_t)hh * pq + tab_off, pq);
         icw_pack2<B24>(dv[0][0], dv[0][1], dv[1][0], dv[1][1], w + hh / 2 * ICW_PACK2_WORDS(B24));
     }
 }
 
 /* ICW_FIR_OCC 5 (96 VGPRs) spills and ran 2.4x slower (profiles/r03_fir_swap_ab.jsonl) */
-template <bool TRIG, bool TAB, int NC>
+template <bool TRIG, bool TAB, int NC, bool PS = false>
 __global__ __launch_bounds__(256, ICW_FIR_OCC) void icw_fir_graph(IcwFirArgs f, IcwK2Args a)
 {
     ICW_FIR_STAMP(0);
@@ -141,7 +178,12 @@ __global__ __launch_bounds__(256, ICW_FIR_OCC) void icw_fir_graph(IcwFirArgs f, 
      * together, so its rotation-table rows come from the L2 for every stream, where tile-fastest order
      * swept the whole block's table once per stream (a 2^20-frame block's table is 32 MB: c2fir 37 HBM
      * bytes per frame against 9.4) */
-    const int s = blockIdx.x;
+    int s = blockIdx.x;
+    if constexpr (PS) {
+        /* the launch's class of streams through its map, then the stream's own input */
+        if (f.map) s = ((icw_csel *)f.map)[blockIdx.x];
+        icw_fir_own_input(f, s);
+    }
     constexpr int nchc = NC;
     const int TF = 256 * ICW_FIR_R / nchc;
     const int tt = (blockIdx.y + f.tile0) * TF;
@@ -185,6 +227,20 @@ __global__ __launch_bounds__(256, ICW_FIR_OCC) void icw_fir_graph(IcwFirArgs f, 
 #endif
 
     icw_cprog *P = icw_prog_c(a.prog);
+    /* PS: the stream's program, its slab of the rotation table (tab_off) and that slab's reference stream,
+     * and its own rate for the inline factors -- the selection rows K2's MIX instances read */
+    size_t tab_off = 0;
+    [[maybe_unused]] IcwRate rt;
+    [[maybe_unused]] bool own_tab = false;
+    if constexpr (PS) {
+        icw_csel *id = (icw_csel *)a.prog_id;
+        P += id[s];
+        const int slab = id[a.n_streams + s];
+        rt.sample_rate = (uint32_t)id[3 * a.n_streams + s];
+        rt.ssr = (unsigned long long)rt.sample_rate * ICW_HZ_SCALE;
+        own_tab = TRIG && a.trig_tab && slab >= 0 && a.n_frame[s] == a.n_frame[id[2 * a.n_streams + s]];
+        tab_off = slab >= 0 ? (size_t)slab * a.slab_stride : 0;
+    }
     IcwRegFile Rf;
     Rf.base = lregs + threadIdx.x;
     for (int r = 0; r < P->n_persist; ++r) {
@@ -192,7 +248,7 @@ __global__ __launch_bounds__(256, ICW_FIR_OCC) void icw_fir_graph(IcwFirArgs f, 
         IcwLR v; v.lre = b[0]; v.lim = b[1]; v.rre = b[2]; v.rim = b[3];
         Rf.set(P->persist_reg[r], v);
     }
-    const bool use_tab = TAB || (TRIG && a.trig_tab && a.n_frame[s] == a.n_frame[0]);
+    const bool use_tab = TAB || (PS ? own_tab : (TRIG && a.trig_tab && a.n_frame[s] == a.n_frame[0]));
     unsigned clip_l = 0, clip_r = 0;
     double pk_l = 0.0, pk_r = 0.0;
     if (nchc == 2) {
@@ -230,10 +286,10 @@ __global__ __launch_bounds__(256, ICW_FIR_OCC) void icw_fir_graph(IcwFirArgs f, 
                 int dv2[2][2];
                 if (rowp)
                     icw_chain_frames_rowp<TRIG, 2>(a, P, sig, s, tt + fr0 + hh, min(2, max(nf - fr0 - hh, 0)), in2, clip_l,
-                                                   clip_r, pk_l, pk_r, dv2, tro_lane, (size_t)hh * pq, pq);
+                                                   clip_r, pk_l, pk_r, dv2, tro_lane, (size_t)hh * pq + tab_off, pq);
                 else
                     icw_chain_frames<TRIG, 2>(a, P, s, tt + fr0 + hh, min(2, max(nf - fr0 - hh, 0)), in2, clip_l, clip_r,
-                                              pk_l, pk_r, dv2);
+                                              pk_l, pk_r, dv2, 0, tab_off);
                 dv[hh][0] = dv2[0][0]; dv[hh][1] = dv2[0][1];
                 dv[hh + 1][0] = dv2[1][0]; dv[hh + 1][1] = dv2[1][1];
             }
@@ -248,7 +304,11 @@ __global__ __launch_bounds__(256, ICW_FIR_OCC) void icw_fir_graph(IcwFirArgs f, 
             if (fr < nf) {
                 IcwLR in;
                 in.lre = xl; in.lim = yl; in.rre = xr; in.rim = yr;
-                icw_frame_graph<TRIG, TAB, true>(a, P, Rf, s, tt + fr, in, use_tab, clip_l, clip_r, pk_l, pk_r, dv[r]);
+                if constexpr (PS)
+                    icw_frame_graph<TRIG, TAB, true, true>(a, P, Rf, s, tt + fr, in, use_tab, clip_l, clip_r, pk_l, pk_r, dv[r],
+                                                           tab_off, &rt);
+                else
+                    icw_frame_graph<TRIG, TAB, true>(a, P, Rf, s, tt + fr, in, use_tab, clip_l, clip_r, pk_l, pk_r, dv[r]);
             }
         }
         }
@@ -284,9 +344,9 @@ __global__ __launch_bounds__(256, ICW_FIR_OCC) void icw_fir_graph(IcwFirArgs f, 
 #define ICW_MONO(SIGV, RP)                                                                                    \
     do {                                                                                                      \
         if (b24) icw_mono_passes<TRIG, SIGV, RP, true>(a, P, s, tt + fr0, nf - fr0, vi, q, clip_l, clip_r, pk_l,  \
-                                                       pk_r, w, tro_lane, pq);                                \
+                                                       pk_r, w, tro_lane, pq, tab_off);                       \
         else icw_mono_passes<TRIG, SIGV, RP, false>(a, P, s, tt + fr0, nf - fr0, vi, q, clip_l, clip_r, pk_l,    \
-                                                    pk_r, w, tro_lane, pq);                                   \
+                                                    pk_r, w, tro_lane, pq, tab_off);                          \
     } while (0)
         if (!rowp) {
             ICW_MONO(0, false);
@@ -316,7 +376,11 @@ __global__ __launch_bounds__(256, ICW_FIR_OCC) void icw_fir_graph(IcwFirArgs f, 
                 IcwLR in;
                 in.lre = in.rre = vi[r];
                 in.lim = in.rim = q[r];
-                icw_frame_graph<TRIG, TAB>(a, P, Rf, s, tt + fr, in, use_tab, clip_l, clip_r, pk_l, pk_r);
+                if constexpr (PS)
+                    icw_frame_graph<TRIG, TAB, false, true>(a, P, Rf, s, tt + fr, in, use_tab, clip_l, clip_r, pk_l, pk_r, nullptr,
+                                                            tab_off, &rt);
+                else
+                    icw_frame_graph<TRIG, TAB>(a, P, Rf, s, tt + fr, in, use_tab, clip_l, clip_r, pk_l, pk_r);
             }
         }
     }
@@ -349,7 +413,7 @@ __global__ __launch_bounds__(256, ICW_FIR_OCC) void icw_fir_graph(IcwFirArgs f, 
 #ifndef ICW_FIR_SIG_NTAP
 #define ICW_FIR_SIG_NTAP ICW_FIR_NTAP
 #endif
-template <int SIG, int NC, bool B24>
+template <int SIG, int NC, bool B24, bool PS = false>
 __global__ __launch_bounds__(256, NC == 2 ? ICW_FIR_SIG_OCC : ICW_FIR_SIG_OCC1) void icw_fir_sig(IcwFirArgs f, IcwK2Args a)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -359,7 +423,11 @@ __global__ __launch_bounds__(256, NC == 2 ? ICW_FIR_SIG_OCC : ICW_FIR_SIG_OCC1) 
     constexpr int TF = 256 * ICW_FIR_R / NC;
     /* Prologue, packing and stores stay written out here (icw_fir_sh / _av / _px, icw_pack2 and icw_store_packed
      * say the same): through them the schedule moved and c2fir / c3fir measured 0.6-2.7 % slower. */
-    const int s = blockIdx.x;
+    int s = blockIdx.x;
+    if constexpr (PS) {
+        if (f.map) s = ((icw_csel *)f.map)[blockIdx.x];
+        icw_fir_own_input(f, s);
+    }
     const int tt = blockIdx.y * TF;
     const int M = f.M, c = M >> 1;
     const int sh = (8 - ((c - 1) & 7)) & 7;
@@ -376,6 +444,14 @@ __global__ __launch_bounds__(256, NC == 2 ? ICW_FIR_SIG_OCC : ICW_FIR_SIG_OCC1) 
 #pragma unroll
     for (int r = 0; r < ICW_FIR_R; ++r) vi[r] = lds[ch * px + icw_fir_phys(ICW_FIR_R * ll + r + ix)];
     icw_cprog *P = icw_prog_c(a.prog);
+    /* PS: the stream's own program (its constants) and slab (its factors); every stream of the launch has
+     * this kernel's signature and is in step with its slab (icw_launch_fir_graph_mix) */
+    size_t tab_off = 0;
+    if constexpr (PS) {
+        icw_csel *id = (icw_csel *)a.prog_id;
+        P += id[s];
+        if constexpr (TRIG) tab_off = (size_t)id[a.n_streams + s] * a.slab_stride;
+    }
     unsigned clip_l = 0, clip_r = 0;
     double pk_l = 0.0, pk_r = 0.0;
     const size_t pq = (size_t)a.trig_perm_q * a.trig_pitch;
@@ -398,7 +474,7 @@ __global__ __launch_bounds__(256, NC == 2 ? ICW_FIR_SIG_OCC : ICW_FIR_SIG_OCC1) 
                 in2[j].lre = xl; in2[j].lim = yl; in2[j].rre = xr; in2[j].rim = yr;
             }
             int dv2[2][2];
-            icw_sig_fast<TRIG, 2, SIG>(a, P, in2, clip_l, clip_r, pk_l, pk_r, dv2, tro_lane, (size_t)hh * pq, pq);
+            icw_sig_fast<TRIG, 2, SIG>(a, P, in2, clip_l, clip_r, pk_l, pk_r, dv2, tro_lane, (size_t)hh * pq + tab_off, pq);
             dv[hh][0] = dv2[0][0]; dv[hh][1] = dv2[0][1];
             dv[hh + 1][0] = dv2[1][0]; dv[hh + 1][1] = dv2[1][1];
         }
@@ -473,7 +549,7 @@ __global__ __launch_bounds__(256, NC == 2 ? ICW_FIR_SIG_OCC : ICW_FIR_SIG_OCC1) 
                     in2[r].lim = in2[r].rim = q[hh + r];
                 }
                 int dv[2][2];
-                icw_sig_fast<TRIG, 2, SIG>(a, P, in2, clip_l, clip_r, pk_l, pk_r, dv, tro_lane, (size_t)hh * pq, pq);
+                icw_sig_fast<TRIG, 2, SIG>(a, P, in2, clip_l, clip_r, pk_l, pk_r, dv, tro_lane, (size_t)hh * pq + tab_off, pq);
 #pragma unroll
                 for (int r = 0; r < 2; ++r) {
                     dl[hh + r] = dv[r][0];
@@ -544,9 +620,13 @@ extern "C" hipError_t icw_launch_fir(const IcwFirArgs *a, hipStream_t st)
     constexpr int TF = 256 * ICW_FIR_R;
     const size_t lds = fir_lds(a->M, a->nt, 1, TF, 0);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (fir_lds_attr((const void *)icw_fir_hilbert, lds) != hipSuccess) return hipErrorInvalidValue;
+    /* streams with different inputs (a->desc): the instance that reads each stream's own; a->nch is then
+     * the widest stream's */
+    const void *fn = a->desc ? (const void *)icw_fir_hilbert_mixed : (const void *)icw_fir_hilbert;
+    if (fir_lds_attr(fn, lds) != hipSuccess) return hipErrorInvalidValue;
     dim3 grid((a->T + TF - 1) / TF, a->nch > 1 ? 2 : 1, a->n_streams);
-    hipLaunchKernelGGL(icw_fir_hilbert, grid, dim3(256), lds, st, *a);
+    if (a->desc) hipLaunchKernelGGL(icw_fir_hilbert_mixed, grid, dim3(256), lds, st, *a);
+    else hipLaunchKernelGGL(icw_fir_hilbert, grid, dim3(256), lds, st, *a);
     return hipGetLastError();
 }
 
@@ -558,37 +638,38 @@ extern "C" size_t icw_fir_graph_lds(int M, int nt, int nch, int n_regs)
     return lds <= 96 * 1024 ? lds : 0;
 }
 
-/* in_step: every stream of the launch is in step with the rotation table (a->trig_tab) */
-template <int NC>
+/* in_step: every stream of the launch is in step with the rotation table (a->trig_tab); PS: with its
+ * own slab of it.  The grid's columns are f->n_streams: the call's streams, or (PS) the class's */
+template <int NC, bool PS>
 static hipError_t launch_fir_graph_nc(const IcwFirArgs *f, const IcwK2Args *a, int in_step, size_t lds, hipStream_t st)
 {
     const int TF = 256 * ICW_FIR_R / NC;
     dim3 grid(f->n_streams, (f->T + TF - 1) / TF - f->tile0);  /* stream-fastest (icw_fir_graph); <= 1 024 tiles */
-    const void *fn = !a->trig ? (const void *)icw_fir_graph<false, false, NC>
-                   : in_step ? (const void *)icw_fir_graph<true, true, NC> : (const void *)icw_fir_graph<true, false, NC>;
+    const void *fn = !a->trig ? (const void *)icw_fir_graph<false, false, NC, PS>
+                   : in_step ? (const void *)icw_fir_graph<true, true, NC, PS> : (const void *)icw_fir_graph<true, false, NC, PS>;
     if (fir_lds_attr(fn, lds) != hipSuccess) return hipErrorInvalidValue;
-    if (!a->trig) hipLaunchKernelGGL((icw_fir_graph<false, false, NC>), grid, dim3(256), lds, st, *f, *a);
-    else if (in_step) hipLaunchKernelGGL((icw_fir_graph<true, true, NC>), grid, dim3(256), lds, st, *f, *a);
-    else hipLaunchKernelGGL((icw_fir_graph<true, false, NC>), grid, dim3(256), lds, st, *f, *a);
+    if (!a->trig) hipLaunchKernelGGL((icw_fir_graph<false, false, NC, PS>), grid, dim3(256), lds, st, *f, *a);
+    else if (in_step) hipLaunchKernelGGL((icw_fir_graph<true, true, NC, PS>), grid, dim3(256), lds, st, *f, *a);
+    else hipLaunchKernelGGL((icw_fir_graph<true, false, NC, PS>), grid, dim3(256), lds, st, *f, *a);
     return hipGetLastError();
 }
 
 /* the signature form over tiles [0, ntile) of every stream */
-template <int SIG, int NC, bool B24>
+template <int SIG, int NC, bool B24, bool PS>
 static hipError_t launch_fir_sig_t(const IcwFirArgs *f, const IcwK2Args *a, int ntile, size_t lds, hipStream_t st)
 {
-    const void *fn = (const void *)icw_fir_sig<SIG, NC, B24>;
+    const void *fn = (const void *)icw_fir_sig<SIG, NC, B24, PS>;
     if (fir_lds_attr(fn, lds) != hipSuccess) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((icw_fir_sig<SIG, NC, B24>), dim3(f->n_streams, ntile), dim3(256), lds, st, *f, *a);
+    hipLaunchKernelGGL((icw_fir_sig<SIG, NC, B24, PS>), dim3(f->n_streams, ntile), dim3(256), lds, st, *f, *a);
     return hipGetLastError();
 }
 
-template <int NC, bool B24>
+template <int NC, bool B24, bool PS>
 static hipError_t launch_fir_sig_d(const IcwFirArgs *f, const IcwK2Args *a, int sig, int ntile, size_t lds,
                                    hipStream_t st)
 {
     hipError_t e = hipErrorInvalidValue;             /* a signature without code of its own */
-    icw_sig_dispatch(sig, [&](auto sc) { e = launch_fir_sig_t<decltype(sc)::value, NC, B24>(f, a, ntile, lds, st); });
+    icw_sig_dispatch(sig, [&](auto sc) { e = launch_fir_sig_t<decltype(sc)::value, NC, B24, PS>(f, a, ntile, lds, st); });
     return e;
 }
 
@@ -597,8 +678,9 @@ static bool fir_sig_known(int sig)
     return icw_sig_dispatch(sig, [](auto) {});
 }
 
-extern "C" hipError_t icw_launch_fir_graph(const IcwFirArgs *f, const IcwK2Args *a, int in_step, int sig_on,
-                                           hipStream_t st)
+/* KF2 over the f->n_streams columns of one launch (PS: one class of a call's streams, f->map) */
+template <bool PS>
+static hipError_t launch_fir_graph(const IcwFirArgs *f, const IcwK2Args *a, int in_step, int sig_on, hipStream_t st)
 {
     if (!fir_ok(f->M, f->nt)) return hipErrorInvalidValue;
     /* the render-only form (icw_fast_render) takes the quantiser from sign_delta alone: mid-riser
@@ -623,13 +705,48 @@ extern "C" hipError_t icw_launch_fir_graph(const IcwFirArgs *f, const IcwK2Args 
         if (nsig > 0) {
             const bool b24 = a->rk.is24 != 0;
             const size_t ls = icw_fir_graph_lds(f->M, f->nt, f->nch, 0);   /* no DSP register file */
-            const hipError_t e = nc == 2 ? (b24 ? launch_fir_sig_d<2, true>(f, a, sig, nsig, ls, st)
-                                                : launch_fir_sig_d<2, false>(f, a, sig, nsig, ls, st))
-                                         : (b24 ? launch_fir_sig_d<1, true>(f, a, sig, nsig, ls, st)
-                                                : launch_fir_sig_d<1, false>(f, a, sig, nsig, ls, st));
+            const hipError_t e = nc == 2 ? (b24 ? launch_fir_sig_d<2, true, PS>(f, a, sig, nsig, ls, st)
+                                                : launch_fir_sig_d<2, false, PS>(f, a, sig, nsig, ls, st))
+                                         : (b24 ? launch_fir_sig_d<1, true, PS>(f, a, sig, nsig, ls, st)
+                                                : launch_fir_sig_d<1, false, PS>(f, a, sig, nsig, ls, st));
             if (e != hipSuccess) return e;
             fl.tile0 = nsig;
         }
     }
-    return nc == 2 ? launch_fir_graph_nc<2>(&fl, a, in_step, lds, st) : launch_fir_graph_nc<1>(&fl, a, in_step, lds, st);
+    return nc == 2 ? launch_fir_graph_nc<2, PS>(&fl, a, in_step, lds, st) : launch_fir_graph_nc<1, PS>(&fl, a, in_step, lds, st);
+}
+
+extern "C" hipError_t icw_launch_fir_graph(const IcwFirArgs *f, const IcwK2Args *a, int in_step, int sig_on,
+                                           hipStream_t st)
+{
+    if (f->desc || f->map || a->prog_id) return hipErrorInvalidValue;   /* icw_launch_fir_graph_mix's call */
+    return launch_fir_graph<false>(f, a, in_step, sig_on, st);
+}
+
+/* KF2 over streams with different lists or inputs: the per-stream instances, once per channel class present
+ * (mono streams, stereo streams), each class through its stream map.  A class whose streams all have one
+ * known signature keeps the signature form for its leading tiles -- every stream with its own program's
+ * constants and its own slab's factors; "in step" is each stream with its slab's reference stream.  The
+ * class's trig replaces the call's (a Master-only class beside a Shift class runs the kernels without the
+ * Shift / PM code). */
+extern "C" hipError_t icw_launch_fir_graph_mix(const IcwFirArgs *f, const IcwK2Args *a, const IcwFirClass *cls, int n_cls,
+                                               int sig_on, hipStream_t st)
+{
+    if (!a->prog_id) return hipErrorInvalidValue;
+    for (int k = 0; k < n_cls; ++k) {
+        const IcwFirClass &c = cls[k];
+        if (c.n <= 0) continue;
+        if (!c.map || c.n > a->n_streams) return hipErrorInvalidValue;
+        IcwFirArgs fc = *f;
+        fc.n_streams = c.n;
+        fc.nch = (uint32_t)(c.nch > 1 ? 2 : 1);
+        fc.map = c.map;
+        fc.sig = c.sig;
+        fc.lr_same = c.nch == 1 ? c.lr_same : 0;
+        IcwK2Args ac = *a;
+        ac.trig = c.trig ? 1 : 0;
+        const hipError_t e = launch_fir_graph<true>(&fc, &ac, c.in_step, sig_on, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }

@@ -485,7 +485,8 @@ __device__ __forceinline__ IcwOpK icw_op_k(icw_cop &op)
  * ROWP: the caller knows where the R frames' table rows are -- frame r's row at
  * a.trig_tab + tro_u + r * tro_step + tro_lane, the first two wave-uniform, the last the lane's (KF2's
  * lanes hold consecutive frames of a tile inside the block, icw_fir_graph) -- so a load needs no
- * per-frame index arithmetic and no clamp.
+ * per-frame index arithmetic and no clamp.  Without ROWP tro_u is the stream's slab of the table (KF2's
+ * per-stream form; 0: the one table).
  * Three shortcuts, each exact: a gain of 1.0 is not multiplied (x * 1.0 is x for every value that is
  * not a signalling NaN, and d is a sum or a converted input here, never one); the bus writes of the
  * block's last frame are tested once per call (one lane of the launch holds it); and the clip
@@ -514,7 +515,7 @@ __device__ __forceinline__ void icw_chain_op(const IcwK2Args &a, icw_cop &op, bo
         for (int r = 0; r < R; ++r) {
             /* (cos, sin) of a channel: one 16-byte load (rows and columns are 16-byte aligned) */
             const double *trow = ROWP ? a.trig_tab + tro_u + (size_t)r * tro_step + tro_lane
-                                      : a.trig_tab + icw_trig_index(min(t0 + r, T - 1), a.trig_perm_q) * a.trig_pitch;
+                                      : a.trig_tab + tro_u + icw_trig_index(min(t0 + r, T - 1), a.trig_perm_q) * a.trig_pitch;
             const double2 f0 = act0 ? *(const double2 *)(trow + k.ts0 * 2) : make_double2(0.0, 0.0);
             const double2 f1 = act1 ? *(const double2 *)(trow + k.ts1 * 2) : make_double2(0.0, 0.0);
             cs[r][0] = f0.x; sn[r][0] = f0.y;

@@ -104,10 +104,13 @@ bool poll_done(const uint32_t *flag, uint32_t seq, hipStream_t st)
  * share, at the counter of the first of them; a pair one stream has computes its factors inline
  * (the table would do the same work and add its traffic); a program without Shift / PM reads
  * nothing, so it is marked as using slab 0 against itself and skips the counter arithmetic.  A
- * context with one list is a one-entry program table (c->prog / c->d_prog). */
-int prepare_mix(icw_ctx *c, int first, int count, hipStream_t st)
+ * context with one list is a one-entry program table (c->prog / c->d_prog).
+ * fir: the FIR converter is on.  Its signature form reads every factor from the table, so every pair
+ * with an active Shift / PM channel gets a slab, one stream or many (256 lists of one shape stay one
+ * signature launch); and the call's streams are listed by channel class for KF2's stream maps. */
+int prepare_mix(icw_ctx *c, int first, int count, bool fir, hipStream_t st)
 {
-    if (c->pid_valid && c->pid_first == first && c->pid_count == count) return ICW_OK;
+    if (c->pid_valid && c->pid_first == first && c->pid_count == count && c->pid_fir == fir) return ICW_OK;
     const size_t S = (size_t)count;
     const bool one = c->progs.empty();
     struct Pair {
@@ -141,16 +144,17 @@ int prepare_mix(icw_ctx *c, int first, int count, hipStream_t st)
             M.chain = 0;
             M.n_regs = std::max(M.n_regs, P.n_regs);
         }
-        if (P.needs_omega && P.n_trig > 0 && !P.is_bus && q.uses >= 2) {
+        if (P.needs_omega && P.n_trig > 0 && !P.is_bus && (q.uses >= 2 || fir)) {
             q.slab = n_slabs++;
             M.n_trig = std::max(M.n_trig, P.n_trig);
         }
     }
-    /* [5][count] selection rows, then [3][n_slabs] (n_slabs <= count / 2: kPidWords per stream hold both) */
-    std::vector<int32_t> h(S * 5 + (size_t)n_slabs * 3, 0);
+    /* [5][count] selection rows, the stream map [count], then [3][n_slabs] (n_slabs <= count: kPidWords per
+     * stream hold them all) */
+    std::vector<int32_t> h(S * 6 + (size_t)n_slabs * 3, 0);
     for (const Pair &q : pairs)
         if (q.slab >= 0) {
-            int32_t *sl = h.data() + S * 5;
+            int32_t *sl = h.data() + S * 6;
             sl[q.slab] = q.e;
             sl[n_slabs + q.slab] = q.ref;
             sl[2 * n_slabs + q.slab] = (int32_t)q.rate;
@@ -165,6 +169,34 @@ int prepare_mix(icw_ctx *c, int first, int count, hipStream_t st)
         h[3 * S + (size_t)i] = (int32_t)q.rate;
         h[4 * S + (size_t)i] = (int32_t)c->inputs[(size_t)(first + i)].nch;
     }
+    /* the channel classes: mono streams first in the map, then stereo ones.  A class keeps the signature
+     * form while every stream's program is a chain of one signature; lr_same (IcwFirArgs) must hold for
+     * every mono stream */
+    c->pid_slab.assign(h.begin() + (long)S, h.begin() + 2 * (long)S);
+    c->pid_ref.assign(h.begin() + 2 * (long)S, h.begin() + 3 * (long)S);
+    size_t at = 0;
+    for (int k = 0; k < 2; ++k) {
+        IcwFirClass &fc = c->pid_cls[k];
+        fc = IcwFirClass{};
+        fc.map = c->d_pid + 5 * S + at;
+        fc.nch = k + 1;
+        fc.lr_same = k == 0;
+        for (int i = 0; i < count; ++i) {
+            if ((c->inputs[(size_t)(first + i)].nch > 1) != (k == 1)) continue;
+            const IcwProg &P = one ? c->prog : c->progs[(size_t)pairs[pair_of[(size_t)i]].e];
+            const int32_t sig = P.chain ? P.sig : 0;
+            if (fc.n == 0) fc.sig = sig;
+            else if (fc.sig != sig) fc.sig = 0;
+            fc.trig |= P.needs_omega ? 1 : 0;
+            const IcwOp &m = P.ops[0];
+            if (!(P.chain && (P.sig & ~ICW_SIG_UNIT) == ICW_SIG_M && !memcmp(&m.gain[0], &m.gain[1], sizeof(double)) &&
+                  m.unit_gain[0] == m.unit_gain[1]))
+                fc.lr_same = 0;
+            h[5 * S + at++] = i;
+            ++fc.n;
+        }
+    }
+    c->pid_map.assign(h.begin() + 5 * (long)S, h.begin() + 6 * (long)S);
     /* ordered after the earlier calls on st, which may still read the rows; waited for, since h goes */
     if (hipMemcpyAsync(c->d_pid, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
@@ -173,6 +205,7 @@ int prepare_mix(icw_ctx *c, int first, int count, hipStream_t st)
     c->pid_first = first;
     c->pid_count = count;
     c->pid_slabs = n_slabs;
+    c->pid_fir = fir;
     return ICW_OK;
 }
 
@@ -208,6 +241,7 @@ struct CallPlan {
     const IcwProg *lp = nullptr, *dP = nullptr;
     bool mix = false;
     int n_slabs = 1;
+    IcwFirClass fir_cls[2] = {};   /* mix with the FIR converter fused: the call's channel classes (prepare_mix) */
     size_t slab_stride = 0;
     /* the mode flags */
     bool cw = false, fir = false, fir_fused = false, fir_async = false, bus = false, fcm = false, dedup = false;
@@ -423,7 +457,7 @@ struct CallPlan {
         at.sample_rate = rate;
         at.tab = c->trig;
         if (mix) {
-            at.slabs = c->d_pid + 5 * (size_t)count;
+            at.slabs = c->d_pid + 6 * (size_t)count;
             at.n_slabs = n_slabs;
             at.slab_stride = slab_stride;
         }
@@ -448,7 +482,11 @@ struct CallPlan {
         af.xd = c->xd[b % n_sets];
         af.x_pitch = x_pitch;
         af.sig = lp->chain ? lp->sig : 0;
-        {
+        af.desc = fir && mixin ? dD : nullptr;      /* streams with different inputs: the kernels read each one's own */
+        if (mix) {
+            /* per-stream lists: signature and lr_same are per channel class (fir_cls) */
+            af.sig = 0;
+        } else {
             /* mono input through a Master-only chain (signature count 1, mode MASTER, chain_in `in`:
              * ICW_SIG_M) whose gains are bit-identical: L and R are one computation */
             const IcwOp &m = lp->ops[0];
@@ -682,7 +720,7 @@ int CallPlan::resolve_plan()
         }
     }
     if (mix) {
-        const int rc = prepare_mix(c, first, count, st);
+        const int rc = prepare_mix(c, first, count, fir, st);
         if (rc != ICW_OK) return rc;
         lp = &c->mix;
     }
@@ -700,8 +738,16 @@ int CallPlan::resolve_plan()
      * else KF on its own stream (the caller's: K1's, idle without the IIR) beside K2.  KF2 needs no
      * block scratch and has no recurrence to pipeline against, so its blocks are as long as the
      * scratch bound allows (fewer launches, fewer partly filled waves of workgroups at their ends) */
-    fir_fused = fir && c->tn.fir_fuse &&
-                   icw_fir_graph_lds(c->fir_M, c->fir_nt, (int)nch, LP.chain ? 0 : LP.n_regs) > 0 && !LP.is_bus;
+    /* (per-stream lists: LP is the mixed program, its n_regs the largest of the call's streams; every
+     * channel class present must fit) */
+    const int fir_regs = LP.chain ? 0 : LP.n_regs;
+    bool fir_fits = icw_fir_graph_lds(c->fir_M, c->fir_nt, (int)nch, fir_regs) > 0;
+    if (fir && mix)
+        for (int k = 0; k < 2; ++k) {
+            fir_cls[k] = c->pid_cls[k];
+            if (fir_cls[k].n > 0 && !icw_fir_graph_lds(c->fir_M, c->fir_nt, k + 1, fir_regs)) fir_fits = false;
+        }
+    fir_fused = fir && c->tn.fir_fuse && fir_fits && !LP.is_bus;
     /* The row kernel without a serial render (C2) has K2 at ~0.16 of K1r's time per frame: 65 536-frame
      * blocks (a quarter of the launches, of their gaps and prologues) ending in a steep tail
      * (65 536 -> 16 384 -> 4 096 -> 1 024: the drain stays one short K2) measured +0.8 % on C2
@@ -715,6 +761,12 @@ int CallPlan::resolve_plan()
     const bool fir_long = fir_fused && dev && !c->serial_render && !bus && !dith_par;
     Tb = std::min(n_frames, ((fir_fused || row_long) && !c->tn.block_env)
                                    ? (fir_long ? kMaxFirBlockFrames : kMaxBlockFrames) : c->tn.max_block);
+    /* per-stream lists through the long FIR blocks: a slab per (list, rate) pair, so the blocks shorten
+     * until the call's table fits kMaxMixTabDoubles */
+    if (mix && fir_long && !c->tn.block_env && n_slabs > 0 && LP.n_trig > 0) {
+        const size_t cap = kMaxMixTabDoubles / ((size_t)n_slabs * 2 * (size_t)LP.n_trig);
+        Tb = std::min(Tb, std::max(kMaxBlockFrames, (int)std::min<size_t>(cap, (size_t)kMaxFirBlockFrames) & ~1023));
+    }
     const double taper = c->tn.taper >= 0.0 ? c->tn.taper
                        : (!cw && k1_mode == 3) ? (c->serial_render ? kAutoTaper : (row_long ? kRowTaper : 0.0)) : 0.0;
     /* the fused FIR converter with a serial render (c5fir): the render of block 0 waits for its
@@ -853,6 +905,20 @@ int CallPlan::size_scratch()
     table = LP.needs_omega && !bus && LP.n_trig > 0 && count > 1;
     in_step = table;
     for (int i = 1; in_step && i < count; ++i) in_step = c->nf_host[first + i] == c->nf_host[first];
+    /* per-stream lists through KF2: a class is in step when each of its streams is in step with its
+     * slab's reference stream (a stream without Shift / PM is its own reference) */
+    if (mix && fir_fused) {
+        size_t at = 0;
+        for (IcwFirClass &fc : fir_cls) {
+            bool ok = table && fc.trig;
+            for (int j = 0; j < fc.n; ++j) {
+                const size_t i = (size_t)c->pid_map[at + (size_t)j];
+                ok = ok && c->pid_slab[i] >= 0 && c->nf_host[f0 + i] == c->nf_host[f0 + (size_t)c->pid_ref[i]];
+            }
+            fc.in_step = ok ? 1 : 0;
+            at += (size_t)fc.n;
+        }
+    }
     /* per-stream lists: one slab per program that has one (prepare_mix), all of the widest one's pitch */
     slab_stride = (size_t)((Tb + 7) & ~7) * 2 * (size_t)LP.n_trig;
     if (table && grow((void **)&c->trig, &c->trig_bytes, (size_t)n_slabs * slab_stride * sizeof(double)))
@@ -1101,7 +1167,9 @@ int CallPlan::run_blocks() const
             const auto af = fir_args(b);
             if (io_in(b, s2) != ICW_OK) return ICW_EDEVICE;
             if (timing && hipEventRecord(c->ev[4 * b], s2) != hipSuccess) return ICW_EDEVICE;
-            if (icw_launch_fir_graph(&af, &a2, in_step, c->tn.fir_sig, s2) != hipSuccess) return ICW_EDEVICE;
+            if ((mix ? icw_launch_fir_graph_mix(&af, &a2, fir_cls, 2, c->tn.fir_sig, s2)
+                     : icw_launch_fir_graph(&af, &a2, in_step, c->tn.fir_sig, s2)) != hipSuccess)
+                return ICW_EDEVICE;
             if (timing && hipEventRecord(c->ev[4 * b + 1], s2) != hipSuccess) return ICW_EDEVICE;
         } else {
             if (fir_async && hipStreamWaitEvent(s2, c->k0done[p], 0) != hipSuccess) return ICW_EDEVICE;

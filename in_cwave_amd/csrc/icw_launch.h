@@ -28,6 +28,10 @@ hipError_t icw_launch_stream1(const IcwS1Args *a, int nord, hipStream_t st);
 /* icw_fir.hip */
 hipError_t icw_launch_fir(const IcwFirArgs *a, hipStream_t st);
 hipError_t icw_launch_fir_graph(const IcwFirArgs *f, const IcwK2Args *a, int in_step, int sig_on, hipStream_t st);
+/* the same over streams with different lists or inputs (a->prog_id set): one launch per class present,
+ * the signature form included */
+hipError_t icw_launch_fir_graph_mix(const IcwFirArgs *f, const IcwK2Args *a, const IcwFirClass *cls, int n_cls, int sig_on,
+                                    hipStream_t st);
 size_t icw_fir_graph_lds(int M, int nt, int nch, int n_regs);
 
 /* icw_render.hip */

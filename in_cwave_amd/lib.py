@@ -162,6 +162,10 @@ class Context:
         beta k_beta, cwave.h:56-58) instead of the quadrature IIR; order 0 restores the IIR"""
         _check(self._lib.icw_set_fir_hilbert(self.h, order, beta), "icw_set_fir_hilbert")
 
+    def enable_stream_fir(self, on=True):
+        """icw_enable_stream_fir: per-stream lists and inputs beside the FIR converter (off on a fresh context)"""
+        _check(self._lib.icw_enable_stream_fir(self.h, int(bool(on))), "icw_enable_stream_fir")
+
     def _own_cfg(self):
         """the live setters record the context's parameters in a copy, never in the caller's Config"""
         self.cfg = abi.Config.from_buffer_copy(self.cfg)
@@ -537,6 +541,27 @@ def transcode_files_lists(cfg, node_lists, in_paths, out_paths, bypass_lists=Non
     st = abi.BatchStats()
     status = (C.c_int * max(1, n))()
     rc = load().icw_transcode_files_lists(C.byref(cfg), ptrs, cnt, byp, ins, outs, n, C.byref(o), C.byref(st), status)
+    return rc, st, [status[i] for i in range(n)]
+
+
+def transcode_files_fir(cfg, node_lists, in_paths, out_paths, k_M, k_beta=8.0, bypass_lists=None, fade_in_ms=0,
+                        fade_out_ms=0, sec_align=0, block_frames=0, device=-1, merge_inputs=False):
+    """icw_transcode_files_fir: transcode_files_lists with the FIR Hilbert converter (k_M, k_beta) on every
+    context of real-input files; returns (rc, stats, per-file status)"""
+    n = len(in_paths)
+    assert len(node_lists) == n and len(out_paths) == n and (bypass_lists is None or len(bypass_lists) == n)
+    ins = (C.c_char_p * max(1, n))(*[str(p).encode() for p in in_paths])
+    outs = (C.c_char_p * max(1, n))(*[str(p).encode() for p in out_paths])
+    arrs = [graph_nodes(nl) for nl in node_lists]
+    ptrs = (C.POINTER(abi.Node) * max(1, n))(*[C.cast(a, C.POINTER(abi.Node)) for a in arrs])
+    cnt = (C.c_int * max(1, n))(*[len(nl) for nl in node_lists])
+    byp = (C.c_int * max(1, n))(*[int(b) for b in bypass_lists]) if bypass_lists is not None else None
+    o = abi.BatchOpts(fade_in_ms, fade_out_ms, sec_align, block_frames, device,
+                      abi.BATCH_MERGE_INPUTS if merge_inputs else 0)
+    st = abi.BatchStats()
+    status = (C.c_int * max(1, n))()
+    rc = load().icw_transcode_files_fir(C.byref(cfg), ptrs, cnt, byp, ins, outs, n, int(k_M), float(k_beta), C.byref(o),
+                                        C.byref(st), status)
     return rc, st, [status[i] for i in range(n)]
 
 

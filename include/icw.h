@@ -202,15 +202,19 @@ int icw_set_input(icw_ctx *ctx, uint32_t sample_rate, uint32_t fmt, uint32_t cha
  * one-input context; only a call over differing inputs takes the table-reading kernel instances.
  * icw_stream_open takes its fades at stream s's own rate.  The five real formats, 1 or >= 2 channels,
  * any rate up to ICW_MAX_FS_SRC; host and device pointers; icw_process_batch and icw_process_streams;
- * register-form and bus-form lists, per-stream lists in the same context, every render, FP_CHECK.
+ * register-form and bus-form lists, per-stream lists in the same context, every render, FP_CHECK, and
+ * the FIR converter (icw_set_fir_hilbert, context-wide, in either order with this call) on a context
+ * that asked for it with icw_enable_stream_fir: its kernels read every stream's own real format, rate
+ * and channels.
  * Limits, each refusal changing nothing:
  *   ICW_EINVAL        a range outside the context, rate 0 or above ICW_MAX_FS_SRC, channels 0, fmt
  *                     out of range.
  *   ICW_EUNSUPPORTED  - a CWAVE format (fmt >= ICW_FMT_CW_F64), or a context whose input is CWAVE:
  *                       whether the quadrature IIR runs at all is decided per call;
- *                     - the FIR converter is on (icw_set_fir_hilbert with k_M > 0);
- *                     - while the count is above 1: icw_set_fir_hilbert(k_M > 0), icw_encode_cwave and
- *                       icw_encode_cwave_iir, and ICW_F_DEBUG_INPUT.
+ *                     - without icw_enable_stream_fir: the FIR converter is on (icw_set_fir_hilbert with
+ *                       k_M > 0), or, while the count is above 1, icw_set_fir_hilbert(k_M > 0);
+ *                     - while the count is above 1: icw_encode_cwave and icw_encode_cwave_iir, and
+ *                       ICW_F_DEBUG_INPUT.
  * Not served: icw_group and the icw_amod_* drop-in (their input stays context-wide).  The state blob
  * does not carry the input, as it does not carry the list: icw_set_state expects the stream's input to
  * be set as it was. */
@@ -299,13 +303,17 @@ int icw_set_render(icw_ctx *ctx, const icw_render_cfg *render);
  *   ICW_EUNSUPPORTED  - the new list, or the list in force, compiles to the bus form (a one-frame
  *                       delay, feedback, more than 16 nodes): the serial graph kernel runs one lane
  *                       per stream on one program.  Such lists stay context-wide (icw_set_graph);
- *                     - the FIR converter is on (icw_set_fir_hilbert with k_M > 0);
- *                     - while the count is above 1: icw_set_fir_hilbert(k_M > 0), icw_set_graph with
+ *                     - without icw_enable_stream_fir: the FIR converter is on (icw_set_fir_hilbert with
+ *                       k_M > 0), or, while the count is above 1, icw_set_fir_hilbert(k_M > 0);
+ *                     - while the count is above 1: icw_set_graph with
  *                       a bus-form list (collapse with a register-form icw_set_graph first), and the
  *                       list primitives icw_graph_del_last / _del_all / _add_last / _set_output_plug
  *                       ("the context's list" is undefined then: edit such streams with
  *                       icw_set_stream_graph and icw_clear_stream_bus_slot).
- * FP_CHECK contexts and CWAVE input are served.  Not served: icw_group (its lists stay
+ * FP_CHECK contexts, CWAVE input and -- on a context that asked for it with icw_enable_stream_fir -- the
+ * FIR converter (icw_set_fir_hilbert, on or off, in either order with this call) are served: with the
+ * converter on, streams that share a chain signature -- 256
+ * Shift frequencies of one list shape -- stay on its signature kernel in one launch.  Not served: icw_group (its lists stay
  * context-wide), the icw_amod_* drop-in and the encoders (they run no list).  The state blob does not
  * carry a list: icw_set_state expects the stream's list to be set as it was. */
 int icw_set_stream_graph(icw_ctx *ctx, int first, int count, const icw_node *nodes, int n_nodes,
@@ -339,9 +347,20 @@ int icw_set_hilbert_config(icw_ctx *ctx, int kahan, int subnorm_reject);
  * for complex samples).  k_M = 0 restores the reference's own quadrature IIR Hilbert (the default).
  * k_M even, 2..ICW_FIR_MAX_ORDER.  Every stream's FIR history (its last k_M inputs) starts at zero;
  * icw_stream_init / icw_stream_reset_hilbert / icw_stream_open(clr_hilb) clear it too.
+ * The converter is context-wide -- one k_M, one k_beta.
+ *   icw_enable_stream_fir(ctx, 1)  serves per-stream lists (icw_set_stream_graph) and per-stream inputs
+ *                                  (icw_set_stream_input) beside the converter from then on: the three
+ *                                  setters work in any order, the converter on or off at any count, and
+ *                                  the converter's kernels take each stream's own list, rate and format.
+ *                                  A fresh context has it off and keeps the refusals listed at the two
+ *                                  setters, so a host that relies on them sees no change.  (ctx, 0) turns
+ *                                  it off again; ICW_EUNSUPPORTED, changing nothing, while the converter
+ *                                  is on and either count is above 1.  icw_transcode_files_fir sets it
+ *                                  on its own contexts.
  * No reference implementation exists for this stage: its parity is unpinned. */
 #define ICW_FIR_MAX_ORDER 4096
 int icw_set_fir_hilbert(icw_ctx *ctx, int32_t k_M, double k_beta);
+int icw_enable_stream_fir(icw_ctx *ctx, int on);
 /* The taps of that design: g[k] = g_{2k+1}, k < nt = (k_M/2 + 1)/2.  Returns nt (or ICW_EINVAL). */
 int icw_fir_taps(int32_t k_M, double k_beta, double *g, int n);
 

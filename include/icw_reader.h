@@ -89,6 +89,18 @@ int icw_transcode_files_lists(const icw_config *cfg, const icw_node *const *node
                               const int *bypass_list, const char *const *in_paths, const char *const *out_paths, int n,
                               const icw_batch_opts *opts, icw_batch_stats *stats, int *status);
 
+/* icw_transcode_files_lists through the FIR Hilbert converter: icw_set_fir_hilbert(k_M, k_beta) is applied
+ * to every context of real-input (WAV / RWAVE) files before the first block; CWAVE files are analytic
+ * already and run as in icw_transcode_files_lists.  ICW_BATCH_MERGE_INPUTS is honoured: a library of mixed
+ * formats with per-file lists goes through the converter in one context per device (per-stream inputs
+ * and lists beside the converter, include/icw.h).  k_M and k_beta as icw_set_fir_hilbert takes them with
+ * the converter on: k_M even, 2..ICW_FIR_MAX_ORDER (0 is refused: that call is icw_transcode_files_lists),
+ * 0 <= k_beta < 1e3; anything else returns ICW_EINVAL before a file is opened -- nothing runs, nothing is
+ * written, stats and status are left alone. */
+int icw_transcode_files_fir(const icw_config *cfg, const icw_node *const *nodes, const int *n_nodes,
+                            const int *bypass_list, const char *const *in_paths, const char *const *out_paths, int n,
+                            int32_t k_M, double k_beta, const icw_batch_opts *opts, icw_batch_stats *stats, int *status);
+
 /* ---- convert: WAV files -> CWAVE files (the external converter cwave.h:56-58 names) ---- */
 typedef struct icw_cwave_enc_opts {
     int32_t  k_M;                       /* FIR Hilbert order: even, 2 .. ICW_FIR_MAX_ORDER */
