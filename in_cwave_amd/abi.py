@@ -117,6 +117,10 @@ FIR_MAX_ORDER = 4096     # ICW_FIR_MAX_ORDER: largest k_M of icw_set_fir_hilbert
 BATCH_MERGE_INPUTS = 1   # ICW_BATCH_MERGE_INPUTS: all real-input files in one context per device
 
 
+# icw_cwave_enc_opts.reserved_ / icw_cwave_enc_iir_opts.reserved_: the same for the file encoders
+ENC_MERGE_INPUTS = 1     # ICW_ENC_MERGE_INPUTS: every accepted file in one context
+
+
 class BatchOpts(C.Structure):
     _fields_ = [("fade_in_ms", C.c_uint32), ("fade_out_ms", C.c_uint32), ("sec_align", C.c_uint32),
                 ("block_frames", C.c_int32), ("device", C.c_int32), ("reserved_", C.c_int32)]
@@ -169,6 +173,7 @@ SIGNATURES = {
     "icw_stream_input_count": (_i, [_vp]),
     "icw_set_fir_hilbert": (_i, [_vp, C.c_int32, C.c_double]),
     "icw_enable_stream_fir": (_i, [_vp, _i]),
+    "icw_enable_stream_encode": (_i, [_vp, _i]),
     "icw_set_graph": (_i, [_vp, C.POINTER(Node), _i, _i, C.POINTER(_i)]),
     "icw_set_stream_graph": (_i, [_vp, _i, _i, C.POINTER(Node), _i, _i, C.POINTER(_i)]),
     "icw_clear_stream_bus_slot": (_i, [_vp, _i, _i, _i]),

@@ -244,6 +244,7 @@ struct GroupPipe {
     const int S, B;
     const size_t fsz, osz;                /* bytes per input frame (the group's widest: the rows' pitch) / output frame */
     const size_t in_b, out_b;
+    std::vector<size_t> ofs;              /* merged encode: every stream's own output frame (<= osz, the rows' pitch); empty: osz */
     unsigned char *hin[2] = {nullptr, nullptr}, *hout[2] = {nullptr, nullptr}, *din[2] = {nullptr, nullptr},
                   *dout[2] = {nullptr, nullptr};
     hipStream_t cs = nullptr, ks = nullptr;
@@ -314,7 +315,8 @@ struct GroupPipe {
             Job &j = *jobs[s];
             const int64_t n = std::min<int64_t>(B, j.total - j.written);
             if (n <= 0 || status[j.idx] != ICW_OK) continue;
-            if (fwrite(buf + (size_t)s * B * osz, osz, (size_t)n, j.out) != (size_t)n) status[j.idx] = ICW_EINVAL;
+            if (fwrite(buf + (size_t)s * B * osz, ofs.empty() ? osz : ofs[(size_t)s], (size_t)n, j.out) != (size_t)n)
+                status[j.idx] = ICW_EINVAL;
             j.written += n;
             st.frames_out += (uint64_t)n;
         }
@@ -447,7 +449,15 @@ struct EncSpec {
     uint32_t hilbert_type = 1;
     int32_t iir_kahan = 1, iir_subnorm_reject = 1;
     uint64_t max_bytes = 0;
+    bool merge = false;                /* ICW_ENC_MERGE_INPUTS: one context, every stream its file's input */
 };
+
+/* bytes of block k (B frames per block) that belong to a file of `total` frames of FB bytes: its part of the
+ * file's CRC and of what is written */
+uint64_t enc_block_bytes(int64_t total, int64_t k, int64_t B, size_t FB)
+{
+    return (uint64_t)std::max<int64_t>(0, std::min<int64_t>(B, total - k * B)) * FB;
+}
 
 /* HCWAVE_V2 (cwave.h:48-60), little-endian */
 void cwave_header(unsigned char *h, const EncSpec &o, uint32_t channels, uint32_t frames, uint32_t rate, uint32_t crc)
@@ -468,7 +478,9 @@ void cwave_header(unsigned char *h, const EncSpec &o, uint32_t channels, uint32_
     p32(h + 44, (uint32_t)(b >> 32));
 }
 
-/* One group of WAV files sharing (rate, format, channels) through the CWAVE encoder: one context, one
+/* One group of WAV files sharing (rate, format, channels) -- or (o.merge) every accepted file, each stream
+ * given its own file's input; the rows are then as wide as the widest input and output frame, and headers,
+ * CRC lengths and writes use each file's own -- through the CWAVE encoder: one context, one
  * fresh stream per file, no fades, no tail.  The CRC of every file's data is chained block by block
  * over the packed frames while they are in HBM (icw_crc32_batch, device pointers). */
 int run_enc_group(std::vector<Job *> &jobs, const EncSpec &o, icw_batch_stats &st, uint64_t *clipped, int *status)
@@ -493,10 +505,21 @@ int run_enc_group(std::vector<Job *> &jobs, const EncSpec &o, icw_batch_stats &s
     int rc = icw_create(&cfg, nullptr, 0, S, o.device, &ctx, nullptr);
     if (rc != ICW_OK) return rc;
     std::unique_ptr<icw_ctx, int (*)(icw_ctx *)> guard(ctx, icw_destroy);
+    if (o.merge && ((rc = icw_enable_stream_encode(ctx, 1)) != ICW_OK || (!o.iir && (rc = icw_enable_stream_fir(ctx, 1)) != ICW_OK)))
+        return rc;
     if (!o.iir && (rc = icw_set_fir_hilbert(ctx, o.k_M, o.k_beta)) != ICW_OK) return rc;
     const auto encode = o.iir ? icw_encode_cwave_iir : icw_encode_cwave;
-    const size_t fsz = wi.frame_bytes;
-    const size_t FB = (size_t)icw_cwave_frame_bytes(o.cw_format, wi.channels);
+    size_t fsz = 0, FB = 0;
+    std::vector<size_t> FBs((size_t)S);
+    for (int s = 0; s < S; ++s) {
+        const icw_wav_info &ji = jobs[s]->info;
+        FBs[(size_t)s] = (size_t)icw_cwave_frame_bytes(o.cw_format, ji.channels);
+        fsz = std::max<size_t>(fsz, ji.frame_bytes);
+        FB = std::max(FB, FBs[(size_t)s]);
+        if ((ji.sample_rate != wi.sample_rate || ji.fmt != wi.fmt || ji.channels != wi.channels) &&
+            (rc = icw_set_stream_input(ctx, s, 1, ji.sample_rate, ji.fmt, ji.channels)) != ICW_OK)
+            return rc;
+    }
     const int skip = o.align ? o.k_M / 2 : 0;            /* aligned: the first k_M/2 output frames are dropped */
     const int B = std::max(o.block_frames > 0 ? o.block_frames : 65536, std::max(skip, 64));
     int64_t T = 0;
@@ -506,11 +529,12 @@ int run_enc_group(std::vector<Job *> &jobs, const EncSpec &o, icw_batch_stats &s
         T = std::max(T, j.total);
         if ((rc = icw_stream_open(ctx, s, j.info.n_samples + skip, 0, 0, 0, 0, 0)) != ICW_OK) return rc;
         unsigned char hdr[ICW_CWAVE_HEADER_BYTES];
-        cwave_header(hdr, o, wi.channels, (uint32_t)j.total, wi.sample_rate, 0);
+        cwave_header(hdr, o, j.info.channels, (uint32_t)j.total, j.info.sample_rate, 0);
         if (fwrite(hdr, 1, sizeof(hdr), j.out) != sizeof(hdr)) status[j.idx] = ICW_EINVAL;
         if (fseeko(j.in, j.info.data_offset, SEEK_SET)) status[j.idx] = ICW_EINVAL;
     }
     GroupPipe pp(jobs, B, fsz, FB, st, status);
+    if (o.merge) pp.ofs = FBs;
     if (!pp.alloc()) return ICW_ENOMEM;
     /* aligned mode: the k_M/2 frames that are dropped go through first, on their own (so that neither the
      * CRC nor the clip counts see them) */
@@ -533,7 +557,7 @@ int run_enc_group(std::vector<Job *> &jobs, const EncSpec &o, icw_batch_stats &s
                 [&](int k, int p) {
                     for (int s = 0; s < S; ++s) {
                         off[s] = (uint64_t)s * B * FB;
-                        len[s] = (uint64_t)std::max<int64_t>(0, std::min<int64_t>(B, jobs[s]->total - (int64_t)k * B)) * FB;
+                        len[s] = enc_block_bytes(jobs[s]->total, k, B, FBs[(size_t)s]);
                     }
                     return icw_crc32_batch(pp.dout[p], off.data(), len.data(), S, crc.data(), crc.data(), ICW_F_DEVICE_PTRS,
                                            o.device, pp.ks);
@@ -545,7 +569,7 @@ int run_enc_group(std::vector<Job *> &jobs, const EncSpec &o, icw_batch_stats &s
         rc = icw_encode_clipped(ctx, s, 0, &nclip);
         if (clipped) clipped[j.idx] = nclip;
         unsigned char hdr[ICW_CWAVE_HEADER_BYTES];
-        cwave_header(hdr, o, wi.channels, (uint32_t)j.total, wi.sample_rate, crc[s]);
+        cwave_header(hdr, o, j.info.channels, (uint32_t)j.total, j.info.sample_rate, crc[s]);
         if (status[j.idx] == ICW_OK && (fseeko(j.out, 0, SEEK_SET) || fwrite(hdr, 1, sizeof(hdr), j.out) != sizeof(hdr)))
             status[j.idx] = ICW_EINVAL;
     }
@@ -567,7 +591,8 @@ int encode_files(const char *const *in_paths, const char *const *out_paths, int 
             return (int)ICW_OK;
         },
         [](int) { return 0; },
-        [&](int, std::vector<Job *> &g, icw_batch_stats &st, int *sts) { return run_enc_group(g, o, st, clipped, sts); });
+        [&](int, std::vector<Job *> &g, icw_batch_stats &st, int *sts) { return run_enc_group(g, o, st, clipped, sts); },
+        o.merge);
 }
 
 /* One group of WAV files sharing (format, channels) through the direct-FFT encoder: whole tracks, no blocks.
@@ -690,6 +715,7 @@ int icw_cwave_encode_files(const char *const *in_paths, const char *const *out_p
     e.cw_format = o.cw_format;
     e.block_frames = o.block_frames;
     e.device = o.device;
+    e.merge = (o.reserved_ & ICW_ENC_MERGE_INPUTS) != 0;
     return encode_files(in_paths, out_paths, n, e, stats, clipped, status);
 }
 
@@ -709,6 +735,7 @@ int icw_cwave_encode_files_iir(const char *const *in_paths, const char *const *o
     e.cw_format = o.cw_format;
     e.block_frames = o.block_frames;
     e.device = o.device;
+    e.merge = (o.reserved_ & ICW_ENC_MERGE_INPUTS) != 0;
     return encode_files(in_paths, out_paths, n, e, stats, clipped, status);
 }
 

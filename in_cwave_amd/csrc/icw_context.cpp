@@ -687,6 +687,17 @@ int icw_enable_stream_fir(icw_ctx *c, int on)
     return ICW_OK;
 }
 
+/* per-stream inputs through the CWAVE encoders, on or off (include/icw.h).  Off again is the fresh
+ * context's state whatever the inputs are -- the encoders then refuse while they differ -- so there is
+ * nothing it could leave half built */
+int icw_enable_stream_encode(icw_ctx *c, int on)
+{
+    if (!c) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->enc_streams = on != 0;
+    return ICW_OK;
+}
+
 int icw_stream_reset_framecnt(icw_ctx *c, int s)
 {
     if (!c || s < 0 || s >= c->n_streams) return ICW_EINVAL;

@@ -120,6 +120,16 @@ struct IcwPackArgs {
     unsigned long long *clipped;   /* [n_streams] saturated / NaN int16 samples, accumulated */
 };
 
+/* KIP over streams with different inputs (icw_iq_pack_mixed): workgroup column y packs desc[y].nch
+ * channels, and p.out is the call's first frame -- the block offset t0 is applied with the stream's own
+ * frame size, as icw_unpack_frames_mixed applies it to the input.  KFE's per-stream form takes IcwEncArgs
+ * as it is (f.desc set, f.t0 the offset, out the call's first frame). */
+struct IcwPackMixArgs {
+    IcwPackArgs p;
+    const IcwInDesc *desc;         /* [n_streams] of the launch */
+    long long t0;                  /* block offset into the call */
+};
+
 /* The direct-FFT encoder (icw_fft.hip, KX): one track of a call */
 struct IcwFftTrack {
     uint64_t in_off, out_off;      /* byte offsets of the track's PCM in `in` and of its frames in `out` */

@@ -85,74 +85,35 @@ __device__ __forceinline__ void icw_tile_out(unsigned char *dst, int nbytes, con
     }
 }
 
+/* KFE's workgroup (icw_fir_encode_body.inc) for the per-stream kernel: the same text as the one-input
+ * kernel's body, with the tile placed by the block offset */
+template <int CWF, int NC>
+__device__ __forceinline__ void icw_fir_encode_ps(const IcwEncArgs &e)
+{
+    constexpr bool PS = true;
+#include "icw_fir_encode_body.inc"
+}
+
 template <int CWF, int NC>
 __global__ __launch_bounds__(256) void icw_fir_encode(IcwEncArgs e)
 {
-    extern __shared__ __attribute__((aligned(16))) double xs[];   /* staged inputs (padded); then the frames */
-    __shared__ unsigned nclip;
-    const IcwFirArgs &a = e.f;
-    constexpr int TF = 256 * ICW_FIR_R;
-    constexpr int CB = icw_cw_bytes<CWF>::value, FB = NC * CB;    /* bytes per channel, per frame */
-    constexpr int NW = ICW_FIR_R * FB / 4;                        /* dwords a lane packs */
-    constexpr int CU = FB / 2, PADU = (CU & 1) ? 0 : 1;           /* its 16-byte units, pad units */
-    const int s = blockIdx.y, tid = threadIdx.x;
-    const int tt = blockIdx.x * TF;
-    const int M = a.M, c = M >> 1;
-    const int sh = icw_fir_sh(c), av = icw_fir_av(c, sh);   /* c - 1 + sh = 8 av */
-    const int nf = min(TF, a.T - tt);
-    const int px = icw_fir_px(sh, M, TF);
-    if (tid == 0) nclip = 0u;
-    icw_fir_stage<NC>(a, s, 0, xs, px, tt, TF, sh, tid, 256);
-    icw_ctap *gs = (icw_ctap *)a.g;
-    __syncthreads();
-    uint32_t w[NW];
-    unsigned clip = 0u;
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {
-        double q[ICW_FIR_R], vi[ICW_FIR_R];
-        icw_fir_sums(xs + k * px, gs, a.nt, tid, av, sh, c, q);
-#pragma unroll
-        for (int r = 0; r < ICW_FIR_R; ++r) vi[r] = xs[k * px + icw_fir_phys(ICW_FIR_R * tid + r + 8 * av + 1)];
-#pragma unroll
-        for (int r = 0; r < ICW_FIR_R; ++r) {
-            const int o = r * FB + k * CB;               /* byte offset in the lane's run: even, a constant */
-            const bool live = ICW_FIR_R * tid + r < nf;
-            if constexpr (CWF == 0) {
-                const unsigned long long bi = (unsigned long long)__double_as_longlong(vi[r]);
-                const unsigned long long bq = (unsigned long long)__double_as_longlong(q[r]);
-                w[o / 4] = (uint32_t)bi;
-                w[o / 4 + 1] = (uint32_t)(bi >> 32);
-                w[o / 4 + 2] = (uint32_t)bq;
-                w[o / 4 + 3] = (uint32_t)(bq >> 32);
-            } else if constexpr (CWF == 1) {
-                w[o / 4] = icw_enc_i16(vi[r], live, clip) | (icw_enc_i16(q[r], live, clip) << 16);
-            } else if constexpr (CWF == 2) {
-                const uint32_t re = icw_enc_i16(vi[r], live, clip), im = __float_as_uint((float)q[r]);
-                if (o & 2) {                             /* the frame starts in a dword's upper half */
-                    w[o / 4] |= re << 16;
-                    w[o / 4 + 1] = im;
-                } else {
-                    w[o / 4] = re | (im << 16);
-                    w[o / 4 + 1] = im >> 16;
-                }
-            } else {
-                w[o / 4] = __float_as_uint((float)vi[r]);
-                w[o / 4 + 1] = __float_as_uint((float)q[r]);
-            }
-        }
-    }
-    __syncthreads();                                     /* every lane has read its inputs */
-    uint4 *ob = (uint4 *)xs;
-#pragma unroll
-    for (int i = 0; i < CU; ++i) ob[tid * (CU + PADU) + i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
-    if (CWF == 1 || CWF == 2) {
-        if (clip) atomicAdd(&nclip, clip);
-    }
-    __syncthreads();
-    if ((CWF == 1 || CWF == 2) && tid == 0 && nclip) atomicAdd(e.clipped + s, (unsigned long long)nclip);
-    unsigned char *dst = e.out + (size_t)s * e.out_stride + (size_t)tt * FB;
-    const int nbytes = nf * FB;
-    icw_tile_out<PADU, CU>(dst, nbytes, xs, tid);
+    constexpr bool PS = false;
+#include "icw_fir_encode_body.inc"
+}
+
+/* KFE over streams with different inputs (e.f.desc; the PS pattern of icw_fir.hip): the workgroup column is
+ * one stream, whose format, sizes and channels come in by scalar loads through the constant address space
+ * (icw_fir_own_input) and replace the launch's; the branch on its channels is wave-uniform, and either side
+ * is the one-input kernel's body -- the same staging, sums, conversions and tile store, so a stream's bytes
+ * are those of a one-input call.  e.out is the call's first frame: the tile goes to frame e.f.t0 + tt of
+ * the stream's row at the stream's own FB, so a mono stream beside a stereo one starts tiles at addresses
+ * that are not 16-byte aligned (icw_tile_out's funnel path).  Dynamic LDS is sized for the widest stream. */
+template <int CWF>
+__global__ __launch_bounds__(256) void icw_fir_encode_mixed(IcwEncArgs e)
+{
+    icw_fir_own_input(e.f, blockIdx.y);
+    if (e.f.nch > 1) icw_fir_encode_ps<CWF, 2>(e);
+    else icw_fir_encode_ps<CWF, 1>(e);
 }
 
 /* KIP: the packer of the IIR encoder (icw_encode_cwave_iir).  The quadrature IIR's analytic signal of a
@@ -167,13 +128,23 @@ __global__ __launch_bounds__(256) void icw_fir_encode(IcwEncArgs e)
  * most two partial dwords at its ends as bytes.  The kernel runs once per block beside nothing it could
  * slow down (the recurrence bounds the call), so its LDS stores are left to conflict. */
 #define ICW_PACK_R 4                                     /* frames per lane */
-template <int CWF, int NC>
-__global__ __launch_bounds__(256) void icw_iq_pack(IcwPackArgs a)
+/* KIP's workgroup: tile blockIdx.x of stream blockIdx.y, NC channels per frame.  frame0: 0, or the
+ * per-stream kernel's block offset (as PS in icw_fir_encode_body); that kernel's image is dynamic LDS,
+ * sized by the launcher for the stereo frame, which holds the mono one. */
+template <int CWF, int NC, bool PS>
+__device__ __forceinline__ void icw_iq_pack_body(IcwPackArgs a, long long frame0)
 {
     constexpr int CB = icw_cw_bytes<CWF>::value, FB = NC * CB;    /* bytes per channel, per frame */
     constexpr int TF = 256 * ICW_PACK_R;
     /* 16 spare bytes: the funnel's second word may lie past the tile's last byte (its bits are shifted out) */
-    __shared__ __attribute__((aligned(16))) unsigned char img[TF * FB + 16];
+    unsigned char *img;
+    if constexpr (PS) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char img_dyn[];
+        img = img_dyn;
+    } else {
+        __shared__ __attribute__((aligned(16))) unsigned char img_own[TF * FB + 16];
+        img = img_own;
+    }
     __shared__ unsigned nclip;
     const int s = blockIdx.y, tid = threadIdx.x;
     const int tt = blockIdx.x * TF;
@@ -219,12 +190,30 @@ __global__ __launch_bounds__(256) void icw_iq_pack(IcwPackArgs a)
         if (clip) atomicAdd(&nclip, clip);
     }
     unsigned char *dst = a.out + (size_t)s * a.out_stride + (size_t)tt * FB;
+    if constexpr (PS) dst += (size_t)frame0 * FB;
     const int nbytes = nf * FB;
     icw_tile_out<0, 1>(dst, nbytes, img, tid);
     if (CWF == 1 || CWF == 2) {
         __syncthreads();
         if (tid == 0 && nclip) atomicAdd(a.clipped + s, (unsigned long long)nclip);
     }
+}
+
+template <int CWF, int NC>
+__global__ __launch_bounds__(256) void icw_iq_pack(IcwPackArgs a)
+{
+    icw_iq_pack_body<CWF, NC, false>(a, 0);
+}
+
+/* KIP over streams with different inputs: the workgroup column's stream takes its channels from the table by a
+ * scalar load and a wave-uniform branch to the one-input kernel's body; its tile goes to frame m.t0 + tt of
+ * the stream's row at the stream's own FB (m.p.out is the call's first frame). */
+template <int CWF>
+__global__ __launch_bounds__(256) void icw_iq_pack_mixed(IcwPackMixArgs m)
+{
+    const __attribute__((address_space(4))) IcwInDesc *d = (const __attribute__((address_space(4))) IcwInDesc *)m.desc + blockIdx.y;
+    if (d->nch > 1) icw_iq_pack_body<CWF, 2, true>(m.p, m.t0);
+    else icw_iq_pack_body<CWF, 1, true>(m.p, m.t0);
 }
 
 /* the reader position and (IIR encoder; the FIR one passes no hq_phase) the Hilbert phases of the streams an
@@ -281,6 +270,37 @@ extern "C" hipError_t icw_launch_fir_encode(const IcwEncArgs *e, int cwf, hipStr
     });
 }
 
+/* KFE of one launch block over streams with different inputs (e->f.desc): LDS for the widest stream of the
+ * call (e->f.nch), whose staged channels and frame image hold every narrower one's */
+template <int CWF>
+static hipError_t launch_fir_encode_mixed_t(const IcwEncArgs *e, hipStream_t st)
+{
+    constexpr int TF = 256 * ICW_FIR_R;
+    const int nc = e->f.nch > 1 ? 2 : 1;
+    const int cu = nc * icw_cw_bytes<CWF>::value / 2, padu = (cu & 1) ? 0 : 1;
+    const size_t lds = std::max((size_t)nc * icw_fir_px(e->f.M, TF) * sizeof(double), (size_t)256 * (cu + padu) * 16);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)icw_fir_encode_mixed<CWF>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((icw_fir_encode_mixed<CWF>), dim3((e->f.T + TF - 1) / TF, e->f.n_streams), dim3(256), lds, st, *e);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t icw_launch_fir_encode_mixed(const IcwEncArgs *e, int cwf, hipStream_t st)
+{
+    const int M = e->f.M, nt = e->f.nt;
+    if (!e->f.desc || !e->out || !e->clipped || e->f.n_streams <= 0) return hipErrorInvalidValue;
+    if (M < 2 || M > ICW_FIR_MAX_M || (M & 1) || nt < 1 || 2 * nt - 1 > M / 2 || e->f.T <= 0) return hipErrorInvalidValue;
+    switch (cwf) {
+    case 0: return launch_fir_encode_mixed_t<0>(e, st);
+    case 1: return launch_fir_encode_mixed_t<1>(e, st);
+    case 2: return launch_fir_encode_mixed_t<2>(e, st);
+    case 3: return launch_fir_encode_mixed_t<3>(e, st);
+    }
+    return hipErrorInvalidValue;
+}
+
 template <int CWF, int NC>
 static hipError_t launch_iq_pack_t(const IcwPackArgs *a, hipStream_t st)
 {
@@ -296,6 +316,30 @@ extern "C" hipError_t icw_launch_iq_pack(const IcwPackArgs *a, int cwf, int nc, 
     return enc_dispatch(cwf, nc > 1, [&](auto fc, auto ncc) {
         return launch_iq_pack_t<decltype(fc)::value, decltype(ncc)::value>(a, st);
     });
+}
+
+template <int CWF>
+static hipError_t launch_iq_pack_mixed_t(const IcwPackMixArgs *a, hipStream_t st)
+{
+    constexpr int TF = 256 * ICW_PACK_R;
+    /* the image of a stereo tile and the funnel's 16 spare bytes: at most 32 784 bytes */
+    const size_t lds = (size_t)TF * 2 * icw_cw_bytes<CWF>::value + 16;
+    hipLaunchKernelGGL((icw_iq_pack_mixed<CWF>), dim3((a->p.T + TF - 1) / TF, a->p.n_streams), dim3(256), lds, st, *a);
+    return hipGetLastError();
+}
+
+/* KIP of one launch block over streams with different inputs (a->desc) */
+extern "C" hipError_t icw_launch_iq_pack_mixed(const IcwPackMixArgs *a, int cwf, hipStream_t st)
+{
+    if (!a->desc || a->p.T <= 0 || a->p.n_streams <= 0 || !a->p.iq || !a->p.out || !a->p.clipped || a->t0 < 0)
+        return hipErrorInvalidValue;
+    switch (cwf) {
+    case 0: return launch_iq_pack_mixed_t<0>(a, st);
+    case 1: return launch_iq_pack_mixed_t<1>(a, st);
+    case 2: return launch_iq_pack_mixed_t<2>(a, st);
+    case 3: return launch_iq_pack_mixed_t<3>(a, st);
+    }
+    return hipErrorInvalidValue;
 }
 
 extern "C" hipError_t icw_launch_enc_advance(long long *pos, uint32_t *hq_phase, int n_streams, long long n, hipStream_t st)

@@ -27,22 +27,9 @@
 
 /* The per-stream form of the FIR kernels (PS; streams with different lists or inputs, as K2's MIX): the
  * workgroup is one stream, so what it selects is wave-uniform and comes in by scalar loads through the
- * constant address space.  The PS = false instances are the kernels of a one-list, one-input call. */
+ * constant address space.  The PS = false instances are the kernels of a one-list, one-input call.
+ * (icw_fir_own_input, the stream's own input: icw_fir_dev.h, shared with the encoder.) */
 typedef const __attribute__((address_space(4))) int32_t icw_csel;
-
-/* the stream's own input replaces the launch's: format, sizes, channels, and the block offset at its own
- * frame size (icw_unpack_frames_mixed); a null table leaves the launch's one input */
-__device__ __forceinline__ void icw_fir_own_input(IcwFirArgs &f, int s)
-{
-    if (f.desc) {
-        const __attribute__((address_space(4))) IcwInDesc *d = (const __attribute__((address_space(4))) IcwInDesc *)f.desc + s;
-        f.fmt = d->fmt;
-        f.csz = d->csz;
-        f.fsz = d->fsz;
-        f.nch = d->nch;
-        f.in += (size_t)f.t0 * f.fsz;
-    }
-}
 
 /* KF: the converter alone, one workgroup per channel and 2048-frame tile of a stream; I / Q rows
  * go out coalesced through LDS to the CWAVE rows K2 reads */

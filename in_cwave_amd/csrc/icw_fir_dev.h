@@ -252,6 +252,20 @@ __device__ __forceinline__ void icw_fir_stage(const IcwFirArgs &f, int s, int ch
     });
 }
 
+/* the stream's own input replaces the launch's: format, sizes, channels, and the block offset at its own
+ * frame size (icw_unpack_frames_mixed); a null table leaves the launch's one input */
+__device__ __forceinline__ void icw_fir_own_input(IcwFirArgs &f, int s)
+{
+    if (f.desc) {
+        const __attribute__((address_space(4))) IcwInDesc *d = (const __attribute__((address_space(4))) IcwInDesc *)f.desc + s;
+        f.fmt = d->fmt;
+        f.csz = d->csz;
+        f.fsz = d->fsz;
+        f.nch = d->nch;
+        f.in += (size_t)f.t0 * f.fsz;
+    }
+}
+
 /* The taps through the constant address space: every lane of a wave reads the same tap, so they
  * come in by scalar loads into SGPRs (the FMA takes one SGPR operand) and leave the LDS pipe to the
  * inputs -- which bounds the sums: 52 -> 44 LDS reads per 8-tap block of a lane's 8 outputs. */

@@ -37,6 +37,10 @@ int grow(void **p, size_t *cur, size_t need)
     return ICW_OK;
 }
 
+/* bytes of n_frames frames of frame_bytes each: what an encoder call's stride must hold, what its staging
+ * rows are */
+size_t icw_enc_row_bytes(int n_frames, uint32_t frame_bytes) { return (size_t)n_frames * frame_bytes; }
+
 /* Launch blocks of one call: (offset, frames) pairs of at most Tb frames.  A block pipeline fills
  * with K0 of the first block alone and drains with K2 (and the serial render) of the last block
  * alone, each on the whole chip (sF).  For calls of many blocks both ends are made short:
@@ -236,6 +240,10 @@ struct CallPlan {
     const IcwInDesc *dD = nullptr;
     unsigned csz = 0, nch = 0, fsz = 0;
     int osz = 0;
+    /* the encoders: the CWAVE output format and its frame bytes at the call's channels (mixin: the widest
+     * stream's -- every stream's row holds n_frames of them, its own frames are icw_enc_frame_bytes) */
+    uint32_t cw_format = 0;
+    int efb = 0;
     unsigned long long ssr = 0;
     /* the list in use */
     const IcwProg *lp = nullptr, *dP = nullptr;
@@ -300,6 +308,16 @@ struct CallPlan {
         a0.x_pitch = x_pitch;
         a0.dedup = dedup ? 1 : 0;
         return a0;
+    }
+
+    /* the same over streams with different inputs: K0 takes each stream's format from the table */
+    IcwK0MixArgs k0_mix_args(int b) const
+    {
+        IcwK0MixArgs m;
+        memset(&m, 0, sizeof(m));
+        m.k0 = k0_args(b);
+        m.desc = dD;
+        return m;
     }
 
     IcwK1Args k1_args(int b) const
@@ -496,6 +514,70 @@ struct CallPlan {
         return af;
     }
 
+    /* where block b's frames go: the one-input kernels get the block's first frame (the host knows the one
+     * frame size); the per-stream ones the call's first frame and apply the offset at their stream's own */
+    unsigned char *enc_out(int b) const { return d_out + (mixin ? 0 : (size_t)blocks[b].first * efb); }
+
+    /* KFE of block b: KF's arguments, the packed frames as the output.  It packs frames instead of writing
+     * K2's rows, and no graph follows it: no row buffer, no chain signature */
+    IcwEncArgs enc_args(int b) const
+    {
+        IcwEncArgs e;
+        memset(&e, 0, sizeof(e));
+        e.f = fir_args(b);
+        e.f.xd = nullptr;
+        e.f.x_pitch = 0;
+        e.f.sig = 0;
+        e.f.lr_same = 0;
+        e.out = enc_out(b);
+        e.out_stride = dos;
+        e.clipped = c->enc_clipped + f0;
+        return e;
+    }
+
+    /* the IIR encoder's K2 of block b -- up to `in`: the output sums and the fs/4 un-mix, then the rows
+     * instead of the graph (they go out although the list is not bus form: K2 ends there); it still counts
+     * the block's de-subnorm rejections.  Nothing is rendered: no output bytes, no pre-render rows.  With
+     * do_render 0 and iq_out set K2 returns after the rows, so what k2_args filled of the render (rk, clips,
+     * peak_bits) is unread; and no graph runs, so no rotation factors whatever the list holds */
+    IcwK2Args enc_k2_args(int b) const
+    {
+        IcwK2Args a2 = k2_args(b);
+        a2.iq_out = c->iq[0];
+        a2.do_render = 0;
+        a2.out = nullptr;
+        a2.out_stride = 0;
+        a2.pre = nullptr;
+        a2.pre_stride = 0;
+        a2.trig = 0;
+        return a2;
+    }
+
+    /* KIP of block b, behind that K2 */
+    IcwPackArgs pack_args(int b) const
+    {
+        IcwPackArgs ap;
+        memset(&ap, 0, sizeof(ap));
+        ap.iq = c->iq[0];
+        ap.n_streams = count;
+        ap.T = blocks[b].second;
+        ap.out = enc_out(b);
+        ap.out_stride = dos;
+        ap.clipped = c->enc_clipped + f0;
+        return ap;
+    }
+
+    /* the same over streams with different inputs: every stream's own channels, its tile at its own frame size */
+    IcwPackMixArgs pack_mix_args(int b) const
+    {
+        IcwPackMixArgs m;
+        memset(&m, 0, sizeof(m));
+        m.p = pack_args(b);
+        m.desc = dD;
+        m.t0 = blocks[b].first;
+        return m;
+    }
+
     IcwAdvArgs adv_args() const
     {
         IcwAdvArgs av;
@@ -527,8 +609,10 @@ struct CallPlan {
     bool stage_copy_in() const;
     bool stage_copy_out(size_t row_bytes) const;
     bool fir_hist_back() const;
-    int enc_format(int FB, bool fir_ok);
-    int enc_buffers(int FB);
+    int enc_format(uint32_t cw_fmt, bool fir_ok);
+    int enc_buffers();
+    int enc_mix_lists();
+    bool enc_copy_out() const;
     void set_pitches();
     void plan_uniform(int max_block);
     int resolve_plan();
@@ -630,28 +714,74 @@ bool CallPlan::fir_hist_back() const
                           S * hrow * sizeof(double), hipMemcpyDeviceToDevice, st) == hipSuccess;
 }
 
-/* The encoders' format checks (real input, the converter asked for on or off, a CWAVE output format,
- * strides that hold the call) and their buffers: the caller's device pointers, or the staging pair
- * with every stream's frames 16-byte aligned.  FB: bytes per output frame. */
-int CallPlan::enc_format(int FB, bool fir_ok)
+/* The encoders' input and format checks.  The input of the call's streams is resolved as resolve_plan
+ * resolves it -- the one all of them have (the launches are then those of a one-input context), or mixin:
+ * the table; the rate plays no part in an encode (no fades of its own, no graph), so streams that differ in
+ * it alone share one input here.  Then: real input, the converter asked for on or off, a CWAVE output
+ * format, and strides that hold the call -- n_frames of the widest input frame and of the widest output
+ * frame; a one-input call with device pointers is not checked, as ever.  Nothing has run when this fails. */
+int CallPlan::enc_format(uint32_t cw_fmt, bool fir_ok)
 {
-    if (cfg.in_format >= ICW_FMT_CW_F64 || !fir_ok || FB == 0) return ICW_EINVAL;
-    fmt = cfg.in_format;
-    rate = cfg.sample_rate;
-    csz = fmt_size(fmt);
-    nch = cfg.in_channels;
-    fsz = csz * nch;
-    if (!dev && (in_stride < (size_t)n_frames * fsz || out_stride < (size_t)n_frames * FB)) return ICW_EINVAL;
+    const IcwInDesc &d0 = c->inputs[f0];
+    fmt = d0.fmt;
+    rate = d0.sample_rate;
+    csz = d0.csz;
+    nch = d0.nch;
+    fsz = d0.fsz;
+    for (int i = 1; i < count; ++i) {
+        const IcwInDesc &d = c->inputs[f0 + (size_t)i];
+        if (d.fmt != fmt || d.nch != d0.nch) mixin = true;
+        fsz = std::max(fsz, d.fsz);
+        nch = std::max(nch, d.nch);
+    }
+    if (mixin) dD = c->d_inputs + f0;
+    fir = c->fir_M > 0;
+    cw_format = cw_fmt;
+    efb = icw_cwave_frame_bytes(cw_fmt, nch);
+    if (fmt >= ICW_FMT_CW_F64 || !fir_ok || efb == 0) return ICW_EINVAL;
+    if ((!dev || mixin) && (in_stride < icw_enc_row_bytes(n_frames, fsz) || out_stride < icw_enc_row_bytes(n_frames, (uint32_t)efb)))
+        return ICW_EINVAL;
     return ICW_OK;
 }
 
-int CallPlan::enc_buffers(int FB)
+/* the encoders' buffers: the caller's device pointers, or the staging pair with every stream's frames
+ * 16-byte aligned */
+int CallPlan::enc_buffers()
 {
     d_in = (const unsigned char *)in;
     d_out = (unsigned char *)out;
     dis = in_stride;
     dos = out_stride;
-    return dev ? ICW_OK : stage_host_io((size_t)n_frames * fsz, ((size_t)n_frames * FB + 15) & ~(size_t)15);
+    return dev ? ICW_OK : stage_host_io(icw_enc_row_bytes(n_frames, fsz), (icw_enc_row_bytes(n_frames, (uint32_t)efb) + 15) & ~(size_t)15);
+}
+
+/* the staged frames back to host pointers: every stream's own n_frames * FB_s bytes, so a narrower stream's
+ * row is written no further than its frames.  One copy per stream where the one-input path makes one 2-D
+ * copy: a 2-D copy has one width, and the widest would write a narrower stream's row past its frames.  Not
+ * measured; the host-pointer path is the convenience path (the file layer and the rate tool use device
+ * pointers), and a host that minds the per-copy cost passes device pointers. */
+bool CallPlan::enc_copy_out() const
+{
+    if (!mixin) return stage_copy_out(icw_enc_row_bytes(n_frames, (uint32_t)efb));
+    for (size_t i = 0; i < S; ++i) {
+        const size_t nb = icw_enc_row_bytes(n_frames, (uint32_t)icw_cwave_frame_bytes(cw_format, c->inputs[f0 + i].nch));
+        if (hipMemcpyAsync((unsigned char *)out + i * out_stride, c->d_out + i * dos, nb, hipMemcpyDeviceToHost, st) != hipSuccess)
+            return false;
+    }
+    return true;
+}
+
+/* The IIR encoder over streams with different inputs runs K2's per-stream instances, as a mixed-input
+ * process call does: the selection rows (prepare_mix: each stream's channels, its list where the lists
+ * differ too) and their launch configuration.  After plan_uniform, which chose the context's one list. */
+int CallPlan::enc_mix_lists()
+{
+    const int rc = prepare_mix(c, first, count, false, st);
+    if (rc != ICW_OK) return rc;
+    mix = true;
+    lp = &c->mix;
+    dP = c->progs.empty() ? c->d_prog : c->d_progs;
+    return ICW_OK;
 }
 
 /* at least n events in v */
@@ -1082,10 +1212,7 @@ int CallPlan::launch_k0(int b) const
     } else {
         if (timing && hipEventRecord(c->ev_k0[2 * b], s0) != hipSuccess) return ICW_EDEVICE;
         if (mixin) {
-            IcwK0MixArgs m;
-            memset(&m, 0, sizeof(m));
-            m.k0 = a0;
-            m.desc = dD;
+            const auto m = k0_mix_args(b);
             if (icw_launch_unpack_mixed(&m, s0) != hipSuccess) return ICW_EDEVICE;
         } else if (icw_launch_unpack(&a0, s0) != hipSuccess) {
             return ICW_EDEVICE;
@@ -1347,7 +1474,9 @@ int icw_cwave_frame_bytes(uint32_t cw_format, uint32_t channels)
 
 /* The FIR converter's analytic signal as packed CWAVE frames (KFE).  The call shares icw_process_streams'
  * converter state -- the per-stream history (double-buffered by launch block, back in fir_hist[fir_par]
- * at the end) and the reader position -- and nothing else of the context. */
+ * at the end) and the reader position -- and nothing else of the context.  Streams with different inputs
+ * (icw_enable_stream_encode) run KFE's per-stream form; a call whose streams share one runs the kernels of a
+ * one-input context. */
 int icw_encode_cwave(icw_ctx *c, int first, int count, const void *in, size_t in_stride, void *out, size_t out_stride,
                      int n_frames, uint32_t cw_format, unsigned flags, void *hip_stream)
 {
@@ -1355,38 +1484,28 @@ int icw_encode_cwave(icw_ctx *c, int first, int count, const void *in, size_t in
         (flags & ~ICW_F_DEVICE_PTRS))
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (c->n_inputs > 1) return ICW_EUNSUPPORTED;        /* per-stream inputs: the encoders take one (include/icw.h) */
-    const int FB = icw_cwave_frame_bytes(cw_format, c->cfg.in_channels);
+    if (c->n_inputs > 1 && !c->enc_streams) return ICW_EUNSUPPORTED;   /* per-stream inputs: asked for (include/icw.h) */
     CallPlan pl(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
     int rc;
-    if ((rc = pl.enc_format(FB, c->fir_M > 0)) != ICW_OK) return rc;
+    if ((rc = pl.enc_format(cw_format, c->fir_M > 0)) != ICW_OK) return rc;
     if (n_frames == 0) return ICW_OK;
     if (set_dev(c)) return ICW_EDEVICE;
     ++c->calls;
     if ((rc = pl.join_legacy_stream()) != ICW_OK) return rc;
     if ((rc = ensure_enc_clipped(c)) != ICW_OK) return rc;
-    if ((rc = pl.enc_buffers(FB)) != ICW_OK) return rc;
+    if ((rc = pl.enc_buffers()) != ICW_OK) return rc;
     if (!pl.dev && !pl.stage_copy_in()) return ICW_EDEVICE;
     pl.plan_uniform(kMaxFirBlockFrames);
+    const int cwf = (int)(cw_format - ICW_FMT_CW_F64);
     for (int b = 0; b < pl.n_blocks; ++b) {
-        IcwEncArgs e;
-        memset(&e, 0, sizeof(e));
-        e.f = pl.fir_args(b);
-        /* KFE packs frames instead of writing K2's rows, and no graph follows it: no row buffer, no
-         * chain signature */
-        e.f.xd = nullptr;
-        e.f.x_pitch = 0;
-        e.f.sig = 0;
-        e.f.lr_same = 0;
-        e.out = pl.d_out + (size_t)pl.blocks[b].first * FB;
-        e.out_stride = pl.dos;
-        e.clipped = c->enc_clipped + pl.f0;
-        if (icw_launch_fir_encode(&e, (int)(cw_format - ICW_FMT_CW_F64), pl.st) != hipSuccess) return ICW_EDEVICE;
+        const auto e = pl.enc_args(b);
+        if ((pl.mixin ? icw_launch_fir_encode_mixed(&e, cwf, pl.st) : icw_launch_fir_encode(&e, cwf, pl.st)) != hipSuccess)
+            return ICW_EDEVICE;
     }
     if (!pl.fir_hist_back()) return ICW_EDEVICE;
     if (icw_launch_enc_advance(c->st.pos + pl.f0, nullptr, count, (long long)n_frames, pl.st) != hipSuccess) return ICW_EDEVICE;
     if (pl.legacy && hipStreamSynchronize(pl.st) != hipSuccess) return ICW_EDEVICE;
-    if (!pl.dev && (!pl.stage_copy_out((size_t)n_frames * FB) || hipStreamSynchronize(pl.st) != hipSuccess)) return ICW_EDEVICE;
+    if (!pl.dev && (!pl.enc_copy_out() || hipStreamSynchronize(pl.st) != hipSuccess)) return ICW_EDEVICE;
     return hipGetLastError() == hipSuccess ? ICW_OK : ICW_EDEVICE;
 }
 
@@ -1395,7 +1514,9 @@ int icw_encode_cwave(icw_ctx *c, int first, int count, const void *in, size_t in
  * the `in` rows: no graph, no render, no meters) -- then the packer KIP.  The recurrence bounds the call
  * and nothing of a block can start before the block's K1 has ended, so the four run in sequence on the
  * caller's stream with one scratch set; the call shares icw_process_streams' converter state (rings,
- * phases, de-subnorm counters, lr_equal) and the reader position, and nothing else of the context. */
+ * phases, de-subnorm counters, lr_equal) and the reader position, and nothing else of the context.
+ * Streams with different inputs (icw_enable_stream_encode) take what a mixed-input process call takes --
+ * the table-reading K0, the same K1, K2's per-stream instances -- and KIP's per-stream form. */
 int icw_encode_cwave_iir(icw_ctx *c, int first, int count, const void *in, size_t in_stride, void *out, size_t out_stride,
                          int n_frames, uint32_t cw_format, unsigned flags, void *hip_stream)
 {
@@ -1403,12 +1524,11 @@ int icw_encode_cwave_iir(icw_ctx *c, int first, int count, const void *in, size_
         (flags & ~ICW_F_DEVICE_PTRS))
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (c->n_inputs > 1) return ICW_EUNSUPPORTED;        /* per-stream inputs: the encoders take one (include/icw.h) */
+    if (c->n_inputs > 1 && !c->enc_streams) return ICW_EUNSUPPORTED;   /* per-stream inputs: asked for (include/icw.h) */
     const icw_config &cfg = c->cfg;
-    const int FB = icw_cwave_frame_bytes(cw_format, cfg.in_channels);
     CallPlan pl(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
     int rc;
-    if ((rc = pl.enc_format(FB, c->fir_M <= 0)) != ICW_OK) return rc;
+    if ((rc = pl.enc_format(cw_format, c->fir_M <= 0)) != ICW_OK) return rc;
     const size_t S = pl.S;
     /* FC() arithmetic changes the values: refused, so K1 / K2 take no census (fes null, fcm false) */
     if (cfg.fp_check) return ICW_EUNSUPPORTED;
@@ -1417,54 +1537,47 @@ int icw_encode_cwave_iir(icw_ctx *c, int first, int count, const void *in, size_
     /* the K1 of a process call over these streams */
     pl.pick_k1();
     pl.plan_uniform(kMaxBlockFrames);
+    if (pl.mixin && (rc = pl.enc_mix_lists()) != ICW_OK) return rc;
     if ((rc = ensure_enc_clipped(c)) != ICW_OK) return rc;
     if (grow((void **)&c->w[0], &c->w_bytes[0], S * 4 * pl.w_pitch * sizeof(double)) ||
         grow((void **)&c->xd[0], &c->xd_bytes[0], S * 4 * pl.x_pitch * sizeof(double)) ||
         grow((void **)&c->iq[0], &c->iq_bytes[0], S * (size_t)pl.Tb * 4 * sizeof(double)))
         return ICW_ENOMEM;
-    if ((rc = pl.enc_buffers(FB)) != ICW_OK) return rc;
+    if ((rc = pl.enc_buffers()) != ICW_OK) return rc;
     /* counted only now that the allocations succeeded: an early ICW_ENOMEM leaves icw_prepare usable */
     ++c->calls;
     c->last_k1 = pl.k1_mode;
     if ((rc = pl.join_legacy_stream()) != ICW_OK) return rc;
     if (!pl.dev && !pl.stage_copy_in()) return ICW_EDEVICE;
     const DevState &ds = c->st;
+    const int cwf = (int)(cw_format - ICW_FMT_CW_F64);
     for (int b = 0; b < pl.n_blocks; ++b) {
-        const auto a0 = pl.k0_args(b);
-        if (icw_launch_unpack(&a0, pl.st) != hipSuccess) return ICW_EDEVICE;
+        if (pl.mixin) {
+            const auto m0 = pl.k0_mix_args(b);
+            if (icw_launch_unpack_mixed(&m0, pl.st) != hipSuccess) return ICW_EDEVICE;
+        } else {
+            const auto a0 = pl.k0_args(b);
+            if (icw_launch_unpack(&a0, pl.st) != hipSuccess) return ICW_EDEVICE;
+        }
         const auto a1 = pl.k1_args(b);
         if (pl.launch_k1(a1, pl.st) != hipSuccess) return ICW_EDEVICE;
-        /* K2 up to `in`: the output sums and the fs/4 un-mix, then the rows instead of the graph; it still
-         * counts the block's de-subnorm rejections */
-        auto a2 = pl.k2_args(b);
-        a2.iq_out = c->iq[0];      /* the rows go out although the list is not bus form: K2 ends there */
-        /* nothing is rendered: no output bytes, no pre-render rows.  With do_render 0 and iq_out set K2
-         * returns after the rows, so what the builder filled of the render (rk, clips, peak_bits) is unread */
-        a2.do_render = 0;
-        a2.out = nullptr;
-        a2.out_stride = 0;
-        a2.pre = nullptr;
-        a2.pre_stride = 0;
-        a2.trig = 0;               /* no graph runs, so no rotation factors whatever the list holds */
+        const auto a2 = pl.enc_k2_args(b);
         if (icw_launch_output(&a2, c->nord, cfg.iir_kahan, pl.st) != hipSuccess) return ICW_EDEVICE;
-
-        IcwPackArgs ap;
-        memset(&ap, 0, sizeof(ap));
-        ap.iq = c->iq[0];
-        ap.n_streams = count;
-        ap.T = pl.blocks[b].second;
-        ap.out = pl.d_out + (size_t)pl.blocks[b].first * FB;
-        ap.out_stride = pl.dos;
-        ap.clipped = c->enc_clipped + pl.f0;
-        if (icw_launch_iq_pack(&ap, (int)(cw_format - ICW_FMT_CW_F64), pl.nch > 1 ? 2 : 1, pl.st) != hipSuccess) return ICW_EDEVICE;
+        if (pl.mixin) {
+            const auto mp = pl.pack_mix_args(b);
+            if (icw_launch_iq_pack_mixed(&mp, cwf, pl.st) != hipSuccess) return ICW_EDEVICE;
+        } else {
+            const auto ap = pl.pack_args(b);
+            if (icw_launch_iq_pack(&ap, cwf, pl.nch > 1 ? 2 : 1, pl.st) != hipSuccess) return ICW_EDEVICE;
+        }
     }
-    if (pl.nch > 1)
-        for (int i = 0; i < count; ++i) c->lr_known[first + i] = 0;   /* stereo: the halves diverge */
+    for (int i = 0; i < count; ++i)
+        if (c->inputs[pl.f0 + (size_t)i].nch > 1) c->lr_known[first + i] = 0;   /* stereo: the halves diverge */
     if (icw_launch_enc_advance(ds.pos + pl.f0, ds.hq_phase + pl.f0 * 2, count, (long long)n_frames, pl.st) != hipSuccess)
         return ICW_EDEVICE;
     if (pl.legacy && hipStreamSynchronize(pl.st) != hipSuccess) return ICW_EDEVICE;
     if (!pl.dev) {
-        if (!pl.stage_copy_out((size_t)n_frames * FB) || hipStreamSynchronize(pl.st) != hipSuccess) return ICW_EDEVICE;
+        if (!pl.enc_copy_out() || hipStreamSynchronize(pl.st) != hipSuccess) return ICW_EDEVICE;
         int e = 0;
         if (hipMemcpy(&e, ds.err, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess || e) return ICW_EDEVICE;
     }

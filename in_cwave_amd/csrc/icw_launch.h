@@ -46,6 +46,11 @@ hipError_t icw_launch_iir_fc(const IcwK1Args *a, int nord, int kahan, int subn, 
 /* icw_encode.hip */
 hipError_t icw_launch_fir_encode(const IcwEncArgs *e, int cwf, hipStream_t st);
 hipError_t icw_launch_iq_pack(const IcwPackArgs *a, int cwf, int nc, hipStream_t st);
+/* the two over streams with different inputs: every workgroup column takes its stream's own format and
+ * channels from the table (e->f.desc / a->desc; a null table is refused) and places its tile at the stream's
+ * own frame size; e->f.nch is the call's widest stream (it sizes KFE's LDS) */
+hipError_t icw_launch_fir_encode_mixed(const IcwEncArgs *e, int cwf, hipStream_t st);
+hipError_t icw_launch_iq_pack_mixed(const IcwPackMixArgs *a, int cwf, hipStream_t st);
 /* hq_phase: null for the FIR encoder (the reader position alone) */
 hipError_t icw_launch_enc_advance(long long *pos, uint32_t *hq_phase, int n_streams, long long n, hipStream_t st);
 

@@ -114,6 +114,7 @@ class Context:
         self.render_size = lib.icw_render_size(h)
         self.fsz = abi.FMT_BYTES[cfg.in_format] * cfg.in_channels
         self.stream_fsz = [self.fsz] * n_streams       # every stream's own frame bytes (set_stream_input)
+        self.stream_channels = [int(cfg.in_channels)] * n_streams   # and channels (the encoders' frame bytes)
 
     def close(self):
         if self.h:
@@ -135,6 +136,7 @@ class Context:
         _check(self._lib.icw_set_input(self.h, sample_rate, fmt, channels), "icw_set_input")
         self.fsz = abi.FMT_BYTES[fmt] * channels
         self.stream_fsz = [self.fsz] * self.n_streams
+        self.stream_channels = [int(channels)] * self.n_streams
 
     def set_stream_input(self, sample_rate, fmt, channels, first=0, count=None):
         """icw_set_stream_input: the input of streams [first, first + count) for the next calls.  A call's
@@ -145,6 +147,7 @@ class Context:
         _check(self._lib.icw_set_stream_input(self.h, int(first), int(count), sample_rate, fmt, channels),
                "icw_set_stream_input")
         self.stream_fsz[first:first + count] = [abi.FMT_BYTES[fmt] * channels] * count
+        self.stream_channels[first:first + count] = [int(channels)] * count
         if len(set(self.stream_fsz)) == 1:
             self.fsz = self.stream_fsz[0]
 
@@ -165,6 +168,17 @@ class Context:
     def enable_stream_fir(self, on=True):
         """icw_enable_stream_fir: per-stream lists and inputs beside the FIR converter (off on a fresh context)"""
         _check(self._lib.icw_enable_stream_fir(self.h, int(bool(on))), "icw_enable_stream_fir")
+
+    def enable_stream_encode(self, on=True):
+        """icw_enable_stream_encode: the CWAVE encoders serve streams with different inputs (off on a fresh
+        context)"""
+        _check(self._lib.icw_enable_stream_encode(self.h, int(bool(on))), "icw_enable_stream_encode")
+
+    def encode_frame_bytes(self, cw_format, first=0, count=None):
+        """every stream's own CWAVE frame bytes in [first, first + count): an encode call's output rows hold
+        stream i's frames at this size, in rows as wide as the call's widest stream needs"""
+        count = self.n_streams - first if count is None else count
+        return [cwave_frame_bytes(cw_format, ch) for ch in self.stream_channels[first:first + count]]
 
     def _own_cfg(self):
         """the live setters record the context's parameters in a copy, never in the caller's Config"""
@@ -311,11 +325,13 @@ class Context:
     def encode_cwave(self, inp, n_frames, cw_format=abi.FMT_CW_F64, first=0, count=None, out=None):
         """icw_encode_cwave, host path: inp uint8 [count, >= n_frames*fsz] through the FIR Hilbert converter
         (set_fir_hilbert) to packed CWAVE frames, uint8 [count, n_frames * frame bytes].  Advances the
-        converter's history and the reader position like a process call; nothing else."""
+        converter's history and the reader position like a process call; nothing else.  Streams with different
+        inputs (enable_stream_encode): rows at each stream's own frame size in, and out at its own
+        encode_frame_bytes, in rows of the call's widest."""
         count = self.n_streams - first if count is None else count
         inp = np.ascontiguousarray(inp)
         assert inp.dtype == np.uint8 and inp.shape[0] == count and inp.shape[1] >= n_frames * self.call_fsz(first, count)
-        fb = cwave_frame_bytes(cw_format, self.cfg.in_channels)
+        fb = max(self.encode_frame_bytes(cw_format, first, count))
         if out is None:
             out = np.zeros((count, n_frames * fb), dtype=np.uint8)
         assert out.dtype == np.uint8 and out.shape[0] == count and out.shape[1] >= n_frames * fb
@@ -335,11 +351,12 @@ class Context:
     def encode_cwave_iir(self, inp, n_frames, cw_format=abi.FMT_CW_F64, first=0, count=None, out=None):
         """icw_encode_cwave_iir, host path: inp uint8 [count, >= n_frames*fsz] through the context's quadrature
         IIR converter to packed CWAVE frames, uint8 [count, n_frames * frame bytes].  Advances the converters
-        (rings, phases, de-subnorm counters) and the reader position like a process call; nothing else."""
+        (rings, phases, de-subnorm counters) and the reader position like a process call; nothing else.
+        Streams with different inputs: as encode_cwave."""
         count = self.n_streams - first if count is None else count
         inp = np.ascontiguousarray(inp)
         assert inp.dtype == np.uint8 and inp.shape[0] == count and inp.shape[1] >= n_frames * self.call_fsz(first, count)
-        fb = cwave_frame_bytes(cw_format, self.cfg.in_channels)
+        fb = max(self.encode_frame_bytes(cw_format, first, count))
         if out is None:
             out = np.zeros((count, n_frames * fb), dtype=np.uint8)
         assert out.dtype == np.uint8 and out.shape[0] == count and out.shape[1] >= n_frames * fb
@@ -571,13 +588,14 @@ def cwave_frame_bytes(cw_format, channels):
 
 
 def cwave_encode_files(in_paths, out_paths, k_M, k_beta=8.0, cw_format=abi.FMT_CW_F64, align=0, block_frames=0,
-                       device=-1):
+                       device=-1, merge_inputs=False):
     """icw_cwave_encode_files: WAV files to V2 CWAVE files through the FIR Hilbert converter; returns
-    (rc, stats, per-file status, per-file clipped int16 samples)"""
+    (rc, stats, per-file status, per-file clipped int16 samples).  merge_inputs: ICW_ENC_MERGE_INPUTS, every
+    file in one context"""
     n = len(in_paths)
     ins = (C.c_char_p * max(1, n))(*[str(p).encode() for p in in_paths])
     outs = (C.c_char_p * max(1, n))(*[str(p).encode() for p in out_paths])
-    o = abi.CwaveEncOpts(k_M, align, k_beta, cw_format, block_frames, device, 0)
+    o = abi.CwaveEncOpts(k_M, align, k_beta, cw_format, block_frames, device, abi.ENC_MERGE_INPUTS if merge_inputs else 0)
     st = abi.BatchStats()
     status = (C.c_int * max(1, n))()
     clipped = (C.c_uint64 * max(1, n))()
@@ -586,13 +604,15 @@ def cwave_encode_files(in_paths, out_paths, k_M, k_beta=8.0, cw_format=abi.FMT_C
 
 
 def cwave_encode_files_iir(in_paths, out_paths, hilbert_type=1, iir_kahan=1, iir_subnorm_reject=1,
-                           cw_format=abi.FMT_CW_F64, block_frames=0, device=-1):
+                           cw_format=abi.FMT_CW_F64, block_frames=0, device=-1, merge_inputs=False):
     """icw_cwave_encode_files_iir: WAV files to V2 CWAVE files (k_M 0) through the quadrature IIR converter;
-    returns (rc, stats, per-file status, per-file clipped int16 samples)"""
+    returns (rc, stats, per-file status, per-file clipped int16 samples).  merge_inputs: ICW_ENC_MERGE_INPUTS,
+    every file in one context"""
     n = len(in_paths)
     ins = (C.c_char_p * max(1, n))(*[str(p).encode() for p in in_paths])
     outs = (C.c_char_p * max(1, n))(*[str(p).encode() for p in out_paths])
-    o = abi.CwaveEncIirOpts(hilbert_type, iir_kahan, iir_subnorm_reject, cw_format, block_frames, device, 0)
+    o = abi.CwaveEncIirOpts(hilbert_type, iir_kahan, iir_subnorm_reject, cw_format, block_frames, device,
+                            abi.ENC_MERGE_INPUTS if merge_inputs else 0)
     st = abi.BatchStats()
     status = (C.c_int * max(1, n))()
     clipped = (C.c_uint64 * max(1, n))()

@@ -213,14 +213,27 @@ int icw_set_input(icw_ctx *ctx, uint32_t sample_rate, uint32_t fmt, uint32_t cha
  *                       whether the quadrature IIR runs at all is decided per call;
  *                     - without icw_enable_stream_fir: the FIR converter is on (icw_set_fir_hilbert with
  *                       k_M > 0), or, while the count is above 1, icw_set_fir_hilbert(k_M > 0);
- *                     - while the count is above 1: icw_encode_cwave and icw_encode_cwave_iir, and
- *                       ICW_F_DEBUG_INPUT.
+ *                     - while the count is above 1: ICW_F_DEBUG_INPUT, and -- without
+ *                       icw_enable_stream_encode -- icw_encode_cwave and icw_encode_cwave_iir.
+ *   icw_enable_stream_encode(ctx, 1)  the two CWAVE encoders (icw_cwave.h) serve calls over streams with
+ *                     different inputs from then on: input rows as above, stream s's frames at
+ *                     out + s*out_stride_bytes at its own icw_cwave_frame_bytes(cw_format, channels_s).  A
+ *                     fresh context has it off and keeps the refusal above, so a host that relies on it
+ *                     sees no change.  (ctx, 0) turns it off again and is ICW_OK whatever is in force (the
+ *                     fresh state: the encoders refuse while the count is above 1); only a NULL context is
+ *                     refused (ICW_EINVAL).  It lifts nothing else: icw_encode_cwave_iir still refuses a
+ *                     cfg.fp_check context, ICW_F_DEBUG_INPUT stays refused, and icw_encode_cwave needs the
+ *                     converter, which beside differing inputs needs icw_enable_stream_fir (without it
+ *                     icw_set_fir_hilbert / icw_set_stream_input return ICW_EUNSUPPORTED as listed, the
+ *                     converter stays off, and icw_encode_cwave returns its ICW_EINVAL for a context
+ *                     without one).  icw_encode_cwave_fft takes no context and is not concerned.
  * Not served: icw_group and the icw_amod_* drop-in (their input stays context-wide).  The state blob
  * does not carry the input, as it does not carry the list: icw_set_state expects the stream's input to
  * be set as it was. */
 int icw_set_stream_input(icw_ctx *ctx, int first, int count, uint32_t sample_rate, uint32_t fmt,
                          uint32_t channels);
 int icw_stream_input_count(const icw_ctx *ctx);
+int icw_enable_stream_encode(icw_ctx *ctx, int on);
 
 /* Live parameter changes (the GUI thread edits the DSP list, the renders and the
  * Hilbert converters while a decode thread runs).  Each applies to every stream of the context from

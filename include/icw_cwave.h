@@ -95,7 +95,19 @@ int icw_cwave_frame_bytes(uint32_t cw_format, uint32_t channels);
  * shorter than the frames, a flag other than ICW_F_DEVICE_PTRS, a cw_format outside ICW_FMT_CW_*, a
  * context with CWAVE input (already analytic) or without icw_set_fir_hilbert(k_M > 0).  ICW_ENOMEM /
  * ICW_EDEVICE: a buffer or a HIP call failed; the streams' state is then unspecified (reset or
- * icw_set_state them). */
+ * icw_set_state them).
+ * Per-stream inputs (icw_set_stream_input, include/icw.h).  While icw_stream_input_count() is above 1 both
+ * encoders return ICW_EUNSUPPORTED, nothing run, unless the context asked with icw_enable_stream_encode(ctx, 1).
+ * Then a call serves streams with different inputs: stream i's PCM at in + i*in_stride at its own frame size
+ * (as icw_process_streams lays it out), its frames at out + i*out_stride at its own
+ * icw_cwave_frame_bytes(cw_format, channels_i) -- bit for bit the bytes a one-input context writes for that
+ * stream.  Both strides must hold n_frames frames of the call's widest stream -- in_stride of the widest input
+ * frame, out_stride n_frames * icw_cwave_frame_bytes(cw_format, the call's most channels) -- for host and
+ * device pointers alike, else ICW_EINVAL, nothing run, nothing written.  The rate plays no part in an
+ * encode; a call whose streams share format and channels runs the kernels of a one-input context (the same
+ * launches, the same arguments), and only a call over differing ones takes the per-stream kernel instances.
+ * cw_format is one per call.  icw_encode_cwave beside differing inputs needs the converter there, hence
+ * icw_enable_stream_fir (include/icw.h); without a converter it returns ICW_EINVAL as above. */
 int icw_encode_cwave(icw_ctx *ctx, int first, int count, const void *in, size_t in_stride_bytes,
                      void *out, size_t out_stride_bytes, int n_frames, uint32_t cw_format,
                      unsigned flags, void *hip_stream);
@@ -117,8 +129,12 @@ int icw_encode_cwave(icw_ctx *ctx, int first, int count, const void *in, size_t 
  * Errors: ICW_EINVAL -- nothing ran, no state changed -- for a bad range or pointer, a host stride shorter
  * than the frames, a flag other than ICW_F_DEVICE_PTRS, a cw_format outside ICW_FMT_CW_*, a context with
  * CWAVE input, or one with the FIR converter on (icw_set_fir_hilbert(k_M > 0): icw_encode_cwave is its
- * call).  ICW_EUNSUPPORTED for a cfg.fp_check context (FC() arithmetic changes the values).  ICW_ENOMEM /
- * ICW_EDEVICE as above. */
+ * call).  ICW_EUNSUPPORTED for a cfg.fp_check context (FC() arithmetic changes the values), with or without
+ * per-stream inputs.  ICW_ENOMEM / ICW_EDEVICE as above.
+ * Per-stream inputs: as at icw_encode_cwave.  A call over differing inputs runs what a process call over
+ * them runs up to the graph (the table-reading unpack, the same recurrence, the output sums of each stream's
+ * own channels); the mono left = right shortcut applies when every stream of the call is mono, and a call
+ * ends the left / right identity of its stereo streams only. */
 int icw_encode_cwave_iir(icw_ctx *ctx, int first, int count, const void *in, size_t in_stride_bytes,
                          void *out, size_t out_stride_bytes, int n_frames, uint32_t cw_format,
                          unsigned flags, void *hip_stream);

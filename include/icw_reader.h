@@ -102,6 +102,15 @@ int icw_transcode_files_fir(const icw_config *cfg, const icw_node *const *nodes,
                             int32_t k_M, double k_beta, const icw_batch_opts *opts, icw_batch_stats *stats, int *status);
 
 /* ---- convert: WAV files -> CWAVE files (the external converter cwave.h:56-58 names) ---- */
+/* icw_cwave_enc_opts.reserved_ / icw_cwave_enc_iir_opts.reserved_ are the flags word (0: one context per
+ * (rate, format, channels) group).  ICW_ENC_MERGE_INPUTS: every accepted file goes into ONE context, each
+ * stream given its file's input (icw_set_stream_input, icw_enable_stream_encode; with the FIR converter
+ * icw_enable_stream_fir), so a library of mixed formats pays the serial IIR once, at full batch width.
+ * The files written are byte for byte those of the flag 0 -- header (each file's own channels and rate),
+ * frames, n_CRC32 -- and `clipped` and the per-file status are the same; stats->n_groups is 1.  align = 1
+ * is unchanged: every file drops its first k_M/2 frames. */
+#define ICW_ENC_MERGE_INPUTS 1
+
 typedef struct icw_cwave_enc_opts {
     int32_t  k_M;                       /* FIR Hilbert order: even, 2 .. ICW_FIR_MAX_ORDER */
     int32_t  align;                     /* 0: causal (what the in-context converter feeds the graph: file frame n
@@ -111,7 +120,7 @@ typedef struct icw_cwave_enc_opts {
     uint32_t cw_format;                 /* ICW_FMT_CW_* of the output */
     int32_t  block_frames;              /* frames per stream per GPU block (0: 65536) */
     int32_t  device;                    /* HIP device, -1: current */
-    int32_t  reserved_;
+    int32_t  reserved_;                 /* flags: 0 or ICW_ENC_MERGE_INPUTS */
 } icw_cwave_enc_opts;
 
 /* Encode n WAV files: in_paths[i] -> out_paths[i], a V2 CWAVE file (magic, hsize 48, version 2, format,
@@ -139,7 +148,7 @@ typedef struct icw_cwave_enc_iir_opts {
     uint32_t cw_format;                 /* ICW_FMT_CW_* of the output */
     int32_t  block_frames;              /* frames per stream per GPU block (0: 65536) */
     int32_t  device;                    /* HIP device, -1: current */
-    int32_t  reserved_;
+    int32_t  reserved_;                 /* flags: 0 or ICW_ENC_MERGE_INPUTS */
 } icw_cwave_enc_iir_opts;
 
 /* icw_cwave_encode_files through icw_encode_cwave_iir (icw_cwave.h): file frame n holds exactly the (I, Q)
