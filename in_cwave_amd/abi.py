@@ -115,6 +115,7 @@ class WavInfo(C.Structure):
 FIR_MAX_ORDER = 4096     # ICW_FIR_MAX_ORDER: largest k_M of icw_set_fir_hilbert / icw_transcode_files_fir
 # icw_batch_opts.reserved_ is the flags word (0: today's grouping, one context per input format)
 BATCH_MERGE_INPUTS = 1   # ICW_BATCH_MERGE_INPUTS: all real-input files in one context per device
+BATCH_MERGE_CWAVE = 2    # ICW_BATCH_MERGE_CWAVE: all CWAVE files in one context per device (the bits are independent)
 
 
 # icw_cwave_enc_opts.reserved_ / icw_cwave_enc_iir_opts.reserved_: the same for the file encoders
@@ -174,6 +175,7 @@ SIGNATURES = {
     "icw_set_fir_hilbert": (_i, [_vp, C.c_int32, C.c_double]),
     "icw_enable_stream_fir": (_i, [_vp, _i]),
     "icw_enable_stream_encode": (_i, [_vp, _i]),
+    "icw_enable_stream_cwave": (_i, [_vp, _i]),
     "icw_set_graph": (_i, [_vp, C.POINTER(Node), _i, _i, C.POINTER(_i)]),
     "icw_set_stream_graph": (_i, [_vp, _i, _i, C.POINTER(Node), _i, _i, C.POINTER(_i)]),
     "icw_clear_stream_bus_slot": (_i, [_vp, _i, _i, _i]),

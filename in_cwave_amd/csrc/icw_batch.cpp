@@ -181,11 +181,13 @@ struct FileLists {
  * channels, key), run each group, close the files and count the results.  accept(i, job) fills the
  * job's info and returns file i's status (ICW_OK to go on); key(i) is the caller's own part of the
  * group key, asked once the file is open; run(key, jobs, stats, status) processes one group. */
-/* merge (ICW_BATCH_MERGE_INPUTS): the real-input files group by the key alone -- one context whose
- * streams each get their own input (icw_set_stream_input); CWAVE files keep the grouping above. */
+/* merge, the ICW_BATCH_* bits: with ICW_BATCH_MERGE_INPUTS the real-input files group by the key alone -- one
+ * context whose streams each get their own input (icw_set_stream_input) -- and with ICW_BATCH_MERGE_CWAVE the
+ * CWAVE files do, in a context of their own (a call covers streams of one kind); without its bit a kind
+ * keeps the grouping above. */
 template <class Accept, class Key, class Run>
 int for_file_groups(const char *const *in_paths, const char *const *out_paths, int n, icw_batch_stats *stats, int *status,
-                    Accept accept, Key key, Run run, bool merge = false)
+                    Accept accept, Key key, Run run, unsigned merge = 0)
 {
     const double t0 = now_s();
     icw_batch_stats st;
@@ -204,7 +206,9 @@ int for_file_groups(const char *const *in_paths, const char *const *out_paths, i
         }
         setvbuf(j.in, nullptr, _IOFBF, 1 << 20);
         setvbuf(j.out, nullptr, _IOFBF, 1 << 20);
-        if (merge && j.info.fmt < ICW_FMT_CW_F64) groups[std::make_tuple(0u, 0u, 0u, key(i))].push_back(&j);
+        const bool cwf = j.info.fmt >= ICW_FMT_CW_F64;
+        if (merge & (cwf ? ICW_BATCH_MERGE_CWAVE : ICW_BATCH_MERGE_INPUTS))
+            groups[std::make_tuple(0u, cwf ? 1u : 0u, 0u, key(i))].push_back(&j);
         else groups[std::make_tuple(j.info.sample_rate, j.info.fmt, j.info.channels, key(i))].push_back(&j);
     }
     int rc = ICW_OK;
@@ -365,7 +369,8 @@ struct GroupPipe {
 };
 
 /* One group of files: one context, one stream per file.  The files share (rate, format, channels), or
- * (ICW_BATCH_MERGE_INPUTS) every stream gets its own file's input before the first block. */
+ * (ICW_BATCH_MERGE_INPUTS, ICW_BATCH_MERGE_CWAVE) every stream gets its own file's input before the first
+ * block. */
 int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::vector<Job *> &jobs,
               const icw_batch_opts &o, icw_batch_stats &st, int *status, const FileLists &fl = FileLists())
 {
@@ -390,6 +395,9 @@ int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::v
     /* a CWAVE group is analytic already: the converter is for real input */
     if (fl.k_M > 0 && wi.fmt < ICW_FMT_CW_F64 &&
         ((rc = icw_enable_stream_fir(ctx, 1)) != ICW_OK || (rc = icw_set_fir_hilbert(ctx, fl.k_M, fl.k_beta)) != ICW_OK))
+        return rc;
+    /* a merged group of CWAVE files: per-stream CWAVE inputs are the context's to ask for */
+    if (wi.fmt >= ICW_FMT_CW_F64 && (o.reserved_ & ICW_BATCH_MERGE_CWAVE) && (rc = icw_enable_stream_cwave(ctx, 1)) != ICW_OK)
         return rc;
     for (int s = 1; s < S && fl.per_stream; ++s) {
         const int i = jobs[s]->idx;
@@ -592,7 +600,7 @@ int encode_files(const char *const *in_paths, const char *const *out_paths, int 
         },
         [](int) { return 0; },
         [&](int, std::vector<Job *> &g, icw_batch_stats &st, int *sts) { return run_enc_group(g, o, st, clipped, sts); },
-        o.merge);
+        o.merge ? ICW_BATCH_MERGE_INPUTS : 0u);
 }
 
 /* One group of WAV files sharing (format, channels) through the direct-FFT encoder: whole tracks, no blocks.
@@ -697,7 +705,7 @@ int icw_cwave_encode_files_fft(const char *const *in_paths, const char *const *o
         },
         [&](int i) { return shape[i]; },
         [&](int, std::vector<Job *> &g, icw_batch_stats &st, int *sts) { return run_fft_group(g, e, st, clipped, sts); },
-        true);
+        ICW_BATCH_MERGE_INPUTS);
 }
 
 int icw_cwave_encode_files(const char *const *in_paths, const char *const *out_paths, int n, const icw_cwave_enc_opts *opts,
@@ -786,7 +794,7 @@ int icw_transcode_files(const icw_config *cfg, const icw_node *nodes, int n_node
         [&](int i, Job &j) { return accept_wav(in_paths[i], out_paths[i], &j.info); },
         [](int) { return 0; },
         [&](int, std::vector<Job *> &g, icw_batch_stats &st, int *sts) { return run_group(*cfg, nodes, n_nodes, g, o, st, sts); },
-        (o.reserved_ & ICW_BATCH_MERGE_INPUTS) != 0);
+        (unsigned)o.reserved_ & (ICW_BATCH_MERGE_INPUTS | ICW_BATCH_MERGE_CWAVE));
 }
 
 namespace {
@@ -840,7 +848,7 @@ int transcode_lists(const icw_config *cfg, const icw_node *const *nodes, const i
             fl.k_beta = k_beta;
             return run_group(*cfg, nullptr, 0, g, o, st, sts, fl);
         },
-        (o.reserved_ & ICW_BATCH_MERGE_INPUTS) != 0);
+        (unsigned)o.reserved_ & (ICW_BATCH_MERGE_INPUTS | ICW_BATCH_MERGE_CWAVE));
 }
 
 }  // namespace

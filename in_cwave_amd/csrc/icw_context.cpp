@@ -391,6 +391,13 @@ bool same_input(const IcwInDesc &a, const IcwInDesc &b)
     return a.fmt == b.fmt && a.nch == b.nch && a.sample_rate == b.sample_rate;
 }
 
+bool any_cwave(const std::vector<IcwInDesc> &v)
+{
+    for (const IcwInDesc &d : v)
+        if (d.fmt >= ICW_FMT_CW_F64) return true;
+    return false;
+}
+
 int count_inputs(const std::vector<IcwInDesc> &v)
 {
     std::vector<const IcwInDesc *> seen;
@@ -646,6 +653,9 @@ int icw_set_fir_hilbert(icw_ctx *c, int32_t M, double beta)
     /* beside per-stream lists or inputs only once the host has asked for it (icw_enable_stream_fir): the
      * converter's kernels then run their per-stream form */
     if (M > 0 && !c->fir_streams && (!c->progs.empty() || c->n_inputs > 1)) return ICW_EUNSUPPORTED;
+    /* nor beside per-stream CWAVE inputs (icw_enable_stream_cwave): the converter's per-stream kernels read
+     * real formats only, and icw_set_stream_input refuses to build that state from its side */
+    if (M > 0 && c->n_inputs > 1 && any_cwave(c->inputs)) return ICW_EUNSUPPORTED;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     c->pid_valid = false;                 /* with the converter on, every (list, rate) pair has a slab */
     for (double *&h : c->fir_hist)
@@ -698,6 +708,17 @@ int icw_enable_stream_encode(icw_ctx *c, int on)
     return ICW_OK;
 }
 
+/* per-stream CWAVE inputs, on or off (include/icw.h).  Off while a stream holds a per-stream CWAVE input
+ * would leave a table the setter refuses to build */
+int icw_enable_stream_cwave(icw_ctx *c, int on)
+{
+    if (!c) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!on && c->n_inputs > 1 && any_cwave(c->inputs)) return ICW_EUNSUPPORTED;
+    c->cw_streams = on != 0;
+    return ICW_OK;
+}
+
 int icw_stream_reset_framecnt(icw_ctx *c, int s)
 {
     if (!c || s < 0 || s >= c->n_streams) return ICW_EINVAL;
@@ -743,14 +764,18 @@ int icw_set_stream_input(icw_ctx *c, int first, int count, uint32_t sample_rate,
         sample_rate > ICW_MAX_FS_SRC || fmt > ICW_FMT_CW_F32 || channels == 0)
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    /* whether K1 runs at all is a per-call decision: CWAVE input stays context-wide.  The FIR converter
-     * is context-wide too; it reads every stream's own real format once icw_enable_stream_fir said so */
-    if (fmt >= ICW_FMT_CW_F64 || c->cfg.in_format >= ICW_FMT_CW_F64 || (c->fir_M > 0 && !c->fir_streams))
-        return ICW_EUNSUPPORTED;
-    if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+    /* whether K1 runs at all is a per-call decision: CWAVE input stays context-wide until
+     * icw_enable_stream_cwave said otherwise (a call then covers streams of one kind).  The FIR converter is
+     * context-wide too; it reads every stream's own real format once icw_enable_stream_fir said so, and never
+     * stands beside per-stream CWAVE inputs */
+    const bool cwf = fmt >= ICW_FMT_CW_F64;
+    if (!c->cw_streams && (cwf || c->cfg.in_format >= ICW_FMT_CW_F64)) return ICW_EUNSUPPORTED;
+    if (c->fir_M > 0 && (!c->fir_streams || cwf)) return ICW_EUNSUPPORTED;
     std::vector<IcwInDesc> nv = c->inputs;
     for (int s = first; s < first + count; ++s) nv[(size_t)s] = make_input(sample_rate, fmt, channels);
     const int n = count_inputs(nv);
+    if (c->fir_M > 0 && n > 1 && any_cwave(nv)) return ICW_EUNSUPPORTED;
+    if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     if (n > 1) {
         /* the device table first: a failed allocation or copy leaves the old inputs in force */
         IcwInDesc *fresh = nullptr;

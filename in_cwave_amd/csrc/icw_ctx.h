@@ -197,6 +197,9 @@ struct icw_ctx {
     /* icw_enable_stream_encode: the CWAVE encoders serve calls over streams with different inputs.  Off on
      * a fresh context, where they keep their refusal while the count is above 1 */
     bool enc_streams = false;
+    /* icw_enable_stream_cwave: icw_set_stream_input takes the CWAVE formats, also on a context whose input is
+     * CWAVE.  Off on a fresh context, where it keeps both refusals */
+    bool cw_streams = false;
     unsigned long long *enc_clipped = nullptr; /* [streams] icw_encode_cwave: saturated / NaN int16 samples (lazy) */
     unsigned long long *s1_stamps = nullptr;   /* ICW_S1_STAMPS=1: K5 phase stamps, printed per call */
     unsigned long long calls = 0;         /* icw_process_* calls so far (icw_prepare needs a fresh context) */

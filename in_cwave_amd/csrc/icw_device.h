@@ -25,7 +25,7 @@ struct IcwProg;
  * the kernels that read the format (K0) or the rate (K4, icw_advance); K2 and the rotation table get
  * the rate and the channels in their per-call selection rows (IcwK2Args.prog_id). */
 struct IcwInDesc {
-    uint32_t fmt, csz, fsz, nch;   /* real sample format, channel/frame bytes, channels */
+    uint32_t fmt, csz, fsz, nch;   /* sample format, channel/frame bytes (CWAVE: csz is the I/Q pair's), channels */
     uint32_t sample_rate, pad_;
     unsigned long long ssr;        /* sample_rate * ICW_HZ_SCALE */
 };
@@ -372,6 +372,21 @@ struct IcwK2Args {
      * stream's sample rate, row 4 its channels (they replace sample_rate / ssr / nch above) */
     const int32_t *prog_id;
     size_t slab_stride;            /* doubles per slab of trig_tab (slabs share trig_pitch) */
+};
+
+/* The direct-input form of the output kernel (icw_output_cw): a call over CWAVE streams with different
+ * inputs (icw_enable_stream_cwave) launches no K0 and K2 reads the file frames itself -- a stereo CW_F64
+ * frame through K0 is 32 B read, 32 B of rows written and 32 B read back.  These go beside IcwK2Args,
+ * as a second kernel argument, so that the argument layout of every other kernel that takes IcwK2Args
+ * (icw_output, icw_stream1, the fused FIR kernels) stays what it was.  The IcwK2Args of such a launch
+ * has cw and prog_id set; its xin / w rows are unused. */
+struct IcwDinArgs {
+    const unsigned char *in;       /* the call's first frame: stream s at in + s*in_stride, the block offset
+                                      (IcwK2Args.t0) applied with the stream's own frame size */
+    size_t in_stride;
+    const long long *pos;          /* [n_streams] reader position at the call's start */
+    const long long *fade;         /* [n_streams][3] n_samples, n_fade_in, n_fade_out */
+    const IcwInDesc *desc;         /* [n_streams] of the launch: the stream's CWAVE format, pair / frame bytes, channels */
 };
 
 /* Per-frame rotation table (one thread per frame): the Shift / PM factors depend only on the frame

@@ -237,6 +237,8 @@ struct CallPlan {
      * take each stream's own from the context's table dD or the selection rows */
     unsigned fmt = 0, rate = 0;
     bool mixin = false;
+    /* mixin over CWAVE streams (icw_enable_stream_cwave): no K0 and no xd rows, K2 reads the frames itself */
+    bool din = false;
     const IcwInDesc *dD = nullptr;
     unsigned csz = 0, nch = 0, fsz = 0;
     int osz = 0;
@@ -396,6 +398,20 @@ struct CallPlan {
         a2.sncnt = (!cw && cfg.iir_subnorm_reject) ? ds.sncnt + f0 * 4 : nullptr;
         a2.fes = fcm ? ds.fes + f0 * 4 * ICW_FES_PITCH : nullptr;
         return a2;
+    }
+
+    /* what K2's direct-input form takes beside k2_args(b): the call's first frame (the kernel applies the
+     * block offset at the stream's own frame size), the reader's state and the descriptor table */
+    IcwDinArgs din_args() const
+    {
+        IcwDinArgs ad;
+        memset(&ad, 0, sizeof(ad));
+        ad.in = d_in;
+        ad.in_stride = dis;
+        ad.pos = ds.pos + f0;
+        ad.fade = ds.fade + f0 * 3;
+        ad.desc = dD;
+        return ad;
     }
 
     /* the dither generator's / serial render's arguments for block b */
@@ -731,6 +747,7 @@ int CallPlan::enc_format(uint32_t cw_fmt, bool fir_ok)
     for (int i = 1; i < count; ++i) {
         const IcwInDesc &d = c->inputs[f0 + (size_t)i];
         if (d.fmt != fmt || d.nch != d0.nch) mixin = true;
+        if (d.fmt >= ICW_FMT_CW_F64) fmt = d.fmt;     /* a CWAVE stream anywhere in the call: refused below */
         fsz = std::max(fsz, d.fsz);
         nch = std::max(nch, d.nch);
     }
@@ -811,10 +828,14 @@ int CallPlan::resolve_plan()
     for (int i = 1; i < count; ++i) {
         const IcwInDesc &d = c->inputs[f0 + (size_t)i];
         if (d.fmt != fmt || d.nch != d0.nch || d.sample_rate != rate) mixin = true;
+        /* one kind per call: whether K1 runs is the call's decision, and the scratch rows differ (2 per
+         * real stream, 4 per complex one) */
+        if ((d.fmt >= ICW_FMT_CW_F64) != (fmt >= ICW_FMT_CW_F64)) return ICW_EUNSUPPORTED;
         fsz = std::max(fsz, d.fsz);
         nch = std::max(nch, d.nch);
     }
     if (mixin) dD = c->d_inputs + f0;
+    din = mixin && fmt >= ICW_FMT_CW_F64;
     osz = 2 * (cfg.need24bits ? 3 : 2);
     ssr = (unsigned long long)rate * ICW_HZ_SCALE;
     timing = flags & 4u;
@@ -1026,7 +1047,7 @@ int CallPlan::size_scratch()
     n_sets = std::min(n_blocks, c->tn.max_sets);
     for (int p = 0; p < n_sets && !fir_fused; ++p) {
         if (!cw && grow((void **)&c->w[p], &c->w_bytes[p], S * 4 * w_pitch * sizeof(double))) return ICW_ENOMEM;
-        if (grow((void **)&c->xd[p], &c->xd_bytes[p], S * 4 * x_pitch * sizeof(double))) return ICW_ENOMEM;
+        if (!din && grow((void **)&c->xd[p], &c->xd_bytes[p], S * 4 * x_pitch * sizeof(double))) return ICW_ENOMEM;
     }
     if (c->serial_render && !d_pre)
         for (int p = 0; p < n_sets; ++p)
@@ -1193,6 +1214,7 @@ int CallPlan::io_in(int b, hipStream_t s0) const
 int CallPlan::launch_k0(int b) const
 {
     if (fir_fused) return ICW_OK;                   /* KF2 converts inside the block's kernel */
+    if (din) return io_in(b, sA);                   /* K2 reads the frames itself: no kernel, no k0done to wait for */
     const int p = b % n_sets;
     const auto a0 = k0_args(b);
     if (b >= n_sets && !cw && sK != sA && hipStreamWaitEvent(sA, c->k1done[p], 0) != hipSuccess) return ICW_EDEVICE;
@@ -1300,7 +1322,12 @@ int CallPlan::run_blocks() const
             if (timing && hipEventRecord(c->ev[4 * b + 1], s2) != hipSuccess) return ICW_EDEVICE;
         } else {
             if (fir_async && hipStreamWaitEvent(s2, c->k0done[p], 0) != hipSuccess) return ICW_EDEVICE;
-            if (icw_launch_output(&a2, c->nord, cfg.iir_kahan, s2) != hipSuccess) return ICW_EDEVICE;
+            if (din) {
+                const auto ad = din_args();
+                if (icw_launch_output_cw(&a2, &ad, s2) != hipSuccess) return ICW_EDEVICE;
+            } else if (icw_launch_output(&a2, c->nord, cfg.iir_kahan, s2) != hipSuccess) {
+                return ICW_EDEVICE;
+            }
         }
         if (hipEventRecord(c->k2done[p], s2) != hipSuccess) return ICW_EDEVICE;
         /* the serial part (K4, K3b) on sR after K2(b): it then overlaps K2(b+1) instead of
@@ -1424,9 +1451,9 @@ int CallPlan::finish_call() const
             m1 += x;
             m2 += y;
         }
-        /* K0 of every launch block (a K5 call and the FIR converter launch none) */
+        /* K0 of every launch block (a K5 call, the FIR converter and K2's direct-input form launch none) */
         double m0 = 0;
-        for (int b = 0; b < n_blocks && !s1 && !fir; ++b) {
+        for (int b = 0; b < n_blocks && !s1 && !fir && !din; ++b) {
             float x = 0;
             if (hipEventElapsedTime(&x, c->ev_k0[2 * b], c->ev_k0[2 * b + 1]) != hipSuccess) return ICW_EDEVICE;
             m0 += x;

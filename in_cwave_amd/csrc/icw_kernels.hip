@@ -351,6 +351,88 @@ __global__ __launch_bounds__(ICW_K2_TILE, ICW_K2_MINWG) void icw_output(IcwK2Arg
     icw_output_body<N, KAHAN, TRIG, FCK, MIX>(a, blockIdx.x, blockIdx.y, lregs);
 }
 
+/* K2's direct-input form, for a call over CWAVE streams with different inputs (icw_set_stream_input
+ * with icw_enable_stream_cwave): no K0 runs and no xd rows exist -- the workgroup reads its stream's
+ * file frames itself.  One stream per workgroup, so the descriptor is wave-uniform: read through the
+ * constant address space it comes in by scalar loads, and the format / alignment choice is made once,
+ * before the workgroup's loads (icw_cw_dispatch), not per sample.  A workgroup issues the loads of all
+ * its a.tpw tiles up front -- one typed load per channel pair where the row is aligned to the pair --
+ * then per frame: mono duplicate, fade on all four values (xwave_reader.c:939-966), and the frame
+ * graph exactly as icw_output's MIX instances run it for a.cw (the stream's own list, rate and slab
+ * from the selection rows).  No quadrature IIR sums, so no N / KAHAN instances; the Hilbert phases and
+ * rings are not touched.  K4 and the serial renders read its iq / rpre rows as they read K2's. */
+template <bool TRIG>
+__global__ __launch_bounds__(ICW_K2_TILE, ICW_K2_MINWG) void icw_output_cw(IcwK2Args a, IcwDinArgs d)
+{
+    constexpr int TILE = ICW_K2_TILE;
+    extern __shared__ __attribute__((aligned(16))) double lregs[];   /* [n_regs][4][TILE] */
+    __shared__ unsigned red_clip[2][ICW_PK_SLOTS];
+    __shared__ double red_pk[2][ICW_PK_SLOTS];
+    const int tl = threadIdx.x, s = blockIdx.y;
+    const int T = a.T;
+    const int tw0 = blockIdx.x * TILE * a.tpw;
+    const int ntile = min(a.tpw, (T - tw0 + TILE - 1) / TILE);
+
+    const __attribute__((address_space(4))) int32_t *id = (const __attribute__((address_space(4))) int32_t *)a.prog_id;
+    IcwRate rt;
+    rt.sample_rate = (uint32_t)id[3 * a.n_streams + s];
+    rt.ssr = (unsigned long long)rt.sample_rate * ICW_HZ_SCALE;
+    icw_cprog *P = icw_prog_c(a.prog) + id[s];
+    const int slab = id[a.n_streams + s];
+    const bool use_tab = TRIG && a.trig_tab && slab >= 0 && a.n_frame[s] == a.n_frame[id[2 * a.n_streams + s]];
+    const size_t tab_off = slab >= 0 ? (size_t)slab * a.slab_stride : 0;
+
+    const __attribute__((address_space(4))) IcwInDesc *ds = (const __attribute__((address_space(4))) IcwInDesc *)d.desc + s;
+    const uint32_t fmt = ds->fmt, csz = ds->csz, fsz = ds->fsz;
+    const bool stereo = ds->nch > 1;
+    const unsigned char *row = d.in + (size_t)s * d.in_stride;
+    const uintptr_t al = (uintptr_t)row | (uintptr_t)fsz;
+    row += (size_t)(a.t0 + tw0) * fsz;                 /* the workgroup's first frame */
+
+    double q[ICW_K2_TPW][4];
+    icw_cw_dispatch(fmt, al, [&](auto fc, auto ac) {
+        constexpr int F = decltype(fc)::value;
+        constexpr bool AL = decltype(ac)::value != 0;
+#pragma unroll
+        for (int k = 0; k < ICW_K2_TPW; ++k) {
+            if (k < ntile && tw0 + k * TILE + tl < T) {
+                const unsigned char *fp = row + (size_t)(k * TILE + tl) * fsz;
+                icw_unpack_iq_f<F, AL>(fp, q[k][0], q[k][1]);
+                if (stereo) icw_unpack_iq_f<F, AL>(fp + csz, q[k][2], q[k][3]);
+                else { q[k][2] = q[k][0]; q[k][3] = q[k][1]; }
+            }
+        }
+    });
+
+    IcwRegFile R;
+    R.base = lregs + tl;
+    /* slots read but never written in the frame hold their block-start values */
+    for (int r = 0; r < P->n_persist; ++r) {
+        const double *b = a.bus + ((size_t)s * ICW_N_INPUTS + P->persist_slot[r]) * 4;
+        IcwLR v; v.lre = b[0]; v.lim = b[1]; v.rre = b[2]; v.rim = b[3];
+        R.set(P->persist_reg[r], v);
+    }
+    const long long pos0 = d.pos[s] + a.t0;
+    const long long ns = d.fade[s * 3 + 0], fi = d.fade[s * 3 + 1], fo = d.fade[s * 3 + 2];
+    unsigned clip_l = 0, clip_r = 0;
+    double pk_l = 0.0, pk_r = 0.0;
+#pragma unroll
+    for (int k = 0; k < ICW_K2_TPW; ++k) {
+        const int t = tw0 + k * TILE + tl;
+        if (k < ntile && t < T) {
+            const double fd = icw_fade(pos0 + t, ns, fi, fo);
+            if (fd >= 0.0) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) q[k][i] *= fd;
+            }
+            IcwLR in;
+            in.lre = q[k][0]; in.lim = q[k][1]; in.rre = q[k][2]; in.rim = q[k][3];
+            icw_frame_graph<TRIG, false, false, true>(a, P, R, s, t, in, use_tab, clip_l, clip_r, pk_l, pk_r, nullptr, tab_off, &rt);
+        }
+    }
+    if (a.do_render) icw_meters_wg(a, s, clip_l, clip_r, pk_l, pk_r, red_clip, red_pk);
+}
+
 /* Per-frame rotation table: the Shift / PM factors of frame t depend only on the modulator frame
  * counter, which all streams of a batch share while they are in step (same call-start counter).
  * One thread per frame evaluates each active channel's factor once (icw_trig, the same code as
@@ -694,6 +776,23 @@ extern "C" hipError_t icw_launch_output(const IcwK2Args *a, int nord, int kahan,
     case 20: return kahan ? launch_k2_t<20, true>(*a, st) : launch_k2_t<20, false>(*a, st);
     }
     return hipErrorInvalidValue;
+}
+
+/* K2's direct-input form: CWAVE streams with different inputs, the selection rows and the descriptor
+ * table set (the host checks the formats and that in_stride holds every stream's frames) */
+extern "C" hipError_t icw_launch_output_cw(const IcwK2Args *a2, const IcwDinArgs *d, hipStream_t st)
+{
+    if (!a2->cw || !a2->prog_id || !d->in || !d->pos || !d->fade || !d->desc) return hipErrorInvalidValue;
+    IcwK2Args a = *a2;
+    int tpw = ICW_K2_TPW;               /* as launch_k2_t: fewer tiles per workgroup while the grid is small */
+    while (tpw > 1 && (long)((a.T + ICW_K2_TILE * tpw - 1) / (ICW_K2_TILE * tpw)) * a.n_streams < 512) tpw >>= 1;
+    a.tpw = tpw;
+    const int span = ICW_K2_TILE * tpw;
+    dim3 grid((a.T + span - 1) / span, a.n_streams);
+    const size_t lds = (size_t)a.n_regs * 4 * ICW_K2_TILE * sizeof(double);
+    if (a.trig) hipLaunchKernelGGL((icw_output_cw<true>), grid, dim3(ICW_K2_TILE), lds, st, a, *d);
+    else hipLaunchKernelGGL((icw_output_cw<false>), grid, dim3(ICW_K2_TILE), lds, st, a, *d);
+    return hipGetLastError();
 }
 
 extern "C" hipError_t icw_launch_trig_table(const IcwTrigArgs *a, hipStream_t st)

@@ -19,6 +19,8 @@ extern "C" {
 hipError_t icw_launch_unpack(const IcwK0Args *a, hipStream_t st);
 hipError_t icw_launch_unpack_mixed(const IcwK0MixArgs *a, hipStream_t st);
 hipError_t icw_launch_output(const IcwK2Args *a, int nord, int kahan, hipStream_t st);
+/* K2 reading the CWAVE file frames itself (no K0, no xd rows): a call over CWAVE streams with different inputs */
+hipError_t icw_launch_output_cw(const IcwK2Args *a, const IcwDinArgs *d, hipStream_t st);
 hipError_t icw_launch_trig_table(const IcwTrigArgs *a, hipStream_t st);
 hipError_t icw_launch_graph_serial(const IcwK4Args *a, hipStream_t st);
 hipError_t icw_launch_advance(const IcwAdvArgs *a, hipStream_t st);

@@ -100,6 +100,53 @@ __device__ __forceinline__ void icw_fmt_dispatch(uint32_t fmt, uintptr_t al, F &
     }
 }
 
+/* one I/Q pair of CWAVE format FMT; AL: the address is aligned to the pair's size, so one typed load
+ * (16 bytes CW_F64, 8 CW_F32, 4 CW_I16) replaces the pair's byte loads.  The conversions are
+ * icw_unpack_iq's, so the bits are.  CW_I16_F32 is a 6-byte pair whose float is 2-byte aligned at
+ * best: always the byte form */
+template <int FMT, bool AL>
+__device__ __forceinline__ void icw_unpack_iq_f(const unsigned char *p, double &vI, double &vQ)
+{
+    if constexpr (AL && FMT == ICW_FMT_CW_F64) {
+        const double2 v = *(const double2 *)p;
+        vI = v.x;
+        vQ = v.y;
+    } else if constexpr (AL && FMT == ICW_FMT_CW_F32) {
+        const float2 v = *(const float2 *)p;
+        vI = (double)v.x;
+        vQ = (double)v.y;
+    } else if constexpr (AL && FMT == ICW_FMT_CW_I16) {
+        const unsigned u = *(const unsigned *)p;
+        vI = (double)(short)(u & 0xffffu);
+        vQ = (double)(short)(u >> 16);
+    } else {
+        icw_unpack_iq(p, FMT, vI, vQ);
+    }
+}
+
+/* calls f(icw_ic<FMT>, icw_ic<AL>) for a uniform CWAVE format, as icw_fmt_dispatch does for the real
+ * ones.  al: the OR of the row's base address and the frame size (aligned when its low bits below the
+ * pair's size are clear: the second channel's pair sits one pair further) */
+template <typename F>
+__device__ __forceinline__ void icw_cw_dispatch(uint32_t fmt, uintptr_t al, F &&f)
+{
+    switch (fmt) {
+    case ICW_FMT_CW_F64:
+        if (al & 15) f(icw_ic<ICW_FMT_CW_F64>(), icw_ic<0>());
+        else f(icw_ic<ICW_FMT_CW_F64>(), icw_ic<1>());
+        break;
+    case ICW_FMT_CW_I16:
+        if (al & 3) f(icw_ic<ICW_FMT_CW_I16>(), icw_ic<0>());
+        else f(icw_ic<ICW_FMT_CW_I16>(), icw_ic<1>());
+        break;
+    case ICW_FMT_CW_I16_F32: f(icw_ic<ICW_FMT_CW_I16_F32>(), icw_ic<0>()); break;
+    default:
+        if (al & 7) f(icw_ic<ICW_FMT_CW_F32>(), icw_ic<0>());
+        else f(icw_ic<ICW_FMT_CW_F32>(), icw_ic<1>());
+        break;
+    }
+}
+
 /* fade factor of xwave_unpack_csample (xwave_reader.c:918-936); < 0 means "no fade" */
 __device__ __forceinline__ double icw_fade(long long ix, long long ns, long long fi, long long fo)
 {

@@ -174,6 +174,11 @@ class Context:
         context)"""
         _check(self._lib.icw_enable_stream_encode(self.h, int(bool(on))), "icw_enable_stream_encode")
 
+    def enable_stream_cwave(self, on=True):
+        """icw_enable_stream_cwave: set_stream_input takes the CWAVE formats, also on a context whose input is
+        CWAVE (off on a fresh context); a call then covers streams of one kind"""
+        _check(self._lib.icw_enable_stream_cwave(self.h, int(bool(on))), "icw_enable_stream_cwave")
+
     def encode_frame_bytes(self, cw_format, first=0, count=None):
         """every stream's own CWAVE frame bytes in [first, first + count): an encode call's output rows hold
         stream i's frames at this size, in rows as wide as the call's widest stream needs"""
@@ -520,16 +525,22 @@ def wav_parse_file(path):
     return info
 
 
+def _batch_flags(merge_inputs, merge_cwave):
+    """icw_batch_opts.reserved_: the ICW_BATCH_* bits"""
+    return (abi.BATCH_MERGE_INPUTS if merge_inputs else 0) | (abi.BATCH_MERGE_CWAVE if merge_cwave else 0)
+
+
 def transcode_files(cfg, nodes, in_paths, out_paths, fade_in_ms=0, fade_out_ms=0, sec_align=0,
-                    block_frames=0, device=-1, merge_inputs=False):
+                    block_frames=0, device=-1, merge_inputs=False, merge_cwave=False):
     """icw_transcode_files: many files through the GPU path; returns (stats, per-file status).
-    merge_inputs: ICW_BATCH_MERGE_INPUTS, all real-input files in one context"""
+    merge_inputs: ICW_BATCH_MERGE_INPUTS, all real-input files in one context; merge_cwave:
+    ICW_BATCH_MERGE_CWAVE, all CWAVE files in one (another) context"""
     n = len(in_paths)
     ins = (C.c_char_p * max(1, n))(*[str(p).encode() for p in in_paths])
     outs = (C.c_char_p * max(1, n))(*[str(p).encode() for p in out_paths])
     arr = graph_nodes(nodes)
     o = abi.BatchOpts(fade_in_ms, fade_out_ms, sec_align, block_frames, device,
-                      abi.BATCH_MERGE_INPUTS if merge_inputs else 0)
+                      _batch_flags(merge_inputs, merge_cwave))
     st = abi.BatchStats()
     status = (C.c_int * max(1, n))()
     rc = load().icw_transcode_files(C.byref(cfg), arr, len(nodes), ins, outs, n, C.byref(o), C.byref(st), status)
@@ -542,7 +553,7 @@ def graph_form(cfg, nodes, bypass_list=0):
 
 
 def transcode_files_lists(cfg, node_lists, in_paths, out_paths, bypass_lists=None, fade_in_ms=0, fade_out_ms=0,
-                          sec_align=0, block_frames=0, device=-1, merge_inputs=False):
+                          sec_align=0, block_frames=0, device=-1, merge_inputs=False, merge_cwave=False):
     """icw_transcode_files_lists: file i through its own list node_lists[i] (bypass_lists[i] where
     given); returns (rc, stats, per-file status)"""
     n = len(in_paths)
@@ -554,7 +565,7 @@ def transcode_files_lists(cfg, node_lists, in_paths, out_paths, bypass_lists=Non
     cnt = (C.c_int * max(1, n))(*[len(nl) for nl in node_lists])
     byp = (C.c_int * max(1, n))(*[int(b) for b in bypass_lists]) if bypass_lists is not None else None
     o = abi.BatchOpts(fade_in_ms, fade_out_ms, sec_align, block_frames, device,
-                      abi.BATCH_MERGE_INPUTS if merge_inputs else 0)
+                      _batch_flags(merge_inputs, merge_cwave))
     st = abi.BatchStats()
     status = (C.c_int * max(1, n))()
     rc = load().icw_transcode_files_lists(C.byref(cfg), ptrs, cnt, byp, ins, outs, n, C.byref(o), C.byref(st), status)
@@ -562,7 +573,7 @@ def transcode_files_lists(cfg, node_lists, in_paths, out_paths, bypass_lists=Non
 
 
 def transcode_files_fir(cfg, node_lists, in_paths, out_paths, k_M, k_beta=8.0, bypass_lists=None, fade_in_ms=0,
-                        fade_out_ms=0, sec_align=0, block_frames=0, device=-1, merge_inputs=False):
+                        fade_out_ms=0, sec_align=0, block_frames=0, device=-1, merge_inputs=False, merge_cwave=False):
     """icw_transcode_files_fir: transcode_files_lists with the FIR Hilbert converter (k_M, k_beta) on every
     context of real-input files; returns (rc, stats, per-file status)"""
     n = len(in_paths)
@@ -574,7 +585,7 @@ def transcode_files_fir(cfg, node_lists, in_paths, out_paths, k_M, k_beta=8.0, b
     cnt = (C.c_int * max(1, n))(*[len(nl) for nl in node_lists])
     byp = (C.c_int * max(1, n))(*[int(b) for b in bypass_lists]) if bypass_lists is not None else None
     o = abi.BatchOpts(fade_in_ms, fade_out_ms, sec_align, block_frames, device,
-                      abi.BATCH_MERGE_INPUTS if merge_inputs else 0)
+                      _batch_flags(merge_inputs, merge_cwave))
     st = abi.BatchStats()
     status = (C.c_int * max(1, n))()
     rc = load().icw_transcode_files_fir(C.byref(cfg), ptrs, cnt, byp, ins, outs, n, int(k_M), float(k_beta), C.byref(o),
@@ -685,14 +696,14 @@ def cwave_encode_files_fft(in_paths, out_paths, cw_format=abi.FMT_CW_F64, device
 
 
 def transcode_files_devices(cfg, nodes, in_paths, out_paths, devices, fade_in_ms=0, fade_out_ms=0, sec_align=0,
-                            block_frames=0, merge_inputs=False):
+                            block_frames=0, merge_inputs=False, merge_cwave=False):
     """icw_transcode_files_devices: the files split over `devices` (one host thread each)"""
     n = len(in_paths)
     ins = (C.c_char_p * max(1, n))(*[str(p).encode() for p in in_paths])
     outs = (C.c_char_p * max(1, n))(*[str(p).encode() for p in out_paths])
     arr = graph_nodes(nodes)
     o = abi.BatchOpts(fade_in_ms, fade_out_ms, sec_align, block_frames, -1,
-                      abi.BATCH_MERGE_INPUTS if merge_inputs else 0)
+                      _batch_flags(merge_inputs, merge_cwave))
     dv = (C.c_int * len(devices))(*devices)
     st = abi.BatchStats()
     status = (C.c_int * max(1, n))()

@@ -209,8 +209,8 @@ int icw_set_input(icw_ctx *ctx, uint32_t sample_rate, uint32_t fmt, uint32_t cha
  * Limits, each refusal changing nothing:
  *   ICW_EINVAL        a range outside the context, rate 0 or above ICW_MAX_FS_SRC, channels 0, fmt
  *                     out of range.
- *   ICW_EUNSUPPORTED  - a CWAVE format (fmt >= ICW_FMT_CW_F64), or a context whose input is CWAVE:
- *                       whether the quadrature IIR runs at all is decided per call;
+ *   ICW_EUNSUPPORTED  - without icw_enable_stream_cwave: a CWAVE format (fmt >= ICW_FMT_CW_F64), or a context
+ *                       whose input is CWAVE: whether the quadrature IIR runs at all is decided per call;
  *                     - without icw_enable_stream_fir: the FIR converter is on (icw_set_fir_hilbert with
  *                       k_M > 0), or, while the count is above 1, icw_set_fir_hilbert(k_M > 0);
  *                     - while the count is above 1: ICW_F_DEBUG_INPUT, and -- without
@@ -227,6 +227,32 @@ int icw_set_input(icw_ctx *ctx, uint32_t sample_rate, uint32_t fmt, uint32_t cha
  *                     icw_set_fir_hilbert / icw_set_stream_input return ICW_EUNSUPPORTED as listed, the
  *                     converter stays off, and icw_encode_cwave returns its ICW_EINVAL for a context
  *                     without one).  icw_encode_cwave_fft takes no context and is not concerned.
+ *   icw_enable_stream_cwave(ctx, 1)  icw_set_stream_input takes ICW_FMT_CW_F64 .. ICW_FMT_CW_F32 from then on (1 or
+ *                     >= 2 channels, any rate up to ICW_MAX_FS_SRC; IcwInDesc-wise the "channel" is the I/Q
+ *                     pair), also on a context created with a CWAVE in_format: a library of CWAVE files in the
+ *                     four frame formats, mono and stereo, at several rates decodes in ONE context.  A fresh
+ *                     context has it off and keeps the two refusals above.  (ctx, 0) returns ICW_EUNSUPPORTED,
+ *                     changing nothing, while the count is above 1 and some stream's input is CWAVE; otherwise
+ *                     ICW_OK.  A NULL context: ICW_EINVAL.
+ *                     A context may then hold real and CWAVE streams side by side, but a call
+ *                     (icw_process_streams, icw_process_batch; icw_prepare's warm-up is one over every stream)
+ *                     covers streams of ONE kind: over both it returns ICW_EUNSUPPORTED and changes nothing --
+ *                     whether K1 runs stays a per-call decision.  A call whose CWAVE streams share one input
+ *                     runs the complex-input launches of a one-input context (K0 + K2); a call over differing
+ *                     CWAVE inputs launches no K0 -- the output kernel reads the file frames itself, with one
+ *                     typed load per I/Q pair where the stream's row and frame size are aligned to the pair
+ *                     (byte loads otherwise, and always for the 6-byte ICW_FMT_CW_I16_F32 pair).  Rows and
+ *                     the stride rule are as above.  Per stream the semantics are the reference's: mono feeds
+ *                     R with L's I/Q, the fade scales all four values at the stream's own rate, the frame
+ *                     counter wraps at the stream's own rate, and the Hilbert phases and rings are not touched
+ *                     -- a stream that plays WAV, CWAVE, WAV continues its converter where the first WAV
+ *                     track left it.  Host and device pointers, register-form and bus-form lists, per-stream
+ *                     lists, every render and FP_CHECK are served.  Refused, changing nothing
+ *                     (ICW_EUNSUPPORTED): a CWAVE format through icw_set_stream_input while the FIR converter
+ *                     is on (k_M > 0), or a real one that would leave CWAVE and other inputs side by side
+ *                     under it; icw_set_fir_hilbert(k_M > 0) while the count is above 1 and some stream's
+ *                     input is CWAVE; ICW_F_DEBUG_INPUT while the count is above 1, as ever.  The encoders
+ *                     return their ICW_EINVAL for a call with a CWAVE stream in it, as for CWAVE input.
  * Not served: icw_group and the icw_amod_* drop-in (their input stays context-wide).  The state blob
  * does not carry the input, as it does not carry the list: icw_set_state expects the stream's input to
  * be set as it was. */
@@ -234,6 +260,7 @@ int icw_set_stream_input(icw_ctx *ctx, int first, int count, uint32_t sample_rat
                          uint32_t channels);
 int icw_stream_input_count(const icw_ctx *ctx);
 int icw_enable_stream_encode(icw_ctx *ctx, int on);
+int icw_enable_stream_cwave(icw_ctx *ctx, int on);
 
 /* Live parameter changes (the GUI thread edits the DSP list, the renders and the
  * Hilbert converters while a decode thread runs).  Each applies to every stream of the context from
@@ -464,7 +491,9 @@ const char *icw_strerror(int status);
 /* The C ABI's version, for bindings to check at load time against the header they were built with.
  *   1  rounds 1-4;
  *   2  icw_mod_context_fopen takes need24bits (its 11th argument, in_cwave.c:212) -- a binding built
- *      against version 1 would pass an undefined bit depth. */
+ *      against version 1 would pass an undefined bit depth.
+ * Entry points that were only added (the per-stream setters and their opt-ins, icw_enable_stream_cwave the
+ * latest) leave it: a binding built against an earlier header of version 2 still calls what it knows. */
 #define ICW_ABI_VERSION 2
 int icw_abi_version(void);
 

@@ -58,8 +58,16 @@ typedef struct icw_batch_opts {
  * channels -- every stream gets its file's input through icw_set_stream_input (and its list where
  * lists differ) -- so a library of mixed formats keeps the batch width.  CWAVE files keep the grouping
  * by (rate, format, channels), a bus-form list still runs in a context of the files that carry the
- * same list, fades and tails are per file at the file's rate, and stats->n_groups counts contexts. */
+ * same list, fades and tails are per file at the file's rate, and stats->n_groups counts contexts.
+ * ICW_BATCH_MERGE_CWAVE: the same for the CWAVE files -- all of them in ONE context per device (another one
+ * than the real-input files': a call covers streams of one kind), which has icw_enable_stream_cwave on and
+ * gives every stream its file's CWAVE format, channels and rate, so a library encoded in the four frame
+ * formats, mono and stereo, at several rates decodes at full batch width.  Honoured by icw_transcode_files,
+ * _lists, _devices and _fir (there the CWAVE context runs without the converter, as CWAVE groups do).  The
+ * bits are independent; without a bit that kind of file is grouped as before, and the output bytes are the
+ * same either way. */
 #define ICW_BATCH_MERGE_INPUTS 1
+#define ICW_BATCH_MERGE_CWAVE  2
 
 typedef struct icw_batch_stats {
     int32_t  n_files, n_groups;         /* files transcoded; contexts used (one per input format) */
