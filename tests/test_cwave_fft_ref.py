@@ -1,7 +1,9 @@
 """CPU: pins tests/cwfft_ref.py, the long-double restatement of the direct-FFT converter's definition
 (include/icw_cwave.h: icw_encode_cwave_fft), before a GPU test uses it: against scipy.signal.hilbert, against
 the same formula through numpy.fft in float64, and on a single-bin cosine.  The GPU tolerance is built on
-numpy.fft's deviation from the long-double result, so that deviation is checked to be non-zero here."""
+numpy.fft's deviation from the long-double result, so that deviation is checked to be non-zero here.  The closed
+form for sparse tracks (impulse_q, the reference of the lengths the long-double transform cannot reach) is pinned
+to that transform within its own rounding, 2^-60 log2(P) max|Q|."""
 import numpy as np
 import pytest
 from scipy.signal import hilbert as signal_hilbert
@@ -54,6 +56,64 @@ def test_against_numpy_fft_and_scipy(n, p):
         assert float(np.max(np.abs(q_np.astype(np.longdouble) - q))) > 0.0
         tol, e_np = R.tolerance(x, q)
         assert e_np > 0.0 and tol >= 4.0 * e_np
+
+
+def _impulses(n, seed, k=16):
+    rng = np.random.default_rng(seed)
+    pos = rng.choice(n, size=min(k, n), replace=False)
+    amp = rng.integers(-30000, 30001, size=pos.size).astype(np.float64)
+    amp[amp == 0] = 1.0
+    return pos, amp
+
+
+@pytest.mark.parametrize("n", [3, 50, 1000, 1024, 4097])
+def test_impulse_closed_form_equals_the_long_double_transform(n):
+    """impulse_q at every frame against hilbert_q of the same sparse track, within the long-double transform's
+    own rounding: 64-bit significands, log2(P) stages"""
+    pos, amp = _impulses(n, 300 + n)
+    x = R.impulse_track(n, pos, amp)
+    assert np.count_nonzero(x) == pos.size
+    q = R.hilbert_q(x)
+    q_cf = R.impulse_q(n, pos, amp, np.arange(n))
+    assert q_cf.dtype == np.longdouble and q_cf.shape == (n,)
+    peak = float(np.max(np.abs(q)))
+    assert peak > 0.0
+    err = float(np.max(np.abs(q_cf - q)))
+    assert err <= 2.0 ** -60 * np.log2(R.pad_len(n)) * peak, (err, peak)
+
+
+def test_impulse_closed_form_two_points_is_zero():
+    assert not R.impulse_q(2, [0, 1], [123.0, -77.0], [0, 1]).any()
+
+
+def test_impulses_at_even_distances_contribute_exactly_nothing():
+    n, probe = 1000, 333
+    pos = np.array([333, 1, 335, 999, 331, 35])              # every distance to the probe is even (0 included)
+    amp = np.array([30000.0, -30000.0, 12345.0, -1.0, 777.0, 29999.0])
+    assert R.impulse_q(n, pos, amp, [probe])[0] == 0
+    # across the wrap of the padded length: d = (2 - 998) mod 1024 = 28
+    assert R.impulse_q(n, [998], [30000.0], [2])[0] == 0
+    # and one odd distance does contribute, with the sign of cot: the frame after a positive impulse is positive
+    assert R.impulse_q(n, pos, amp, [probe + 1])[0] != 0
+    assert R.impulse_q(n, [10], [1.0], [11])[0] > 0 > R.impulse_q(n, [10], [1.0], [9])[0]
+
+
+@pytest.mark.parametrize("n", [1000, 4097])
+def test_impulse_tolerance_is_tolerance_over_the_probes(n):
+    pos, amp = _impulses(n, 500 + n)
+    x = R.impulse_track(n, pos, amp)
+    at = np.arange(n)
+    q_cf = R.impulse_q(n, pos, amp, at)
+    bound, e_np = R.impulse_tolerance(n, pos, amp, at, q_cf)
+    bound_fft, e_fft = R.tolerance(x, R.hilbert_q(x))
+    # the two references agree to 2^-60 log2(P) max|Q|, far below e_np, so the two bounds agree to that
+    slack = 4 * 2.0 ** -60 * np.log2(R.pad_len(n)) * float(np.max(np.abs(q_cf)))
+    assert e_np > 0.0 and abs(e_np - e_fft) <= slack and abs(bound - bound_fft) <= 4 * slack
+    assert bound == max(4.0 * e_np, 2.0 ** -52 * np.log2(R.pad_len(n)) * float(np.max(np.abs(q_cf))))
+    # over a subset of the frames e_np can only shrink, and a precomputed numpy transform gives the same pair
+    sub = at[::7]
+    b2, e2 = R.impulse_tolerance(n, pos, amp, sub, q_cf[::7], q_np=R.hilbert_q_np(x))
+    assert e2 <= e_np and (b2, e2) == R.impulse_tolerance(n, pos, amp, sub, q_cf[::7])
 
 
 def test_two_frames_have_no_quadrature():

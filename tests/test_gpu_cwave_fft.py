@@ -4,8 +4,9 @@ The converter's definition is the project's (include/icw_cwave.h), restated in l
 (pinned on the CPU by test_cwave_fft_ref.py):
   1. accuracy: I bit for bit the unpacked samples; max|Q - reference| <= max(4 e_np, 2^-52 log2(P) max|reference|),
      e_np = numpy.fft's float64 deviation from the same reference -- a bound from the reference side only;
-  2. pass structure: the same check with the sub-transform capped so that a transform runs as one, two, three
-     and four passes, the pass count the plan reports, and equal bytes from two runs;
+  2. pass structure: the same check with the sub-transform capped so that a transform runs as one to six
+     passes (among them blocks narrower than a tile before the last pass, and a one-stage pass), the pass count
+     the plan reports, and equal bytes from two runs;
   3. every input format x mono / stereo / 3 channels; the lossy formats == cwenc_ref.frames of the F64 frames'
      I / Q, and the clip count;
   4. a track's bytes do not depend on the call's other tracks or on the pointer kind;
@@ -48,7 +49,7 @@ class Track:
 @pytest.fixture(scope="module")
 def tracks():
     """computed once, shared by the tests, never modified"""
-    return {n: Track(n, 1000 + n) for n in sorted(set(SIZES + [128]))}
+    return {n: Track(n, 1000 + n) for n in sorted(set(SIZES + [128, 1024, 2048, 32768]))}
 
 
 def check_accuracy(t, frames, what=""):
@@ -74,7 +75,8 @@ def test_accuracy(icw, tracks, n):
 
 # ------------------------------------------------------------------ 2. pass structure
 @pytest.mark.parametrize("n,cap,passes", [(128, 4, 2), (128, 7, 1), (128, 0, 1), (128, 3, 3), (128, 2, 4),
-                                          (4096, 4, 3), (4096, 7, 2), (4096, 0, 2)])
+                                          (4096, 4, 3), (4096, 7, 2), (4096, 0, 2),
+                                          (1024, 5, 2), (1024, 6, 2), (32768, 5, 3), (32768, 3, 5), (2048, 2, 6)])
 def test_pass_structure(icw, tracks, n, cap, passes):
     t = tracks[n]
     assert L.encode_cwave_fft_passes(n, cap) == passes
