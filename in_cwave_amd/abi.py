@@ -222,6 +222,7 @@ SIGNATURES = {
     "icw_last_timing": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i)]),
     "icw_last_k0_timing": (_i, [_vp, C.POINTER(C.c_double)]),
     "icw_last_k1_kernel": (_i, [_vp]),
+    "icw_last_dither_chunks": (_i, [_vp, C.POINTER(_i)]),
     "icw_get_fp_census": (_i, [_vp, _i, _i, C.POINTER(C.c_uint32)]),
     "icw_cwave_parse": (_i, [_vp, _sz, C.c_int64, C.POINTER(CwaveHeader), C.POINTER(C.c_uint32),
                              C.POINTER(C.c_uint32)]),

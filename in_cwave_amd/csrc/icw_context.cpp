@@ -1295,6 +1295,13 @@ int icw_last_k1_kernel(const icw_ctx *c)
     return c->last_k1;
 }
 
+int icw_last_dither_chunks(const icw_ctx *c, int *chunk_frames)
+{
+    if (!c) return ICW_EINVAL;
+    if (chunk_frames) *chunk_frames = c->last_dchunk_frames;
+    return c->last_dchunks;
+}
+
 int icw_last_timing(icw_ctx *c, double ms[2], int launches[2])
 {
     if (!c || !ms || !launches) return ICW_EINVAL;

@@ -184,6 +184,9 @@ struct icw_ctx {
     double last_ms[2]{};
     int last_launches[2]{};
     int last_k1 = -1;                     /* ICW_K1_* of the last real-input call */
+    /* the dither generator's chunks of the last icw_process_* call's first launch block and their length
+     * (icw_last_dither_chunks; 0: no generator ran) */
+    int last_dchunks = 0, last_dchunk_frames = 0;
     /* FIR Hilbert converter (icw_set_fir_hilbert): order (0: the quadrature IIR), taps, and the
      * per-stream input history [streams][2][M], double-buffered by launch block (fir_par) */
     int fir_M = 0, fir_nt = 0;

@@ -9,6 +9,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/icw.h"   /* ICW_RENDER_* (icw_dith_words) */
+
 #define ICW_MAX_OPS   64     /* DSP ops (nodes) per graph on the device path */
 #define ICW_MAX_REG_OPS 16   /* ops of a graph the frame-parallel register program accepts */
 #define ICW_MAX_REGS  8      /* value registers: `in`, node outputs, persistent slots */
@@ -320,6 +322,23 @@ struct IcwK3Args {
     uint32_t *dbk;                 /* [n_gen][ICW_DBK] the chunk's starting generator state (K3t -> K3f) */
 };
 #define ICW_DBK 628                /* u32 per backup: 624 words, idx, pad, prev_rnd (a double at 626) */
+
+/* MT19937 words one sample of the dither term consumes when no pair is rejected: two per dsopen value,
+ * RPDF and STPDF one value, TPDF two, GAUSS twelve (0: no generator) */
+constexpr int icw_dith_words(int render_type)
+{
+    return render_type == ICW_RENDER_GAUSS ? 24 : render_type == ICW_RENDER_TPDF ? 4
+         : (render_type == ICW_RENDER_RPDF || render_type == ICW_RENDER_STPDF) ? 2 : 0;
+}
+
+/* The split generator's chunk length: a launch block of T frames runs in chunks of this many frames, as
+ * many samples' words as a generator's row of wcap words holds (the block's length if that is less).
+ * The launcher (icw_launch_dither) cuts by it and the host reports it (icw_last_dither_chunks). */
+inline int icw_dith_chunk_frames(int T, size_t wcap, int W)
+{
+    const size_t fit = W > 0 ? wcap / (size_t)W : 0;
+    return fit < (size_t)T ? (int)fit : T;
+}
 
 /* Arguments of the output kernel (frame-parallel: Kahan output sums, unmix, graph, render). */
 struct IcwK2Args {

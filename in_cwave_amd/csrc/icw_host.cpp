@@ -450,6 +450,10 @@ struct CallPlan {
             a3.wpitch = a3.wcap = c->dwcap;
             a3.dflag = c->dflag;
             a3.dbk = c->dbk;
+            if (b == 0) {                /* what the launcher will cut this block into (icw_last_dither_chunks) */
+                c->last_dchunk_frames = icw_dith_chunk_frames(T, a3.wcap, icw_dith_words(a3.rk.render_type));
+                c->last_dchunks = c->last_dchunk_frames > 0 ? (T + c->last_dchunk_frames - 1) / c->last_dchunk_frames : 0;
+            }
         }
         return a3;
     }
@@ -1081,10 +1085,12 @@ int CallPlan::size_scratch()
         for (int p = 0; p < n_sets; ++p)
             if (grow((void **)&c->dith[p], &c->dith_bytes[p], S * 2 * (size_t)(Tb + 1) * sizeof(double))) return ICW_ENOMEM;
     if (dither) {
-        /* chunk rows: 2^26 words (256 MB) shared among the G generators, but never less than 1 024 frames
-         * of the widest draw (GAUSS, 24 words per sample) and never more than the block's.  The floor
-         * wins over the 2^26 share from 2 731 generators on, so the buffer is G * cap <= max(2^26,
-         * 24 576 G) words: 256 MB up to there, 96 KB per generator beyond */
+        /* chunk rows (a row of cap words holds icw_dith_chunk_frames frames of the call's draw, icw_device.h:
+         * the one place the chunk length is worked out): 2^26 words (256 MB) shared among the G
+         * generators, but never less than 1 024 frames of the widest draw (GAUSS, 24 words per sample)
+         * and never more than the block's.  The floor wins over the 2^26 share from 2 731 generators on,
+         * so the buffer is G * cap <= max(2^26, 24 576 G) words: 256 MB up to there, 96 KB per generator
+         * beyond */
         const size_t G = S * 2;
         size_t cap = std::max<size_t>(((size_t)1 << 26) / G, (size_t)24 * 1024);
         cap = std::min(cap, (size_t)24 * (size_t)(Tb + 1));
@@ -1479,6 +1485,7 @@ int icw_process_streams(icw_ctx *c, int first, int count, const void *in, size_t
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c)) return ICW_EDEVICE;
     ++c->calls;
+    c->last_dchunks = c->last_dchunk_frames = 0;
     CallPlan pl(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
     pl.dbg = dbg;
     int rc;

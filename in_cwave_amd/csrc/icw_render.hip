@@ -227,7 +227,7 @@ __device__ __forceinline__ void icw_dither_coop_body(const IcwK3Args &a, int g, 
  *   K3f  icw_dith_fix      a wave per flagged generator only: the chunk again from the backup, the
  *                          sequential way (icw_dither_coop_body, rejections and all), output and state.
  * The serial part left is the twist chain itself; K3a did the windows' tempering, pairing, ballots and
- * samples on the same wave between twists.  Chunks of at most a.wcap / W frames (icw_launch_dither). */
+ * samples on the same wave between twists.  Chunks of icw_dith_chunk_frames (icw_device.h) frames. */
 __global__ __launch_bounds__(64) void icw_dith_twist(IcwK3Args a, int W)
 {
     __shared__ uint32_t mt[624];
@@ -1127,8 +1127,8 @@ template <int RT>
 static hipError_t icw_launch_dither_t(const IcwK3Args *a, hipStream_t st)
 {
     if (!a->wbuf) return hipErrorInvalidValue;
-    constexpr int W = 2 * (RT == ICW_RENDER_GAUSS ? 12 : (RT == ICW_RENDER_TPDF ? 2 : 1));
-    const int chunk = (int)std::min<size_t>((size_t)a->T, a->wcap / W);
+    constexpr int W = icw_dith_words(RT);
+    const int chunk = icw_dith_chunk_frames(a->T, a->wcap, W);
     if (chunk <= 0) return hipErrorInvalidValue;
     for (int t0 = 0; t0 < a->T; t0 += chunk) {
         IcwK3Args c = *a;

@@ -420,6 +420,15 @@ class Context:
         """ICW_K1_* of the last real-input call: 0 lane-per-chain, 1 pair, 2 MFMA, 3 row broadcast"""
         return int(self._lib.icw_last_k1_kernel(self.h))
 
+    def last_dither_chunks(self):
+        """icw_last_dither_chunks: (chunks, chunk_frames) of the dither generator over the first launch block of
+        the last process call; (0, 0) if that call ran no generator"""
+        v = C.c_int()
+        n = int(self._lib.icw_last_dither_chunks(self.h, C.byref(v)))
+        if n < 0:
+            _check(n, "icw_last_dither_chunks")
+        return n, v.value
+
     def last_k0_ms(self):
         """icw_last_k0_timing: K0's time in the last timed call, summed over its launch blocks"""
         v = C.c_double()

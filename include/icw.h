@@ -478,6 +478,12 @@ int icw_last_k0_timing(icw_ctx *ctx, double *ms);
 #define ICW_K1_FC     4   /* icw_iir_state_fc: FP_CHECK (cfg.fp_check) arithmetic and census */
 int icw_last_k1_kernel(const icw_ctx *ctx);
 
+/* The split dither generator cuts a launch block into chunks, as many frames as its word rows hold
+ * (DESIGN 4).  Returns the number of chunks of the first launch block of the last icw_process_* call, 0 if
+ * that call ran no generator (a ROUND render); chunk_frames, which may be null, receives the chunk length
+ * used for that block (the last chunk may be shorter). */
+int icw_last_dither_chunks(const icw_ctx *ctx, int *chunk_frames);
+
 /* FP-exception census of stream s (FP_EXCEPT_STATS, fp_check.h:62-72) when cfg.fp_check is set:
  * counts[0] Hilbert left (mc->fes_hilb_left), [1] Hilbert right, [2] render left (fes_sr_left),
  * [3] render right; each {total, snan, qnan, ninf, nden, pden, pinf}.  reset != 0 clears them
@@ -492,8 +498,9 @@ const char *icw_strerror(int status);
  *   1  rounds 1-4;
  *   2  icw_mod_context_fopen takes need24bits (its 11th argument, in_cwave.c:212) -- a binding built
  *      against version 1 would pass an undefined bit depth.
- * Entry points that were only added (the per-stream setters and their opt-ins, icw_enable_stream_cwave the
- * latest) leave it: a binding built against an earlier header of version 2 still calls what it knows. */
+ * Entry points that were only added (the per-stream setters and their opt-ins, icw_enable_stream_cwave,
+ * icw_last_dither_chunks the latest) leave it: a binding built against an earlier header of version 2 still
+ * calls what it knows. */
 #define ICW_ABI_VERSION 2
 int icw_abi_version(void);
 
