@@ -311,6 +311,9 @@ def test_large_batch_sampled_against_oracle(oracle, icw, streams, ch):
     """BASELINE C3 / C4 shard sizes (4096 mono, 2048 stereo streams per GPU) on a short run: many
     lane groups, the mono dedup, several CU-partitioned K1 workgroups.  A sample of streams from
     the start, the middle, the last lane group and the very end is checked bit for bit."""
+    # These widths fill every wave and lane group, and the streams are sampled: the ragged widths (partial
+    # last groups, both sides of the automatic kernel choices), with every stream of distinct inputs
+    # checked, are in test_gpu_batch_widths.py.
     fs = 96000 if ch == 1 else 48000
     cfg = graph.default_config(fs, channels=ch)
     nodes = graph.graph_master_only() if ch == 1 else graph.graph_shift_master()
