@@ -183,6 +183,9 @@ SIGNATURES = {
     "icw_graph_form": (_i, [C.POINTER(Config), C.POINTER(Node), _i, _i]),
     "icw_set_render": (_i, [_vp, C.POINTER(RenderCfg)]),
     "icw_set_outbits": (_i, [_vp, _i]),
+    "icw_set_stream_render": (_i, [_vp, _i, _i, C.POINTER(RenderCfg), _i]),
+    "icw_stream_render_count": (_i, [_vp]),
+    "icw_stream_render_size": (_i, [_vp, _i]),
     "icw_clear_bus_slot": (_i, [_vp, _i]),
     "icw_graph_del_last": (_i, [_vp]),
     "icw_graph_del_all": (_i, [_vp]),

@@ -145,7 +145,7 @@ void free_all(icw_ctx *c)
 {
     DevState &s = c->st;
     void *ptrs[] = {c->enc_clipped, c->s1_stamps, s.mt, s.mt_idx, s.rs, s.lr_equal, s.fes, s.err, s.hist, s.sncnt, s.hq_phase, s.pos, s.fade,
-                    s.n_frame, s.bus, s.clips, s.peak_bits, c->d_prog, c->d_progs, c->d_pid, c->d_inputs, c->trig, c->d_in, c->d_out,
+                    s.n_frame, s.bus, s.clips, s.peak_bits, c->d_prog, c->d_progs, c->d_pid, c->d_inputs, c->d_rtab, c->trig, c->d_in, c->d_out,
                     c->d_pre, c->d_xin,
                     c->d_fir_g, c->fir_hist[0], c->fir_hist[1], c->dwords, c->dbk, c->dflag};
     for (void *p : ptrs)
@@ -267,7 +267,11 @@ int apply_graph(icw_ctx *c, std::vector<icw_node> &nv, int bypass, const std::ve
     int rc = build_prog(cfg, nv, P);
     if (rc) return rc;
     if (!c->tn.chain_ok) P.chain = P.sig = 0;
-    const bool serial = needs_serial(cfg, c->rk, P, c->tn.dith_par), rstate = needs_render_state(cfg, c->rk, P, c->tn.dith_par);
+    /* per-stream renders in force: K4 hands over to one serial render, so a bus-form list is refused
+     * (include/icw.h); how each entry runs does not depend on a register-form list */
+    if (!c->renders.empty() && P.is_bus) return ICW_EUNSUPPORTED;
+    const bool serial = c->renders.empty() ? needs_serial(cfg, c->rk, P, c->tn.dith_par) : c->serial_render;
+    const bool rstate = c->renders.empty() ? needs_render_state(cfg, c->rk, P, c->tn.dith_par) : c->render_state;
     if (rstate && (rc = ensure_render_state(c))) return rc;
     if (hipMemcpy(c->d_prog, &P, sizeof(IcwProg), hipMemcpyHostToDevice) != hipSuccess) return ICW_EDEVICE;
     c->cfg.bypass_list = cfg.bypass_list;
@@ -407,6 +411,155 @@ int count_inputs(const std::vector<IcwInDesc> &v)
         if (k == seen.size()) seen.push_back(&d);
     }
     return (int)seen.size();
+}
+
+/* ---- per-stream renders (icw_set_stream_render) ---- */
+
+/* a (render, depth) pair as a table entry: render_consts, and how it runs behind the context's list */
+RenderEnt make_render(const icw_ctx *c, const icw_render_cfg &r, int is24)
+{
+    RenderEnt e;
+    e.cfg = r;
+    e.is24 = is24 ? 1 : 0;
+    render_consts(r, e.is24, c->tn.k3r_spec, e.rk);
+    icw_config cfg = c->cfg;
+    cfg.render = r;
+    cfg.need24bits = e.is24;
+    e.serial = needs_serial(cfg, e.rk, c->prog, c->tn.dith_par);
+    e.rstate = needs_render_state(cfg, e.rk, c->prog, c->tn.dith_par);
+    e.dither = r.render_type != ICW_RENDER_ROUND;
+    return e;
+}
+
+bool same_render(const RenderEnt &a, const RenderEnt &b)
+{
+    return a.is24 == b.is24 && !memcmp(&a.cfg.dth_bits, &b.cfg.dth_bits, sizeof(double)) &&
+           a.cfg.quantz_type == b.cfg.quantz_type && a.cfg.render_type == b.cfg.render_type &&
+           a.cfg.nshape_type == b.cfg.nshape_type && a.cfg.sign_bits16 == b.cfg.sign_bits16 &&
+           a.cfg.sign_bits24 == b.cfg.sign_bits24;
+}
+
+/* the assignment in force as a table: the context's entries, or its one render as entry 0 of every stream */
+void renders_in_force(const icw_ctx *c, std::vector<RenderEnt> &ents, std::vector<int32_t> &of)
+{
+    ents = c->renders;
+    of = c->render_of;
+    if (ents.empty()) {
+        RenderEnt e;
+        e.cfg = c->cfg.render;
+        e.is24 = c->cfg.need24bits ? 1 : 0;
+        e.rk = c->rk;
+        e.serial = c->serial_render;
+        e.rstate = c->render_state;
+        e.dither = c->cfg.render.render_type != ICW_RENDER_ROUND;
+        ents.push_back(e);
+        of.assign((size_t)c->n_streams, 0);
+    }
+}
+
+/* the clip bound stream s's peak is measured against */
+double stream_hi(const icw_ctx *c, int s)
+{
+    return c->renders.empty() ? c->rk.hi : c->renders[(size_t)c->render_of[(size_t)s]].rk.hi;
+}
+
+/* fold_peaks for the streams of [first, first + count) whose bound moves to new_hi[s - first] */
+bool fold_peaks_range(icw_ctx *c, int first, int count, const std::vector<double> &new_hi)
+{
+    std::vector<unsigned long long> pb((size_t)count * 2);
+    if (hipMemcpy(pb.data(), c->st.peak_bits + (size_t)first * 2, pb.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return false;
+    for (int i = 0; i < count; ++i) {
+        const double hi = stream_hi(c, first + i);
+        if (hi == new_hi[(size_t)i]) continue;
+        if (hipMemset(c->st.peak_bits + (size_t)(first + i) * 2, 0, 16) != hipSuccess) return false;
+        for (int ch = 0; ch < 2; ++ch) {
+            double mx;
+            memcpy(&mx, &pb[(size_t)i * 2 + ch], 8);
+            const double cv = mx ? 20.0 * log10(mx / hi) : ICW_SR_ZERO_SIGNAL_DB;
+            double &pv = c->peak_db[(size_t)(first + i) * 2 + ch];
+            if (cv > pv) pv = cv;
+        }
+    }
+    return true;
+}
+
+/* Install an assignment (the caller holds c->mu and has waited for the context's work): ents[of[s]] is
+ * stream s's render, and the shaping state of streams [first, first + count) restarts.  The table is
+ * compacted like the list table -- equal entries become one, unused ones go, the survivors numbered in
+ * order of their first stream.  Refusals and the device copies (table and index row, into fresh memory)
+ * come before any state is touched, so a failure leaves the old renders in force; then the peaks of the
+ * streams whose bound moves are folded against their old bound, the shaping state restarts (the MT19937
+ * words go on) and the host side follows.  One entry left: a one-render context again. */
+int install_renders(icw_ctx *c, std::vector<RenderEnt> &ents, std::vector<int32_t> &of, int first, int count)
+{
+    std::vector<RenderEnt> ne;
+    std::vector<int32_t> map(ents.size(), -1);
+    for (int32_t &e : of) {
+        if (map[(size_t)e] < 0) {
+            size_t k = 0;
+            while (k < ne.size() && !same_render(ne[k], ents[(size_t)e])) ++k;
+            if (k == ne.size()) ne.push_back(ents[(size_t)e]);
+            map[(size_t)e] = (int32_t)k;
+        }
+        e = map[(size_t)e];
+    }
+    const size_t n = ne.size(), S = (size_t)c->n_streams;
+    /* more than one render: K3's FP_CHECK form, K4 and the FIR converter's fused render take one */
+    if (n > 1 && (c->fir_M > 0 || c->cfg.fp_check || c->prog.is_bus)) return ICW_EUNSUPPORTED;
+    bool serial = false, rstate = false;
+    for (const RenderEnt &e : ne) {
+        serial |= e.serial;
+        rstate |= e.rstate;
+    }
+    int rc;
+    if (rstate && (rc = ensure_render_state(c))) return rc;
+    IcwRenderEnt *fresh = nullptr;
+    if (n > 1) {
+        const size_t tb = n * sizeof(IcwRenderEnt);
+        std::vector<unsigned char> h(tb + S * sizeof(int32_t), 0);
+        for (size_t k = 0; k < n; ++k) {
+            IcwRenderEnt d;
+            memset(&d, 0, sizeof(d));
+            d.rk = ne[k].rk;
+            d.serial = ne[k].serial ? 1 : 0;
+            d.dither = ne[k].dither ? 1 : 0;
+            d.fsz = ne[k].osz();
+            memcpy(h.data() + k * sizeof(IcwRenderEnt), &d, sizeof(d));
+        }
+        memcpy(h.data() + tb, of.data(), S * sizeof(int32_t));
+        if (hipMalloc((void **)&fresh, h.size()) != hipSuccess) return ICW_ENOMEM;
+        if (hipMemcpy(fresh, h.data(), h.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(fresh);
+            return ICW_EDEVICE;
+        }
+    }
+    std::vector<double> new_hi((size_t)count);
+    for (int i = 0; i < count; ++i) new_hi[(size_t)i] = ne[(size_t)of[(size_t)(first + i)]].rk.hi;
+    bool ok = fold_peaks_range(c, first, count, new_hi);
+    /* sound_render_recalc: prev_rnd, the shaper rings and prev_ns_err start again, the RNG goes on */
+    if (ok && c->st.rs)
+        ok = hipMemset(c->st.rs + (size_t)first * 2 * ICW_RSTATE, 0, (size_t)count * 2 * ICW_RSTATE * sizeof(double)) == hipSuccess;
+    if (!ok) {
+        if (fresh) (void)hipFree(fresh);
+        return ICW_EDEVICE;
+    }
+    if (c->d_rtab) (void)hipFree(c->d_rtab);
+    c->d_rtab = fresh;
+    c->d_rof = fresh ? (int32_t *)((unsigned char *)fresh + n * sizeof(IcwRenderEnt)) : nullptr;
+    c->cfg.render = ne[0].cfg;
+    c->cfg.need24bits = ne[0].is24;
+    c->rk = ne[0].rk;
+    c->serial_render = serial;
+    c->render_state = rstate;
+    if (n == 1) {
+        c->renders.clear();
+        c->render_of.clear();
+    } else {
+        c->renders.swap(ne);
+        c->render_of.swap(of);
+    }
+    return ICW_OK;
 }
 
 }  // namespace
@@ -656,6 +809,8 @@ int icw_set_fir_hilbert(icw_ctx *c, int32_t M, double beta)
     /* nor beside per-stream CWAVE inputs (icw_enable_stream_cwave): the converter's per-stream kernels read
      * real formats only, and icw_set_stream_input refuses to build that state from its side */
     if (M > 0 && c->n_inputs > 1 && any_cwave(c->inputs)) return ICW_EUNSUPPORTED;
+    /* nor beside per-stream renders (icw_set_stream_render): the fused converter renders with one */
+    if (M > 0 && !c->renders.empty()) return ICW_EUNSUPPORTED;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     c->pid_valid = false;                 /* with the converter on, every (list, rate) pair has a slab */
     for (double *&h : c->fir_hist)
@@ -1003,6 +1158,15 @@ int icw_set_render(icw_ctx *c, const icw_render_cfg *r)
     if (!c || !r || !render_cfg_ok(*r)) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+    if (!c->renders.empty()) {
+        /* the streams' renders differ: every stream gets the new setting at its own depth, so the table
+         * collapses to as many entries as depths in force; every stream's shaping state restarts */
+        std::vector<RenderEnt> ents;
+        std::vector<int32_t> of;
+        renders_in_force(c, ents, of);
+        for (RenderEnt &e : ents) e = make_render(c, *r, e.is24);
+        return install_renders(c, ents, of, 0, c->n_streams);
+    }
     IcwRenderK k;
     render_consts(*r, c->cfg.need24bits, c->tn.k3r_spec, k);
     icw_config cfg = c->cfg;
@@ -1032,6 +1196,14 @@ int icw_set_outbits(icw_ctx *c, int need24bits)
     const int is24 = need24bits ? 1 : 0;
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+    if (!c->renders.empty()) {
+        /* the streams' renders differ: every stream gets the new depth and keeps its own setting */
+        std::vector<RenderEnt> ents;
+        std::vector<int32_t> of;
+        renders_in_force(c, ents, of);
+        for (RenderEnt &e : ents) e = make_render(c, e.cfg, is24);
+        return install_renders(c, ents, of, 0, c->n_streams);
+    }
     IcwRenderK k;
     render_consts(c->cfg.render, is24, c->tn.k3r_spec, k);
     icw_config cfg = c->cfg;
@@ -1084,7 +1256,44 @@ int icw_set_hilbert_config(icw_ctx *c, int kahan, int subnorm_reject)
     return ICW_OK;
 }
 
-int icw_render_size(const icw_ctx *c) { return c ? (c->cfg.need24bits ? 3 : 2) : ICW_EINVAL; }
+/* the largest sample size in force, so that a buffer sized by it holds every stream's frames */
+int icw_render_size(const icw_ctx *c)
+{
+    if (!c) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(const_cast<icw_ctx *>(c)->mu);
+    int is24 = c->cfg.need24bits ? 1 : 0;
+    for (const RenderEnt &e : c->renders) is24 |= e.is24;
+    return is24 ? 3 : 2;
+}
+
+/* icw_set_render followed by icw_set_outbits for streams [first, first + count) (include/icw.h) */
+int icw_set_stream_render(icw_ctx *c, int first, int count, const icw_render_cfg *r, int need24bits)
+{
+    if (!c || first < 0 || count <= 0 || first > c->n_streams - count || !r || !render_cfg_ok(*r)) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+    /* the assignment as it is, the new entry for the range, then the table compacted */
+    std::vector<RenderEnt> ents;
+    std::vector<int32_t> of;
+    renders_in_force(c, ents, of);
+    ents.push_back(make_render(c, *r, need24bits ? 1 : 0));
+    for (int s = first; s < first + count; ++s) of[(size_t)s] = (int32_t)ents.size() - 1;
+    return install_renders(c, ents, of, first, count);
+}
+
+int icw_stream_render_count(const icw_ctx *c)
+{
+    if (!c) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(const_cast<icw_ctx *>(c)->mu);
+    return c->renders.empty() ? 1 : (int)c->renders.size();
+}
+
+int icw_stream_render_size(const icw_ctx *c, int s)
+{
+    if (!c || s < 0 || s >= c->n_streams) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(const_cast<icw_ctx *>(c)->mu);
+    return (c->renders.empty() ? c->cfg.need24bits != 0 : c->renders[(size_t)c->render_of[(size_t)s]].is24 != 0) ? 3 : 2;
+}
 
 int icw_host_alloc(size_t bytes, void **p)
 {
@@ -1142,7 +1351,7 @@ int icw_get_meters(icw_ctx *c, int s, int reset, icw_meters *m)
          * 20*log10(max|q| / hi) because the map is monotone; 0 -> SR_ZERO_SIGNAL_DB */
         double mx;
         memcpy(&mx, &pb[ch], 8);
-        double cv = mx / c->rk.hi;
+        double cv = mx / stream_hi(c, s);     /* the stream's own bound (icw_set_stream_render) */
         cv = cv ? 20.0 * log10(cv) : ICW_SR_ZERO_SIGNAL_DB;
         double &pv = c->peak_db[(size_t)s * 2 + ch];
         if (cv > pv) pv = cv;

@@ -71,6 +71,16 @@ struct CuSplit {
     hipStream_t k1 = nullptr, rest = nullptr, dith = nullptr, render = nullptr;
 };
 
+/* one entry of the context's render table: the setting as given, its constants and how it runs.  With more
+ * than one entry no list is bus form and FP_CHECK is off (both refused), so `serial` is the render's own */
+struct RenderEnt {
+    icw_render_cfg cfg{};
+    int is24 = 0;
+    IcwRenderK rk{};
+    bool serial = false, dither = false, rstate = false;
+    int osz() const { return is24 ? 6 : 4; }      /* bytes per output frame */
+};
+
 #pragma GCC visibility pop
 
 struct icw_ctx {
@@ -114,6 +124,15 @@ struct icw_ctx {
     std::vector<IcwInDesc> inputs;        /* [streams] */
     int n_inputs = 1;
     IcwInDesc *d_inputs = nullptr;
+    /* per-stream renders (icw_set_stream_render).  While every stream has one (render, depth) the table is
+     * empty and cfg.render / cfg.need24bits / rk / serial_render above and below are that render, as
+     * before.  Otherwise: the distinct entries, every stream's index, and on the device the table followed
+     * by the index row [n_streams] in one allocation (d_rof points into it); cfg.render, cfg.need24bits
+     * and rk then hold entry 0, serial_render and render_state whether any entry needs them. */
+    std::vector<RenderEnt> renders;
+    std::vector<int32_t> render_of;       /* [streams] */
+    IcwRenderEnt *d_rtab = nullptr;
+    int32_t *d_rof = nullptr;
     DevState st;
     /* host mirrors of meters that survive "reset" semantics */
     std::vector<double> peak_db;          /* [streams][2] */

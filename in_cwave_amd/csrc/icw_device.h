@@ -323,6 +323,37 @@ struct IcwK3Args {
 };
 #define ICW_DBK 628                /* u32 per backup: 624 words, idx, pad, prev_rnd (a double at 626) */
 
+/* One render of the context's render table (icw_set_stream_render), kept on the device while the streams'
+ * renders differ: its constants, how it runs and its frame size. */
+struct IcwRenderEnt {
+    IcwRenderK rk;
+    int32_t serial;                /* the serial render kernels take it (a noise shaper, or ICW_DITH_PAR=0) */
+    int32_t dither;                /* render_type != ROUND: K3a's rows hold its dither terms */
+    int32_t fsz;                   /* bytes per output frame: 4 (16-bit) or 6 (24-bit) */
+    int32_t pad_;
+};
+
+/* Arguments of the mixed render kernel (KR, icw_render_mixed): the frame-parallel renders of a call over
+ * streams with different renders, from the pre-render rows K2 wrote with do_render 0.  Workgroup row y is
+ * stream y of the launch; its entry is tab[ent[y]], and a stream whose entry is serial is skipped (the
+ * serial render kernels write its frames, run by run). */
+struct IcwKRArgs {
+    const double *pre;             /* [n_streams][pre_stride]: (lOut, rOut) per frame of the block */
+    size_t pre_stride;             /* doubles per stream */
+    unsigned char *out;            /* the call's first frame: stream s at out + s*out_stride, the block offset
+                                      t0 applied with the stream's own frame size */
+    size_t out_stride;
+    const IcwRenderEnt *tab;       /* the context's render table */
+    const int32_t *ent;            /* [n_streams] of the launch: index into tab */
+    const double *dith;            /* nullable: K3a's rnd * dth_mul, generator-major [n_streams * 2][dith_pitch],
+                                      filled for the dithered streams only */
+    size_t dith_pitch;
+    uint32_t *clips;               /* [n_streams][2] */
+    unsigned long long *peak_bits; /* [n_streams][2] */
+    int32_t n_streams, T;
+    long long t0;                  /* block offset into the call */
+};
+
 /* MT19937 words one sample of the dither term consumes when no pair is rejected: two per dsopen value,
  * RPDF and STPDF one value, TPDF two, GAUSS twelve (0: no generator) */
 constexpr int icw_dith_words(int render_type)

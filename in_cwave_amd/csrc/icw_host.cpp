@@ -241,6 +241,20 @@ struct CallPlan {
     bool din = false;
     const IcwInDesc *dD = nullptr;
     unsigned csz = 0, nch = 0, fsz = 0;
+    /* the resolved render: the one every stream of the call has -- the context's, or the one table entry
+     * all of them share -- or (mixr, icw_set_stream_render) streams with different entries: then K2 leaves
+     * every stream's pre-render doubles (serial_render holds, as for a serial render), the call's streams are
+     * cut into runs of one entry each, osz is the widest frame and rk is unread */
+    IcwRenderK rk{};
+    bool serial_render = false, mixr = false;
+    unsigned render_type = 0;
+    struct Run {
+        int s0, n;                 /* the run's first stream (index into the call's range) and its streams */
+        const RenderEnt *e;
+    };
+    std::vector<Run> runs;
+    int serial_gen = 0;            /* mixr: the call's channels with a serial entry (the K3c / K3b choice) */
+    bool any_par = false;          /* mixr: some stream's entry is frame-parallel (KR runs) */
     int osz = 0;
     /* the encoders: the CWAVE output format and its frame bytes at the call's channels (mixin: the widest
      * stream's -- every stream's row holds n_frames of them, its own frames are icw_enc_frame_bytes) */
@@ -373,15 +387,15 @@ struct CallPlan {
         if (d_pre) {
             a2.pre = d_pre + (size_t)t0 * 2;
             a2.pre_stride = (size_t)n_frames * 2;
-        } else if (c->serial_render) {
+        } else if (serial_render) {
             a2.pre = c->rpre[p];
             a2.pre_stride = (size_t)T * 2;
         }
-        a2.do_render = c->serial_render ? 0 : 1;
+        a2.do_render = serial_render ? 0 : 1;
         a2.n_regs = lp->chain ? 0 : lp->n_regs;    /* a chain program keeps its values in VGPRs */
         a2.clips = ds.clips + f0 * 2;
         a2.peak_bits = ds.peak_bits + f0 * 2;
-        a2.rk = c->rk;
+        a2.rk = rk;
         memcpy(a2.pc, c->pc, sizeof(a2.pc));
         memcpy(a2.pd, c->pd, sizeof(a2.pd));
         a2.d0 = c->d0;
@@ -433,18 +447,18 @@ struct CallPlan {
         a3.peak_bits = ds.peak_bits + f0 * 2;
         a3.n_gen = count * 2;
         a3.mt_pitch = c->n_streams * 2;
-        a3.rk = c->rk;
+        a3.rk = rk;
         a3.fes = fcm ? ds.fes + f0 * 4 * ICW_FES_PITCH : nullptr;
         /* the row-broadcast render (16 lanes per channel) while its waves stay few; FP_CHECK
          * keeps the compact lane-per-channel form */
-        a3.row = c->serial_render && !fcm && (c->tn.render_row == 1 || (c->tn.render_row < 0 && a3.n_gen <= kRowRenderMax)) ? 1 : 0;
+        a3.row = serial_render && !fcm && (c->tn.render_row == 1 || (c->tn.render_row < 0 && a3.n_gen <= kRowRenderMax)) ? 1 : 0;
         a3.err = ds.err;
         if (dither) {
             a3.dith = c->dith[b % n_sets];
             /* the row render and the frame-parallel one read runs of one channel: generator-major
              * [count*2][T rounded up to even] (16-byte pairs); the lane-per-channel renders time-major
              * [T][count*2] */
-            a3.dith_gm = (a3.row || !c->serial_render) ? 1 : 0;
+            a3.dith_gm = (a3.row || !serial_render) ? 1 : 0;
             a3.dith_pitch = a3.dith_gm ? (size_t)(T + (T & 1)) : (size_t)count * 2;
             a3.wbuf = c->dwords;
             a3.wpitch = a3.wcap = c->dwcap;
@@ -456,6 +470,74 @@ struct CallPlan {
             }
         }
         return a3;
+    }
+
+    /* The same for one run of a call over streams with different renders: the arguments offset to the
+     * run's first stream, the way a subset call offsets by f0; n_streams and n_gen are the run's, rk its
+     * entry's, and its frames are the entry's size.  The K3c / K3b choice is the call's (serial_gen).  The
+     * dither scratch is addressed by the run's first generator -- the rows at g0 * (T rounded up to even)
+     * doubles, which holds either layout of a run -- so runs never alias. */
+    IcwK3Args k3_run_args(int b, const IcwK2Args &a2, const Run &r) const
+    {
+        const int t0 = blocks[b].first, T = blocks[b].second;
+        const size_t r0 = f0 + (size_t)r.s0, g0 = (size_t)r.s0 * 2, Tp = (size_t)(T + (T & 1));
+        IcwK3Args a3;
+        memset(&a3, 0, sizeof(a3));
+        a3.pre = a2.pre + (size_t)r.s0 * a2.pre_stride;
+        a3.pre_stride = a2.pre_stride;
+        a3.n_streams = r.n;
+        a3.T = T;
+        a3.out = d_out + (size_t)r.s0 * dos + (size_t)t0 * r.e->osz();
+        a3.out_stride = dos;
+        a3.mt = ds.mt + r0 * 2;
+        a3.mt_idx = ds.mt_idx + r0 * 2;
+        a3.rs = ds.rs + r0 * 2 * ICW_RSTATE;
+        a3.clips = ds.clips + r0 * 2;
+        a3.peak_bits = ds.peak_bits + r0 * 2;
+        a3.n_gen = r.n * 2;
+        a3.mt_pitch = c->n_streams * 2;
+        a3.rk = r.e->rk;
+        a3.row = r.e->serial && (c->tn.render_row == 1 || (c->tn.render_row < 0 && serial_gen <= kRowRenderMax)) ? 1 : 0;
+        a3.err = ds.err;
+        if (r.e->dither) {
+            a3.dith = c->dith[b % n_sets] + g0 * Tp;
+            a3.dith_gm = (a3.row || !r.e->serial) ? 1 : 0;
+            a3.dith_pitch = a3.dith_gm ? Tp : (size_t)r.n * 2;
+            a3.wbuf = c->dwords + g0 * c->dwcap;
+            a3.wpitch = a3.wcap = c->dwcap;
+            a3.dflag = c->dflag + g0;
+            a3.dbk = c->dbk + g0 * ICW_DBK;
+            if (b == 0 && c->last_dchunks == 0) {    /* the call's first generator run (icw_last_dither_chunks) */
+                c->last_dchunk_frames = icw_dith_chunk_frames(T, a3.wcap, icw_dith_words(a3.rk.render_type));
+                c->last_dchunks = c->last_dchunk_frames > 0 ? (T + c->last_dchunk_frames - 1) / c->last_dchunk_frames : 0;
+            }
+        }
+        return a3;
+    }
+
+    /* KR of block b: every stream of the call whose entry is frame-parallel, from K2's pre rows.  The
+     * dither rows are the runs' (generator-major, T rounded up to even apart: row 2s + ch of the call) */
+    IcwKRArgs kr_args(int b, const IcwK2Args &a2) const
+    {
+        const int T = blocks[b].second;
+        IcwKRArgs ar;
+        memset(&ar, 0, sizeof(ar));
+        ar.pre = a2.pre;
+        ar.pre_stride = a2.pre_stride;
+        ar.out = d_out;
+        ar.out_stride = dos;
+        ar.tab = c->d_rtab;
+        ar.ent = c->d_rof + f0;
+        if (dither) {
+            ar.dith = c->dith[b % n_sets];
+            ar.dith_pitch = (size_t)(T + (T & 1));
+        }
+        ar.clips = ds.clips + f0 * 2;
+        ar.peak_bits = ds.peak_bits + f0 * 2;
+        ar.n_streams = count;
+        ar.T = T;
+        ar.t0 = blocks[b].first;
+        return ar;
     }
 
     /* the bus-form graph of block b, behind its K2 */
@@ -628,6 +710,8 @@ struct CallPlan {
     int stage_host_io(size_t in_row, size_t out_row);
     bool stage_copy_in() const;
     bool stage_copy_out(size_t row_bytes) const;
+    size_t out_row_bytes(size_t i) const;
+    bool copy_out_own() const;
     bool fir_hist_back() const;
     int enc_format(uint32_t cw_fmt, bool fir_ok);
     int enc_buffers();
@@ -721,6 +805,22 @@ bool CallPlan::stage_copy_in() const
 bool CallPlan::stage_copy_out(size_t row_bytes) const
 {
     return hipMemcpy2DAsync(out, out_stride, c->d_out, dos, row_bytes, S, hipMemcpyDeviceToHost, st) == hipSuccess;
+}
+
+/* the rendered bytes of stream i of the call: n_frames frames of its own size (mixr), else of the call's */
+size_t CallPlan::out_row_bytes(size_t i) const
+{
+    return (size_t)n_frames * (size_t)(mixr ? c->renders[(size_t)c->render_of[f0 + i]].osz() : osz);
+}
+
+/* the staged frames of a call over streams with different renders back to host pointers: every stream's own
+ * bytes, so a 16-bit stream's row is written no further than its frames (a 2-D copy has one width) */
+bool CallPlan::copy_out_own() const
+{
+    for (size_t i = 0; i < S; ++i)
+        if (hipMemcpyAsync((unsigned char *)out + i * out_stride, c->d_out + i * dos, out_row_bytes(i), hipMemcpyDeviceToHost, st) != hipSuccess)
+            return false;
+    return true;
 }
 
 /* FIR history: the current rows of every stream stay in fir_hist[fir_par] between calls (a call on
@@ -840,7 +940,31 @@ int CallPlan::resolve_plan()
     }
     if (mixin) dD = c->d_inputs + f0;
     din = mixin && fmt >= ICW_FMT_CW_F64;
+    /* the render of the call's streams, resolved like the input */
+    rk = c->rk;
+    serial_render = c->serial_render;
+    render_type = cfg.render.render_type;
     osz = 2 * (cfg.need24bits ? 3 : 2);
+    if (!c->renders.empty()) {
+        const int32_t e0 = c->render_of[f0];
+        for (int i = 1; i < count && !mixr; ++i) mixr = c->render_of[f0 + (size_t)i] != e0;
+        const RenderEnt &r0 = c->renders[(size_t)e0];
+        rk = r0.rk;
+        serial_render = r0.serial;
+        render_type = r0.cfg.render_type;
+        osz = r0.osz();
+        if (mixr) {
+            serial_render = true;
+            for (int i = 0; i < count; ++i) {
+                const RenderEnt *e = &c->renders[(size_t)c->render_of[f0 + (size_t)i]];
+                if (runs.empty() || runs.back().e != e) runs.push_back(Run{i, 0, e});
+                ++runs.back().n;
+                osz = std::max(osz, e->osz());
+                if (e->serial) serial_gen += 2;
+                else any_par = true;
+            }
+        }
+    }
     ssr = (unsigned long long)rate * ICW_HZ_SCALE;
     timing = flags & 4u;
     /* ICW_F_DEBUG_INPUT: K0's output of every launch block is copied aside (test hook, host dbg) */
@@ -852,7 +976,7 @@ int CallPlan::resolve_plan()
     /* every stream's row holds the call's frames at the widest frame of the call (mixin: K0 reads by
      * the table, so the bound is checked for device pointers too) */
     if ((!dev || mixin) && in_stride < (size_t)n_frames * fsz) return ICW_EINVAL;
-    if (!dev && out_stride < (size_t)n_frames * osz) return ICW_EINVAL;
+    if ((!dev || mixr) && out_stride < (size_t)n_frames * osz) return ICW_EINVAL;
 
     /* FIR Hilbert converter (icw_set_fir_hilbert): real input becomes complex samples in KF and
      * the block continues as CWAVE input does */
@@ -907,13 +1031,17 @@ int CallPlan::resolve_plan()
      * blocks (a quarter of the launches, of their gaps and prologues) ending in a steep tail
      * (65 536 -> 16 384 -> 4 096 -> 1 024: the drain stays one short K2) measured +0.8 % on C2
      * (3 170 -> 3 196 Msamples/s; 32 768 with r = 0.5 +0.5 %, 65 536 with no tail +0.5 %). */
-    const bool row_long = !cw && k1_mode == 3 && !c->serial_render && !c->tn.block_env && n_frames >= 4 * kMaxBlockFrames;
+    const bool row_long = !cw && k1_mode == 3 && !serial_render && !c->tn.block_env && n_frames >= 4 * kMaxBlockFrames;
     /* a dithered render with the flat shaper, rendered frame-parallel in the output kernel (K2 / KF2 /
      * K5) from K3a's dither rows (needs_serial) */
-    dith_par = !c->serial_render && cfg.render.render_type != ICW_RENDER_ROUND;
-    dither = cfg.render.render_type != ICW_RENDER_ROUND;     /* K3a: serial or frame-parallel render */
+    dith_par = !serial_render && render_type != ICW_RENDER_ROUND;
+    dither = render_type != ICW_RENDER_ROUND;     /* K3a: serial or frame-parallel render */
+    if (mixr) {
+        dither = false;                              /* K3a runs for the runs with a dithered entry */
+        for (const Run &r : runs) dither = dither || r.e->dither;
+    }
     /* (with a dither generator, blocks of kMaxBlockFrames let K3a of the next block run beside KF2) */
-    const bool fir_long = fir_fused && dev && !c->serial_render && !bus && !dith_par;
+    const bool fir_long = fir_fused && dev && !serial_render && !bus && !dith_par;
     Tb = std::min(n_frames, ((fir_fused || row_long) && !c->tn.block_env)
                                    ? (fir_long ? kMaxFirBlockFrames : kMaxBlockFrames) : c->tn.max_block);
     /* per-stream lists through the long FIR blocks: a slab per (list, rate) pair, so the blocks shorten
@@ -923,17 +1051,17 @@ int CallPlan::resolve_plan()
         Tb = std::min(Tb, std::max(kMaxBlockFrames, (int)std::min<size_t>(cap, (size_t)kMaxFirBlockFrames) & ~1023));
     }
     const double taper = c->tn.taper >= 0.0 ? c->tn.taper
-                       : (!cw && k1_mode == 3) ? (c->serial_render ? kAutoTaper : (row_long ? kRowTaper : 0.0)) : 0.0;
+                       : (!cw && k1_mode == 3) ? (serial_render ? kAutoTaper : (row_long ? kRowTaper : 0.0)) : 0.0;
     /* the fused FIR converter with a serial render (c5fir): the render of block 0 waits for its
      * converter and dither alone, so block 0 is short and the next ones ramp up (kFirRenderRamp:
      * profiles/r04_c5fir_timeline_after.txt had 2.2 ms of fill in a 24.3 ms step) */
-    const bool fir_ramp = fir_fused && c->serial_render && !c->tn.block_env && c->tn.first_block > 0;
+    const bool fir_ramp = fir_fused && serial_render && !c->tn.block_env && c->tn.first_block > 0;
     blocks = fir_ramp ? plan_blocks(n_frames, Tb, c->tn.first_block_env ? c->tn.first_block : kFirRenderFirst, 0.0,
                                        c->tn.taper_min, c->tn.fir_ramp > 0.0 ? c->tn.fir_ramp : kFirRenderRamp)
                          : plan_blocks(n_frames, Tb, fir_fused ? 0 : c->tn.first_block, taper, c->tn.taper_min);
     n_blocks = (int)blocks.size();
     /* K5 (icw_stream1): one stream, one block, the row recurrence, register-form graph, ROUND / flat */
-    s1 = c->tn.stream1 && count == 1 && n_blocks == 1 && !cw && !fcm && k1_mode == 3 && !c->serial_render &&
+    s1 = c->tn.stream1 && count == 1 && n_blocks == 1 && !cw && !fcm && k1_mode == 3 && !serial_render &&
             !bus && n_frames <= ICW_S1_MAX && !xin;
     return ICW_OK;
 }
@@ -949,8 +1077,8 @@ int CallPlan::stage_io()
     pinned = !dev && stage_in + stage_out + 16 <= kPinnedStage;
     /* pinned host buffers on a call of several launch blocks: each block's input slice goes in and
      * its output slice comes out on the copy stream, beside the other blocks' kernels */
-    pipe_io = !dev && !pinned && n_blocks > 1 && !c->tn.serialize && !mixin && host_pinned(in, c->device) &&
-                 host_pinned(out, c->device);       /* (mixin: a block's slice differs per stream, one copy up front) */
+    pipe_io = !dev && !pinned && n_blocks > 1 && !c->tn.serialize && !mixin && !mixr && host_pinned(in, c->device) &&
+                 host_pinned(out, c->device);       /* (mixin, mixr: a block's slice differs per stream, one copy up front / at the end) */
     if (pinned) {
         if (c->h_stage_bytes < stage_in + stage_out + 16) {
             if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -1053,7 +1181,7 @@ int CallPlan::size_scratch()
         if (!cw && grow((void **)&c->w[p], &c->w_bytes[p], S * 4 * w_pitch * sizeof(double))) return ICW_ENOMEM;
         if (!din && grow((void **)&c->xd[p], &c->xd_bytes[p], S * 4 * x_pitch * sizeof(double))) return ICW_ENOMEM;
     }
-    if (c->serial_render && !d_pre)
+    if (serial_render && !d_pre)
         for (int p = 0; p < n_sets; ++p)
             if (grow((void **)&c->rpre[p], &c->rpre_bytes[p], S * (size_t)Tb * 2 * sizeof(double))) return ICW_ENOMEM;
     /* the shared rotation table pays from two streams on; one stream computes its factors inline */
@@ -1302,7 +1430,7 @@ int CallPlan::run_blocks() const
             a2.trig_perm_q = at.perm_q;
         }
         /* rpre[p] / iq[p] were last read by the serial render of block b - n_sets (on sR) */
-        if (c->serial_render && b >= n_sets && sR != s2 && hipStreamWaitEvent(s2, c->k3done[p], 0) != hipSuccess)
+        if (serial_render && b >= n_sets && sR != s2 && hipStreamWaitEvent(s2, c->k3done[p], 0) != hipSuccess)
             return ICW_EDEVICE;
         if (dith_par) {
             /* K3a of this block on its own stream (it depends only on the generators' state, so it runs
@@ -1338,12 +1466,37 @@ int CallPlan::run_blocks() const
         if (hipEventRecord(c->k2done[p], s2) != hipSuccess) return ICW_EDEVICE;
         /* the serial part (K4, K3b) on sR after K2(b): it then overlaps K2(b+1) instead of
          * delaying it on sA */
-        if (c->serial_render && sR != s2 && hipStreamWaitEvent(sR, c->k2done[p], 0) != hipSuccess) return ICW_EDEVICE;
+        if (serial_render && sR != s2 && hipStreamWaitEvent(sR, c->k2done[p], 0) != hipSuccess) return ICW_EDEVICE;
         if (bus) {
             const auto a4 = k4_args(b, a2);
             if (icw_launch_graph_serial(&a4, sR) != hipSuccess) return ICW_EDEVICE;
         }
-        if (c->serial_render) {
+        if (mixr) {
+            /* streams with different renders: K3a of every run with a dithered entry on the dither stream
+             * (dith[p] was last read by the renders of block b - n_sets), then on the render stream the serial
+             * runs in order and KR for every frame-parallel stream */
+            if (dither) {
+                if (b >= n_sets && sD != sR && hipStreamWaitEvent(sD, c->k3done[p], 0) != hipSuccess) return ICW_EDEVICE;
+                for (const Run &r : runs) {
+                    if (!r.e->dither) continue;
+                    const auto a3 = k3_run_args(b, a2, r);
+                    if (icw_launch_dither(&a3, sD) != hipSuccess) return ICW_EDEVICE;
+                }
+                if (hipEventRecord(c->ditdone[p], sD) != hipSuccess ||
+                    (sD != sR && hipStreamWaitEvent(sR, c->ditdone[p], 0) != hipSuccess))
+                    return ICW_EDEVICE;
+            }
+            for (const Run &r : runs) {
+                if (!r.e->serial) continue;
+                const auto a3 = k3_run_args(b, a2, r);
+                if (icw_launch_render(&a3, sR) != hipSuccess) return ICW_EDEVICE;
+            }
+            if (any_par) {
+                const auto ar = kr_args(b, a2);
+                if (icw_launch_render_mixed(&ar, sR) != hipSuccess) return ICW_EDEVICE;
+            }
+            if (hipEventRecord(c->k3done[p], sR) != hipSuccess) return ICW_EDEVICE;
+        } else if (serial_render) {
             const auto a3 = k3_args(b, a2);
             if (dither) {
                 /* K3a for this block on its own stream: dith[p] was last read by K3b of block b-2 */
@@ -1356,10 +1509,10 @@ int CallPlan::run_blocks() const
             if (icw_launch_render(&a3, sR) != hipSuccess) return ICW_EDEVICE;
             if (hipEventRecord(c->k3done[p], sR) != hipSuccess) return ICW_EDEVICE;
         }
-        if (timing && hipEventRecord(c->ev[4 * b + 3], c->serial_render ? sR : s2) != hipSuccess) return ICW_EDEVICE;
+        if (timing && hipEventRecord(c->ev[4 * b + 3], serial_render ? sR : s2) != hipSuccess) return ICW_EDEVICE;
         if (pipe_io) {
             /* this block's output slice, once its last writer (K2, or the serial render) is done */
-            if (hipStreamWaitEvent(sC, c->serial_render ? c->k3done[p] : c->k2done[p], 0) != hipSuccess ||
+            if (hipStreamWaitEvent(sC, serial_render ? c->k3done[p] : c->k2done[p], 0) != hipSuccess ||
                 hipMemcpy2DAsync((unsigned char *)out + (size_t)t0 * osz, out_stride, d_out + (size_t)t0 * osz,
                                  dos, (size_t)T * osz, S, hipMemcpyDeviceToHost, sC) != hipSuccess)
                 return ICW_EDEVICE;
@@ -1402,7 +1555,7 @@ int CallPlan::finish_call() const
     if (!dev) {
         unsigned char *h_out = pinned ? c->h_stage + stage_in : nullptr;
         if (pinned ? (!zcopy && hipMemcpyAsync(h_out, d_out, dos * S + sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess)
-                      : (!pipe_io && !stage_copy_out(dos)))
+                      : (!pipe_io && !(mixr ? copy_out_own() : stage_copy_out(dos))))
             return ICW_EDEVICE;
         if (d_pre && hipMemcpyAsync(dbg, d_pre, S * (size_t)n_frames * 2 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
             return ICW_EDEVICE;
@@ -1418,7 +1571,7 @@ int CallPlan::finish_call() const
                            : hipStreamSynchronize(st) != hipSuccess)
                 return ICW_EDEVICE;
             memcpy(&e, h_out + dos * S, sizeof(int));     /* the flag icw_advance copied */
-            for (size_t i = 0; i < S; ++i) memcpy((unsigned char *)out + i * out_stride, h_out + i * dos, dos);
+            for (size_t i = 0; i < S; ++i) memcpy((unsigned char *)out + i * out_stride, h_out + i * dos, out_row_bytes(i));
         } else {
             if (hipStreamSynchronize(st) != hipSuccess) return ICW_EDEVICE;
             if (hipMemcpy(&e, c->st.err, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return ICW_EDEVICE;
@@ -1656,7 +1809,7 @@ int icw_prepare(icw_ctx *c, int n_frames)
     /* rows of the widest frame among the streams' inputs (one input: the context's frame) */
     unsigned fsz = 0;
     for (const IcwInDesc &d : c->inputs) fsz = std::max(fsz, d.fsz);
-    const size_t osz = 2 * (size_t)(c->cfg.need24bits ? 3 : 2), row = (size_t)n_frames * fsz;
+    const size_t osz = 2 * (size_t)icw_render_size(c), row = (size_t)n_frames * fsz;
     std::vector<unsigned char> in(row * S, 0), out((size_t)n_frames * osz * S);
     for (size_t i = 0; i < S; ++i)
         if (c->inputs[i].fmt == ICW_FMT_U8) std::fill(in.begin() + i * row, in.begin() + (i + 1) * row, (unsigned char)0x80);   /* u8 silence */

@@ -39,6 +39,8 @@ size_t icw_fir_graph_lds(int M, int nt, int nch, int n_regs);
 /* icw_render.hip */
 hipError_t icw_launch_render(const IcwK3Args *a, hipStream_t st);
 hipError_t icw_launch_dither(const IcwK3Args *a, hipStream_t st);
+/* KR: the frame-parallel renders of a call over streams with different renders, from K2's pre-render rows */
+hipError_t icw_launch_render_mixed(const IcwKRArgs *a, hipStream_t st);
 
 /* icw_iir.hip */
 hipError_t icw_launch_iir_state(const IcwK1Args *a, int nord, int kahan, int subn, hipStream_t st);

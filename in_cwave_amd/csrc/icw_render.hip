@@ -2,7 +2,8 @@
  * icw_render.hip -- gfx950 (CDNA4) kernels of the renders that are serial per channel: the dither
  * generator (K3a: icw_dith_twist / icw_dith_samples / icw_dith_fix), the serial render (K3b:
  * icw_render_serial), the row render (K3c: icw_render_rowc) and the FP_CHECK render (icw_render_fc),
- * with their launchers.  The elementwise render lives in the output kernels (icw_kernels.hip).
+ * with their launchers.  The elementwise render lives in the output kernels (icw_kernels.hip); KR
+ * (icw_render_mixed) is that render as a kernel of its own, for a call over streams with different renders.
  *
  * Built like icw_kernels.hip (`-ffp-contract=off`, no fast-math): every floating-point expression
  * keeps the operand order of the reference.
@@ -1122,7 +1123,111 @@ __global__ __launch_bounds__(64) void icw_render_fc(IcwK3Args a)
     icw_fes_flush(fe, a.fes + ((size_t)s * 4 + 2 + ch) * ICW_FES_PITCH);
 }
 
+/* ------------------------------------------------------ mixed render kernel (KR) -------- */
+/* A call over streams with different renders (icw_set_stream_render): K2 ran with do_render 0 and left
+ * every stream's pre-render doubles in the `pre` rows; the serial entries' streams go through K3b / K3c
+ * run by run, and this kernel renders every stream whose entry is elementwise -- ROUND, or a dithered
+ * render with the flat shaper from K3a's rows -- frame-parallel, a frame per thread, ICW_KR_TPW tiles of
+ * 256 frames per workgroup.  One stream per workgroup row, so the entry is wave-uniform: it is read once
+ * through the constant address space (scalar loads), and a workgroup of a serial entry's stream returns
+ * at once.  The arithmetic is icw_render_round (icw_quant_dev.h), the steps K2's in-kernel render runs,
+ * on the doubles K2 stored: the same bits.  Frames are packed at the stream's own size; a 6-byte row
+ * beside 4-byte rows leaves rows that are not dword aligned, so 24-bit frames go out as bytes (K2's
+ * icw_frame_store) and a 16-bit frame as one dword only where the row is aligned.  Meters: a wave
+ * reduction, LDS, then one atomic per channel and workgroup, with K2's conditions. */
+#define ICW_KR_TILE 256
+#define ICW_KR_TPW  4
+__global__ __launch_bounds__(ICW_KR_TILE) void icw_render_mixed(IcwKRArgs a)
+{
+    typedef const __attribute__((address_space(4))) IcwRenderEnt *EntP;
+    typedef const __attribute__((address_space(4))) int32_t *IdxP;
+    __shared__ unsigned red_clip[2][ICW_KR_TILE / 64];
+    __shared__ double red_pk[2][ICW_KR_TILE / 64];
+    const int tl = threadIdx.x, s = blockIdx.y;
+    const EntP e = (EntP)a.tab + ((IdxP)a.ent)[s];
+    if (e->serial) return;                            /* workgroup-uniform, before any barrier */
+    IcwRenderK k;
+    k.norm_mul = e->rk.norm_mul;
+    k.hi = e->rk.hi;
+    k.lo = e->rk.lo;
+    k.round_offset = e->rk.round_offset;
+    k.sign_delta = e->rk.sign_delta;
+    k.norm_shift = e->rk.norm_shift;
+    const bool is24 = e->rk.is24 != 0;
+    const bool dith = e->dither != 0 && a.dith != nullptr;
+    const int fsz = is24 ? 6 : 4;
+    const int T = a.T;
+    const double *pre = a.pre + (size_t)s * a.pre_stride;
+    const double *dl = dith ? a.dith + (size_t)(2 * s) * a.dith_pitch : nullptr;
+    unsigned char *o = a.out + (size_t)s * a.out_stride + (size_t)a.t0 * fsz;
+    const bool pre16 = ((uintptr_t)pre & 15u) == 0u, out4 = ((uintptr_t)o & 3u) == 0u;
+    unsigned clip_l = 0, clip_r = 0;
+    double pk_l = 0.0, pk_r = 0.0;
+    const int tw0 = blockIdx.x * ICW_KR_TILE * ICW_KR_TPW;
+#pragma unroll
+    for (int i = 0; i < ICW_KR_TPW; ++i) {
+        const int t = tw0 + i * ICW_KR_TILE + tl;
+        if (t >= T) break;
+        double xl, xr;
+        if (pre16) {
+            const double2 p = *(const double2 *)(pre + (size_t)t * 2);
+            xl = p.x; xr = p.y;
+        } else {
+            xl = pre[(size_t)t * 2]; xr = pre[(size_t)t * 2 + 1];
+        }
+        int vl, vr;
+        if (dith) {
+            const double d0 = dl[t], d1 = dl[a.dith_pitch + t];
+            vl = icw_render_round<true>(xl, k, clip_l, pk_l, d0);
+            vr = icw_render_round<true>(xr, k, clip_r, pk_r, d1);
+        } else {
+            vl = icw_render_round(xl, k, clip_l, pk_l);
+            vr = icw_render_round(xr, k, clip_r, pk_r);
+        }
+        if (is24) {
+            unsigned char *q = o + (size_t)t * 6;
+            q[0] = (unsigned char)vl; q[1] = (unsigned char)(vl >> 8); q[2] = (unsigned char)(vl >> 16);
+            q[3] = (unsigned char)vr; q[4] = (unsigned char)(vr >> 8); q[5] = (unsigned char)(vr >> 16);
+        } else if (out4) {
+            *(unsigned *)(o + (size_t)t * 4) = ((unsigned)vl & 0xffffu) | ((unsigned)vr << 16);
+        } else {
+            unsigned char *q = o + (size_t)t * 4;
+            q[0] = (unsigned char)vl; q[1] = (unsigned char)(vl >> 8);
+            q[2] = (unsigned char)vr; q[3] = (unsigned char)(vr >> 8);
+        }
+    }
+    /* the peaks are maxima of |q| from +0.0, never a NaN: any order gives the same value */
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        clip_l += __shfl_xor(clip_l, m);
+        clip_r += __shfl_xor(clip_r, m);
+        pk_l = fmax(pk_l, __shfl_xor(pk_l, m));
+        pk_r = fmax(pk_r, __shfl_xor(pk_r, m));
+    }
+    if ((tl & 63) == 0) {
+        red_clip[0][tl >> 6] = clip_l; red_clip[1][tl >> 6] = clip_r;
+        red_pk[0][tl >> 6] = pk_l; red_pk[1][tl >> 6] = pk_r;
+    }
+    __syncthreads();
+    if (tl < 2) {
+        unsigned cs = 0; double pm = 0.0;
+        for (int i = 0; i < ICW_KR_TILE / 64; ++i) { cs += red_clip[tl][i]; pm = fmax(pm, red_pk[tl][i]); }
+        if (cs) atomicAdd(&a.clips[s * 2 + tl], cs);
+        if (pm > 0.0) atomicMax(&a.peak_bits[s * 2 + tl], (unsigned long long)__double_as_longlong(pm));
+    }
+}
+
 /* ---------------------------------------------------------------- launch wrappers ------- */
+extern "C" hipError_t icw_launch_render_mixed(const IcwKRArgs *a, hipStream_t st)
+{
+    if (a->T <= 0 || a->n_streams <= 0) return hipSuccess;
+    if (!a->tab || !a->ent || !a->pre || !a->out) return hipErrorInvalidValue;
+    const int per = ICW_KR_TILE * ICW_KR_TPW;
+    hipLaunchKernelGGL(icw_render_mixed, dim3((unsigned)((a->T + per - 1) / per), (unsigned)a->n_streams), dim3(ICW_KR_TILE),
+                       0, st, *a);
+    return hipGetLastError();
+}
+
 template <int RT>
 static hipError_t icw_launch_dither_t(const IcwK3Args *a, hipStream_t st)
 {

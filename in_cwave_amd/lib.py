@@ -112,6 +112,7 @@ class Context:
         self.cfg = cfg
         self.n_streams = n_streams
         self.render_size = lib.icw_render_size(h)
+        self.stream_rs = [self.render_size] * n_streams   # every stream's own sample bytes (set_stream_render)
         self.fsz = abi.FMT_BYTES[cfg.in_format] * cfg.in_channels
         self.stream_fsz = [self.fsz] * n_streams       # every stream's own frame bytes (set_stream_input)
         self.stream_channels = [int(cfg.in_channels)] * n_streams   # and channels (the encoders' frame bytes)
@@ -265,6 +266,31 @@ class Context:
         self._own_cfg()
         self.cfg.need24bits = int(bool(need24bits))
         self.render_size = self._lib.icw_render_size(self.h)
+        self.stream_rs = [self.render_size] * self.n_streams
+
+    def set_stream_render(self, render, need24bits, first=0, count=None):
+        """icw_set_stream_render: the render (an abi.RenderCfg) and the output depth of streams
+        [first, first + count) for the next calls.  A call's output rows then hold each stream's frames at
+        its own size (2 * stream_render_size(s)), in rows as wide as the call's widest stream needs;
+        render_size is the largest in force."""
+        count = self.n_streams - first if count is None else count
+        _check(self._lib.icw_set_stream_render(self.h, int(first), int(count), C.byref(render), int(bool(need24bits))),
+               "icw_set_stream_render")
+        self.stream_rs[first:first + count] = [3 if need24bits else 2] * count
+        self.render_size = self._lib.icw_render_size(self.h)
+
+    def stream_render_count(self):
+        """icw_stream_render_count: distinct (render, depth) pairs in force (1 on a fresh context)"""
+        return int(self._lib.icw_stream_render_count(self.h))
+
+    def stream_render_size(self, s):
+        """icw_stream_render_size: bytes per output channel-sample of stream s, 2 or 3"""
+        return int(self._lib.icw_stream_render_size(self.h, int(s)))
+
+    def call_osz(self, first=0, count=None):
+        """the widest output frame among streams [first, first + count): what a call's output rows are sized by"""
+        count = self.n_streams - first if count is None else count
+        return 2 * max(self.stream_rs[first:first + count])
 
     def set_hilbert_filter(self, type_):
         """mod_context_change_all_hilberts_filter (icw_set_hilbert_filter)"""
@@ -288,11 +314,13 @@ class Context:
 
     def process(self, inp, n_frames, first=0, count=None, want_pre=False, out=None):
         """Host numpy path: inp uint8 [count, >= n_frames*fsz]; returns (out uint8 [count, n_frames*2*rs],
-        pre float64 [count, n_frames, 2] or None).  out: a preallocated output array (reused)."""
+        pre float64 [count, n_frames, 2] or None).  out: a preallocated output array (reused).  Streams with
+        different renders (set_stream_render): rs is the call's widest, and stream i's frames fill the first
+        n_frames * 2 * stream_rs[first + i] bytes of its row."""
         count = self.n_streams - first if count is None else count
         inp = np.ascontiguousarray(inp)
         assert inp.dtype == np.uint8 and inp.shape[0] == count and inp.shape[1] >= n_frames * self.call_fsz(first, count)
-        osz = 2 * self.render_size
+        osz = self.call_osz(first, count)       # the widest stream of the call (set_stream_render)
         if out is None:
             out = np.zeros((count, n_frames * osz), dtype=np.uint8)
         assert out.dtype == np.uint8 and out.flags.c_contiguous and out.shape[0] == count

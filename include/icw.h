@@ -376,6 +376,55 @@ int icw_set_outbits(icw_ctx *ctx, int need24bits);
 int icw_set_hilbert_filter(icw_ctx *ctx, uint32_t type);
 int icw_set_hilbert_config(icw_ctx *ctx, int kahan, int subnorm_reject);
 
+/* Per-stream renders: a batch whose streams each carry their own render -- output depth, dither type,
+ * quantiser, noise shaper, sign bits (the reference reads need24bits per track, in_cwave.c:212, and its
+ * SR_VCONFIG is an ordinary per-job setting) -- in ONE context, so a host that wants some tracks as 16-bit
+ * TPDF + MEW44 and others as 24-bit ROUND keeps the batch width.
+ *   icw_set_stream_render     icw_set_render followed by icw_set_outbits for streams [first, first + count)
+ *                             only, in force from the next call on (the context's work is waited for).  For
+ *                             those streams: new constants, prev_rnd, the shaper rings and prev_ns_err
+ *                             restart (also when the setting is unchanged, as sound_render_recalc does),
+ *                             the MT19937 words go on, and the peaks so far are folded into the stream's dB
+ *                             meter against its old bound.  A context whose renders were all ROUND + flat
+ *                             gets its serial-render state on the first edit that needs it, seeded as
+ *                             icw_set_render seeds it.  The context keeps the distinct (render, depth)
+ *                             entries and an index per stream; streams given the same pair share one
+ *                             entry, unused entries go, and one entry left is a one-render context again,
+ *                             which issues the launches it always did.
+ *   icw_stream_render_count   distinct (render, depth) pairs in force (1 on a fresh context).
+ *   icw_stream_render_size    bytes per output channel-sample of stream s: 2 or 3.  icw_render_size returns
+ *                             the largest in force, so a buffer sized by it stays large enough.
+ * icw_set_render and icw_set_outbits keep their meaning, every stream: icw_set_render gives every stream the
+ * new icw_render_cfg and keeps each stream's own depth (the table collapses to as many entries as depths in
+ * force); icw_set_outbits gives every stream the new depth and keeps each stream's own icw_render_cfg; each
+ * restarts the shaping state of every stream, as ever.  icw_get_meters converts stream s's peak against
+ * stream s's own bound.
+ * A call's output layout: stream s starts at out + s*out_stride_bytes, as ever, and its frames have that
+ * stream's own size, 4 or 6 bytes; out_stride_bytes must hold n_frames frames of every stream of the call
+ * (device pointers included where the call's streams differ), else ICW_EINVAL.  Host staging rows are sized
+ * by the widest, and a call over differing renders does not take the block-by-block copy of pinned host
+ * buffers.  A call whose streams all share one entry (a one-stream call included) is resolved on the host
+ * and launches exactly what a one-render context with that entry launches; only a call over differing
+ * entries takes the new path: the output kernel leaves every stream's pre-render doubles, the serial
+ * entries' streams go through the dither generator and the serial render in runs of consecutive streams
+ * with one entry, and one kernel renders every stream whose entry is frame-parallel.
+ * Per-stream lists and per-stream inputs, real and CWAVE, are served in the same context, in any order of
+ * the setters; host and device pointers; icw_process_batch and icw_process_streams.
+ * Limits, each refusal changing nothing:
+ *   ICW_EINVAL        a range outside the context, render == NULL, or a field of it out of range.
+ *   ICW_EUNSUPPORTED  while the count is above 1, or on the call that would raise it above 1:
+ *                     - the FIR converter on (k_M > 0), and icw_set_fir_hilbert(k_M > 0);
+ *                     - a cfg.fp_check context;
+ *                     - a bus-form list in force, and icw_set_graph (or a list primitive) with a bus-form
+ *                       list.
+ * Not served: icw_group and the icw_amod_* drop-in (their render stays context-wide), and per-file renders
+ * in icw_transcode_files*.  The two encoders run no render and are not concerned.  The state blob does not
+ * carry the render selection, as it carries neither list nor input: icw_set_state expects the stream's
+ * render to be set as it was. */
+int icw_set_stream_render(icw_ctx *ctx, int first, int count, const icw_render_cfg *render, int need24bits);
+int icw_stream_render_count(const icw_ctx *ctx);      /* distinct (render, depth) in force; 1 on a fresh context */
+int icw_stream_render_size(const icw_ctx *ctx, int s); /* bytes per output channel-sample of stream s: 2 or 3 */
+
 /* FIR Hilbert converter: the converter that CWAVE files record in their header (cwave.h:40,56-58:
  * "Hilbert FIR filter order" k_M, "Hilbert FIR filter parameter" k_beta; gui_cwave.c:159-172 shows
  * them; the converter program is not part of in_cwave).  With k_M > 0, real input is turned on the
