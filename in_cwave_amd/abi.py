@@ -194,6 +194,8 @@ SIGNATURES = {
     "icw_prepare": (_i, [_vp, _i]),
     "icw_set_hilbert_filter": (_i, [_vp, C.c_uint32]),
     "icw_set_hilbert_config": (_i, [_vp, _i, _i]),
+    "icw_set_stream_hilbert": (_i, [_vp, _i, _i, C.c_uint32, _i, _i]),
+    "icw_stream_hilbert_count": (_i, [_vp]),
     "icw_fir_taps": (_i, [C.c_int32, C.c_double, _vp, C.c_int]),
     "icw_mod_context_create": (_vp, [C.POINTER(Config), C.POINTER(Node), _i, _i, C.POINTER(_i)]),
     "icw_mod_context_destroy": (None, [_vp]),

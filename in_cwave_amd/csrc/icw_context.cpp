@@ -145,7 +145,7 @@ void free_all(icw_ctx *c)
 {
     DevState &s = c->st;
     void *ptrs[] = {c->enc_clipped, c->s1_stamps, s.mt, s.mt_idx, s.rs, s.lr_equal, s.fes, s.err, s.hist, s.sncnt, s.hq_phase, s.pos, s.fade,
-                    s.n_frame, s.bus, s.clips, s.peak_bits, c->d_prog, c->d_progs, c->d_pid, c->d_inputs, c->d_rtab, c->trig, c->d_in, c->d_out,
+                    s.n_frame, s.bus, s.clips, s.peak_bits, c->d_prog, c->d_progs, c->d_pid, c->d_inputs, c->d_rtab, c->d_hpc, c->trig, c->d_in, c->d_out,
                     c->d_pre, c->d_xin,
                     c->d_fir_g, c->fir_hist[0], c->fir_hist[1], c->dwords, c->dbk, c->dflag};
     for (void *p : ptrs)
@@ -169,18 +169,40 @@ void free_all(icw_ctx *c)
     if (c->stream) (void)hipStreamDestroy(c->stream);
 }
 
-/* filter coefficients of cfg.hilbert_type exactly as iir_rp_create (hblpf.c:849-856) */
+/* a (type, summation, reject) setting as a table entry: the filter coefficients of the type exactly as
+ * iir_rp_create (hblpf.c:849-856) */
+HilbEnt make_hilb(uint32_t type, int kahan, int subn)
+{
+    HilbEnt e;
+    const int t = (int)type;
+    e.type = type;
+    e.kahan = kahan ? 1 : 0;
+    e.subn = subn ? 1 : 0;
+    e.nord = icw_hb_order[t];
+    const double a0 = u2d(icw_hb_a[t][0]);
+    e.d0 = u2d(icw_hb_b[t][0]) / a0;
+    for (int i = 0; i < e.nord; ++i) {
+        e.pc[i] = -u2d(icw_hb_a[t][i + 1]) / a0;
+        e.pd[i] = u2d(icw_hb_b[t][i + 1]) / a0;
+    }
+    return e;
+}
+
+/* the context's one converter setting: cfg's three fields and the coefficients of its type */
+void set_one_hilb(icw_ctx *c, const HilbEnt &e)
+{
+    c->cfg.hilbert_type = e.type;
+    c->cfg.iir_kahan = e.kahan;
+    c->cfg.iir_subnorm_reject = e.subn;
+    c->nord = e.nord;
+    c->d0 = e.d0;
+    memcpy(c->pc, e.pc, sizeof(c->pc));
+    memcpy(c->pd, e.pd, sizeof(c->pd));
+}
+
 void set_filter(icw_ctx *c)
 {
-    const int t = (int)c->cfg.hilbert_type;
-    c->nord = icw_hb_order[t];
-    const double a0 = u2d(icw_hb_a[t][0]);
-    c->d0 = u2d(icw_hb_b[t][0]) / a0;
-    for (int i = 0; i < ICW_MAX_IIR_ORDER; ++i) c->pc[i] = c->pd[i] = 0.0;
-    for (int i = 0; i < c->nord; ++i) {
-        c->pc[i] = -u2d(icw_hb_a[t][i + 1]) / a0;
-        c->pd[i] = u2d(icw_hb_b[t][i + 1]) / a0;
-    }
+    set_one_hilb(c, make_hilb(c->cfg.hilbert_type, c->cfg.iir_kahan, c->cfg.iir_subnorm_reject));
 }
 
 /* renders of streams [f, f + n) as sound_render_init leaves them (in_cwave.c:69-70): MT19937
@@ -270,6 +292,8 @@ int apply_graph(icw_ctx *c, std::vector<icw_node> &nv, int bypass, const std::ve
     /* per-stream renders in force: K4 hands over to one serial render, so a bus-form list is refused
      * (include/icw.h); how each entry runs does not depend on a register-form list */
     if (!c->renders.empty() && P.is_bus) return ICW_EUNSUPPORTED;
+    /* nor beside per-stream Hilbert converters: the bus-form path's K2 runs one instance */
+    if (!c->hilbs.empty() && P.is_bus) return ICW_EUNSUPPORTED;
     const bool serial = c->renders.empty() ? needs_serial(cfg, c->rk, P, c->tn.dith_par) : c->serial_render;
     const bool rstate = c->renders.empty() ? needs_render_state(cfg, c->rk, P, c->tn.dith_par) : c->render_state;
     if (rstate && (rc = ensure_render_state(c))) return rc;
@@ -562,6 +586,104 @@ int install_renders(icw_ctx *c, std::vector<RenderEnt> &ents, std::vector<int32_
     return ICW_OK;
 }
 
+/* ---- per-stream Hilbert converters (icw_set_stream_hilbert) ---- */
+
+bool same_hilb(const HilbEnt &a, const HilbEnt &b) { return a.type == b.type && a.kahan == b.kahan && a.subn == b.subn; }
+
+/* the assignment in force as a table: the context's entries, or its one setting as entry 0 of every stream */
+void hilbs_in_force(const icw_ctx *c, std::vector<HilbEnt> &ents, std::vector<int32_t> &of)
+{
+    ents = c->hilbs;
+    of = c->hilb_of;
+    if (ents.empty()) {
+        ents.push_back(make_hilb(c->cfg.hilbert_type, c->cfg.iir_kahan, c->cfg.iir_subnorm_reject));
+        of.assign((size_t)c->n_streams, 0);
+    }
+}
+
+uint32_t stream_hilb_type(const icw_ctx *c, int s)
+{
+    return c->hilbs.empty() ? c->cfg.hilbert_type : c->hilbs[(size_t)c->hilb_of[(size_t)s]].type;
+}
+
+/* the order of stream s's converters: what its state blob records */
+int stream_nord(const icw_ctx *c, int s)
+{
+    return c->hilbs.empty() ? c->nord : c->hilbs[(size_t)c->hilb_of[(size_t)s]].nord;
+}
+
+/* Install an assignment (the caller holds c->mu and has waited for the context's work): ents[of[s]] is
+ * stream s's converter setting.  The table is compacted like the list and render tables -- equal entries
+ * become one, unused ones go, the survivors numbered in order of their first stream.  Refusals and the
+ * device copy (the entries' coefficients, into fresh memory with room for a call's run descriptors) come
+ * before any state is touched, so a failure leaves the old settings in force.  Then every stream whose type
+ * changes has its converters re-created as hq_rp_create does (zero rings, phases 0, counters 0, lr_equal 1),
+ * a stream that keeps its type keeps its rings, and the de-subnorm counters of streams [first, first +
+ * count) restart (iir_rp_setcfg).  One entry left: a one-setting context again. */
+int install_hilberts(icw_ctx *c, std::vector<HilbEnt> &ents, std::vector<int32_t> &of, int first, int count)
+{
+    std::vector<HilbEnt> ne;
+    std::vector<int32_t> map(ents.size(), -1);
+    for (int32_t &e : of) {
+        if (map[(size_t)e] < 0) {
+            size_t k = 0;
+            while (k < ne.size() && !same_hilb(ne[k], ents[(size_t)e])) ++k;
+            if (k == ne.size()) ne.push_back(ents[(size_t)e]);
+            map[(size_t)e] = (int32_t)k;
+        }
+        e = map[(size_t)e];
+    }
+    const size_t n = ne.size(), S = (size_t)c->n_streams;
+    /* more than one setting: the FIR converter replaces the IIR for every stream, K1f (FP_CHECK) and the
+     * bus-form path run one instance */
+    if (n > 1 && (c->fir_M > 0 || c->cfg.fp_check || c->prog.is_bus)) return ICW_EUNSUPPORTED;
+    double *fresh = nullptr;
+    const size_t pc_bytes = n * 20 * sizeof(double), run_bytes = S * sizeof(IcwK1Run);
+    if (n > 1) {
+        std::vector<double> h(n * 20);
+        for (size_t k = 0; k < n; ++k) memcpy(&h[k * 20], ne[k].pc, sizeof(ne[k].pc));
+        if (hipMalloc((void **)&fresh, pc_bytes + run_bytes + 5 * S * sizeof(int32_t)) != hipSuccess) return ICW_ENOMEM;
+        if (hipMemcpy(fresh, h.data(), pc_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(fresh);
+            return ICW_EDEVICE;
+        }
+    }
+    DevState &s = c->st;
+    bool ok = true;
+    for (size_t i = 0; i < S && ok; ++i) {
+        if (ne[(size_t)of[i]].type == stream_hilb_type(c, (int)i)) continue;
+        size_t j = i + 1;                              /* a stretch of streams whose type changes */
+        while (j < S && ne[(size_t)of[j]].type != stream_hilb_type(c, (int)j)) ++j;
+        const size_t m = j - i;
+        ok &= hipMemset(s.hist + i * 4 * ICW_HIST_PITCH, 0, m * 4 * ICW_HIST_PITCH * sizeof(double)) == hipSuccess;
+        ok &= hipMemset(s.sncnt + i * 4, 0, m * 4 * sizeof(unsigned long long)) == hipSuccess;
+        ok &= hipMemset(s.hq_phase + i * 2, 0, m * 2 * sizeof(uint32_t)) == hipSuccess;
+        ok &= hipMemsetD32((hipDeviceptr_t)(s.lr_equal + i * 2), 1, m * 2) == hipSuccess;
+        for (size_t k = i; k < j; ++k) c->lr_known[k] = 1;
+        i = j - 1;
+    }
+    if (ok && count > 0)
+        ok = hipMemset(s.sncnt + (size_t)first * 4, 0, (size_t)count * 4 * sizeof(unsigned long long)) == hipSuccess;
+    if (!ok) {
+        if (fresh) (void)hipFree(fresh);
+        return ICW_EDEVICE;
+    }
+    if (c->d_hpc) (void)hipFree(c->d_hpc);
+    c->d_hpc = fresh;
+    c->d_hruns = fresh ? (IcwK1Run *)((unsigned char *)fresh + pc_bytes) : nullptr;
+    c->d_hpid = fresh ? (int32_t *)((unsigned char *)fresh + pc_bytes + run_bytes) : nullptr;
+    c->hrun_valid = false;
+    set_one_hilb(c, ne[0]);
+    if (n == 1) {
+        c->hilbs.clear();
+        c->hilb_of.clear();
+    } else {
+        c->hilbs.swap(ne);
+        c->hilb_of.swap(of);
+    }
+    return ICW_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -811,6 +933,8 @@ int icw_set_fir_hilbert(icw_ctx *c, int32_t M, double beta)
     if (M > 0 && c->n_inputs > 1 && any_cwave(c->inputs)) return ICW_EUNSUPPORTED;
     /* nor beside per-stream renders (icw_set_stream_render): the fused converter renders with one */
     if (M > 0 && !c->renders.empty()) return ICW_EUNSUPPORTED;
+    /* nor beside per-stream Hilbert converters (icw_set_stream_hilbert): it replaces the IIR for every stream */
+    if (M > 0 && !c->hilbs.empty()) return ICW_EUNSUPPORTED;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     c->pid_valid = false;                 /* with the converter on, every (list, rate) pair has a slab */
     for (double *&h : c->fir_hist)
@@ -1227,6 +1351,16 @@ int icw_set_hilbert_filter(icw_ctx *c, uint32_t type)
 {
     if (!c || type > 5) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->hilbs.empty()) {
+        /* the streams' converters differ: every stream gets the type and keeps its summation, so the table
+         * collapses to as many entries as summations in force; only the streams whose type differs restart */
+        if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+        std::vector<HilbEnt> ents;
+        std::vector<int32_t> of;
+        hilbs_in_force(c, ents, of);
+        for (HilbEnt &e : ents) e = make_hilb(type, e.kahan, e.subn);
+        return install_hilberts(c, ents, of, 0, 0);
+    }
     if (type == c->cfg.hilbert_type) return ICW_OK;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     /* hq_rp_create: zero rings, ring index 0, counters 0, phase 0 -- for every stream */
@@ -1248,12 +1382,42 @@ int icw_set_hilbert_config(icw_ctx *c, int kahan, int subnorm_reject)
     if (!c) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+    if (!c->hilbs.empty()) {
+        /* the streams' converters differ: every stream gets the summation and keeps its type (and rings) */
+        std::vector<HilbEnt> ents;
+        std::vector<int32_t> of;
+        hilbs_in_force(c, ents, of);
+        for (HilbEnt &e : ents) e = make_hilb(e.type, kahan, subnorm_reject);
+        return install_hilberts(c, ents, of, 0, c->n_streams);
+    }
     /* iir_rp_setcfg: the rings stay, the de-subnorm counters start again ("new world") */
     if (hipMemset(c->st.sncnt, 0, (size_t)c->n_streams * 4 * sizeof(unsigned long long)) != hipSuccess)
         return ICW_EDEVICE;
     c->cfg.iir_kahan = kahan ? 1 : 0;
     c->cfg.iir_subnorm_reject = subnorm_reject ? 1 : 0;
     return ICW_OK;
+}
+
+/* icw_set_hilbert_filter followed by icw_set_hilbert_config for streams [first, first + count) (include/icw.h) */
+int icw_set_stream_hilbert(icw_ctx *c, int first, int count, uint32_t type, int kahan, int subnorm_reject)
+{
+    if (!c || first < 0 || count <= 0 || first > c->n_streams - count || type > 5) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+    /* the assignment as it is, the new entry for the range, then the table compacted */
+    std::vector<HilbEnt> ents;
+    std::vector<int32_t> of;
+    hilbs_in_force(c, ents, of);
+    ents.push_back(make_hilb(type, kahan, subnorm_reject));
+    for (int s = first; s < first + count; ++s) of[(size_t)s] = (int32_t)ents.size() - 1;
+    return install_hilberts(c, ents, of, first, count);
+}
+
+int icw_stream_hilbert_count(const icw_ctx *c)
+{
+    if (!c) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(const_cast<icw_ctx *>(c)->mu);
+    return c->hilbs.empty() ? 1 : (int)c->hilbs.size();
 }
 
 /* the largest sample size in force, so that a buffer sized by it holds every stream's frames */
@@ -1408,7 +1572,7 @@ int icw_get_state(icw_ctx *c, int s, void *blob, size_t size)
     IcwBlob b;
     memset(&b, 0, sizeof(b));
     b.magic = kBlobMagic;
-    b.nord = (uint32_t)c->nord;
+    b.nord = (uint32_t)stream_nord(c, s);     /* the stream's own order (icw_set_stream_hilbert) */
     b.has_render = c->render_state ? 1u : 0u;
     b.fir_M = (uint32_t)c->fir_M;
     long long fd[3];
@@ -1445,7 +1609,7 @@ int icw_set_state(icw_ctx *c, int s, const void *blob, size_t size)
     memcpy(&b, blob, sizeof(b));
     /* a blob holds the state of the render and converter forms in force when it was saved: the
      * serial-render words exist only with a dithered / shaped render, the FIR history only at its order */
-    if (b.magic != kBlobMagic || b.nord != (uint32_t)c->nord || b.has_render != (c->render_state ? 1u : 0u) ||
+    if (b.magic != kBlobMagic || b.nord != (uint32_t)stream_nord(c, s) || b.has_render != (c->render_state ? 1u : 0u) ||
         b.fir_M != (uint32_t)c->fir_M)
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);

@@ -81,6 +81,24 @@ struct RenderEnt {
     int osz() const { return is24 ? 6 : 4; }      /* bytes per output frame */
 };
 
+/* one entry of the context's Hilbert converter table: the setting as given, its order and coefficients
+ * (iir_rp_create, hblpf.c:849-856) */
+struct HilbEnt {
+    uint32_t type = 0;
+    int kahan = 1, subn = 1;
+    int nord = 0;
+    double pc[20]{}, pd[20]{}, d0 = 0.0;
+};
+
+/* workgroups of wg_waves waves that a run of n streams takes in a mixed recurrence launch: whole wave
+ * pairs of 4 chain slots per filter in the row form, whole 128-lane groups of 32 streams (64 under the
+ * mono dedup) in the lane form, then whole workgroups */
+inline int icw_k1_run_wgs(int n, bool dedup, bool row, int wg_waves)
+{
+    const int waves = row ? (((dedup ? n : 2 * n) + 3) / 4) * 2 : ((n + (dedup ? 63 : 31)) / (dedup ? 64 : 32)) * 2;
+    return (waves + wg_waves - 1) / wg_waves;
+}
+
 #pragma GCC visibility pop
 
 struct icw_ctx {
@@ -133,6 +151,22 @@ struct icw_ctx {
     std::vector<int32_t> render_of;       /* [streams] */
     IcwRenderEnt *d_rtab = nullptr;
     int32_t *d_rof = nullptr;
+    /* per-stream Hilbert converters (icw_set_stream_hilbert).  While every stream has one (type, summation,
+     * reject) the table is empty and cfg.hilbert_type / iir_kahan / iir_subnorm_reject and nord / pc / pd / d0
+     * above are that setting, as before.  Otherwise: the distinct entries, every stream's index, and on the
+     * device one allocation -- the entries' pc[20] rows, then room for a call's run descriptors [n_streams]
+     * and their K2 selection rows [5][n_streams] (d_hruns, d_hpid point into it); cfg and nord / pc / pd / d0
+     * then hold entry 0.  The run descriptors are built by the first call that needs them and kept while
+     * the call's shape (hrun_*) and the settings stay. */
+    std::vector<HilbEnt> hilbs;
+    std::vector<int32_t> hilb_of;         /* [streams] */
+    double *d_hpc = nullptr;
+    IcwK1Run *d_hruns = nullptr;
+    int32_t *d_hpid = nullptr;
+    bool hrun_valid = false;
+    int hrun_first = 0, hrun_count = 0, hrun_n = 0, hrun_wgs = 0, hrun_waves = 0;
+    bool hrun_dedup = false, hrun_row = false, hrun_mix = false;
+    unsigned long long pid_gen = 0, hrun_pid_gen = 0;   /* prepare_mix rebuilds counted: the selection rows' source */
     DevState st;
     /* host mirrors of meters that survive "reset" semantics */
     std::vector<double> peak_db;          /* [streams][2] */

@@ -217,6 +217,21 @@ struct IcwK1Args {
                                       render L, R); null: no FC() arithmetic */
 };
 
+/* One run of a call over streams with different Hilbert converters (icw_set_stream_hilbert): consecutive
+ * streams of one (type, summation, reject) entry.  The mixed recurrence kernels (icw_iir_row_mixed,
+ * icw_iir_state_mixed) get the call's runs as a device table, ordered by wg0; a workgroup belongs to the
+ * last run whose wg0 is not above its index, offsets the IcwK1Args pointers to the run's first stream and
+ * runs the existing body of the run's order.  A run is rounded up to whole workgroups, so no wave (and no
+ * workgroup) holds two runs. */
+struct IcwK1Run {
+    int32_t wg0;                   /* first workgroup of the run */
+    int32_t s0, n;                 /* first stream (index into the call's range) and streams */
+    int32_t nord;                  /* 15 / 18 / 19 / 20 */
+    int32_t kahan, subn;           /* the lane form's instance (the row form runs Kahan + reject only) */
+    int32_t pc_off;                /* doubles from the coefficient table to the entry's pc[20] */
+    int32_t pad_;
+};
+
 /* One compiled DSP node (adv_modulator.c:637-751), executed in list order tail -> head. */
 struct IcwOp {
     int32_t mode;                  /* ICW_MODE_* */

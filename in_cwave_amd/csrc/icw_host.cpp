@@ -206,6 +206,7 @@ int prepare_mix(icw_ctx *c, int first, int count, bool fir, hipStream_t st)
         hipStreamSynchronize(st) != hipSuccess)
         return ICW_EDEVICE;
     c->pid_valid = true;
+    ++c->pid_gen;
     c->pid_first = first;
     c->pid_count = count;
     c->pid_slabs = n_slabs;
@@ -271,6 +272,20 @@ struct CallPlan {
     bool cw = false, fir = false, fir_fused = false, fir_async = false, bus = false, fcm = false, dedup = false;
     bool dither = false, dith_par = false, table = false, in_step = false, s1 = false;
     int k1_mode = 0, row_waves = 0;
+    /* the resolved Hilbert converter: the one every stream of the call has -- the context's, or the one table
+     * entry all of them share -- or (mixh, icw_set_stream_hilbert) real-input streams with different entries:
+     * then the call's streams are cut into maximal runs of consecutive streams with one entry, K1 is one
+     * mixed launch over the runs' descriptors, K2 one launch per run, and hb is unread.  max_nord sizes the
+     * w rows (each run keeps its own N history rows in front) */
+    HilbEnt hb_one;
+    const HilbEnt *hb = &hb_one;
+    bool mixh = false;
+    struct HRun {
+        int s0, n;                 /* the run's first stream (index into the call's range) and its streams */
+        const HilbEnt *e;
+    };
+    std::vector<HRun> hruns;
+    int max_nord = 0, hwgs = 0;    /* mixh: the mixed launch's workgroups (prepare_hruns) */
     /* the block plan */
     std::vector<std::pair<int, int>> blocks;
     int n_blocks = 0, n_sets = 1, Tb = 0;
@@ -293,7 +308,29 @@ struct CallPlan {
              int n_frames_, unsigned flags_, void *hip_stream)
         : c(c_), cfg(c_->cfg), ds(c_->st), first(first_), count(count_), n_frames(n_frames_), S((size_t)count_), f0((size_t)first_), in(in_), out(out_),
           in_stride(in_stride_), out_stride(out_stride_), flags(flags_), dev(flags_ & ICW_F_DEVICE_PTRS),
-          legacy(!hip_stream && (flags_ & ICW_F_DEVICE_PTRS)), st(hip_stream ? (hipStream_t)hip_stream : c_->stream) {}
+          legacy(!hip_stream && (flags_ & ICW_F_DEVICE_PTRS)), st(hip_stream ? (hipStream_t)hip_stream : c_->stream)
+    {
+        /* the context's one converter setting (resolve_plan looks at the table where there is one) */
+        hb_one.type = cfg.hilbert_type;
+        hb_one.kahan = cfg.iir_kahan;
+        hb_one.subn = cfg.iir_subnorm_reject;
+        hb_one.nord = max_nord = c->nord;
+        hb_one.d0 = c->d0;
+        memcpy(hb_one.pc, c->pc, sizeof(hb_one.pc));
+        memcpy(hb_one.pd, c->pd, sizeof(hb_one.pd));
+    }
+
+    /* waves per workgroup of the call's K1 (the row form: 2 unless ICW_K1_WG says otherwise) */
+    int k1_wg_waves(bool row) const { return (c->tn.k1_wg_env || !row) ? c->tn.k1_wg : 2; }
+
+    /* mixh: the waves of the mixed launch in either form -- every run rounded up to whole workgroups */
+    int mixed_waves(bool row) const
+    {
+        const int wgw = k1_wg_waves(row);
+        int w = 0;
+        for (const HRun &r : hruns) w += icw_k1_run_wgs(r.n, dedup, row, wgw) * wgw;
+        return w;
+    }
 
     /* what K0 and the FIR converter take alike: the reader's side of block b */
     template <class A>
@@ -356,8 +393,8 @@ struct CallPlan {
         a1.hq_phase = ds.hq_phase + f0 * 2;
         a1.t0 = blocks[b].first;
         a1.info_dup = c->info_dup[p];
-        memcpy(a1.pc, c->pc, sizeof(a1.pc));
-        a1.wg_waves = (c->tn.k1_wg_env || k1_mode != 3) ? c->tn.k1_wg : 2;
+        memcpy(a1.pc, hb->pc, sizeof(a1.pc));      /* (mixh: unread, every run reads its entry's from the table) */
+        a1.wg_waves = k1_wg_waves(k1_mode == 3);
         a1.dedup = dedup ? 1 : 0;
         a1.fes = fcm ? ds.fes + f0 * 4 * ICW_FES_PITCH : nullptr;
         return a1;
@@ -396,9 +433,9 @@ struct CallPlan {
         a2.clips = ds.clips + f0 * 2;
         a2.peak_bits = ds.peak_bits + f0 * 2;
         a2.rk = rk;
-        memcpy(a2.pc, c->pc, sizeof(a2.pc));
-        memcpy(a2.pd, c->pd, sizeof(a2.pd));
-        a2.d0 = c->d0;
+        memcpy(a2.pc, hb->pc, sizeof(a2.pc));
+        memcpy(a2.pd, hb->pd, sizeof(a2.pd));
+        a2.d0 = hb->d0;
         a2.cw = cw ? 1 : 0;
         a2.info_dup = cw ? nullptr : c->info_dup[p];
         a2.xin = c->xd[p];
@@ -409,9 +446,39 @@ struct CallPlan {
             a2.prog_id = c->d_pid;
             a2.slab_stride = slab_stride;
         }
-        a2.sncnt = (!cw && cfg.iir_subnorm_reject) ? ds.sncnt + f0 * 4 : nullptr;
+        a2.sncnt = (!cw && hb->subn) ? ds.sncnt + f0 * 4 : nullptr;
         a2.fes = fcm ? ds.fes + f0 * 4 * ICW_FES_PITCH : nullptr;
         return a2;
+    }
+
+    /* K2 of one run of a call over streams with different Hilbert converters: the block's arguments as
+     * run_blocks completed them, offset to the run's first stream the way a subset call offsets by f0, with
+     * the run's streams, its entry's coefficients and its reject.  The selection rows are the run's own
+     * (prepare_hruns); without them the rotation table is read against the launch's stream 0, so a run
+     * whose first stream is not in step with the call's gets none and computes its factors inline. */
+    IcwK2Args k2_run_args(const IcwK2Args &a2, const HRun &r) const
+    {
+        const size_t s0 = (size_t)r.s0;
+        IcwK2Args a = a2;
+        a.w = a2.w + s0 * 4 * a2.w_pitch;
+        a.n_streams = r.n;
+        a.n_chains = r.n * 4;
+        a.hq_phase = a2.hq_phase + s0 * 2;
+        a.n_frame = a2.n_frame + s0;
+        a.bus = a2.bus + s0 * ICW_N_INPUTS * 4;
+        a.out = a2.out + s0 * a2.out_stride;
+        if (a2.pre) a.pre = a2.pre + s0 * a2.pre_stride;
+        a.clips = a2.clips + s0 * 2;
+        a.peak_bits = a2.peak_bits + s0 * 2;
+        memcpy(a.pc, r.e->pc, sizeof(a.pc));
+        memcpy(a.pd, r.e->pd, sizeof(a.pd));
+        a.d0 = r.e->d0;
+        a.info_dup = a2.info_dup + s0 * 2;
+        a.sncnt = r.e->subn ? ds.sncnt + (f0 + s0) * 4 : nullptr;
+        if (a2.dith) a.dith = a2.dith + s0 * 2 * a2.dith_pitch;
+        if (a2.prog_id) a.prog_id = c->d_hpid + 5 * s0;
+        else if (a2.trig_tab && c->nf_host[f0 + s0] != c->nf_host[f0]) a.trig_tab = nullptr;
+        return a;
     }
 
     /* what K2's direct-input form takes beside k2_args(b): the call's first frame (the kernel applies the
@@ -706,6 +773,8 @@ struct CallPlan {
     /* the steps of a call, in the order the entry points take them */
     void pick_k1();
     hipError_t launch_k1(const IcwK1Args &a1, hipStream_t s) const;
+    hipError_t launch_k2(const IcwK2Args &a2, hipStream_t s) const;
+    int prepare_hruns();
     int join_legacy_stream() const;
     int stage_host_io(size_t in_row, size_t out_row);
     bool stage_copy_in() const;
@@ -743,7 +812,15 @@ void CallPlan::pick_k1()
      * lane-per-chain kernel (64 chains per wave).  The row kernel needs Kahan + the reject.  (Round
      * 1 kept it off with a serial render; with the partition working, C5 gains 9 % from it.) */
     row_waves = (int)(((dedup ? count : 2L * count) + 3) / 4) * 2;
-    const bool row_ok = cfg.iir_kahan && cfg.iir_subnorm_reject;
+    bool row_ok = hb->kahan && hb->subn;
+    if (mixh) {
+        /* streams with different converters: the rule on the mixed launch's real waves (every run rounds up
+         * to whole wave pairs, so many short runs need more waves than their streams in one run), and the
+         * row form only when every entry of the call is Kahan + reject */
+        row_waves = mixed_waves(true);
+        row_ok = true;
+        for (const HRun &r : hruns) row_ok = row_ok && r.e->kahan && r.e->subn;
+    }
     k1_mode = c->tn.k1_mode;
     if (k1_mode < 0) k1_mode = (row_ok && row_waves <= (c->n_cu / 2) * c->tn.k1_wpc) ? 3 : 0;
     if (k1_mode == 3 && !row_ok) k1_mode = 0;
@@ -753,9 +830,84 @@ void CallPlan::pick_k1()
 /* the plan's K1 on stream s */
 hipError_t CallPlan::launch_k1(const IcwK1Args &a1, hipStream_t s) const
 {
-    return k1_mode == ICW_K1_FC ? icw_launch_iir_fc(&a1, c->nord, cfg.iir_kahan, cfg.iir_subnorm_reject, s)
-         : k1_mode == 3         ? icw_launch_iir_row(&a1, c->nord, cfg.iir_kahan, cfg.iir_subnorm_reject, s)
-                                   : icw_launch_iir_state(&a1, c->nord, cfg.iir_kahan, cfg.iir_subnorm_reject, s);
+    if (mixh) return icw_launch_iir_mixed(&a1, k1_mode == 3, c->d_hruns, (int)hruns.size(), hwgs, c->d_hpc, s);
+    return k1_mode == ICW_K1_FC ? icw_launch_iir_fc(&a1, hb->nord, hb->kahan, hb->subn, s)
+         : k1_mode == 3         ? icw_launch_iir_row(&a1, hb->nord, hb->kahan, hb->subn, s)
+                                   : icw_launch_iir_state(&a1, hb->nord, hb->kahan, hb->subn, s);
+}
+
+/* the plan's K2 on stream s: one launch, or one per run of a call over different converters */
+hipError_t CallPlan::launch_k2(const IcwK2Args &a2, hipStream_t s) const
+{
+    if (!mixh) return icw_launch_output(&a2, hb->nord, hb->kahan, s);
+    for (const HRun &r : hruns) {
+        const IcwK2Args ar = k2_run_args(a2, r);
+        const hipError_t e = icw_launch_output(&ar, r.e->nord, r.e->kahan, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+/* A call over streams with different Hilbert converters: the run descriptors of the mixed K1 launch on the
+ * device (and, where the lists or inputs differ too, every run's own K2 selection rows: the call's rows cut
+ * by run, the reference stream relative to the run's first).  Kept while the call's shape and the settings
+ * stay; rebuilt otherwise, ordered after the earlier calls on st, which may still read the old ones. */
+int CallPlan::prepare_hruns()
+{
+    const bool row = k1_mode == 3;
+    const int wgw = k1_wg_waves(row);
+    if (c->hrun_valid && c->hrun_first == first && c->hrun_count == count && c->hrun_dedup == dedup && c->hrun_row == row &&
+        c->hrun_waves == wgw && c->hrun_mix == mix && (!mix || c->hrun_pid_gen == c->pid_gen)) {
+        hwgs = c->hrun_wgs;
+        return ICW_OK;
+    }
+    std::vector<IcwK1Run> h(hruns.size());
+    int wg = 0;
+    for (size_t k = 0; k < hruns.size(); ++k) {
+        const HRun &r = hruns[k];
+        IcwK1Run d;
+        memset(&d, 0, sizeof(d));
+        d.wg0 = wg;
+        d.s0 = r.s0;
+        d.n = r.n;
+        d.nord = r.e->nord;
+        d.kahan = r.e->kahan;
+        d.subn = r.e->subn;
+        d.pc_off = (int32_t)(r.e - c->hilbs.data()) * 20;
+        h[k] = d;
+        wg += icw_k1_run_wgs(r.n, dedup, row, wgw);
+    }
+    std::vector<int32_t> rows;
+    if (mix) {
+        rows.assign(5 * S, 0);
+        const bool one = c->progs.empty();
+        for (const HRun &r : hruns) {
+            int32_t *q = rows.data() + 5 * (size_t)r.s0;
+            for (int i = 0; i < r.n; ++i) {
+                const size_t k = (size_t)(r.s0 + i);
+                q[i] = one ? 0 : c->prog_of[f0 + k];
+                q[r.n + i] = c->pid_slab[k];
+                q[2 * r.n + i] = c->pid_ref[k] - r.s0;
+                q[3 * r.n + i] = (int32_t)c->inputs[f0 + k].sample_rate;
+                q[4 * r.n + i] = (int32_t)c->inputs[f0 + k].nch;
+            }
+        }
+    }
+    if (hipMemcpyAsync(c->d_hruns, h.data(), h.size() * sizeof(IcwK1Run), hipMemcpyHostToDevice, st) != hipSuccess ||
+        (mix && hipMemcpyAsync(c->d_hpid, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return ICW_EDEVICE;
+    c->hrun_valid = true;
+    c->hrun_first = first;
+    c->hrun_count = count;
+    c->hrun_dedup = dedup;
+    c->hrun_row = row;
+    c->hrun_waves = wgw;
+    c->hrun_mix = mix;
+    c->hrun_pid_gen = c->pid_gen;
+    c->hrun_n = (int)hruns.size();
+    c->hrun_wgs = hwgs = wg;
+    return ICW_OK;
 }
 
 /* ---- what the process call and the encoders share ---- */
@@ -965,6 +1117,22 @@ int CallPlan::resolve_plan()
             }
         }
     }
+    /* the Hilbert converter of the call's streams, resolved like the input and the render.  A CWAVE-input
+     * call runs no recurrence and no output sums: it takes the first stream's entry and no runs */
+    if (!c->hilbs.empty()) {
+        hb = &c->hilbs[(size_t)c->hilb_of[f0]];
+        max_nord = hb->nord;
+        if (fmt < ICW_FMT_CW_F64) {
+            for (int i = 0; i < count; ++i) {
+                const HilbEnt *e = &c->hilbs[(size_t)c->hilb_of[f0 + (size_t)i]];
+                if (hruns.empty() || hruns.back().e != e) hruns.push_back(HRun{i, 0, e});
+                ++hruns.back().n;
+                max_nord = std::max(max_nord, e->nord);
+            }
+            mixh = hruns.size() > 1;
+        }
+        if (!mixh) hruns.clear();
+    }
     ssr = (unsigned long long)rate * ICW_HZ_SCALE;
     timing = flags & 4u;
     /* ICW_F_DEBUG_INPUT: K0's output of every launch block is copied aside (test hook, host dbg) */
@@ -1152,7 +1320,7 @@ int CallPlan::stage_io()
 /* row pitches of the block scratch for blocks of at most Tb frames */
 void CallPlan::set_pitches()
 {
-    w_pitch = (size_t)Tb + c->nord + 1;
+    w_pitch = (size_t)Tb + max_nord + 1;
     x_pitch = ((size_t)Tb + ICW_MAX_IIR_ORDER + 2) & ~(size_t)1;   /* look-ahead pad */
 }
 
@@ -1177,6 +1345,10 @@ int CallPlan::size_scratch()
     const IcwProg &LP = *lp;
     set_pitches();
     n_sets = std::min(n_blocks, c->tn.max_sets);
+    if (mixh) {
+        const int rc = prepare_hruns();
+        if (rc != ICW_OK) return rc;
+    }
     for (int p = 0; p < n_sets && !fir_fused; ++p) {
         if (!cw && grow((void **)&c->w[p], &c->w_bytes[p], S * 4 * w_pitch * sizeof(double))) return ICW_ENOMEM;
         if (!din && grow((void **)&c->xd[p], &c->xd_bytes[p], S * 4 * x_pitch * sizeof(double))) return ICW_ENOMEM;
@@ -1249,7 +1421,8 @@ int CallPlan::pick_streams()
         sA = sD = sR = st;
     } else if (!cw) {
         /* plain K1: 128-lane groups of 32 streams (64 with the dedup); the variants: a lane per chain */
-        const int k1_waves = (k1_mode == 0 || k1_mode == ICW_K1_FC)
+        const int k1_waves = mixh ? mixed_waves(k1_mode == 3)
+                           : (k1_mode == 0 || k1_mode == ICW_K1_FC)
                                  ? ((count + (dedup ? 63 : 31)) / (dedup ? 64 : 32)) * 2 : row_waves;
         constexpr int kXcd = 8;                               /* MI355X: 8 XCDs */
         const int k1_cus = ((k1_waves + c->tn.k1_wpc - 1) / c->tn.k1_wpc + kXcd - 1) / kXcd * kXcd;
@@ -1323,7 +1496,7 @@ int CallPlan::run_stream1() const
         a5.k2.dith_pitch = a3.dith_pitch;
     }
     if (timing && hipEventRecord(c->ev[0], st) != hipSuccess) return ICW_EDEVICE;
-    if (icw_launch_stream1(&a5, c->nord, st) != hipSuccess) return ICW_EDEVICE;
+    if (icw_launch_stream1(&a5, hb->nord, st) != hipSuccess) return ICW_EDEVICE;
     if (timing && (hipEventRecord(c->ev[1], st) != hipSuccess || hipEventRecord(c->ev[2], st) != hipSuccess ||
                       hipEventRecord(c->ev[3], st) != hipSuccess))
         return ICW_EDEVICE;
@@ -1459,7 +1632,7 @@ int CallPlan::run_blocks() const
             if (din) {
                 const auto ad = din_args();
                 if (icw_launch_output_cw(&a2, &ad, s2) != hipSuccess) return ICW_EDEVICE;
-            } else if (icw_launch_output(&a2, c->nord, cfg.iir_kahan, s2) != hipSuccess) {
+            } else if (launch_k2(a2, s2) != hipSuccess) {
                 return ICW_EDEVICE;
             }
         }
@@ -1672,6 +1845,7 @@ int icw_encode_cwave(icw_ctx *c, int first, int count, const void *in, size_t in
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (c->n_inputs > 1 && !c->enc_streams) return ICW_EUNSUPPORTED;   /* per-stream inputs: asked for (include/icw.h) */
+    if (!c->hilbs.empty()) return ICW_EUNSUPPORTED;                    /* per-stream Hilbert converters: not served */
     CallPlan pl(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
     int rc;
     if ((rc = pl.enc_format(cw_format, c->fir_M > 0)) != ICW_OK) return rc;
@@ -1712,6 +1886,7 @@ int icw_encode_cwave_iir(icw_ctx *c, int first, int count, const void *in, size_
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (c->n_inputs > 1 && !c->enc_streams) return ICW_EUNSUPPORTED;   /* per-stream inputs: asked for (include/icw.h) */
+    if (!c->hilbs.empty()) return ICW_EUNSUPPORTED;                    /* per-stream Hilbert converters: not served */
     const icw_config &cfg = c->cfg;
     CallPlan pl(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
     int rc;
@@ -1749,7 +1924,7 @@ int icw_encode_cwave_iir(icw_ctx *c, int first, int count, const void *in, size_
         const auto a1 = pl.k1_args(b);
         if (pl.launch_k1(a1, pl.st) != hipSuccess) return ICW_EDEVICE;
         const auto a2 = pl.enc_k2_args(b);
-        if (icw_launch_output(&a2, c->nord, cfg.iir_kahan, pl.st) != hipSuccess) return ICW_EDEVICE;
+        if (pl.launch_k2(a2, pl.st) != hipSuccess) return ICW_EDEVICE;
         if (pl.mixin) {
             const auto mp = pl.pack_mix_args(b);
             if (icw_launch_iq_pack_mixed(&mp, cwf, pl.st) != hipSuccess) return ICW_EDEVICE;

@@ -8,6 +8,9 @@
  *                     is a VGPR ring rotated at compile time (unrolled by the filter order N).
  *   icw_iir_state_fc  the FP_CHECK variant (FC() arithmetic and census).
  *   icw_iir_row       one 16-lane DPP row per chain: the products lane-parallel (small batches).
+ *   icw_iir_row_mixed, icw_iir_state_mixed
+ *                     the same two bodies over runs of streams with different Hilbert converters: one
+ *                     launch, every workgroup in the body of its run's order (icw_set_stream_hilbert).
  *
  * Two slower experiments (MFMA product feed, chain + helper wave pair) are archived, not built
  * into the library: tools/k1_experimental.hip.
@@ -214,139 +217,27 @@ __device__ __forceinline__ int icw_k1_block(int b, int nb, int tpb)
     return ((c * 8 + (j & 7)) << 1) | (j >> 3);
 }
 
+/* the lane kernel: its body is icw_iir_state_body.inc, shared with the mixed kernel's runs */
 template <int N, bool KAHAN, bool SUBN>
 __global__ __launch_bounds__(256) void icw_iir_state(IcwK1Args a)
 {
-    int s, ch, f;
-    if (!icw_k1_chain(icw_k1_block(blockIdx.x, gridDim.x, blockDim.x) * blockDim.x + threadIdx.x, a.n_streams,
-                      a.dedup != 0, s, ch, f))
-        return;
-    const int g = s * 4 + ch * 2 + f;
-    const int n_chains = a.n_chains;
-    double pc[20];
-#pragma unroll
-    for (int i = 0; i < 20; ++i) pc[i] = a.pc[i];
+#define ICW_K1S_LANE icw_k1_block(blockIdx.x, gridDim.x, blockDim.x) * blockDim.x + threadIdx.x
+#define ICW_K1S_PC(i) a.pc[i]
+#include "icw_iir_state_body.inc"
+#undef ICW_K1S_LANE
+#undef ICW_K1S_PC
+}
 
-    double R[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) R[N - 1 - i] = a.hist[(size_t)g * ICW_HIST_PITCH + i];
-
-    /* this block's start (for K2); each (stream, filter) flag is read and written by one wave */
-    if (ch == 0) a.info_dup[s * 2 + f] = a.lr_equal[s * 2 + f];
-    const double *xp = a.xd + (size_t)(s * 2 + ch) * a.x_pitch;     /* the channel's signed row (K0) */
-    double *wrow = a.w + (size_t)g * a.w_pitch;
-    /* block-relative sample n has a zero input iff (phi + n) is odd (I: k = hq + t0 + n odd;
-     * Q: k + 1 odd) */
-    const unsigned phi = (a.hq_phase[s * 2 + ch] + (unsigned)a.t0 + (unsigned)f) & 1u;
-    /* history rows [0, N): row j = z_{N-1-j} = R[j] */
-#pragma unroll
-    for (int j = 0; j < N; ++j) wrow[j] = R[j];
-
-    const int T = a.T;
-    unsigned cnt = 0;
-    int t = 0;
-    if (T >= N) {
-        /* xv[j] holds the input of step j of the current block; right after a step consumes it the
-         * same register is refilled with the next block's input, so loads run N samples ahead
-         * with no register copies */
-        double xv[N];
-        icw_load_x<N>(xv, xp);
-        bool zfast = false;
-        unsigned phi0 = 0;
-        if constexpr (KAHAN && SUBN) {
-            /* the fast path needs one zero-input parity across the wave */
-            phi0 = __builtin_amdgcn_readfirstlane(phi);
-            zfast = __all(phi == phi0) && T >= 3 * N;
-        }
-        if constexpr (KAHAN && SUBN && !(N & 1)) {
-            /* even order: block-relative step J of every block (t a multiple of N) is a zero input
-             * iff (phi0 + J) is odd */
-            if (zfast) {
-                if (phi0) icw_even_blocks<N, 0, SUBN>(R, xv, xp, wrow, pc, cnt, t, T);
-                else icw_even_blocks<N, 1, SUBN>(R, xv, xp, wrow, pc, cnt, t, T);
-            }
-        }
-        if constexpr (KAHAN && SUBN && (N & 1)) {
-            if (zfast) {
-                /* speculative pairs of blocks ("Speculative blocks") that start on a nonzero sample; a
-                 * failed block ends them and the exact loops below take over at its start */
-                if ((phi0 + (unsigned)t) & 1u) {
-                    icw_block_steps_pf<N, 0, KAHAN, SUBN>(R, xv, xp + t + N, pc, cnt, true);
-                    icw_store_block<N>(R, wrow + N + t);
-                    t += N;
-                }
-                double mn = __builtin_inf();       /* smallest |sum| of the speculative block */
-                bool fail = false;
-                ICW_DRAIN_VMEM();
-                while (!fail && t + 2 * N <= T) {
-                    /* a failed pair's stores land past [t, t + N), the restart state, and the
-                     * exact re-run overwrites them */
-                    icw_block_steps_zpf<N, 0, 1, SUBN, true>(R, xv, xp + t + N, pc, cnt, &mn);
-                    icw_store_block<N>(R, wrow + N + t);
-                    icw_block_steps_zpf<N, 0, 0, SUBN, true>(R, xv, xp + t + 2 * N, pc, cnt, &mn);
-                    icw_store_block<N>(R, wrow + 2 * N + t);
-                    fail = __any(mn < 1.0);
-                    if (!fail) t += 2 * N;
-                }
-                if (fail) {
-                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-#pragma unroll
-                    for (int j = 0; j < N; ++j) R[j] = wrow[t + j];
-                }
-                icw_load_x<N>(xv, xp + t);   /* the block's inputs (the zero steps left slots unloaded) */
-                if (fail) {
-                    /* exact from here: the same zero-input pairs with the reject */
-                    ICW_DRAIN_VMEM();
-                    if (((phi0 + (unsigned)t) & 1u) && t + N <= T) {
-                        icw_block_steps_pf<N, 0, KAHAN, SUBN>(R, xv, xp + t + N, pc, cnt, true);
-                        icw_store_block<N>(R, wrow + N + t);
-                        t += N;
-                    }
-                    for (; t + 2 * N <= T; t += 2 * N) {
-                        icw_block_steps_zpf<N, 0, 1, SUBN>(R, xv, xp + t + N, pc, cnt);
-                        icw_store_block<N>(R, wrow + N + t);
-                        icw_block_steps_zpf<N, 0, 0, SUBN>(R, xv, xp + t + 2 * N, pc, cnt);
-                        icw_store_block<N>(R, wrow + 2 * N + t);
-                    }
-                    icw_load_x<N>(xv, xp + t);
-                }
-            }
-        }
-        for (; t + N <= T; t += N) {
-            icw_block_steps_pf<N, 0, KAHAN, SUBN>(R, xv, xp + t + N, pc, cnt, ((phi + (unsigned)t) & 1u) != 0u);
-            icw_store_block<N>(R, wrow + N + t);
-        }
-    }
-    const int rem = T - t;
-    if (rem > 0) {
-        double xv[N];
-#pragma unroll
-        for (int j = 0; j < N; ++j) xv[j] = (j < rem) ? xp[t + j] : 0.0;
-        icw_block_steps<N, 0, KAHAN, SUBN>(R, xv, pc, cnt, rem, ((phi + (unsigned)t) & 1u) != 0u);
-        double *wo = wrow + N + t;
-#pragma unroll
-        for (int j = 0; j < N; ++j)
-            if (j < rem) wo[j] = R[j];
-        icw_normalise_ring<N>(R, rem);
-    }
-    /* the de-subnorm count is taken by K2 from the w rows (a rejected w is exactly 0.0), so the
-     * recurrence does not spend issue slots on it: cnt is dead here and compiled away */
-    (void)cnt;
-    icw_store_hist<N, 0>(R, a.hist, g, n_chains);
-    if (a.dedup) {
-        icw_store_hist<N, 0>(R, a.hist, g + 2, n_chains);
-        a.lr_equal[s * 2 + f] = 1u;
-        return;
-    }
-    /* is this (stream, filter)'s right converter still bit-identical to its left one?  The two
-     * channels of a stream are lanes l, l ^ 1 of this wave */
-    bool eq = true;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const double o = __shfl_xor(R[i], 1);
-        eq = eq && (__double_as_longlong(o) == __double_as_longlong(R[i]));
-    }
-    if (ch == 0) a.lr_equal[s * 2 + f] = eq ? 1u : 0u;
+/* the same body for lane gi of a run's share of a mixed launch (icw_iir_state_mixed): a the run's arguments,
+ * pcx its entry's coefficients in the context's table */
+template <int N, bool KAHAN, bool SUBN>
+__device__ __forceinline__ void icw_iir_state_run(const IcwK1Args &a, int gi, const double *pcx)
+{
+#define ICW_K1S_LANE gi
+#define ICW_K1S_PC(i) icw_ld_const(pcx, i)
+#include "icw_iir_state_body.inc"
+#undef ICW_K1S_LANE
+#undef ICW_K1S_PC
 }
 
 /* ----------------------------------------------- IIR state kernel with FC() (K1f) -------- */
@@ -418,6 +309,87 @@ __global__ __launch_bounds__(256) void icw_iir_row(IcwK1Args a)
     icw_iir_row_body<N>(a, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
+/* ------------------------------- mixed recurrence kernels (icw_set_stream_hilbert) -------- */
+/* A call over streams whose Hilbert converters differ: one launch covers the call's runs (IcwK1Run,
+ * icw_device.h).  A workgroup finds its run by a binary search over the runs' first workgroups -- scalar
+ * loads through the constant address space, the index is the workgroup's -- offsets the arguments to the
+ * run's first stream the way a subset call offsets them, and takes a workgroup-uniform switch into the
+ * body of the run's order: the code of icw_iir_row<N> / icw_iir_state<N, KAHAN, SUBN>, the arithmetic and
+ * its order included.  A run is rounded up to whole workgroups (hence to whole wave pairs / 128-lane
+ * groups), so the bodies' wave-wide parity and __any checks see one run's chains only. */
+__device__ __forceinline__ const __attribute__((address_space(4))) IcwK1Run *icw_k1_find_run(const IcwK1Run *runs,
+                                                                                             int n_runs, int b)
+{
+    const __attribute__((address_space(4))) IcwK1Run *r = (const __attribute__((address_space(4))) IcwK1Run *)runs;
+    int lo = 0, hi = n_runs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (r[mid].wg0 <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    return r + lo;
+}
+
+/* the launch's arguments offset to a run of n streams from stream s0 of the call */
+__device__ __forceinline__ IcwK1Args icw_k1_run_args(const IcwK1Args &a, int s0, int n)
+{
+    IcwK1Args b = a;
+    b.xd = a.xd + (size_t)s0 * 2 * a.x_pitch;
+    b.hist = a.hist + (size_t)s0 * 4 * ICW_HIST_PITCH;
+    b.sncnt = a.sncnt + (size_t)s0 * 4;
+    b.w = a.w + (size_t)s0 * 4 * a.w_pitch;
+    b.lr_equal = a.lr_equal + (size_t)s0 * 2;
+    b.info_dup = a.info_dup + (size_t)s0 * 2;
+    b.hq_phase = a.hq_phase + (size_t)s0 * 2;
+    b.n_streams = n;
+    b.n_chains = n * 4;
+    return b;
+}
+
+__global__ __launch_bounds__(256) void icw_iir_row_mixed(IcwK1Args a, const IcwK1Run *runs, int n_runs,
+                                                         const double *pctab)
+{
+    const auto *r = icw_k1_find_run(runs, n_runs, blockIdx.x);
+    const int nord = r->nord;
+    const double *pc = pctab + r->pc_off;
+    const IcwK1Args b = icw_k1_run_args(a, r->s0, r->n);
+    const int gl = (blockIdx.x - r->wg0) * blockDim.x + threadIdx.x;
+    switch (nord) {
+    case 15: icw_iir_row_body<15, false, true>(b, gl, nullptr, 0, nullptr, pc); break;
+    case 18: icw_iir_row_body<18, false, true>(b, gl, nullptr, 0, nullptr, pc); break;
+    case 19: icw_iir_row_body<19, false, true>(b, gl, nullptr, 0, nullptr, pc); break;
+    case 20: icw_iir_row_body<20, false, true>(b, gl, nullptr, 0, nullptr, pc); break;
+    }
+}
+
+template <int N>
+__device__ __forceinline__ void icw_iir_state_any(const IcwK1Args &b, int gi, int kahan, int subn, const double *pc)
+{
+    if (kahan) {
+        if (subn) icw_iir_state_run<N, true, true>(b, gi, pc);
+        else icw_iir_state_run<N, true, false>(b, gi, pc);
+    } else {
+        if (subn) icw_iir_state_run<N, false, true>(b, gi, pc);
+        else icw_iir_state_run<N, false, false>(b, gi, pc);
+    }
+}
+
+__global__ __launch_bounds__(256) void icw_iir_state_mixed(IcwK1Args a, const IcwK1Run *runs, int n_runs,
+                                                           const double *pctab)
+{
+    const auto *r = icw_k1_find_run(runs, n_runs, blockIdx.x);
+    const int nord = r->nord, kahan = r->kahan, subn = r->subn;
+    const double *pc = pctab + r->pc_off;
+    const IcwK1Args b = icw_k1_run_args(a, r->s0, r->n);
+    const int gi = (blockIdx.x - r->wg0) * blockDim.x + threadIdx.x;
+    switch (nord) {
+    case 15: icw_iir_state_any<15>(b, gi, kahan, subn, pc); break;
+    case 18: icw_iir_state_any<18>(b, gi, kahan, subn, pc); break;
+    case 19: icw_iir_state_any<19>(b, gi, kahan, subn, pc); break;
+    case 20: icw_iir_state_any<20>(b, gi, kahan, subn, pc); break;
+    }
+}
+
 
 /* ---------------------------------------------------------------- launch wrappers ------- */
 template <int N, bool K, bool S>
@@ -468,6 +440,17 @@ extern "C" hipError_t icw_launch_iir_row(const IcwK1Args *a, int nord, int kahan
     case 20: return launch_k1r_t<20>(*a, st);
     }
     return hipErrorInvalidValue;
+}
+
+/* the mixed kernels: n_wgs workgroups of a->wg_waves waves, laid out run by run (icw_k1_run_wgs) */
+extern "C" hipError_t icw_launch_iir_mixed(const IcwK1Args *a, int row, const IcwK1Run *runs, int n_runs, int n_wgs,
+                                           const double *pctab, hipStream_t st)
+{
+    if (!runs || !pctab || n_runs < 1 || n_wgs < 1 || a->wg_waves < 1 || a->wg_waves > 4 || a->fes) return hipErrorInvalidValue;
+    const int tpb = 64 * a->wg_waves;
+    if (row) hipLaunchKernelGGL(icw_iir_row_mixed, dim3(n_wgs), dim3(tpb), 0, st, *a, runs, n_runs, pctab);
+    else hipLaunchKernelGGL(icw_iir_state_mixed, dim3(n_wgs), dim3(tpb), 0, st, *a, runs, n_runs, pctab);
+    return hipGetLastError();
 }
 
 template <int N>

@@ -22,6 +22,13 @@ __device__ __forceinline__ double icw_chain_x(double v, bool qodd)
     return (((J & 1) != 0) != qodd) ? 0.0 : v;
 }
 
+/* p[i] of a table no kernel writes, through the constant address space: a wave-uniform index is a scalar
+ * load, so the value stays in SGPRs as a kernel argument's does */
+__device__ __forceinline__ double icw_ld_const(const double *p, int i)
+{
+    return ((const __attribute__((address_space(4))) double *)p)[i];
+}
+
 /* ------------------------------------------------------------ IIR state kernel (K1) ----- */
 /* mn = min(mn, |s|) in one instruction: v_min_f64 with the abs modifier (the fmin builtin adds a
  * NaN-quieting v_max_f64 per operand in IEEE mode).  A NaN s leaves mn unchanged, as it leaves the
@@ -283,9 +290,11 @@ __device__ __forceinline__ void icw_row_publish(int *prog, int gl, int f, int do
     }
 }
 
-template <int N, bool PUB = false>
+/* PCX: the loop-back coefficients are pcx[] instead of a.pc -- the mixed kernel's run reads its entry's from
+ * the context's table (icw_iir_row_mixed) */
+template <int N, bool PUB = false, bool PCX = false>
 __device__ __forceinline__ void icw_iir_row_body(const IcwK1Args &a, int gl, double *lw = nullptr, int lpitch = 0,
-                                                 int *prog = nullptr)
+                                                 int *prog = nullptr, const double *pcx = nullptr)
 {
     const int wv = gl >> 6, r = (gl >> 4) & 3, lr = gl & 15;
     const int f = wv & 1;
@@ -296,11 +305,15 @@ __device__ __forceinline__ void icw_iir_row_body(const IcwK1Args &a, int gl, dou
     const int g = s * 4 + ch * 2 + f;
     const bool writer = lr == 0;
 
+    const auto pcv = [&](int i) {
+        if constexpr (PCX) return icw_ld_const(pcx, i);
+        else return a.pc[i];
+    };
     IcwRowC c;
-    c.c0 = a.pc[0];
-    c.c1 = a.pc[1];
-    c.pl = (lr + 1 < N) ? a.pc[lr + 1] : 0.0;
-    c.pl2 = (lr + 17 < N) ? a.pc[lr + 17] : (icw_row_c0p<N>() && lr == icw_row_c0_lane<N>()) ? a.pc[0] : 0.0;
+    c.c0 = pcv(0);
+    c.c1 = pcv(1);
+    c.pl = (lr + 1 < N) ? pcv(lr + 1) : 0.0;
+    c.pl2 = (lr + 17 < N) ? pcv(lr + 17) : (icw_row_c0p<N>() && lr == icw_row_c0_lane<N>()) ? pcv(0) : 0.0;
     c.one = 1.0;
 
     double W[N], P[N], P2[N];

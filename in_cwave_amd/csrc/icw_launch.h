@@ -46,6 +46,11 @@ hipError_t icw_launch_render_mixed(const IcwKRArgs *a, hipStream_t st);
 hipError_t icw_launch_iir_state(const IcwK1Args *a, int nord, int kahan, int subn, hipStream_t st);
 hipError_t icw_launch_iir_row(const IcwK1Args *a, int nord, int kahan, int subn, hipStream_t st);
 hipError_t icw_launch_iir_fc(const IcwK1Args *a, int nord, int kahan, int subn, hipStream_t st);
+/* the mixed recurrence kernels (streams with different Hilbert converters): the call's runs as a device
+ * table ordered by wg0, n_wgs workgroups of a->wg_waves waves in all, pctab the entries' coefficients.
+ * row: the row form (every run Kahan + reject), else the lane form */
+hipError_t icw_launch_iir_mixed(const IcwK1Args *a, int row, const IcwK1Run *runs, int n_runs, int n_wgs,
+                                const double *pctab, hipStream_t st);
 
 /* icw_encode.hip */
 hipError_t icw_launch_fir_encode(const IcwEncArgs *e, int cwf, hipStream_t st);

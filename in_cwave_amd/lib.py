@@ -304,6 +304,18 @@ class Context:
         self._own_cfg()
         self.cfg.iir_kahan, self.cfg.iir_subnorm_reject = int(bool(kahan)), int(bool(subnorm_reject))
 
+    def set_stream_hilbert(self, type_, kahan, subnorm_reject, first=0, count=None):
+        """icw_set_stream_hilbert: the Hilbert converter (type 0..5, Kahan or baseline summation, the
+        subnormal reject) of streams [first, first + count) for the next calls.  cfg is not followed: it
+        keeps what the context-wide setters last gave."""
+        count = self.n_streams - first if count is None else count
+        _check(self._lib.icw_set_stream_hilbert(self.h, int(first), int(count), int(type_), int(bool(kahan)),
+                                                int(bool(subnorm_reject))), "icw_set_stream_hilbert")
+
+    def stream_hilbert_count(self):
+        """icw_stream_hilbert_count: distinct (type, kahan, reject) settings in force (1 on a fresh context)"""
+        return int(self._lib.icw_stream_hilbert_count(self.h))
+
     def stream_open(self, s, n_samples, fade_in_ms=0, fade_out_ms=0, sec_align=0, clr_nframe=0, clr_hilb=0):
         _check(self._lib.icw_stream_open(self.h, s, n_samples, fade_in_ms, fade_out_ms, sec_align,
                                          clr_nframe, clr_hilb), "icw_stream_open")

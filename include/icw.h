@@ -425,6 +425,52 @@ int icw_set_stream_render(icw_ctx *ctx, int first, int count, const icw_render_c
 int icw_stream_render_count(const icw_ctx *ctx);      /* distinct (render, depth) in force; 1 on a fresh context */
 int icw_stream_render_size(const icw_ctx *ctx, int s); /* bytes per output channel-sample of stream s: 2 or 3 */
 
+/* Per-stream Hilbert converters: a batch whose streams each carry their own quadrature IIR converter -- the
+ * type (IIR_HBLPF_IX of a job's in_cwave.cfg, 0..5: orders 15 / 19 / 18 / 19 / 20 / 20), the summation
+ * (IIR_SUM_KAHAN) and the subnormal reject (IIR_SUBN_ZERO) -- in ONE context, so a host that serves jobs from
+ * several configs keeps the batch width, and with it the rate of the serial recurrence that bounds every
+ * real-input call.
+ *   icw_set_stream_hilbert    icw_set_hilbert_filter followed by icw_set_hilbert_config for streams [first,
+ *                             first + count) only, in force from the next call on (the context's work is
+ *                             waited for).  A stream whose type changes has its converters re-created as
+ *                             hq_rp_create does (zero rings, phases 0, de-subnorm counters 0, the left / right
+ *                             identity known again); a stream already at that type keeps its rings.  The
+ *                             de-subnorm counters of every stream of the range restart, also when the setting
+ *                             is unchanged (iir_rp_setcfg).  The context keeps the distinct (type, kahan,
+ *                             reject) entries, each with its order and coefficients, and an index per stream;
+ *                             streams given the same setting share one entry, unused entries go, and one
+ *                             entry left is a one-setting context again, which issues the launches it always
+ *                             did.
+ *   icw_stream_hilbert_count  distinct (type, kahan, reject) settings in force (1 on a fresh context).
+ * icw_set_hilbert_filter and icw_set_hilbert_config keep their meaning, every stream: icw_set_hilbert_filter
+ * gives every stream the type and keeps each stream's summation and reject (only the streams whose type
+ * differs are re-created); icw_set_hilbert_config gives every stream the summation and the reject, keeps each
+ * stream's type and rings, and restarts every counter.
+ * A call whose streams all share one entry (a one-stream call, a subset inside one run) is resolved on the
+ * host and launches exactly what a one-setting context with that entry launches.  Only a call over differing
+ * entries takes the new path: its streams are cut into runs of consecutive streams with one entry; the
+ * recurrence is one launch of a mixed kernel over all runs (the row form when every entry of the call is
+ * Kahan + reject and the automatic rule holds on the launch's real waves -- every run rounds up to whole wave
+ * pairs --, else the lane form; ICW_K1_MODE forces either as ever), and the output kernel runs once per run.
+ * Many short runs therefore cost many small output launches.  A CWAVE-input call runs no recurrence and is
+ * not concerned.  The state blob records the stream's own order; it does not carry the selection, as it
+ * carries neither list, input nor render: icw_set_state expects the stream's setting to be as it was.
+ * Per-stream lists, per-stream inputs (real and CWAVE) and per-stream renders are served in the same
+ * context, in any order of the setters; host and device pointers; icw_process_batch and icw_process_streams.
+ * Limits, each refusal changing nothing:
+ *   ICW_EINVAL        a range outside the context, or type > 5.
+ *   ICW_EUNSUPPORTED  while the count is above 1, or on the call that would raise it above 1:
+ *                     - the FIR converter on (k_M > 0), and icw_set_fir_hilbert(k_M > 0);
+ *                     - a cfg.fp_check context;
+ *                     - a bus-form list in force, and icw_set_graph (or a list primitive) with a bus-form
+ *                       list;
+ *                     and, while the count is above 1, the two context encoders icw_encode_cwave and
+ *                     icw_encode_cwave_iir.
+ * Not served: icw_group and the icw_amod_* drop-in (their converter stays context-wide), and per-file
+ * converter settings in icw_transcode_files*. */
+int icw_set_stream_hilbert(icw_ctx *ctx, int first, int count, uint32_t type, int kahan, int subnorm_reject);
+int icw_stream_hilbert_count(const icw_ctx *ctx);     /* distinct (type, kahan, reject) in force; 1 on a fresh context */
+
 /* FIR Hilbert converter: the converter that CWAVE files record in their header (cwave.h:40,56-58:
  * "Hilbert FIR filter order" k_M, "Hilbert FIR filter parameter" k_beta; gui_cwave.c:159-172 shows
  * them; the converter program is not part of in_cwave).  With k_M > 0, real input is turned on the
