@@ -188,9 +188,12 @@ HilbEnt make_hilb(uint32_t type, int kahan, int subn)
     return e;
 }
 
-/* the context's one converter setting: cfg's three fields and the coefficients of its type */
-void set_one_hilb(icw_ctx *c, const HilbEnt &e)
+bool same_hilb(const HilbEnt &a, const HilbEnt &b) { return a.type == b.type && a.kahan == b.kahan && a.subn == b.subn; }
+
+/* the converter table's mirrors: cfg's three fields and the coefficients of entry 0 */
+void mirror_hilbs(icw_ctx *c)
 {
+    const HilbEnt &e = c->hilbs.ents[0];
     c->cfg.hilbert_type = e.type;
     c->cfg.iir_kahan = e.kahan;
     c->cfg.iir_subnorm_reject = e.subn;
@@ -200,9 +203,17 @@ void set_one_hilb(icw_ctx *c, const HilbEnt &e)
     memcpy(c->pd, e.pd, sizeof(c->pd));
 }
 
-void set_filter(icw_ctx *c)
+/* converters of streams [f, f + n) as hq_rp_create leaves them: zero rings, phases 0, counters 0, lr_equal 1.
+ * Queued on st; the caller waits for it */
+bool reset_rings(icw_ctx *c, size_t f, size_t n, hipStream_t st)
 {
-    set_one_hilb(c, make_hilb(c->cfg.hilbert_type, c->cfg.iir_kahan, c->cfg.iir_subnorm_reject));
+    DevState &s = c->st;
+    bool ok = hipMemsetAsync(s.hist + f * 4 * ICW_HIST_PITCH, 0, n * 4 * ICW_HIST_PITCH * sizeof(double), st) == hipSuccess;
+    ok &= hipMemsetAsync(s.sncnt + f * 4, 0, n * 4 * sizeof(unsigned long long), st) == hipSuccess;
+    ok &= hipMemsetAsync(s.hq_phase + f * 2, 0, n * 2 * sizeof(uint32_t), st) == hipSuccess;
+    ok &= hipMemsetD32Async((hipDeviceptr_t)(s.lr_equal + f * 2), 1, n * 2, st) == hipSuccess;
+    for (size_t i = 0; i < n; ++i) c->lr_known[f + i] = 1;
+    return ok;
 }
 
 /* renders of streams [f, f + n) as sound_render_init leaves them (in_cwave.c:69-70): MT19937
@@ -246,74 +257,15 @@ int ensure_render_state(icw_ctx *c)
     return ICW_OK;
 }
 
-/* The device keeps each channel's largest |q| and get_meters turns it into dB against the render's
- * current hi bound.  Before a render change moves that bound, the peaks so far are folded into the
- * host's dB meters against the old bound (the reference converts every sample with the bound of
- * its time, sound_render.c:769-780) and the device maxima start again. */
-bool fold_peaks(icw_ctx *c)
+/* sound_render_recalc for streams [f, f + n): prev_rnd, the shaper rings and prev_ns_err start again, the
+ * MT19937 words go on (sound_render.c:527-580) */
+bool restart_shaping(icw_ctx *c, size_t f, size_t n)
 {
-    const size_t n = (size_t)c->n_streams * 2;
-    std::vector<unsigned long long> pb(n);
-    bool ok = hipMemcpy(pb.data(), c->st.peak_bits, n * 8, hipMemcpyDeviceToHost) == hipSuccess;
-    ok &= hipMemset(c->st.peak_bits, 0, n * 8) == hipSuccess;
-    if (!ok) return false;
-    for (size_t i = 0; i < n; ++i) {
-        double mx;
-        memcpy(&mx, &pb[i], 8);
-        const double cv = mx ? 20.0 * log10(mx / c->rk.hi) : ICW_SR_ZERO_SIGNAL_DB;
-        if (cv > c->peak_db[i]) c->peak_db[i] = cv;
-    }
-    return true;
+    return !c->st.rs || hipMemset(c->st.rs + f * 2 * ICW_RSTATE, 0, n * 2 * ICW_RSTATE * sizeof(double)) == hipSuccess;
 }
 
-/* mod_context_clear_all_inouts (in_cwave.c:255-261): slot `slot` of every stream's bus to zero.
- * The context's work has been waited for (quiesce). */
-int clear_slot(icw_ctx *c, int slot)
-{
-    if (slot < 0 || slot >= ICW_N_INPUTS) return ICW_OK;
-    const size_t pitch = (size_t)ICW_N_INPUTS * 4 * sizeof(double);
-    return hipMemset2D(c->st.bus + (size_t)slot * 4, pitch, 0, 4 * sizeof(double), (size_t)c->n_streams) == hipSuccess
-               ? ICW_OK : ICW_EDEVICE;
-}
-
-/* A live list edit (the caller holds c->mu and has waited for the context's work): compile the
- * normalised list nv, install the program, then zero the bus slots the reference's edit clears.  The
- * program goes to the device first, so a failed copy leaves the old program and the old bus on both
- * sides; a failed clear after it returns ICW_EDEVICE with the new program in place (the context is
- * quiesced, so the order of the two steps changes no output). */
-int apply_graph(icw_ctx *c, std::vector<icw_node> &nv, int bypass, const std::vector<int> &clears)
-{
-    icw_config cfg = c->cfg;
-    cfg.bypass_list = bypass;
-    IcwProg P;
-    int rc = build_prog(cfg, nv, P);
-    if (rc) return rc;
-    if (!c->tn.chain_ok) P.chain = P.sig = 0;
-    /* per-stream renders in force: K4 hands over to one serial render, so a bus-form list is refused
-     * (include/icw.h); how each entry runs does not depend on a register-form list */
-    if (!c->renders.empty() && P.is_bus) return ICW_EUNSUPPORTED;
-    /* nor beside per-stream Hilbert converters: the bus-form path's K2 runs one instance */
-    if (!c->hilbs.empty() && P.is_bus) return ICW_EUNSUPPORTED;
-    const bool serial = c->renders.empty() ? needs_serial(cfg, c->rk, P, c->tn.dith_par) : c->serial_render;
-    const bool rstate = c->renders.empty() ? needs_render_state(cfg, c->rk, P, c->tn.dith_par) : c->render_state;
-    if (rstate && (rc = ensure_render_state(c))) return rc;
-    if (hipMemcpy(c->d_prog, &P, sizeof(IcwProg), hipMemcpyHostToDevice) != hipSuccess) return ICW_EDEVICE;
-    c->cfg.bypass_list = cfg.bypass_list;
-    c->nodes = nv;
-    c->prog = P;
-    /* a one-list context with per-stream inputs launches from c->mix and the selection rows, both
-     * built from this list (prepare_mix): they are rebuilt by the next call */
-    c->pid_valid = false;
-    c->serial_render = serial;
-    c->render_state = rstate;
-    for (int slot : clears)
-        if (clear_slot(c, slot) != ICW_OK) return ICW_EDEVICE;
-    return ICW_OK;
-}
-
-/* ---- per-stream DSP lists (icw_set_stream_graph) ---- */
-
-/* clear_slot for streams [first, first + count) only */
+/* mod_context_clear_all_inouts (in_cwave.c:255-261) for streams [first, first + count): slot `slot` of their
+ * bus to zero.  The context's work has been waited for (quiesce). */
 int clear_slot_range(icw_ctx *c, int first, int count, int slot)
 {
     if (slot < 0 || slot >= ICW_N_INPUTS || count <= 0) return ICW_OK;
@@ -322,122 +274,7 @@ int clear_slot_range(icw_ctx *c, int first, int count, int slot)
                        (size_t)count) == hipSuccess ? ICW_OK : ICW_EDEVICE;
 }
 
-bool same_list(const std::vector<icw_node> &a, const std::vector<icw_node> &b)
-{
-    return a.size() == b.size() && (a.empty() || !memcmp(a.data(), b.data(), a.size() * sizeof(icw_node)));
-}
-
-/* The program table of a per-stream assignment: entry e compiled from lists[e], stream s running
- * entry of[s].  Entries that compiled to the same program from the same list become one, entries
- * no stream runs go, and the survivors are numbered in order of their first stream. */
-void prog_table_compact(std::vector<IcwProg> &progs, std::vector<std::vector<icw_node>> &lists,
-                        std::vector<int32_t> &of)
-{
-    std::vector<IcwProg> np;
-    std::vector<std::vector<icw_node>> nl;
-    std::vector<int32_t> map(progs.size(), -1);
-    for (int32_t &e : of) {
-        if (map[(size_t)e] < 0) {
-            size_t k = 0;
-            while (k < np.size() && !(!memcmp(&np[k], &progs[(size_t)e], sizeof(IcwProg)) && same_list(nl[k], lists[(size_t)e]))) ++k;
-            if (k == np.size()) {
-                np.push_back(progs[(size_t)e]);
-                nl.push_back(lists[(size_t)e]);
-            }
-            map[(size_t)e] = (int32_t)k;
-        }
-        e = map[(size_t)e];
-    }
-    progs.swap(np);
-    lists.swap(nl);
-}
-
-/* Install a compacted table (the caller holds c->mu and has waited for the context's work).  The
- * device copies come first, into memory the running table does not use where the table grows, so a
- * failed copy leaves the old lists in force on both sides.  One entry: the context is a one-list
- * context again (prog / d_prog / nodes), and issues the launches it always did. */
-int install_table(icw_ctx *c, std::vector<IcwProg> &progs, std::vector<std::vector<icw_node>> &lists,
-                  std::vector<int32_t> &of)
-{
-    const size_t n = progs.size();
-    IcwProg *fresh = nullptr;
-    if (n > 1) {
-        if (n > c->d_progs_cap && hipMalloc((void **)&fresh, n * sizeof(IcwProg)) != hipSuccess) return ICW_ENOMEM;
-        if (!c->d_pid && dalloc(&c->d_pid, (size_t)c->n_streams * kPidWords) != ICW_OK) {
-            if (fresh) (void)hipFree(fresh);
-            c->d_pid = nullptr;
-            return ICW_ENOMEM;
-        }
-        if (hipMemcpy(fresh ? fresh : c->d_progs, progs.data(), n * sizeof(IcwProg), hipMemcpyHostToDevice) != hipSuccess) {
-            if (fresh) (void)hipFree(fresh);
-            return ICW_EDEVICE;
-        }
-    }
-    /* d_prog follows prog (entry 0): the paths that read the pair (the encoders) see one program */
-    if (hipMemcpy(c->d_prog, &progs[0], sizeof(IcwProg), hipMemcpyHostToDevice) != hipSuccess) {
-        if (fresh) (void)hipFree(fresh);
-        return ICW_EDEVICE;
-    }
-    if (fresh) {
-        if (c->d_progs) (void)hipFree(c->d_progs);
-        c->d_progs = fresh;
-        c->d_progs_cap = n;
-    }
-    c->prog = progs[0];
-    c->nodes = lists[0];
-    c->pid_valid = false;
-    if (n == 1) {
-        c->cfg.bypass_list = progs[0].bypass;
-        c->progs.clear();
-        c->plists.clear();
-        c->prog_of.clear();
-    } else {
-        c->progs.swap(progs);
-        c->plists.swap(lists);
-        c->prog_of.swap(of);
-    }
-    return ICW_OK;
-}
-
-/* ---- per-stream inputs (icw_set_stream_input) ---- */
-
-IcwInDesc make_input(uint32_t sample_rate, uint32_t fmt, uint32_t channels)
-{
-    IcwInDesc d;
-    memset(&d, 0, sizeof(d));
-    d.fmt = fmt;
-    d.csz = fmt_size(fmt);
-    d.fsz = d.csz * channels;
-    d.nch = channels;
-    d.sample_rate = sample_rate;
-    d.ssr = (unsigned long long)sample_rate * ICW_HZ_SCALE;
-    return d;
-}
-
-bool same_input(const IcwInDesc &a, const IcwInDesc &b)
-{
-    return a.fmt == b.fmt && a.nch == b.nch && a.sample_rate == b.sample_rate;
-}
-
-bool any_cwave(const std::vector<IcwInDesc> &v)
-{
-    for (const IcwInDesc &d : v)
-        if (d.fmt >= ICW_FMT_CW_F64) return true;
-    return false;
-}
-
-int count_inputs(const std::vector<IcwInDesc> &v)
-{
-    std::vector<const IcwInDesc *> seen;
-    for (const IcwInDesc &d : v) {
-        size_t k = 0;
-        while (k < seen.size() && !same_input(*seen[k], d)) ++k;
-        if (k == seen.size()) seen.push_back(&d);
-    }
-    return (int)seen.size();
-}
-
-/* ---- per-stream renders (icw_set_stream_render) ---- */
+/* ---- the render table (icw_set_render, icw_set_outbits, icw_set_stream_render) ---- */
 
 /* a (render, depth) pair as a table entry: render_consts, and how it runs behind the context's list */
 RenderEnt make_render(const icw_ctx *c, const icw_render_cfg &r, int is24)
@@ -463,79 +300,62 @@ bool same_render(const RenderEnt &a, const RenderEnt &b)
            a.cfg.sign_bits24 == b.cfg.sign_bits24;
 }
 
-/* the assignment in force as a table: the context's entries, or its one render as entry 0 of every stream */
-void renders_in_force(const icw_ctx *c, std::vector<RenderEnt> &ents, std::vector<int32_t> &of)
+/* the render table's mirrors: entry 0, and whether any entry runs serial / keeps render state */
+void mirror_renders(icw_ctx *c)
 {
-    ents = c->renders;
-    of = c->render_of;
-    if (ents.empty()) {
-        RenderEnt e;
-        e.cfg = c->cfg.render;
-        e.is24 = c->cfg.need24bits ? 1 : 0;
-        e.rk = c->rk;
-        e.serial = c->serial_render;
-        e.rstate = c->render_state;
-        e.dither = c->cfg.render.render_type != ICW_RENDER_ROUND;
-        ents.push_back(e);
-        of.assign((size_t)c->n_streams, 0);
+    const RenderEnt &e0 = c->renders.ents[0];
+    c->cfg.render = e0.cfg;
+    c->cfg.need24bits = e0.is24;
+    c->rk = e0.rk;
+    c->serial_render = c->render_state = false;
+    for (const RenderEnt &e : c->renders.ents) {
+        c->serial_render |= e.serial;
+        c->render_state |= e.rstate;
     }
 }
 
-/* the clip bound stream s's peak is measured against */
-double stream_hi(const icw_ctx *c, int s)
+/* The device keeps each channel's largest |q| and get_meters turns it into dB against the render's
+ * current hi bound.  Before a render change moves that bound, the peaks so far are folded into the
+ * host's dB meters against the old bound (the reference converts every sample with the bound of
+ * its time, sound_render.c:769-780) and the device maxima start again: for the streams of [first, first +
+ * count) whose bound differs in t, a stretch of them per memset; nothing is read when no bound moves. */
+bool fold_peaks(icw_ctx *c, const StreamTable<RenderEnt> &t, int first, int count)
 {
-    return c->renders.empty() ? c->rk.hi : c->renders[(size_t)c->render_of[(size_t)s]].rk.hi;
-}
-
-/* fold_peaks for the streams of [first, first + count) whose bound moves to new_hi[s - first] */
-bool fold_peaks_range(icw_ctx *c, int first, int count, const std::vector<double> &new_hi)
-{
+    const auto moves = [&](int s) { return c->renders.at((size_t)s).rk.hi != t.at((size_t)s).rk.hi; };
+    const int end = first + count;
+    int i = first;
+    while (i < end && !moves(i)) ++i;
+    if (i == end) return true;
     std::vector<unsigned long long> pb((size_t)count * 2);
     if (hipMemcpy(pb.data(), c->st.peak_bits + (size_t)first * 2, pb.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
         return false;
-    for (int i = 0; i < count; ++i) {
-        const double hi = stream_hi(c, first + i);
-        if (hi == new_hi[(size_t)i]) continue;
-        if (hipMemset(c->st.peak_bits + (size_t)(first + i) * 2, 0, 16) != hipSuccess) return false;
-        for (int ch = 0; ch < 2; ++ch) {
+    while (i < end) {
+        int j = i + 1;
+        while (j < end && moves(j)) ++j;
+        if (hipMemset(c->st.peak_bits + (size_t)i * 2, 0, (size_t)(j - i) * 16) != hipSuccess) return false;
+        for (size_t k = (size_t)i * 2; k < (size_t)j * 2; ++k) {
             double mx;
-            memcpy(&mx, &pb[(size_t)i * 2 + ch], 8);
-            const double cv = mx ? 20.0 * log10(mx / hi) : ICW_SR_ZERO_SIGNAL_DB;
-            double &pv = c->peak_db[(size_t)(first + i) * 2 + ch];
-            if (cv > pv) pv = cv;
+            memcpy(&mx, &pb[k - (size_t)first * 2], 8);
+            const double cv = mx ? 20.0 * log10(mx / c->renders.at(k / 2).rk.hi) : ICW_SR_ZERO_SIGNAL_DB;
+            if (cv > c->peak_db[k]) c->peak_db[k] = cv;
         }
+        for (i = j; i < end && !moves(i); ++i) {}
     }
     return true;
 }
 
-/* Install an assignment (the caller holds c->mu and has waited for the context's work): ents[of[s]] is
- * stream s's render, and the shaping state of streams [first, first + count) restarts.  The table is
- * compacted like the list table -- equal entries become one, unused ones go, the survivors numbered in
- * order of their first stream.  Refusals and the device copies (table and index row, into fresh memory)
- * come before any state is touched, so a failure leaves the old renders in force; then the peaks of the
- * streams whose bound moves are folded against their old bound, the shaping state restarts (the MT19937
- * words go on) and the host side follows.  One entry left: a one-render context again. */
-int install_renders(icw_ctx *c, std::vector<RenderEnt> &ents, std::vector<int32_t> &of, int first, int count)
+/* Install a candidate render table (the caller holds c->mu and has waited for the context's work); the
+ * shaping state of streams [first, first + count) restarts.  Refusals and the device copies (table and index
+ * row, into fresh memory) come before any state is touched, so a failure leaves the old renders in force;
+ * then the peaks of the streams whose bound moves are folded against their old bound, the shaping state
+ * restarts (the MT19937 words go on) and the host side follows. */
+int install_renders(icw_ctx *c, StreamTable<RenderEnt> &t, int first, int count)
 {
-    std::vector<RenderEnt> ne;
-    std::vector<int32_t> map(ents.size(), -1);
-    for (int32_t &e : of) {
-        if (map[(size_t)e] < 0) {
-            size_t k = 0;
-            while (k < ne.size() && !same_render(ne[k], ents[(size_t)e])) ++k;
-            if (k == ne.size()) ne.push_back(ents[(size_t)e]);
-            map[(size_t)e] = (int32_t)k;
-        }
-        e = map[(size_t)e];
-    }
-    const size_t n = ne.size(), S = (size_t)c->n_streams;
+    const size_t n = t.size(), S = (size_t)c->n_streams;
     /* more than one render: K3's FP_CHECK form, K4 and the FIR converter's fused render take one */
     if (n > 1 && (c->fir_M > 0 || c->cfg.fp_check || c->prog.is_bus)) return ICW_EUNSUPPORTED;
-    bool serial = false, rstate = false;
-    for (const RenderEnt &e : ne) {
-        serial |= e.serial;
-        rstate |= e.rstate;
-    }
+    bool rstate = false;
+    for (const RenderEnt &e : t.ents) rstate |= e.rstate;
     int rc;
     if (rstate && (rc = ensure_render_state(c))) return rc;
     IcwRenderEnt *fresh = nullptr;
@@ -545,95 +365,236 @@ int install_renders(icw_ctx *c, std::vector<RenderEnt> &ents, std::vector<int32_
         for (size_t k = 0; k < n; ++k) {
             IcwRenderEnt d;
             memset(&d, 0, sizeof(d));
-            d.rk = ne[k].rk;
-            d.serial = ne[k].serial ? 1 : 0;
-            d.dither = ne[k].dither ? 1 : 0;
-            d.fsz = ne[k].osz();
+            d.rk = t.ents[k].rk;
+            d.serial = t.ents[k].serial ? 1 : 0;
+            d.dither = t.ents[k].dither ? 1 : 0;
+            d.fsz = t.ents[k].osz();
             memcpy(h.data() + k * sizeof(IcwRenderEnt), &d, sizeof(d));
         }
-        memcpy(h.data() + tb, of.data(), S * sizeof(int32_t));
+        memcpy(h.data() + tb, t.of.data(), S * sizeof(int32_t));
         if (hipMalloc((void **)&fresh, h.size()) != hipSuccess) return ICW_ENOMEM;
         if (hipMemcpy(fresh, h.data(), h.size(), hipMemcpyHostToDevice) != hipSuccess) {
             (void)hipFree(fresh);
             return ICW_EDEVICE;
         }
     }
-    std::vector<double> new_hi((size_t)count);
-    for (int i = 0; i < count; ++i) new_hi[(size_t)i] = ne[(size_t)of[(size_t)(first + i)]].rk.hi;
-    bool ok = fold_peaks_range(c, first, count, new_hi);
-    /* sound_render_recalc: prev_rnd, the shaper rings and prev_ns_err start again, the RNG goes on */
-    if (ok && c->st.rs)
-        ok = hipMemset(c->st.rs + (size_t)first * 2 * ICW_RSTATE, 0, (size_t)count * 2 * ICW_RSTATE * sizeof(double)) == hipSuccess;
-    if (!ok) {
+    if (!fold_peaks(c, t, first, count) || !restart_shaping(c, (size_t)first, (size_t)count)) {
         if (fresh) (void)hipFree(fresh);
         return ICW_EDEVICE;
     }
     if (c->d_rtab) (void)hipFree(c->d_rtab);
     c->d_rtab = fresh;
     c->d_rof = fresh ? (int32_t *)((unsigned char *)fresh + n * sizeof(IcwRenderEnt)) : nullptr;
-    c->cfg.render = ne[0].cfg;
-    c->cfg.need24bits = ne[0].is24;
-    c->rk = ne[0].rk;
-    c->serial_render = serial;
-    c->render_state = rstate;
-    if (n == 1) {
-        c->renders.clear();
-        c->render_of.clear();
-    } else {
-        c->renders.swap(ne);
-        c->render_of.swap(of);
+    c->renders = std::move(t);
+    mirror_renders(c);
+    return ICW_OK;
+}
+
+/* ---- the list table (icw_set_graph, icw_set_stream_graph, the list primitives) ---- */
+
+bool same_list(const ListEnt &a, const ListEnt &b)
+{
+    return !memcmp(&a.prog, &b.prog, sizeof(IcwProg)) && a.nodes.size() == b.nodes.size() &&
+           (a.nodes.empty() || !memcmp(a.nodes.data(), b.nodes.data(), a.nodes.size() * sizeof(icw_node)));
+}
+
+/* the list table's mirrors: entry 0 (with several entries is_bus = 0, which is all the render setters ask of it) */
+void mirror_lists(icw_ctx *c)
+{
+    const ListEnt &e = c->lists.ents[0];
+    c->prog = e.prog;
+    c->nodes = e.nodes;
+    c->cfg.bypass_list = e.prog.bypass;
+}
+
+/* Install a candidate list table (the caller holds c->mu and has waited for the context's work).  The
+ * device copies come first, into memory the running table does not use where the table grows, so a
+ * failed copy leaves the old lists in force on both sides.  One entry: the context launches from d_prog,
+ * as it always did. */
+int install_lists(icw_ctx *c, StreamTable<ListEnt> &t)
+{
+    const size_t n = t.size();
+    IcwProg *fresh = nullptr;
+    if (n > 1) {
+        std::vector<IcwProg> h(n);                   /* the contiguous array d_progs holds */
+        for (size_t k = 0; k < n; ++k) h[k] = t.ents[k].prog;
+        if (n > c->d_progs_cap && hipMalloc((void **)&fresh, n * sizeof(IcwProg)) != hipSuccess) return ICW_ENOMEM;
+        if (!c->d_pid && dalloc(&c->d_pid, (size_t)c->n_streams * kPidWords) != ICW_OK) {
+            if (fresh) (void)hipFree(fresh);
+            c->d_pid = nullptr;
+            return ICW_ENOMEM;
+        }
+        if (hipMemcpy(fresh ? fresh : c->d_progs, h.data(), n * sizeof(IcwProg), hipMemcpyHostToDevice) != hipSuccess) {
+            if (fresh) (void)hipFree(fresh);
+            return ICW_EDEVICE;
+        }
+    }
+    /* d_prog follows prog (entry 0): the paths that read the pair (the encoders) see one program */
+    if (hipMemcpy(c->d_prog, &t.ents[0].prog, sizeof(IcwProg), hipMemcpyHostToDevice) != hipSuccess) {
+        if (fresh) (void)hipFree(fresh);
+        return ICW_EDEVICE;
+    }
+    if (fresh) {
+        if (c->d_progs) (void)hipFree(c->d_progs);
+        c->d_progs = fresh;
+        c->d_progs_cap = n;
+    }
+    c->lists = std::move(t);
+    mirror_lists(c);
+    /* c->mix and the selection rows are built from the lists (prepare_mix): rebuilt by the next call */
+    c->pid_valid = false;
+    return ICW_OK;
+}
+
+/* the normalised list nv as a table entry: compiled under the context's config with its own bypass flag */
+int compile_list(const icw_ctx *c, const std::vector<icw_node> &nv, int bypass, ListEnt &L)
+{
+    icw_config cfg = c->cfg;
+    cfg.bypass_list = bypass;
+    L.nodes = nv;
+    const int rc = build_prog(cfg, nv, L.prog);
+    if (rc == ICW_OK && !c->tn.chain_ok) L.prog.chain = L.prog.sig = 0;
+    return rc;
+}
+
+/* replace_output_plug (adv_modulator.c:176-209) of the nodes a list edit removed or re-plugged, matched by
+ * position against every old entry (include/icw.h): their old output slots read zero from now on */
+std::vector<std::vector<int>> matched_clears_per_entry(const icw_ctx *c, const std::vector<icw_node> &nv)
+{
+    std::vector<std::vector<int>> per(c->lists.size());
+    for (size_t e = 0; e < per.size(); ++e) matched_clears(c->lists.ents[e].nodes, nv, per[e]);
+    return per;
+}
+
+/* the clears of an installed list edit over streams [first, first + count): per[e] for the streams that ran
+ * entry e before (old_of), a stretch of them per memset.  The lists went to the device first, so a failed
+ * copy left the old lists and the old bus on both sides; a failed clear here returns ICW_EDEVICE with the new
+ * lists in place (the context is quiesced, so the order of the two steps changes no output). */
+int clear_matched(icw_ctx *c, const std::vector<int32_t> &old_of, int first, int count, const std::vector<std::vector<int>> &per)
+{
+    for (int i = first; i < first + count;) {
+        int j = i + 1;
+        while (j < first + count && old_of[(size_t)j] == old_of[(size_t)i]) ++j;
+        for (int slot : per[(size_t)old_of[(size_t)i]])
+            if (clear_slot_range(c, i, j - i, slot) != ICW_OK) return ICW_EDEVICE;
+        i = j;
     }
     return ICW_OK;
 }
 
-/* ---- per-stream Hilbert converters (icw_set_stream_hilbert) ---- */
-
-bool same_hilb(const HilbEnt &a, const HilbEnt &b) { return a.type == b.type && a.kahan == b.kahan && a.subn == b.subn; }
-
-/* the assignment in force as a table: the context's entries, or its one setting as entry 0 of every stream */
-void hilbs_in_force(const icw_ctx *c, std::vector<HilbEnt> &ents, std::vector<int32_t> &of)
+/* A context-wide list edit (icw_set_graph, the list primitives; the caller holds c->mu and has waited for
+ * the context's work): compile the normalised list nv and put every stream on it; per[e] are the clears of
+ * the streams of entry e. */
+int apply_graph(icw_ctx *c, const std::vector<icw_node> &nv, int bypass, const std::vector<std::vector<int>> &per)
 {
-    ents = c->hilbs;
-    of = c->hilb_of;
-    if (ents.empty()) {
-        ents.push_back(make_hilb(c->cfg.hilbert_type, c->cfg.iir_kahan, c->cfg.iir_subnorm_reject));
-        of.assign((size_t)c->n_streams, 0);
+    ListEnt L;
+    int rc = compile_list(c, nv, bypass, L);
+    if (rc) return rc;
+    /* a bus-form list runs K4, one lane per stream on one program into one serial render, and one K2
+     * instance: refused while the lists, the renders or the converters differ (include/icw.h; the host
+     * collapses with a register-form list first) */
+    if (L.prog.is_bus && (c->lists.size() > 1 || c->renders.size() > 1 || c->hilbs.size() > 1)) return ICW_EUNSUPPORTED;
+    /* How the render runs follows the list only here, and only for the one render of a one-render context: a
+     * bus-form list makes it serial.  Several renders stand beside register-form lists alone (above), which
+     * change none of them, and the per-stream list setter takes register-form lists only -- so neither
+     * recomputes, as neither ever did. */
+    RenderEnt r0 = c->renders.ents[0];
+    if (c->renders.size() == 1) {
+        r0.serial = needs_serial(c->cfg, r0.rk, L.prog, c->tn.dith_par);
+        r0.rstate = needs_render_state(c->cfg, r0.rk, L.prog, c->tn.dith_par);
+        if (r0.rstate && (rc = ensure_render_state(c))) return rc;
     }
+    const std::vector<int32_t> old_of = c->lists.of;
+    StreamTable<ListEnt> t;
+    t.reset((size_t)c->n_streams, L);
+    if ((rc = install_lists(c, t)) != ICW_OK) return rc;
+    if (c->renders.size() == 1) {
+        c->renders.ents[0] = r0;
+        mirror_renders(c);
+    }
+    return clear_matched(c, old_of, 0, c->n_streams, per);
 }
 
-uint32_t stream_hilb_type(const icw_ctx *c, int s)
+
+/* ---- the input table (icw_set_input, icw_set_stream_input) ---- */
+
+IcwInDesc make_input(uint32_t sample_rate, uint32_t fmt, uint32_t channels)
 {
-    return c->hilbs.empty() ? c->cfg.hilbert_type : c->hilbs[(size_t)c->hilb_of[(size_t)s]].type;
+    IcwInDesc d;
+    memset(&d, 0, sizeof(d));
+    d.fmt = fmt;
+    d.csz = fmt_size(fmt);
+    d.fsz = d.csz * channels;
+    d.nch = channels;
+    d.sample_rate = sample_rate;
+    d.ssr = (unsigned long long)sample_rate * ICW_HZ_SCALE;
+    return d;
 }
 
-/* the order of stream s's converters: what its state blob records */
-int stream_nord(const icw_ctx *c, int s)
+bool same_input(const IcwInDesc &a, const IcwInDesc &b)
 {
-    return c->hilbs.empty() ? c->nord : c->hilbs[(size_t)c->hilb_of[(size_t)s]].nord;
+    return a.fmt == b.fmt && a.nch == b.nch && a.sample_rate == b.sample_rate;
 }
 
-/* Install an assignment (the caller holds c->mu and has waited for the context's work): ents[of[s]] is
- * stream s's converter setting.  The table is compacted like the list and render tables -- equal entries
- * become one, unused ones go, the survivors numbered in order of their first stream.  Refusals and the
- * device copy (the entries' coefficients, into fresh memory with room for a call's run descriptors) come
- * before any state is touched, so a failure leaves the old settings in force.  Then every stream whose type
- * changes has its converters re-created as hq_rp_create does (zero rings, phases 0, counters 0, lr_equal 1),
- * a stream that keeps its type keeps its rings, and the de-subnorm counters of streams [first, first +
- * count) restart (iir_rp_setcfg).  One entry left: a one-setting context again. */
-int install_hilberts(icw_ctx *c, std::vector<HilbEnt> &ents, std::vector<int32_t> &of, int first, int count)
+bool any_cwave(const StreamTable<IcwInDesc> &t)
 {
-    std::vector<HilbEnt> ne;
-    std::vector<int32_t> map(ents.size(), -1);
-    for (int32_t &e : of) {
-        if (map[(size_t)e] < 0) {
-            size_t k = 0;
-            while (k < ne.size() && !same_hilb(ne[k], ents[(size_t)e])) ++k;
-            if (k == ne.size()) ne.push_back(ents[(size_t)e]);
-            map[(size_t)e] = (int32_t)k;
+    for (const IcwInDesc &d : t.ents)
+        if (d.fmt >= ICW_FMT_CW_F64) return true;
+    return false;
+}
+
+/* the input table's mirrors: cfg's three fields are the one input.  While the inputs differ they keep the
+ * one last in force alone, not entry 0: icw_set_stream_input's CWAVE refusal and the encoders' plan read
+ * them, and did so before the inputs were a table */
+void mirror_inputs(icw_ctx *c)
+{
+    if (c->inputs.size() > 1) return;
+    const IcwInDesc &d = c->inputs.ents[0];
+    c->cfg.sample_rate = d.sample_rate;
+    c->cfg.in_format = d.fmt;
+    c->cfg.in_channels = d.nch;
+}
+
+/* Install a candidate input table (the caller holds c->mu and has waited for the context's work).  The device
+ * table, one descriptor per stream, comes first (it is allocated by the first install that needs it): a
+ * failed allocation or copy leaves the old inputs in force */
+int install_inputs(icw_ctx *c, StreamTable<IcwInDesc> &t)
+{
+    if (t.size() > 1) {
+        const size_t S = (size_t)c->n_streams;
+        std::vector<IcwInDesc> h(S);
+        for (size_t s = 0; s < S; ++s) h[s] = t.at(s);
+        IcwInDesc *fresh = nullptr;
+        if (!c->d_inputs && hipMalloc((void **)&fresh, S * sizeof(IcwInDesc)) != hipSuccess) return ICW_ENOMEM;
+        if (!c->d_pid && dalloc(&c->d_pid, S * kPidWords) != ICW_OK) {
+            if (fresh) (void)hipFree(fresh);
+            if (c->d_pid) (void)hipFree(c->d_pid);
+            c->d_pid = nullptr;
+            return ICW_ENOMEM;
         }
-        e = map[(size_t)e];
+        if (hipMemcpy(fresh ? fresh : c->d_inputs, h.data(), S * sizeof(IcwInDesc), hipMemcpyHostToDevice) != hipSuccess) {
+            if (fresh) (void)hipFree(fresh);
+            return ICW_EDEVICE;
+        }
+        if (fresh) c->d_inputs = fresh;
     }
-    const size_t n = ne.size(), S = (size_t)c->n_streams;
+    c->inputs = std::move(t);
+    mirror_inputs(c);
+    c->pid_valid = false;                 /* the selection rows carry the rate and the channels */
+    return ICW_OK;
+}
+
+/* ---- the converter table (icw_set_hilbert_filter, icw_set_hilbert_config, icw_set_stream_hilbert) ---- */
+
+/* Install a candidate converter table (the caller holds c->mu and has waited for the context's work).
+ * Refusals and the device copy (the entries' coefficients, into fresh memory with room for a call's run
+ * descriptors) come before any state is touched, so a failure leaves the old settings in force.  Then every
+ * stream whose type changes has its converters re-created (reset_rings), a stretch of them at a time; a
+ * stream that keeps its type keeps its rings; and the de-subnorm counters of streams [first, first + count)
+ * restart (iir_rp_setcfg: "new world"). */
+int install_hilberts(icw_ctx *c, StreamTable<HilbEnt> &t, int first, int count)
+{
+    const size_t n = t.size(), S = (size_t)c->n_streams;
     /* more than one setting: the FIR converter replaces the IIR for every stream, K1f (FP_CHECK) and the
      * bus-form path run one instance */
     if (n > 1 && (c->fir_M > 0 || c->cfg.fp_check || c->prog.is_bus)) return ICW_EUNSUPPORTED;
@@ -641,29 +602,25 @@ int install_hilberts(icw_ctx *c, std::vector<HilbEnt> &ents, std::vector<int32_t
     const size_t pc_bytes = n * 20 * sizeof(double), run_bytes = S * sizeof(IcwK1Run);
     if (n > 1) {
         std::vector<double> h(n * 20);
-        for (size_t k = 0; k < n; ++k) memcpy(&h[k * 20], ne[k].pc, sizeof(ne[k].pc));
+        for (size_t k = 0; k < n; ++k) memcpy(&h[k * 20], t.ents[k].pc, sizeof(t.ents[k].pc));
         if (hipMalloc((void **)&fresh, pc_bytes + run_bytes + 5 * S * sizeof(int32_t)) != hipSuccess) return ICW_ENOMEM;
         if (hipMemcpy(fresh, h.data(), pc_bytes, hipMemcpyHostToDevice) != hipSuccess) {
             (void)hipFree(fresh);
             return ICW_EDEVICE;
         }
     }
-    DevState &s = c->st;
+    const auto changes = [&](size_t s) { return t.at(s).type != c->hilbs.at(s).type; };
     bool ok = true;
     for (size_t i = 0; i < S && ok; ++i) {
-        if (ne[(size_t)of[i]].type == stream_hilb_type(c, (int)i)) continue;
-        size_t j = i + 1;                              /* a stretch of streams whose type changes */
-        while (j < S && ne[(size_t)of[j]].type != stream_hilb_type(c, (int)j)) ++j;
-        const size_t m = j - i;
-        ok &= hipMemset(s.hist + i * 4 * ICW_HIST_PITCH, 0, m * 4 * ICW_HIST_PITCH * sizeof(double)) == hipSuccess;
-        ok &= hipMemset(s.sncnt + i * 4, 0, m * 4 * sizeof(unsigned long long)) == hipSuccess;
-        ok &= hipMemset(s.hq_phase + i * 2, 0, m * 2 * sizeof(uint32_t)) == hipSuccess;
-        ok &= hipMemsetD32((hipDeviceptr_t)(s.lr_equal + i * 2), 1, m * 2) == hipSuccess;
-        for (size_t k = i; k < j; ++k) c->lr_known[k] = 1;
-        i = j - 1;
+        if (!changes(i)) continue;
+        size_t j = i + 1;
+        while (j < S && changes(j)) ++j;
+        ok = reset_rings(c, i, j - i, c->stream);
+        i = j;
     }
+    ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
     if (ok && count > 0)
-        ok = hipMemset(s.sncnt + (size_t)first * 4, 0, (size_t)count * 4 * sizeof(unsigned long long)) == hipSuccess;
+        ok = hipMemset(c->st.sncnt + (size_t)first * 4, 0, (size_t)count * 4 * sizeof(unsigned long long)) == hipSuccess;
     if (!ok) {
         if (fresh) (void)hipFree(fresh);
         return ICW_EDEVICE;
@@ -673,14 +630,8 @@ int install_hilberts(icw_ctx *c, std::vector<HilbEnt> &ents, std::vector<int32_t
     c->d_hruns = fresh ? (IcwK1Run *)((unsigned char *)fresh + pc_bytes) : nullptr;
     c->d_hpid = fresh ? (int32_t *)((unsigned char *)fresh + pc_bytes + run_bytes) : nullptr;
     c->hrun_valid = false;
-    set_one_hilb(c, ne[0]);
-    if (n == 1) {
-        c->hilbs.clear();
-        c->hilb_of.clear();
-    } else {
-        c->hilbs.swap(ne);
-        c->hilb_of.swap(of);
-    }
+    c->hilbs = std::move(t);
+    mirror_hilbs(c);
     return ICW_OK;
 }
 
@@ -724,24 +675,29 @@ int icw_create(const icw_config *cfg, const icw_node *nodes, int n_nodes, int n_
     }
     c->device = device;
     if (set_dev(c)) { delete c; return ICW_EDEVICE; }
-    c->nodes.assign(nodes, nodes + n_nodes);
-    const bool ok = graph_accept(c->nodes);
-    if (!ok) c->nodes.assign(1, default_master());
+    ListEnt L;
+    L.nodes.assign(nodes, nodes + n_nodes);
+    const bool ok = graph_accept(L.nodes);
+    if (!ok) L.nodes.assign(1, default_master());
     if (accepted) *accepted = ok ? 1 : 0;
     c->tn = icw_read_tuning();
-    int rc = build_prog(*cfg, c->nodes, c->prog);
+    int rc = build_prog(*cfg, L.nodes, L.prog);
     if (rc) { delete c; return rc; }
-    if (!c->tn.chain_ok) c->prog.chain = c->prog.sig = 0;
-    set_filter(c);
-    render_consts(cfg->render, cfg->need24bits, c->tn.k3r_spec, c->rk);
-    c->serial_render = needs_serial(*cfg, c->rk, c->prog, c->tn.dith_par);
-    c->render_state = needs_render_state(*cfg, c->rk, c->prog, c->tn.dith_par);
+    if (!c->tn.chain_ok) L.prog.chain = L.prog.sig = 0;
+    /* the four tables, one entry each, and their mirrors (the render's entry is made behind the list's) */
+    c->n_streams = n_streams;
+    c->lists.reset((size_t)n_streams, L);
+    mirror_lists(c);
+    c->inputs.reset((size_t)n_streams, make_input(cfg->sample_rate, cfg->in_format, cfg->in_channels));
+    c->hilbs.reset((size_t)n_streams, make_hilb(cfg->hilbert_type, cfg->iir_kahan, cfg->iir_subnorm_reject));
+    mirror_hilbs(c);
+    c->renders.reset((size_t)n_streams, make_render(c, cfg->render, cfg->need24bits));
+    mirror_renders(c);
     for (int ch = 0; ch < 2; ++ch) {
         uint32_t *st = c->mt_seed_state[ch];
         st[0] = ch ? cfg->seed_right : cfg->seed_left;         /* mtrnd_init_seed, mt_jrnd.c:28-47 */
         for (uint32_t j = 1; j < 624; ++j) st[j] = 1812433253u * (st[j - 1] ^ (st[j - 1] >> 30)) + j;
     }
-    c->n_streams = n_streams;
     const size_t S = (size_t)n_streams, C = S * 4;
     rc = ICW_OK;
     DevState &s = c->st;
@@ -787,7 +743,6 @@ int icw_create(const icw_config *cfg, const icw_node *nodes, int n_nodes, int n_
     c->peak_db.assign(S * 2, ICW_SR_ZERO_SIGNAL_DB);
     c->lr_known.assign(S, 1);
     c->nf_host.assign(S, 0ull);
-    c->inputs.assign(S, make_input(cfg->sample_rate, cfg->in_format, cfg->in_channels));
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, c->device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
@@ -820,12 +775,7 @@ int icw_stream_init(icw_ctx *c, int first, int count)
     DevState &s = c->st;
     const size_t f = (size_t)first, n = (size_t)count;
     hipStream_t st = c->stream;
-    bool ok = true;
-    ok &= hipMemsetAsync(s.hist + f * 4 * ICW_HIST_PITCH, 0, n * 4 * ICW_HIST_PITCH * sizeof(double), st) == hipSuccess;
-    ok &= hipMemsetAsync(s.sncnt + f * 4, 0, n * 4 * sizeof(unsigned long long), st) == hipSuccess;
-    ok &= hipMemsetAsync(s.hq_phase + f * 2, 0, n * 2 * sizeof(uint32_t), st) == hipSuccess;
-    ok &= hipMemsetD32Async((hipDeviceptr_t)(s.lr_equal + f * 2), 1, n * 2, st) == hipSuccess;
-    for (size_t i = 0; i < n; ++i) c->lr_known[f + i] = 1;
+    bool ok = reset_rings(c, f, n, st);
     ok &= hipMemsetAsync(s.pos + f, 0, n * sizeof(long long), st) == hipSuccess;
     ok &= hipMemsetAsync(s.n_frame + f, 0, n * sizeof(unsigned long long), st) == hipSuccess;
     for (size_t i = 0; i < n; ++i) c->nf_host[f + i] = 0;
@@ -853,7 +803,7 @@ int icw_stream_open(icw_ctx *c, int s, int64_t n_samples, uint32_t fade_in, uint
     (void)sec_align;   /* the virtual zero tail is produced by the reader (xwave_read_samples) */
     std::lock_guard<std::mutex> lk(c->mu);
     /* the fades at the stream's own rate (icw_set_stream_input; the context's while the inputs are one) */
-    const uint64_t rate = c->inputs[(size_t)s].sample_rate;
+    const uint64_t rate = c->inputs.at((size_t)s).sample_rate;
     long long nfi = (long long)(((uint64_t)fade_in * rate) / 1000ULL);
     long long nfo = (long long)(((uint64_t)fade_out * rate) / 1000ULL);
     if (nfi + nfo >= n_samples) {
@@ -873,18 +823,11 @@ int icw_stream_open(icw_ctx *c, int s, int64_t n_samples, uint32_t fade_in, uint
         ok &= hipMemset(c->st.n_frame + s, 0, sizeof(unsigned long long)) == hipSuccess;
         c->nf_host[s] = 0;
     }
-    if (clr_hilb) {
-        ok &= hipMemset(c->st.hist + (size_t)s * 4 * ICW_HIST_PITCH, 0, 4 * ICW_HIST_PITCH * sizeof(double)) == hipSuccess;
-        ok &= hipMemset(c->st.sncnt + (size_t)s * 4, 0, 4 * sizeof(unsigned long long)) == hipSuccess;
-        ok &= hipMemset(c->st.hq_phase + (size_t)s * 2, 0, 2 * sizeof(uint32_t)) == hipSuccess;
-        ok &= hipMemsetD32((hipDeviceptr_t)(c->st.lr_equal + (size_t)s * 2), 1, 2) == hipSuccess;
-        c->lr_known[s] = 1;
-        ok &= fir_clear(c, (size_t)s, 1, c->stream) && hipStreamSynchronize(c->stream) == hipSuccess;
-    }
-    /* sound_render_set_outbits -> sound_render_recalc: prev_rnd, shaper buffers and prev_ns_err
-     * reset, the RNG is not (sound_render.c:527-580) */
-    if (c->st.rs)
-        ok &= hipMemset(c->st.rs + (size_t)s * 2 * ICW_RSTATE, 0, 2 * ICW_RSTATE * sizeof(double)) == hipSuccess;
+    if (clr_hilb)
+        ok &= reset_rings(c, (size_t)s, 1, c->stream) && fir_clear(c, (size_t)s, 1, c->stream) &&
+              hipStreamSynchronize(c->stream) == hipSuccess;
+    /* sound_render_set_outbits -> sound_render_recalc */
+    ok &= restart_shaping(c, (size_t)s, 1);
     return ok ? ICW_OK : ICW_EDEVICE;
 }
 
@@ -895,12 +838,8 @@ int icw_stream_reset_hilbert(icw_ctx *c, int s)
     if (set_dev(c)) return ICW_EDEVICE;
     c->touched = true;
     bool ok = quiesce(c) == hipSuccess;
-    ok &= hipMemset(c->st.hist + (size_t)s * 4 * ICW_HIST_PITCH, 0, 4 * ICW_HIST_PITCH * sizeof(double)) == hipSuccess;
-    ok &= hipMemset(c->st.sncnt + (size_t)s * 4, 0, 4 * sizeof(unsigned long long)) == hipSuccess;
-    ok &= hipMemset(c->st.hq_phase + (size_t)s * 2, 0, 2 * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMemsetD32((hipDeviceptr_t)(c->st.lr_equal + (size_t)s * 2), 1, 2) == hipSuccess;
-    c->lr_known[s] = 1;
-    ok &= fir_clear(c, (size_t)s, 1, c->stream) && hipStreamSynchronize(c->stream) == hipSuccess;
+    ok &= reset_rings(c, (size_t)s, 1, c->stream) && fir_clear(c, (size_t)s, 1, c->stream) &&
+          hipStreamSynchronize(c->stream) == hipSuccess;
     return ok ? ICW_OK : ICW_EDEVICE;
 }
 
@@ -927,14 +866,14 @@ int icw_set_fir_hilbert(icw_ctx *c, int32_t M, double beta)
     std::lock_guard<std::mutex> lk(c->mu);
     /* beside per-stream lists or inputs only once the host has asked for it (icw_enable_stream_fir): the
      * converter's kernels then run their per-stream form */
-    if (M > 0 && !c->fir_streams && (!c->progs.empty() || c->n_inputs > 1)) return ICW_EUNSUPPORTED;
+    if (M > 0 && !c->fir_streams && (c->lists.size() > 1 || c->inputs.size() > 1)) return ICW_EUNSUPPORTED;
     /* nor beside per-stream CWAVE inputs (icw_enable_stream_cwave): the converter's per-stream kernels read
      * real formats only, and icw_set_stream_input refuses to build that state from its side */
-    if (M > 0 && c->n_inputs > 1 && any_cwave(c->inputs)) return ICW_EUNSUPPORTED;
+    if (M > 0 && c->inputs.size() > 1 && any_cwave(c->inputs)) return ICW_EUNSUPPORTED;
     /* nor beside per-stream renders (icw_set_stream_render): the fused converter renders with one */
-    if (M > 0 && !c->renders.empty()) return ICW_EUNSUPPORTED;
+    if (M > 0 && c->renders.size() > 1) return ICW_EUNSUPPORTED;
     /* nor beside per-stream Hilbert converters (icw_set_stream_hilbert): it replaces the IIR for every stream */
-    if (M > 0 && !c->hilbs.empty()) return ICW_EUNSUPPORTED;
+    if (M > 0 && c->hilbs.size() > 1) return ICW_EUNSUPPORTED;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     c->pid_valid = false;                 /* with the converter on, every (list, rate) pair has a slab */
     for (double *&h : c->fir_hist)
@@ -971,7 +910,7 @@ int icw_enable_stream_fir(icw_ctx *c, int on)
     if (!c) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     /* off while the two are in force together would leave a state the setters refuse to build */
-    if (!on && c->fir_M > 0 && (!c->progs.empty() || c->n_inputs > 1)) return ICW_EUNSUPPORTED;
+    if (!on && c->fir_M > 0 && (c->lists.size() > 1 || c->inputs.size() > 1)) return ICW_EUNSUPPORTED;
     c->fir_streams = on != 0;
     return ICW_OK;
 }
@@ -993,7 +932,7 @@ int icw_enable_stream_cwave(icw_ctx *c, int on)
 {
     if (!c) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!on && c->n_inputs > 1 && any_cwave(c->inputs)) return ICW_EUNSUPPORTED;
+    if (!on && c->inputs.size() > 1 && any_cwave(c->inputs)) return ICW_EUNSUPPORTED;
     c->cw_streams = on != 0;
     return ICW_OK;
 }
@@ -1026,14 +965,10 @@ int icw_set_input(icw_ctx *c, uint32_t sample_rate, uint32_t fmt, uint32_t chann
     if (!c || sample_rate == 0 || sample_rate > ICW_MAX_FS_SRC || fmt > ICW_FMT_CW_F32 || channels == 0) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
-    c->cfg.sample_rate = sample_rate;
-    c->cfg.in_format = fmt;
-    c->cfg.in_channels = channels;
     /* every stream: a context whose streams differed is a one-input context again */
-    c->inputs.assign((size_t)c->n_streams, make_input(sample_rate, fmt, channels));
-    c->pid_valid = false;                 /* the selection rows carry the rate and the channels */
-    c->n_inputs = 1;
-    return ICW_OK;
+    StreamTable<IcwInDesc> t;
+    t.reset((size_t)c->n_streams, make_input(sample_rate, fmt, channels));
+    return install_inputs(c, t);
 }
 
 /* icw_set_input for streams [first, first + count) (include/icw.h) */
@@ -1050,44 +985,17 @@ int icw_set_stream_input(icw_ctx *c, int first, int count, uint32_t sample_rate,
     const bool cwf = fmt >= ICW_FMT_CW_F64;
     if (!c->cw_streams && (cwf || c->cfg.in_format >= ICW_FMT_CW_F64)) return ICW_EUNSUPPORTED;
     if (c->fir_M > 0 && (!c->fir_streams || cwf)) return ICW_EUNSUPPORTED;
-    std::vector<IcwInDesc> nv = c->inputs;
-    for (int s = first; s < first + count; ++s) nv[(size_t)s] = make_input(sample_rate, fmt, channels);
-    const int n = count_inputs(nv);
-    if (c->fir_M > 0 && n > 1 && any_cwave(nv)) return ICW_EUNSUPPORTED;
+    StreamTable<IcwInDesc> t = c->inputs.assigned((size_t)first, (size_t)count, make_input(sample_rate, fmt, channels), same_input);
+    if (c->fir_M > 0 && t.size() > 1 && any_cwave(t)) return ICW_EUNSUPPORTED;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
-    if (n > 1) {
-        /* the device table first: a failed allocation or copy leaves the old inputs in force */
-        IcwInDesc *fresh = nullptr;
-        if (!c->d_inputs && hipMalloc((void **)&fresh, nv.size() * sizeof(IcwInDesc)) != hipSuccess) return ICW_ENOMEM;
-        if (!c->d_pid && dalloc(&c->d_pid, (size_t)c->n_streams * kPidWords) != ICW_OK) {
-            if (fresh) (void)hipFree(fresh);
-            if (c->d_pid) (void)hipFree(c->d_pid);
-            c->d_pid = nullptr;
-            return ICW_ENOMEM;
-        }
-        if (hipMemcpy(fresh ? fresh : c->d_inputs, nv.data(), nv.size() * sizeof(IcwInDesc), hipMemcpyHostToDevice) !=
-            hipSuccess) {
-            if (fresh) (void)hipFree(fresh);
-            return ICW_EDEVICE;
-        }
-        if (fresh) c->d_inputs = fresh;
-    } else {
-        /* one input again, whichever call gave it: the context-wide one */
-        c->cfg.sample_rate = sample_rate;
-        c->cfg.in_format = fmt;
-        c->cfg.in_channels = channels;
-    }
-    c->inputs.swap(nv);
-    c->n_inputs = n;
-    c->pid_valid = false;
-    return ICW_OK;
+    return install_inputs(c, t);
 }
 
 int icw_stream_input_count(const icw_ctx *c)
 {
     if (!c) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(const_cast<icw_ctx *>(c)->mu);
-    return c->n_inputs;
+    return (int)c->inputs.size();
 }
 
 /* Live edits: what the reference's GUI thread changes while a decode thread runs
@@ -1102,34 +1010,9 @@ int icw_set_graph(icw_ctx *c, const icw_node *nodes, int n_nodes, int bypass_lis
     if (!ok) return ICW_EGRAPH;
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
-    /* replace_output_plug (adv_modulator.c:176-209) of the removed / re-plugged nodes, matched by
-     * position (include/icw.h): their old output slots read zero from now on */
-    std::vector<int> clears;
-    if (!c->progs.empty()) {
-        /* the streams' lists differ: every one of them is replaced (the table collapses to this list),
-         * each stream's clears matched against its own old list.  A bus-form list is refused here
-         * (include/icw.h): the host collapses with a register-form list first. */
-        icw_config cfg = c->cfg;
-        cfg.bypass_list = bypass_list ? 1 : 0;
-        IcwProg P;
-        int rc = build_prog(cfg, nv, P);
-        if (rc) return rc;
-        if (P.is_bus) return ICW_EUNSUPPORTED;
-        std::vector<std::vector<int>> per(c->plists.size());
-        for (size_t e = 0; e < c->plists.size(); ++e) matched_clears(c->plists[e], nv, per[e]);
-        const std::vector<int32_t> of = c->prog_of;
-        if ((rc = apply_graph(c, nv, cfg.bypass_list, clears)) != ICW_OK) return rc;
-        c->progs.clear();
-        c->plists.clear();
-        c->prog_of.clear();
-        c->pid_valid = false;
-        for (int s = 0; s < c->n_streams; ++s)
-            for (int slot : per[(size_t)of[(size_t)s]])
-                if (clear_slot_range(c, s, 1, slot) != ICW_OK) return ICW_EDEVICE;
-        return ICW_OK;
-    }
-    matched_clears(c->nodes, nv, clears);
-    return apply_graph(c, nv, bypass_list ? 1 : 0, clears);
+    /* every stream's list is replaced (a table of several collapses to this list), each stream's clears
+     * matched against its own old list */
+    return apply_graph(c, nv, bypass_list ? 1 : 0, matched_clears_per_entry(c, nv));
 }
 
 /* icw_set_graph for streams [first, first + count) (include/icw.h) */
@@ -1147,34 +1030,15 @@ int icw_set_stream_graph(icw_ctx *c, int first, int count, const icw_node *nodes
     /* K4 runs one lane per stream on a scalar program: bus-form lists stay context-wide; the FIR
      * converter serves per-stream lists once icw_enable_stream_fir said so */
     if ((c->fir_M > 0 && !c->fir_streams) || c->prog.is_bus) return ICW_EUNSUPPORTED;
-    icw_config cfg = c->cfg;
-    cfg.bypass_list = bypass_list ? 1 : 0;
-    IcwProg P;
-    int rc = build_prog(cfg, nv, P);
+    ListEnt L;
+    int rc = compile_list(c, nv, bypass_list ? 1 : 0, L);
     if (rc) return rc;
-    if (P.is_bus) return ICW_EUNSUPPORTED;
-    if (!c->tn.chain_ok) P.chain = P.sig = 0;
-    /* the assignment as it is, the new entry for the range, then the table compacted */
-    std::vector<IcwProg> progs = c->progs;
-    std::vector<std::vector<icw_node>> lists = c->plists;
-    std::vector<int32_t> of = c->prog_of;
-    if (progs.empty()) {
-        progs.push_back(c->prog);
-        lists.push_back(c->nodes);
-        of.assign((size_t)c->n_streams, 0);
-    }
-    std::vector<std::vector<int>> per(lists.size());
-    for (size_t e = 0; e < lists.size(); ++e) matched_clears(lists[e], nv, per[e]);
-    const std::vector<int32_t> old_of = of;
-    progs.push_back(P);
-    lists.push_back(nv);
-    for (int s = first; s < first + count; ++s) of[(size_t)s] = (int32_t)progs.size() - 1;
-    prog_table_compact(progs, lists, of);
-    if ((rc = install_table(c, progs, lists, of)) != ICW_OK) return rc;
-    for (int s = first; s < first + count; ++s)
-        for (int slot : per[(size_t)old_of[(size_t)s]])
-            if (clear_slot_range(c, s, 1, slot) != ICW_OK) return ICW_EDEVICE;
-    return ICW_OK;
+    if (L.prog.is_bus) return ICW_EUNSUPPORTED;
+    const std::vector<std::vector<int>> per = matched_clears_per_entry(c, nv);
+    const std::vector<int32_t> old_of = c->lists.of;
+    StreamTable<ListEnt> t = c->lists.assigned((size_t)first, (size_t)count, L, same_list);
+    if ((rc = install_lists(c, t)) != ICW_OK) return rc;
+    return clear_matched(c, old_of, first, count, per);
 }
 
 int icw_clear_stream_bus_slot(icw_ctx *c, int first, int count, int slot)
@@ -1204,7 +1068,7 @@ int icw_stream_graph_count(const icw_ctx *c)
 {
     if (!c) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(const_cast<icw_ctx *>(c)->mu);
-    return c->progs.empty() ? 1 : (int)c->progs.size();
+    return (int)c->lists.size();
 }
 
 /* the list primitives (include/icw.h): the reference's own edits, each with replace_output_plug's
@@ -1213,21 +1077,21 @@ int icw_graph_del_last(icw_ctx *c)
 {
     if (!c) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->progs.empty()) return ICW_EUNSUPPORTED;                 /* no one list to edit (include/icw.h) */
+    if (c->lists.size() > 1) return ICW_EUNSUPPORTED;               /* no one list to edit (include/icw.h) */
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     if (c->nodes.size() <= 1) return ICW_OK;                        /* am.tail->prev == NULL */
     std::vector<icw_node> nv(c->nodes.begin(), c->nodes.end() - 1);
     std::vector<int> clears;
     const int r = plug_slot(c->nodes.back());
     if (r >= 0) clears.push_back(r);
-    return apply_graph(c, nv, c->cfg.bypass_list, clears);
+    return apply_graph(c, nv, c->cfg.bypass_list, {clears});
 }
 
 int icw_graph_del_all(icw_ctx *c)
 {
     if (!c) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->progs.empty()) return ICW_EUNSUPPORTED;
+    if (c->lists.size() > 1) return ICW_EUNSUPPORTED;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     if (c->nodes.size() <= 1) return ICW_OK;
     std::vector<int> clears;
@@ -1236,7 +1100,7 @@ int icw_graph_del_all(icw_ctx *c)
         if (r >= 0) clears.push_back(r);
     }
     std::vector<icw_node> nv(c->nodes.begin(), c->nodes.begin() + 1);
-    return apply_graph(c, nv, c->cfg.bypass_list, clears);
+    return apply_graph(c, nv, c->cfg.bypass_list, {clears});
 }
 
 int icw_graph_add_last(icw_ctx *c, const icw_node *node)
@@ -1244,19 +1108,19 @@ int icw_graph_add_last(icw_ctx *c, const icw_node *node)
     if (!c || !node) return ICW_EINVAL;
     if (node->mode == ICW_MODE_MASTER) return ICW_EGRAPH;           /* create_node_dsp: NULL */
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->progs.empty()) return ICW_EUNSUPPORTED;
+    if (c->lists.size() > 1) return ICW_EUNSUPPORTED;
     std::vector<icw_node> nv(c->nodes);
     nv.push_back(*node);
     if (!graph_accept(nv)) return ICW_EGRAPH;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
-    return apply_graph(c, nv, c->cfg.bypass_list, std::vector<int>());
+    return apply_graph(c, nv, c->cfg.bypass_list, {{}});
 }
 
 int icw_graph_set_output_plug(icw_ctx *c, int index, int n)
 {
     if (!c || n < -1 || n >= ICW_N_INPUTS || n == 0) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->progs.empty()) return ICW_EUNSUPPORTED;
+    if (c->lists.size() > 1) return ICW_EUNSUPPORTED;
     if (index < 0 || index >= (int)c->nodes.size()) return ICW_EINVAL;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     std::vector<icw_node> nv(c->nodes);
@@ -1266,7 +1130,7 @@ int icw_graph_set_output_plug(icw_ctx *c, int index, int n)
         clears.push_back(r);
         if (n >= 0) nv[index].n_out = n;
     }
-    return apply_graph(c, nv, c->cfg.bypass_list, clears);
+    return apply_graph(c, nv, c->cfg.bypass_list, {clears});
 }
 
 int icw_clear_bus_slot(icw_ctx *c, int slot)
@@ -1274,160 +1138,32 @@ int icw_clear_bus_slot(icw_ctx *c, int slot)
     if (!c || slot < 0 || slot >= ICW_N_INPUTS) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
-    return clear_slot(c, slot);
+    return clear_slot_range(c, 0, c->n_streams, slot);
 }
 
+/* srenders_set_vcfg: every stream gets the setting at its own depth (a table of several collapses to as many
+ * entries as depths in force), and every stream's shaping state restarts */
 int icw_set_render(icw_ctx *c, const icw_render_cfg *r)
 {
     if (!c || !r || !render_cfg_ok(*r)) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
-    if (!c->renders.empty()) {
-        /* the streams' renders differ: every stream gets the new setting at its own depth, so the table
-         * collapses to as many entries as depths in force; every stream's shaping state restarts */
-        std::vector<RenderEnt> ents;
-        std::vector<int32_t> of;
-        renders_in_force(c, ents, of);
-        for (RenderEnt &e : ents) e = make_render(c, *r, e.is24);
-        return install_renders(c, ents, of, 0, c->n_streams);
-    }
-    IcwRenderK k;
-    render_consts(*r, c->cfg.need24bits, c->tn.k3r_spec, k);
-    icw_config cfg = c->cfg;
-    cfg.render = *r;
-    const bool serial = needs_serial(cfg, k, c->prog, c->tn.dith_par), rstate = needs_render_state(cfg, k, c->prog, c->tn.dith_par);
-    int rc;
-    if (rstate && (rc = ensure_render_state(c))) return rc;
-    if (k.hi != c->rk.hi && !fold_peaks(c)) return ICW_EDEVICE;
-    /* sound_render_recalc: prev_rnd, the shaper rings and prev_ns_err start again, the RNG goes on */
-    if (c->st.rs && hipMemset(c->st.rs, 0, (size_t)c->n_streams * 2 * ICW_RSTATE * sizeof(double)) != hipSuccess)
-        return ICW_EDEVICE;
-    c->cfg.render = *r;
-    c->rk = k;
-    c->serial_render = serial;
-    c->render_state = rstate;
-    return ICW_OK;
+    StreamTable<RenderEnt> t = c->renders.mapped([&](const RenderEnt &e) { return make_render(c, *r, e.is24); }, same_render);
+    return install_renders(c, t, 0, c->n_streams);
 }
 
 /* sound_render_set_outbits (sound_render.c:617-621) on both renders of every stream, as
  * mod_context_fopen applies the.cfg.need24bits at every track open (in_cwave.c:212, 233-234): the
  * new bounds, norm_mul and norm_shift, then sound_render_recalc (prev_rnd, the shaper rings and
  * prev_ns_err restart; the MT19937 generators go on).  Applied even when the depth is unchanged,
- * since recalc runs either way. */
+ * since recalc runs either way.  Every stream keeps its own setting. */
 int icw_set_outbits(icw_ctx *c, int need24bits)
 {
     if (!c) return ICW_EINVAL;
-    const int is24 = need24bits ? 1 : 0;
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
-    if (!c->renders.empty()) {
-        /* the streams' renders differ: every stream gets the new depth and keeps its own setting */
-        std::vector<RenderEnt> ents;
-        std::vector<int32_t> of;
-        renders_in_force(c, ents, of);
-        for (RenderEnt &e : ents) e = make_render(c, e.cfg, is24);
-        return install_renders(c, ents, of, 0, c->n_streams);
-    }
-    IcwRenderK k;
-    render_consts(c->cfg.render, is24, c->tn.k3r_spec, k);
-    icw_config cfg = c->cfg;
-    cfg.need24bits = is24;
-    const bool serial = needs_serial(cfg, k, c->prog, c->tn.dith_par), rstate = needs_render_state(cfg, k, c->prog, c->tn.dith_par);
-    int rc;
-    if (rstate && (rc = ensure_render_state(c))) return rc;
-    /* peaks so far in dB against the old bound (sound_render.c:769-780 converts each sample with the
-     * bound of its time) */
-    if (k.hi != c->rk.hi && !fold_peaks(c)) return ICW_EDEVICE;
-    if (c->st.rs && hipMemset(c->st.rs, 0, (size_t)c->n_streams * 2 * ICW_RSTATE * sizeof(double)) != hipSuccess)
-        return ICW_EDEVICE;
-    c->cfg.need24bits = is24;
-    c->rk = k;
-    c->serial_render = serial;
-    c->render_state = rstate;
-    return ICW_OK;
-}
-
-int icw_set_hilbert_filter(icw_ctx *c, uint32_t type)
-{
-    if (!c || type > 5) return ICW_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->hilbs.empty()) {
-        /* the streams' converters differ: every stream gets the type and keeps its summation, so the table
-         * collapses to as many entries as summations in force; only the streams whose type differs restart */
-        if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
-        std::vector<HilbEnt> ents;
-        std::vector<int32_t> of;
-        hilbs_in_force(c, ents, of);
-        for (HilbEnt &e : ents) e = make_hilb(type, e.kahan, e.subn);
-        return install_hilberts(c, ents, of, 0, 0);
-    }
-    if (type == c->cfg.hilbert_type) return ICW_OK;
-    if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
-    /* hq_rp_create: zero rings, ring index 0, counters 0, phase 0 -- for every stream */
-    const size_t S = (size_t)c->n_streams;
-    DevState &s = c->st;
-    bool ok = hipMemset(s.hist, 0, S * 4 * ICW_HIST_PITCH * sizeof(double)) == hipSuccess;
-    ok &= hipMemset(s.sncnt, 0, S * 4 * sizeof(unsigned long long)) == hipSuccess;
-    ok &= hipMemset(s.hq_phase, 0, S * 2 * sizeof(uint32_t)) == hipSuccess;
-    ok &= hipMemsetD32((hipDeviceptr_t)s.lr_equal, 1, S * 2) == hipSuccess;
-    if (!ok) return ICW_EDEVICE;
-    c->lr_known.assign(S, 1);
-    c->cfg.hilbert_type = type;
-    set_filter(c);
-    return ICW_OK;
-}
-
-int icw_set_hilbert_config(icw_ctx *c, int kahan, int subnorm_reject)
-{
-    if (!c) return ICW_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
-    if (!c->hilbs.empty()) {
-        /* the streams' converters differ: every stream gets the summation and keeps its type (and rings) */
-        std::vector<HilbEnt> ents;
-        std::vector<int32_t> of;
-        hilbs_in_force(c, ents, of);
-        for (HilbEnt &e : ents) e = make_hilb(e.type, kahan, subnorm_reject);
-        return install_hilberts(c, ents, of, 0, c->n_streams);
-    }
-    /* iir_rp_setcfg: the rings stay, the de-subnorm counters start again ("new world") */
-    if (hipMemset(c->st.sncnt, 0, (size_t)c->n_streams * 4 * sizeof(unsigned long long)) != hipSuccess)
-        return ICW_EDEVICE;
-    c->cfg.iir_kahan = kahan ? 1 : 0;
-    c->cfg.iir_subnorm_reject = subnorm_reject ? 1 : 0;
-    return ICW_OK;
-}
-
-/* icw_set_hilbert_filter followed by icw_set_hilbert_config for streams [first, first + count) (include/icw.h) */
-int icw_set_stream_hilbert(icw_ctx *c, int first, int count, uint32_t type, int kahan, int subnorm_reject)
-{
-    if (!c || first < 0 || count <= 0 || first > c->n_streams - count || type > 5) return ICW_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
-    /* the assignment as it is, the new entry for the range, then the table compacted */
-    std::vector<HilbEnt> ents;
-    std::vector<int32_t> of;
-    hilbs_in_force(c, ents, of);
-    ents.push_back(make_hilb(type, kahan, subnorm_reject));
-    for (int s = first; s < first + count; ++s) of[(size_t)s] = (int32_t)ents.size() - 1;
-    return install_hilberts(c, ents, of, first, count);
-}
-
-int icw_stream_hilbert_count(const icw_ctx *c)
-{
-    if (!c) return ICW_EINVAL;
-    std::lock_guard<std::mutex> lk(const_cast<icw_ctx *>(c)->mu);
-    return c->hilbs.empty() ? 1 : (int)c->hilbs.size();
-}
-
-/* the largest sample size in force, so that a buffer sized by it holds every stream's frames */
-int icw_render_size(const icw_ctx *c)
-{
-    if (!c) return ICW_EINVAL;
-    std::lock_guard<std::mutex> lk(const_cast<icw_ctx *>(c)->mu);
-    int is24 = c->cfg.need24bits ? 1 : 0;
-    for (const RenderEnt &e : c->renders) is24 |= e.is24;
-    return is24 ? 3 : 2;
+    StreamTable<RenderEnt> t = c->renders.mapped([&](const RenderEnt &e) { return make_render(c, e.cfg, need24bits); }, same_render);
+    return install_renders(c, t, 0, c->n_streams);
 }
 
 /* icw_set_render followed by icw_set_outbits for streams [first, first + count) (include/icw.h) */
@@ -1436,27 +1172,74 @@ int icw_set_stream_render(icw_ctx *c, int first, int count, const icw_render_cfg
     if (!c || first < 0 || count <= 0 || first > c->n_streams - count || !r || !render_cfg_ok(*r)) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
-    /* the assignment as it is, the new entry for the range, then the table compacted */
-    std::vector<RenderEnt> ents;
-    std::vector<int32_t> of;
-    renders_in_force(c, ents, of);
-    ents.push_back(make_render(c, *r, need24bits ? 1 : 0));
-    for (int s = first; s < first + count; ++s) of[(size_t)s] = (int32_t)ents.size() - 1;
-    return install_renders(c, ents, of, first, count);
+    StreamTable<RenderEnt> t = c->renders.assigned((size_t)first, (size_t)count, make_render(c, *r, need24bits), same_render);
+    return install_renders(c, t, first, count);
 }
 
 int icw_stream_render_count(const icw_ctx *c)
 {
     if (!c) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(const_cast<icw_ctx *>(c)->mu);
-    return c->renders.empty() ? 1 : (int)c->renders.size();
+    return (int)c->renders.size();
 }
 
 int icw_stream_render_size(const icw_ctx *c, int s)
 {
     if (!c || s < 0 || s >= c->n_streams) return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(const_cast<icw_ctx *>(c)->mu);
-    return (c->renders.empty() ? c->cfg.need24bits != 0 : c->renders[(size_t)c->render_of[(size_t)s]].is24 != 0) ? 3 : 2;
+    return c->renders.at((size_t)s).is24 ? 3 : 2;
+}
+
+/* the largest sample size in force, so that a buffer sized by it holds every stream's frames */
+int icw_render_size(const icw_ctx *c)
+{
+    if (!c) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(const_cast<icw_ctx *>(c)->mu);
+    int is24 = 0;
+    for (const RenderEnt &e : c->renders.ents) is24 |= e.is24;
+    return is24 ? 3 : 2;
+}
+
+/* mod_context_change_all_hilberts_filter: every stream gets the type and keeps its summation (a table of
+ * several collapses to as many entries as summations in force).  Only the streams whose type changes restart
+ * (hq_rp_create), and no de-subnorm counter restarts otherwise */
+int icw_set_hilbert_filter(icw_ctx *c, uint32_t type)
+{
+    if (!c || type > 5) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    /* the one type in force again: nothing to do, and the device is neither touched nor waited for */
+    if (c->hilbs.size() == 1 && c->hilbs.ents[0].type == type) return ICW_OK;
+    if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+    StreamTable<HilbEnt> t = c->hilbs.mapped([&](const HilbEnt &e) { return make_hilb(type, e.kahan, e.subn); }, same_hilb);
+    return install_hilberts(c, t, 0, 0);
+}
+
+/* mod_context_change_all_hilberts_config -> iir_rp_setcfg: every stream gets the summation and keeps its type
+ * and its rings; the de-subnorm counters of every stream start again */
+int icw_set_hilbert_config(icw_ctx *c, int kahan, int subnorm_reject)
+{
+    if (!c) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+    StreamTable<HilbEnt> t = c->hilbs.mapped([&](const HilbEnt &e) { return make_hilb(e.type, kahan, subnorm_reject); }, same_hilb);
+    return install_hilberts(c, t, 0, c->n_streams);
+}
+
+/* icw_set_hilbert_filter followed by icw_set_hilbert_config for streams [first, first + count) (include/icw.h) */
+int icw_set_stream_hilbert(icw_ctx *c, int first, int count, uint32_t type, int kahan, int subnorm_reject)
+{
+    if (!c || first < 0 || count <= 0 || first > c->n_streams - count || type > 5) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+    StreamTable<HilbEnt> t = c->hilbs.assigned((size_t)first, (size_t)count, make_hilb(type, kahan, subnorm_reject), same_hilb);
+    return install_hilberts(c, t, first, count);
+}
+
+int icw_stream_hilbert_count(const icw_ctx *c)
+{
+    if (!c) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(const_cast<icw_ctx *>(c)->mu);
+    return (int)c->hilbs.size();
 }
 
 int icw_host_alloc(size_t bytes, void **p)
@@ -1515,7 +1298,7 @@ int icw_get_meters(icw_ctx *c, int s, int reset, icw_meters *m)
          * 20*log10(max|q| / hi) because the map is monotone; 0 -> SR_ZERO_SIGNAL_DB */
         double mx;
         memcpy(&mx, &pb[ch], 8);
-        double cv = mx / stream_hi(c, s);     /* the stream's own bound (icw_set_stream_render) */
+        double cv = mx / c->renders.at((size_t)s).rk.hi;     /* the stream's own bound */
         cv = cv ? 20.0 * log10(cv) : ICW_SR_ZERO_SIGNAL_DB;
         double &pv = c->peak_db[(size_t)s * 2 + ch];
         if (cv > pv) pv = cv;
@@ -1572,7 +1355,7 @@ int icw_get_state(icw_ctx *c, int s, void *blob, size_t size)
     IcwBlob b;
     memset(&b, 0, sizeof(b));
     b.magic = kBlobMagic;
-    b.nord = (uint32_t)stream_nord(c, s);     /* the stream's own order (icw_set_stream_hilbert) */
+    b.nord = (uint32_t)c->hilbs.at((size_t)s).nord;     /* the stream's own order */
     b.has_render = c->render_state ? 1u : 0u;
     b.fir_M = (uint32_t)c->fir_M;
     long long fd[3];
@@ -1609,7 +1392,7 @@ int icw_set_state(icw_ctx *c, int s, const void *blob, size_t size)
     memcpy(&b, blob, sizeof(b));
     /* a blob holds the state of the render and converter forms in force when it was saved: the
      * serial-render words exist only with a dithered / shaped render, the FIR history only at its order */
-    if (b.magic != kBlobMagic || b.nord != (uint32_t)stream_nord(c, s) || b.has_render != (c->render_state ? 1u : 0u) ||
+    if (b.magic != kBlobMagic || b.nord != (uint32_t)c->hilbs.at((size_t)s).nord || b.has_render != (c->render_state ? 1u : 0u) ||
         b.fir_M != (uint32_t)c->fir_M)
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);

@@ -13,6 +13,7 @@
 #include "../../include/icw.h"
 #include "icw_device.h"
 #include "icw_graph_compile.h"
+#include "icw_stream_table.h"
 #include "icw_tuning.h"
 
 constexpr double kAutoTaper = 0.85;          /* tail block ratio where the taper is on by default */
@@ -71,8 +72,15 @@ struct CuSplit {
     hipStream_t k1 = nullptr, rest = nullptr, dith = nullptr, render = nullptr;
 };
 
-/* one entry of the context's render table: the setting as given, its constants and how it runs.  With more
- * than one entry no list is bus form and FP_CHECK is off (both refused), so `serial` is the render's own */
+/* one entry of the context's list table: the compiled program and the normalised list it came from */
+struct ListEnt {
+    IcwProg prog{};
+    std::vector<icw_node> nodes;
+};
+
+/* one entry of the context's render table: the setting as given, its constants and how it runs behind the
+ * list in force.  With more than one entry no list is bus form and FP_CHECK is off (both refused), so
+ * `serial` is the render's own */
 struct RenderEnt {
     icw_render_cfg cfg{};
     int is24 = 0;
@@ -112,14 +120,24 @@ struct icw_ctx {
     IcwRenderK rk{};
     IcwProg prog{};
     IcwProg *d_prog = nullptr;
-    /* per-stream DSP lists (icw_set_stream_graph).  While every stream runs one list the table is
-     * empty and nodes / prog / d_prog above are that list, as before.  Otherwise: the distinct
-     * compiled programs (never bus form), the normalised list each came from, every stream's index,
-     * and the table on the device; prog / d_prog then hold entry 0 (is_bus = 0, which is all the
-     * render setters ask of it). */
-    std::vector<IcwProg> progs;
-    std::vector<std::vector<icw_node>> plists;
-    std::vector<int32_t> prog_of;         /* [streams] */
+    /* The four per-stream settings -- DSP lists (icw_set_stream_graph), inputs (icw_set_stream_input), renders
+     * (icw_set_stream_render) and Hilbert converters (icw_set_stream_hilbert) -- are one StreamTable each: the
+     * distinct values in force and every stream's index.  A context whose streams share a setting holds a
+     * one-entry table; nothing asks whether a table is "there".  Every edit, context-wide or per-stream,
+     * builds a candidate table and goes through the setting's install (icw_context.cpp), which puts the
+     * device side in place first and then swaps the table in.
+     * The fields the rest of the library reads are mirrors of entry 0, each written by its table's mirror_*
+     * function alone: nodes / prog / cfg.bypass_list (lists), cfg.render / cfg.need24bits / rk (renders) and
+     * cfg.hilbert_type / iir_kahan / iir_subnorm_reject / nord / pc / pd / d0 (converters); serial_render and
+     * render_state are "some render entry needs it"; cfg.sample_rate / in_format / in_channels are the one
+     * input, and while the inputs differ the one last in force alone.
+     * The device keeps tables only for more than one entry: d_progs (the entries' programs; never bus form),
+     * d_inputs (one descriptor per stream), d_rtab + d_rof (entries, then the index row, one allocation),
+     * d_hpc (below).  A one-entry context launches from d_prog and the scalar arguments. */
+    StreamTable<ListEnt> lists;
+    StreamTable<IcwInDesc> inputs;
+    StreamTable<RenderEnt> renders;
+    StreamTable<HilbEnt> hilbs;
     IcwProg *d_progs = nullptr;
     size_t d_progs_cap = 0;               /* entries d_progs has room for */
     /* a call over streams with different lists or inputs: K2's [5][count] selection rows, then the
@@ -135,31 +153,13 @@ struct icw_ctx {
     IcwFirClass pid_cls[2] = {};
     std::vector<int32_t> pid_map, pid_slab, pid_ref;
     IcwProg mix{};                        /* that call's launch configuration: needs_omega, n_trig, chain, n_regs */
-    /* per-stream inputs (icw_set_stream_input): every stream's descriptor, always filled, and the number
-     * of distinct ones.  While that is 1, cfg.sample_rate / in_format / in_channels are the one input, as
-     * before; above 1 the device table [n_streams] holds the descriptors (it is allocated by the first
-     * assignment that needs it) and cfg keeps the input last given context-wide. */
-    std::vector<IcwInDesc> inputs;        /* [streams] */
-    int n_inputs = 1;
     IcwInDesc *d_inputs = nullptr;
-    /* per-stream renders (icw_set_stream_render).  While every stream has one (render, depth) the table is
-     * empty and cfg.render / cfg.need24bits / rk / serial_render above and below are that render, as
-     * before.  Otherwise: the distinct entries, every stream's index, and on the device the table followed
-     * by the index row [n_streams] in one allocation (d_rof points into it); cfg.render, cfg.need24bits
-     * and rk then hold entry 0, serial_render and render_state whether any entry needs them. */
-    std::vector<RenderEnt> renders;
-    std::vector<int32_t> render_of;       /* [streams] */
     IcwRenderEnt *d_rtab = nullptr;
     int32_t *d_rof = nullptr;
-    /* per-stream Hilbert converters (icw_set_stream_hilbert).  While every stream has one (type, summation,
-     * reject) the table is empty and cfg.hilbert_type / iir_kahan / iir_subnorm_reject and nord / pc / pd / d0
-     * above are that setting, as before.  Otherwise: the distinct entries, every stream's index, and on the
-     * device one allocation -- the entries' pc[20] rows, then room for a call's run descriptors [n_streams]
-     * and their K2 selection rows [5][n_streams] (d_hruns, d_hpid point into it); cfg and nord / pc / pd / d0
-     * then hold entry 0.  The run descriptors are built by the first call that needs them and kept while
-     * the call's shape (hrun_*) and the settings stay. */
-    std::vector<HilbEnt> hilbs;
-    std::vector<int32_t> hilb_of;         /* [streams] */
+    /* the converter table on the device, one allocation: the entries' pc[20] rows, then room for a call's run
+     * descriptors [n_streams] and their K2 selection rows [5][n_streams] (d_hruns, d_hpid point into it).  The
+     * run descriptors are built by the first call that needs them and kept while the call's shape (hrun_*)
+     * and the settings stay. */
     double *d_hpc = nullptr;
     IcwK1Run *d_hruns = nullptr;
     int32_t *d_hpid = nullptr;

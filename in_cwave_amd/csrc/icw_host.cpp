@@ -107,8 +107,7 @@ bool poll_done(const uint32_t *flag, uint32_t seq, hipStream_t st)
  * one slab per pair with an active Shift / PM channel that at least two of the call's streams
  * share, at the counter of the first of them; a pair one stream has computes its factors inline
  * (the table would do the same work and add its traffic); a program without Shift / PM reads
- * nothing, so it is marked as using slab 0 against itself and skips the counter arithmetic.  A
- * context with one list is a one-entry program table (c->prog / c->d_prog).
+ * nothing, so it is marked as using slab 0 against itself and skips the counter arithmetic.
  * fir: the FIR converter is on.  Its signature form reads every factor from the table, so every pair
  * with an active Shift / PM channel gets a slab, one stream or many (256 lists of one shape stay one
  * signature launch); and the call's streams are listed by channel class for KF2's stream maps. */
@@ -116,7 +115,6 @@ int prepare_mix(icw_ctx *c, int first, int count, bool fir, hipStream_t st)
 {
     if (c->pid_valid && c->pid_first == first && c->pid_count == count && c->pid_fir == fir) return ICW_OK;
     const size_t S = (size_t)count;
-    const bool one = c->progs.empty();
     struct Pair {
         int32_t e;
         uint32_t rate;
@@ -125,8 +123,8 @@ int prepare_mix(icw_ctx *c, int first, int count, bool fir, hipStream_t st)
     std::vector<Pair> pairs;
     std::vector<size_t> pair_of(S);
     for (int i = 0; i < count; ++i) {
-        const int32_t e = one ? 0 : c->prog_of[(size_t)(first + i)];
-        const uint32_t rate = c->inputs[(size_t)(first + i)].sample_rate;
+        const int32_t e = c->lists.index((size_t)(first + i));
+        const uint32_t rate = c->inputs.at((size_t)(first + i)).sample_rate;
         size_t k = 0;
         while (k < pairs.size() && !(pairs[k].e == e && pairs[k].rate == rate)) ++k;
         if (k == pairs.size()) pairs.push_back(Pair{e, rate, 0, i, -1});
@@ -134,7 +132,7 @@ int prepare_mix(icw_ctx *c, int first, int count, bool fir, hipStream_t st)
         pair_of[(size_t)i] = k;
     }
     IcwProg &M = c->mix;
-    M.is_bus = one ? c->prog.is_bus : 0;
+    M.is_bus = c->prog.is_bus;               /* (several lists: none is bus form) */
     M.needs_omega = 0;
     M.n_trig = 0;
     M.chain = 1;
@@ -142,7 +140,7 @@ int prepare_mix(icw_ctx *c, int first, int count, bool fir, hipStream_t st)
     M.n_regs = 0;
     int n_slabs = 0;
     for (Pair &q : pairs) {
-        const IcwProg &P = one ? c->prog : c->progs[(size_t)q.e];
+        const IcwProg &P = c->lists.ents[(size_t)q.e].prog;
         M.needs_omega |= P.needs_omega;
         if (!P.chain) {
             M.chain = 0;
@@ -165,13 +163,13 @@ int prepare_mix(icw_ctx *c, int first, int count, bool fir, hipStream_t st)
         }
     for (int i = 0; i < count; ++i) {
         const Pair &q = pairs[pair_of[(size_t)i]];
-        const IcwProg &P = one ? c->prog : c->progs[(size_t)q.e];
+        const IcwProg &P = c->lists.ents[(size_t)q.e].prog;
         const bool no_trig = !(P.needs_omega && P.n_trig > 0);
         h[(size_t)i] = q.e;
         h[S + (size_t)i] = no_trig ? 0 : q.slab;
         h[2 * S + (size_t)i] = no_trig ? i : (q.slab >= 0 ? q.ref : i);
         h[3 * S + (size_t)i] = (int32_t)q.rate;
-        h[4 * S + (size_t)i] = (int32_t)c->inputs[(size_t)(first + i)].nch;
+        h[4 * S + (size_t)i] = (int32_t)c->inputs.at((size_t)(first + i)).nch;
     }
     /* the channel classes: mono streams first in the map, then stereo ones.  A class keeps the signature
      * form while every stream's program is a chain of one signature; lr_same (IcwFirArgs) must hold for
@@ -186,8 +184,8 @@ int prepare_mix(icw_ctx *c, int first, int count, bool fir, hipStream_t st)
         fc.nch = k + 1;
         fc.lr_same = k == 0;
         for (int i = 0; i < count; ++i) {
-            if ((c->inputs[(size_t)(first + i)].nch > 1) != (k == 1)) continue;
-            const IcwProg &P = one ? c->prog : c->progs[(size_t)pairs[pair_of[(size_t)i]].e];
+            if ((c->inputs.at((size_t)(first + i)).nch > 1) != (k == 1)) continue;
+            const IcwProg &P = c->lists.ents[(size_t)pairs[pair_of[(size_t)i]].e].prog;
             const int32_t sig = P.chain ? P.sig : 0;
             if (fc.n == 0) fc.sig = sig;
             else if (fc.sig != sig) fc.sig = 0;
@@ -272,20 +270,18 @@ struct CallPlan {
     bool cw = false, fir = false, fir_fused = false, fir_async = false, bus = false, fcm = false, dedup = false;
     bool dither = false, dith_par = false, table = false, in_step = false, s1 = false;
     int k1_mode = 0, row_waves = 0;
-    /* the resolved Hilbert converter: the one every stream of the call has -- the context's, or the one table
-     * entry all of them share -- or (mixh, icw_set_stream_hilbert) real-input streams with different entries:
+    /* the resolved Hilbert converter: the one table entry every stream of the call has -- or (mixh, icw_set_stream_hilbert) real-input streams with different entries:
      * then the call's streams are cut into maximal runs of consecutive streams with one entry, K1 is one
      * mixed launch over the runs' descriptors, K2 one launch per run, and hb is unread.  max_nord sizes the
      * w rows (each run keeps its own N history rows in front) */
-    HilbEnt hb_one;
-    const HilbEnt *hb = &hb_one;
+    const HilbEnt *hb;
     bool mixh = false;
     struct HRun {
         int s0, n;                 /* the run's first stream (index into the call's range) and its streams */
         const HilbEnt *e;
     };
     std::vector<HRun> hruns;
-    int max_nord = 0, hwgs = 0;    /* mixh: the mixed launch's workgroups (prepare_hruns) */
+    int max_nord, hwgs = 0;        /* mixh: the mixed launch's workgroups (prepare_hruns) */
     /* the block plan */
     std::vector<std::pair<int, int>> blocks;
     int n_blocks = 0, n_sets = 1, Tb = 0;
@@ -308,16 +304,9 @@ struct CallPlan {
              int n_frames_, unsigned flags_, void *hip_stream)
         : c(c_), cfg(c_->cfg), ds(c_->st), first(first_), count(count_), n_frames(n_frames_), S((size_t)count_), f0((size_t)first_), in(in_), out(out_),
           in_stride(in_stride_), out_stride(out_stride_), flags(flags_), dev(flags_ & ICW_F_DEVICE_PTRS),
-          legacy(!hip_stream && (flags_ & ICW_F_DEVICE_PTRS)), st(hip_stream ? (hipStream_t)hip_stream : c_->stream)
+          legacy(!hip_stream && (flags_ & ICW_F_DEVICE_PTRS)), hb(&c_->hilbs.at((size_t)first_)), max_nord(hb->nord),
+          st(hip_stream ? (hipStream_t)hip_stream : c_->stream)
     {
-        /* the context's one converter setting (resolve_plan looks at the table where there is one) */
-        hb_one.type = cfg.hilbert_type;
-        hb_one.kahan = cfg.iir_kahan;
-        hb_one.subn = cfg.iir_subnorm_reject;
-        hb_one.nord = max_nord = c->nord;
-        hb_one.d0 = c->d0;
-        memcpy(hb_one.pc, c->pc, sizeof(hb_one.pc));
-        memcpy(hb_one.pd, c->pd, sizeof(hb_one.pd));
     }
 
     /* waves per workgroup of the call's K1 (the row form: 2 unless ICW_K1_WG says otherwise) */
@@ -873,23 +862,22 @@ int CallPlan::prepare_hruns()
         d.nord = r.e->nord;
         d.kahan = r.e->kahan;
         d.subn = r.e->subn;
-        d.pc_off = (int32_t)(r.e - c->hilbs.data()) * 20;
+        d.pc_off = (int32_t)(r.e - c->hilbs.ents.data()) * 20;
         h[k] = d;
         wg += icw_k1_run_wgs(r.n, dedup, row, wgw);
     }
     std::vector<int32_t> rows;
     if (mix) {
         rows.assign(5 * S, 0);
-        const bool one = c->progs.empty();
         for (const HRun &r : hruns) {
             int32_t *q = rows.data() + 5 * (size_t)r.s0;
             for (int i = 0; i < r.n; ++i) {
                 const size_t k = (size_t)(r.s0 + i);
-                q[i] = one ? 0 : c->prog_of[f0 + k];
+                q[i] = c->lists.index(f0 + k);
                 q[r.n + i] = c->pid_slab[k];
                 q[2 * r.n + i] = c->pid_ref[k] - r.s0;
-                q[3 * r.n + i] = (int32_t)c->inputs[f0 + k].sample_rate;
-                q[4 * r.n + i] = (int32_t)c->inputs[f0 + k].nch;
+                q[3 * r.n + i] = (int32_t)c->inputs.at(f0 + k).sample_rate;
+                q[4 * r.n + i] = (int32_t)c->inputs.at(f0 + k).nch;
             }
         }
     }
@@ -962,7 +950,7 @@ bool CallPlan::stage_copy_out(size_t row_bytes) const
 /* the rendered bytes of stream i of the call: n_frames frames of its own size (mixr), else of the call's */
 size_t CallPlan::out_row_bytes(size_t i) const
 {
-    return (size_t)n_frames * (size_t)(mixr ? c->renders[(size_t)c->render_of[f0 + i]].osz() : osz);
+    return (size_t)n_frames * (size_t)(mixr ? c->renders.at(f0 + i).osz() : osz);
 }
 
 /* the staged frames of a call over streams with different renders back to host pointers: every stream's own
@@ -994,14 +982,14 @@ bool CallPlan::fir_hist_back() const
  * frame; a one-input call with device pointers is not checked, as ever.  Nothing has run when this fails. */
 int CallPlan::enc_format(uint32_t cw_fmt, bool fir_ok)
 {
-    const IcwInDesc &d0 = c->inputs[f0];
+    const IcwInDesc &d0 = c->inputs.at(f0);
     fmt = d0.fmt;
     rate = d0.sample_rate;
     csz = d0.csz;
     nch = d0.nch;
     fsz = d0.fsz;
-    for (int i = 1; i < count; ++i) {
-        const IcwInDesc &d = c->inputs[f0 + (size_t)i];
+    for (int i = 1; i < count && c->inputs.size() > 1; ++i) {
+        const IcwInDesc &d = c->inputs.at(f0 + (size_t)i);
         if (d.fmt != fmt || d.nch != d0.nch) mixin = true;
         if (d.fmt >= ICW_FMT_CW_F64) fmt = d.fmt;     /* a CWAVE stream anywhere in the call: refused below */
         fsz = std::max(fsz, d.fsz);
@@ -1037,7 +1025,7 @@ bool CallPlan::enc_copy_out() const
 {
     if (!mixin) return stage_copy_out(icw_enc_row_bytes(n_frames, (uint32_t)efb));
     for (size_t i = 0; i < S; ++i) {
-        const size_t nb = icw_enc_row_bytes(n_frames, (uint32_t)icw_cwave_frame_bytes(cw_format, c->inputs[f0 + i].nch));
+        const size_t nb = icw_enc_row_bytes(n_frames, (uint32_t)icw_cwave_frame_bytes(cw_format, c->inputs.at(f0 + i).nch));
         if (hipMemcpyAsync((unsigned char *)out + i * out_stride, c->d_out + i * dos, nb, hipMemcpyDeviceToHost, st) != hipSuccess)
             return false;
     }
@@ -1053,7 +1041,7 @@ int CallPlan::enc_mix_lists()
     if (rc != ICW_OK) return rc;
     mix = true;
     lp = &c->mix;
-    dP = c->progs.empty() ? c->d_prog : c->d_progs;
+    dP = c->lists.size() > 1 ? c->d_progs : c->d_prog;
     return ICW_OK;
 }
 
@@ -1073,16 +1061,16 @@ bool grow_events(std::vector<hipEvent_t> &v, int n, unsigned flags)
 /* the format, the list and the modes of the call, and its launch blocks */
 int CallPlan::resolve_plan()
 {
-    /* the input of the call's streams: the one all of them have, resolved here (the launches are
-     * then those of a one-input context), or the table */
-    const IcwInDesc &d0 = c->inputs[f0];
+    /* the input of the call's streams: the one table entry all of them have, resolved here (the launches
+     * are then those of a one-input context), or the table.  A one-entry table is not scanned, here and below */
+    const IcwInDesc &d0 = c->inputs.at(f0);
     fmt = d0.fmt;
     rate = d0.sample_rate;
     csz = d0.csz;
     nch = d0.nch;
     fsz = d0.fsz;
-    for (int i = 1; i < count; ++i) {
-        const IcwInDesc &d = c->inputs[f0 + (size_t)i];
+    for (int i = 1; i < count && c->inputs.size() > 1; ++i) {
+        const IcwInDesc &d = c->inputs.at(f0 + (size_t)i);
         if (d.fmt != fmt || d.nch != d0.nch || d.sample_rate != rate) mixin = true;
         /* one kind per call: whether K1 runs is the call's decision, and the scratch rows differ (2 per
          * real stream, 4 per complex one) */
@@ -1093,51 +1081,38 @@ int CallPlan::resolve_plan()
     if (mixin) dD = c->d_inputs + f0;
     din = mixin && fmt >= ICW_FMT_CW_F64;
     /* the render of the call's streams, resolved like the input */
-    rk = c->rk;
-    serial_render = c->serial_render;
-    render_type = cfg.render.render_type;
-    osz = 2 * (cfg.need24bits ? 3 : 2);
-    if (!c->renders.empty()) {
-        const int32_t e0 = c->render_of[f0];
-        for (int i = 1; i < count && !mixr; ++i) mixr = c->render_of[f0 + (size_t)i] != e0;
-        const RenderEnt &r0 = c->renders[(size_t)e0];
-        rk = r0.rk;
-        serial_render = r0.serial;
-        render_type = r0.cfg.render_type;
-        osz = r0.osz();
-        if (mixr) {
-            serial_render = true;
-            for (int i = 0; i < count; ++i) {
-                const RenderEnt *e = &c->renders[(size_t)c->render_of[f0 + (size_t)i]];
-                if (runs.empty() || runs.back().e != e) runs.push_back(Run{i, 0, e});
-                ++runs.back().n;
-                osz = std::max(osz, e->osz());
-                if (e->serial) serial_gen += 2;
-                else any_par = true;
-            }
+    const RenderEnt &r0 = c->renders.at(f0);
+    rk = r0.rk;
+    serial_render = r0.serial;
+    render_type = r0.cfg.render_type;
+    osz = r0.osz();
+    mixr = !c->renders.uniform(f0, S);
+    if (mixr) {
+        serial_render = true;
+        for (int i = 0; i < count; ++i) {
+            const RenderEnt *e = &c->renders.at(f0 + (size_t)i);
+            if (runs.empty() || runs.back().e != e) runs.push_back(Run{i, 0, e});
+            ++runs.back().n;
+            osz = std::max(osz, e->osz());
+            if (e->serial) serial_gen += 2;
+            else any_par = true;
         }
     }
-    /* the Hilbert converter of the call's streams, resolved like the input and the render.  A CWAVE-input
-     * call runs no recurrence and no output sums: it takes the first stream's entry and no runs */
-    if (!c->hilbs.empty()) {
-        hb = &c->hilbs[(size_t)c->hilb_of[f0]];
-        max_nord = hb->nord;
-        if (fmt < ICW_FMT_CW_F64) {
-            for (int i = 0; i < count; ++i) {
-                const HilbEnt *e = &c->hilbs[(size_t)c->hilb_of[f0 + (size_t)i]];
-                if (hruns.empty() || hruns.back().e != e) hruns.push_back(HRun{i, 0, e});
-                ++hruns.back().n;
-                max_nord = std::max(max_nord, e->nord);
-            }
-            mixh = hruns.size() > 1;
+    /* the Hilbert converter of the call's streams (hb: the first stream's entry), resolved like the input and
+     * the render.  A CWAVE-input call runs no recurrence and no output sums: it takes that entry and no runs */
+    mixh = fmt < ICW_FMT_CW_F64 && !c->hilbs.uniform(f0, S);
+    if (mixh)
+        for (int i = 0; i < count; ++i) {
+            const HilbEnt *e = &c->hilbs.at(f0 + (size_t)i);
+            if (hruns.empty() || hruns.back().e != e) hruns.push_back(HRun{i, 0, e});
+            ++hruns.back().n;
+            max_nord = std::max(max_nord, e->nord);
         }
-        if (!mixh) hruns.clear();
-    }
     ssr = (unsigned long long)rate * ICW_HZ_SCALE;
     timing = flags & 4u;
     /* ICW_F_DEBUG_INPUT: K0's output of every launch block is copied aside (test hook, host dbg) */
     xin = flags & ICW_F_DEBUG_INPUT;
-    if (xin && c->n_inputs > 1) return ICW_EUNSUPPORTED;
+    if (xin && c->inputs.size() > 1) return ICW_EUNSUPPORTED;
     if (xin && (dev || !dbg || (flags & ICW_F_DEBUG_PRE) || fmt >= ICW_FMT_CW_F64 || c->fir_M > 0 ||
                    cfg.fp_check))
         return ICW_EINVAL;
@@ -1150,22 +1125,13 @@ int CallPlan::resolve_plan()
      * the block continues as CWAVE input does */
     fir = c->fir_M > 0 && fmt < ICW_FMT_CW_F64;
     cw = fmt >= ICW_FMT_CW_F64 || fir;
-    /* the list of the call's streams: the context's one, the one table entry all of them run, or --
-     * streams with different lists or inputs -- the table with K2's per-stream selection (prepare_mix;
-     * a one-list context is a one-entry table) */
-    lp = &c->prog;
-    dP = c->d_prog;
-    mix = mixin;
-    if (!c->progs.empty()) {
-        const int32_t e0 = c->prog_of[(size_t)first];
-        for (int i = 1; i < count && !mix; ++i) mix = c->prog_of[(size_t)(first + i)] != e0;
-        if (!mix) {
-            lp = &c->progs[(size_t)e0];
-            dP = c->d_progs + e0;
-        } else {
-            dP = c->d_progs;
-        }
-    }
+    /* the list of the call's streams: the one table entry all of them run, or -- streams with different
+     * lists or inputs -- the table with K2's per-stream selection (prepare_mix).  The device holds the table
+     * only for more than one entry; a one-list context launches from d_prog */
+    lp = &c->lists.at(f0).prog;
+    dP = c->lists.size() > 1 ? c->d_progs : c->d_prog;
+    mix = mixin || !c->lists.uniform(f0, S);
+    if (!mix) dP += c->lists.index(f0);
     if (mix) {
         const int rc = prepare_mix(c, first, count, fir, st);
         if (rc != ICW_OK) return rc;
@@ -1695,7 +1661,7 @@ int CallPlan::run_blocks() const
     }
     if (!cw && nch > 1)
         for (int i = 0; i < count; ++i)
-            if (c->inputs[f0 + (size_t)i].nch > 1) c->lr_known[first + i] = 0;   /* stereo: the halves diverge */
+            if (c->inputs.at(f0 + (size_t)i).nch > 1) c->lr_known[first + i] = 0;   /* stereo: the halves diverge */
     /* join: the caller's stream continues after every kernel of the call, then the call-start
      * position / phases / frame counters advance (icw_advance) */
     for (hipStream_t x : {sK, sA, sD, sR, sF, sC})
@@ -1721,7 +1687,7 @@ int CallPlan::finish_call() const
 {
     for (int i = 0; i < count; ++i) {   /* icw_advance's arithmetic */
         unsigned long long &v = c->nf_host[first + i];
-        const unsigned long long wrap = c->inputs[f0 + (size_t)i].ssr;    /* the stream's own (ssr while they are one) */
+        const unsigned long long wrap = c->inputs.at(f0 + (size_t)i).ssr;    /* the stream's own (ssr while they are one) */
         v = c->cfg.frmod_scaled ? (v + (unsigned long long)n_frames) % wrap : v + (unsigned long long)n_frames;
     }
     if (legacy && hipStreamSynchronize(st) != hipSuccess) return ICW_EDEVICE;
@@ -1844,8 +1810,8 @@ int icw_encode_cwave(icw_ctx *c, int first, int count, const void *in, size_t in
         (flags & ~ICW_F_DEVICE_PTRS))
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (c->n_inputs > 1 && !c->enc_streams) return ICW_EUNSUPPORTED;   /* per-stream inputs: asked for (include/icw.h) */
-    if (!c->hilbs.empty()) return ICW_EUNSUPPORTED;                    /* per-stream Hilbert converters: not served */
+    if (c->inputs.size() > 1 && !c->enc_streams) return ICW_EUNSUPPORTED;   /* per-stream inputs: asked for (include/icw.h) */
+    if (c->hilbs.size() > 1) return ICW_EUNSUPPORTED;                   /* per-stream Hilbert converters: not served */
     CallPlan pl(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
     int rc;
     if ((rc = pl.enc_format(cw_format, c->fir_M > 0)) != ICW_OK) return rc;
@@ -1885,8 +1851,8 @@ int icw_encode_cwave_iir(icw_ctx *c, int first, int count, const void *in, size_
         (flags & ~ICW_F_DEVICE_PTRS))
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (c->n_inputs > 1 && !c->enc_streams) return ICW_EUNSUPPORTED;   /* per-stream inputs: asked for (include/icw.h) */
-    if (!c->hilbs.empty()) return ICW_EUNSUPPORTED;                    /* per-stream Hilbert converters: not served */
+    if (c->inputs.size() > 1 && !c->enc_streams) return ICW_EUNSUPPORTED;   /* per-stream inputs: asked for (include/icw.h) */
+    if (c->hilbs.size() > 1) return ICW_EUNSUPPORTED;                   /* per-stream Hilbert converters: not served */
     const icw_config &cfg = c->cfg;
     CallPlan pl(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
     int rc;
@@ -1934,7 +1900,7 @@ int icw_encode_cwave_iir(icw_ctx *c, int first, int count, const void *in, size_
         }
     }
     for (int i = 0; i < count; ++i)
-        if (c->inputs[pl.f0 + (size_t)i].nch > 1) c->lr_known[first + i] = 0;   /* stereo: the halves diverge */
+        if (c->inputs.at(pl.f0 + (size_t)i).nch > 1) c->lr_known[first + i] = 0;   /* stereo: the halves diverge */
     if (icw_launch_enc_advance(ds.pos + pl.f0, ds.hq_phase + pl.f0 * 2, count, (long long)n_frames, pl.st) != hipSuccess)
         return ICW_EDEVICE;
     if (pl.legacy && hipStreamSynchronize(pl.st) != hipSuccess) return ICW_EDEVICE;
@@ -1983,11 +1949,11 @@ int icw_prepare(icw_ctx *c, int n_frames)
     }
     /* rows of the widest frame among the streams' inputs (one input: the context's frame) */
     unsigned fsz = 0;
-    for (const IcwInDesc &d : c->inputs) fsz = std::max(fsz, d.fsz);
+    for (const IcwInDesc &d : c->inputs.ents) fsz = std::max(fsz, d.fsz);
     const size_t osz = 2 * (size_t)icw_render_size(c), row = (size_t)n_frames * fsz;
     std::vector<unsigned char> in(row * S, 0), out((size_t)n_frames * osz * S);
     for (size_t i = 0; i < S; ++i)
-        if (c->inputs[i].fmt == ICW_FMT_U8) std::fill(in.begin() + i * row, in.begin() + (i + 1) * row, (unsigned char)0x80);   /* u8 silence */
+        if (c->inputs.at(i).fmt == ICW_FMT_U8) std::fill(in.begin() + i * row, in.begin() + (i + 1) * row, (unsigned char)0x80);   /* u8 silence */
     int rc = icw_process_streams(c, 0, (int)S, in.data(), (size_t)n_frames * fsz, out.data(), (size_t)n_frames * osz,
                                  n_frames, 0u, nullptr, nullptr);
     if (rc == ICW_OK) rc = icw_stream_init(c, 0, (int)S);
