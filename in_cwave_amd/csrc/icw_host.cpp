@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <optional>
 #include <vector>
 
 #include "../../include/icw.h"
@@ -99,6 +100,15 @@ bool poll_done(const uint32_t *flag, uint32_t seq, hipStream_t st)
         }
         __builtin_ia32_pause();
     }
+}
+
+/* a Master-only chain (signature count 1, mode MASTER, chain_in `in`: ICW_SIG_M) whose gains are
+ * bit-identical: on mono input L and R are one computation (IcwFirArgs.lr_same) */
+bool lr_same_master(const IcwProg &P)
+{
+    const IcwOp &m = P.ops[0];
+    return P.chain && (P.sig & ~ICW_SIG_UNIT) == ICW_SIG_M && !memcmp(&m.gain[0], &m.gain[1], sizeof(double)) &&
+           m.unit_gain[0] == m.unit_gain[1];
 }
 
 /* A call over streams [first, first + count) that run different lists or have different inputs: K2's
@@ -190,10 +200,7 @@ int prepare_mix(icw_ctx *c, int first, int count, bool fir, hipStream_t st)
             if (fc.n == 0) fc.sig = sig;
             else if (fc.sig != sig) fc.sig = 0;
             fc.trig |= P.needs_omega ? 1 : 0;
-            const IcwOp &m = P.ops[0];
-            if (!(P.chain && (P.sig & ~ICW_SIG_UNIT) == ICW_SIG_M && !memcmp(&m.gain[0], &m.gain[1], sizeof(double)) &&
-                  m.unit_gain[0] == m.unit_gain[1]))
-                fc.lr_same = 0;
+            if (!lr_same_master(P)) fc.lr_same = 0;
             h[5 * S + at++] = i;
             ++fc.n;
         }
@@ -240,20 +247,17 @@ struct CallPlan {
     bool din = false;
     const IcwInDesc *dD = nullptr;
     unsigned csz = 0, nch = 0, fsz = 0;
-    /* the resolved render: the one every stream of the call has -- the context's, or the one table entry
-     * all of them share -- or (mixr, icw_set_stream_render) streams with different entries: then K2 leaves
-     * every stream's pre-render doubles (serial_render holds, as for a serial render), the call's streams are
-     * cut into runs of one entry each, osz is the widest frame and rk is unread */
+    /* the resolved render.  The call's streams are cut into runs of one render table entry each
+     * (StreamTable::runs); the render step works through the runs.  One run: the entry every stream of the
+     * call has, and rk, serial_render and osz are its.  More (mixr, icw_set_stream_render): K2 leaves every
+     * stream's pre-render doubles (serial_render holds, as for a serial render), osz is the widest frame
+     * and rk is unread */
     IcwRenderK rk{};
     bool serial_render = false, mixr = false;
     unsigned render_type = 0;
-    struct Run {
-        int s0, n;                 /* the run's first stream (index into the call's range) and its streams */
-        const RenderEnt *e;
-    };
-    std::vector<Run> runs;
-    int serial_gen = 0;            /* mixr: the call's channels with a serial entry (the K3c / K3b choice) */
-    bool any_par = false;          /* mixr: some stream's entry is frame-parallel (KR runs) */
+    StreamRuns<RenderEnt> runs;
+    int serial_gen = 0;            /* the call's channels with a serial entry (the K3c / K3b choice) */
+    bool any_par = false;          /* some stream's entry is frame-parallel (mixr: KR runs) */
     int osz = 0;
     /* the encoders: the CWAVE output format and its frame bytes at the call's channels (mixin: the widest
      * stream's -- every stream's row holds n_frames of them, its own frames are icw_enc_frame_bytes) */
@@ -270,17 +274,14 @@ struct CallPlan {
     bool cw = false, fir = false, fir_fused = false, fir_async = false, bus = false, fcm = false, dedup = false;
     bool dither = false, dith_par = false, table = false, in_step = false, s1 = false;
     int k1_mode = 0, row_waves = 0;
-    /* the resolved Hilbert converter: the one table entry every stream of the call has -- or (mixh, icw_set_stream_hilbert) real-input streams with different entries:
-     * then the call's streams are cut into maximal runs of consecutive streams with one entry, K1 is one
-     * mixed launch over the runs' descriptors, K2 one launch per run, and hb is unread.  max_nord sizes the
-     * w rows (each run keeps its own N history rows in front) */
+    /* the resolved Hilbert converter, cut into runs like the render; K2 is one launch per run.  One run: the
+     * entry every stream of the call has (hb) -- also what a CWAVE-input call and the encoders hold, which
+     * cut nothing.  More (mixh, icw_set_stream_hilbert, real input): K1 is one mixed launch over the runs'
+     * descriptors and hb, the first run's entry, is unread.  max_nord sizes the w rows (each run keeps its
+     * own N history rows in front) */
     const HilbEnt *hb;
     bool mixh = false;
-    struct HRun {
-        int s0, n;                 /* the run's first stream (index into the call's range) and its streams */
-        const HilbEnt *e;
-    };
-    std::vector<HRun> hruns;
+    StreamRuns<HilbEnt> hruns;
     int max_nord, hwgs = 0;        /* mixh: the mixed launch's workgroups (prepare_hruns) */
     /* the block plan */
     std::vector<std::pair<int, int>> blocks;
@@ -304,7 +305,8 @@ struct CallPlan {
              int n_frames_, unsigned flags_, void *hip_stream)
         : c(c_), cfg(c_->cfg), ds(c_->st), first(first_), count(count_), n_frames(n_frames_), S((size_t)count_), f0((size_t)first_), in(in_), out(out_),
           in_stride(in_stride_), out_stride(out_stride_), flags(flags_), dev(flags_ & ICW_F_DEVICE_PTRS),
-          legacy(!hip_stream && (flags_ & ICW_F_DEVICE_PTRS)), hb(&c_->hilbs.at((size_t)first_)), max_nord(hb->nord),
+          legacy(!hip_stream && (flags_ & ICW_F_DEVICE_PTRS)), hb(&c_->hilbs.at((size_t)first_)),
+          hruns(StreamRuns<HilbEnt>::single(count_, hb)), max_nord(hb->nord),
           st(hip_stream ? (hipStream_t)hip_stream : c_->stream)
     {
     }
@@ -317,7 +319,7 @@ struct CallPlan {
     {
         const int wgw = k1_wg_waves(row);
         int w = 0;
-        for (const HRun &r : hruns) w += icw_k1_run_wgs(r.n, dedup, row, wgw) * wgw;
+        for (const auto &r : hruns) w += icw_k1_run_wgs(r.n, dedup, row, wgw) * wgw;
         return w;
     }
 
@@ -352,16 +354,6 @@ struct CallPlan {
         return a0;
     }
 
-    /* the same over streams with different inputs: K0 takes each stream's format from the table */
-    IcwK0MixArgs k0_mix_args(int b) const
-    {
-        IcwK0MixArgs m;
-        memset(&m, 0, sizeof(m));
-        m.k0 = k0_args(b);
-        m.desc = dD;
-        return m;
-    }
-
     IcwK1Args k1_args(int b) const
     {
         const int p = b % n_sets;
@@ -389,6 +381,7 @@ struct CallPlan {
         return a1;
     }
 
+    /* what is the call's of block b's K2 arguments; k2_run_args completes them for a run */
     IcwK2Args k2_args(int b) const
     {
         const int t0 = blocks[b].first, T = blocks[b].second, p = b % n_sets;
@@ -422,9 +415,6 @@ struct CallPlan {
         a2.clips = ds.clips + f0 * 2;
         a2.peak_bits = ds.peak_bits + f0 * 2;
         a2.rk = rk;
-        memcpy(a2.pc, hb->pc, sizeof(a2.pc));
-        memcpy(a2.pd, hb->pd, sizeof(a2.pd));
-        a2.d0 = hb->d0;
         a2.cw = cw ? 1 : 0;
         a2.info_dup = cw ? nullptr : c->info_dup[p];
         a2.xin = c->xd[p];
@@ -435,17 +425,17 @@ struct CallPlan {
             a2.prog_id = c->d_pid;
             a2.slab_stride = slab_stride;
         }
-        a2.sncnt = (!cw && hb->subn) ? ds.sncnt + f0 * 4 : nullptr;
         a2.fes = fcm ? ds.fes + f0 * 4 * ICW_FES_PITCH : nullptr;
         return a2;
     }
 
-    /* K2 of one run of a call over streams with different Hilbert converters: the block's arguments as
-     * run_blocks completed them, offset to the run's first stream the way a subset call offsets by f0, with
-     * the run's streams, its entry's coefficients and its reject.  The selection rows are the run's own
-     * (prepare_hruns); without them the rotation table is read against the launch's stream 0, so a run
+    /* K2 of one run of the call's converters: the block's arguments as run_blocks completed them, offset to
+     * the run's first stream the way a subset call offsets by f0, with the run's streams, its entry's
+     * coefficients and its reject (real input only: a CWAVE or FIR call counts no rejections).  A call's one
+     * run changes no address and keeps the call's selection rows.  Of several (mixh) each has rows of its
+     * own (prepare_hruns); without rows the rotation table is read against the launch's stream 0, so a run
      * whose first stream is not in step with the call's gets none and computes its factors inline. */
-    IcwK2Args k2_run_args(const IcwK2Args &a2, const HRun &r) const
+    IcwK2Args k2_run_args(const IcwK2Args &a2, const StreamRun<HilbEnt> &r) const
     {
         const size_t s0 = (size_t)r.s0;
         IcwK2Args a = a2;
@@ -463,9 +453,9 @@ struct CallPlan {
         memcpy(a.pd, r.e->pd, sizeof(a.pd));
         a.d0 = r.e->d0;
         a.info_dup = a2.info_dup + s0 * 2;
-        a.sncnt = r.e->subn ? ds.sncnt + (f0 + s0) * 4 : nullptr;
+        a.sncnt = (!cw && r.e->subn) ? ds.sncnt + (f0 + s0) * 4 : nullptr;
         if (a2.dith) a.dith = a2.dith + s0 * 2 * a2.dith_pitch;
-        if (a2.prog_id) a.prog_id = c->d_hpid + 5 * s0;
+        if (a2.prog_id) a.prog_id = mixh ? c->d_hpid + 5 * s0 : a2.prog_id;
         else if (a2.trig_tab && c->nf_host[f0 + s0] != c->nf_host[f0]) a.trig_tab = nullptr;
         return a;
     }
@@ -484,56 +474,12 @@ struct CallPlan {
         return ad;
     }
 
-    /* the dither generator's / serial render's arguments for block b */
-    IcwK3Args k3_args(int b, const IcwK2Args &a2) const
-    {
-        const int T = blocks[b].second;
-        IcwK3Args a3;
-        memset(&a3, 0, sizeof(a3));
-        a3.pre = a2.pre;
-        a3.pre_stride = a2.pre_stride;
-        a3.n_streams = count;
-        a3.T = T;
-        a3.out = a2.out;
-        a3.out_stride = dos;
-        a3.mt = ds.mt + f0 * 2;          /* column offset: [624][G] layout, pitch G */
-        a3.mt_idx = ds.mt_idx + f0 * 2;
-        a3.rs = ds.rs + f0 * 2 * ICW_RSTATE;
-        a3.clips = ds.clips + f0 * 2;
-        a3.peak_bits = ds.peak_bits + f0 * 2;
-        a3.n_gen = count * 2;
-        a3.mt_pitch = c->n_streams * 2;
-        a3.rk = rk;
-        a3.fes = fcm ? ds.fes + f0 * 4 * ICW_FES_PITCH : nullptr;
-        /* the row-broadcast render (16 lanes per channel) while its waves stay few; FP_CHECK
-         * keeps the compact lane-per-channel form */
-        a3.row = serial_render && !fcm && (c->tn.render_row == 1 || (c->tn.render_row < 0 && a3.n_gen <= kRowRenderMax)) ? 1 : 0;
-        a3.err = ds.err;
-        if (dither) {
-            a3.dith = c->dith[b % n_sets];
-            /* the row render and the frame-parallel one read runs of one channel: generator-major
-             * [count*2][T rounded up to even] (16-byte pairs); the lane-per-channel renders time-major
-             * [T][count*2] */
-            a3.dith_gm = (a3.row || !serial_render) ? 1 : 0;
-            a3.dith_pitch = a3.dith_gm ? (size_t)(T + (T & 1)) : (size_t)count * 2;
-            a3.wbuf = c->dwords;
-            a3.wpitch = a3.wcap = c->dwcap;
-            a3.dflag = c->dflag;
-            a3.dbk = c->dbk;
-            if (b == 0) {                /* what the launcher will cut this block into (icw_last_dither_chunks) */
-                c->last_dchunk_frames = icw_dith_chunk_frames(T, a3.wcap, icw_dith_words(a3.rk.render_type));
-                c->last_dchunks = c->last_dchunk_frames > 0 ? (T + c->last_dchunk_frames - 1) / c->last_dchunk_frames : 0;
-            }
-        }
-        return a3;
-    }
-
-    /* The same for one run of a call over streams with different renders: the arguments offset to the
-     * run's first stream, the way a subset call offsets by f0; n_streams and n_gen are the run's, rk its
-     * entry's, and its frames are the entry's size.  The K3c / K3b choice is the call's (serial_gen).  The
-     * dither scratch is addressed by the run's first generator -- the rows at g0 * (T rounded up to even)
-     * doubles, which holds either layout of a run -- so runs never alias. */
-    IcwK3Args k3_run_args(int b, const IcwK2Args &a2, const Run &r) const
+    /* The dither generator's / serial render's arguments for block b and one run of the call's renders: the
+     * arguments offset to the run's first stream, the way a subset call offsets by f0; n_streams and n_gen
+     * are the run's, rk its entry's, and its frames are the entry's size.  The K3c / K3b choice is the
+     * call's (serial_gen).  The dither scratch is addressed by the run's first generator -- the rows at
+     * g0 * (T rounded up to even) doubles, which holds either layout of a run -- so runs never alias. */
+    IcwK3Args k3_args(int b, const IcwK2Args &a2, const StreamRun<RenderEnt> &r) const
     {
         const int t0 = blocks[b].first, T = blocks[b].second;
         const size_t r0 = f0 + (size_t)r.s0, g0 = (size_t)r.s0 * 2, Tp = (size_t)(T + (T & 1));
@@ -553,7 +499,10 @@ struct CallPlan {
         a3.n_gen = r.n * 2;
         a3.mt_pitch = c->n_streams * 2;
         a3.rk = r.e->rk;
-        a3.row = r.e->serial && (c->tn.render_row == 1 || (c->tn.render_row < 0 && serial_gen <= kRowRenderMax)) ? 1 : 0;
+        a3.fes = fcm ? ds.fes + r0 * 4 * ICW_FES_PITCH : nullptr;   /* (FP_CHECK: one render entry, one run) */
+        /* the row-broadcast render (16 lanes per channel) while its waves stay few; FP_CHECK
+         * keeps the compact lane-per-channel form */
+        a3.row = r.e->serial && !fcm && (c->tn.render_row == 1 || (c->tn.render_row < 0 && serial_gen <= kRowRenderMax)) ? 1 : 0;
         a3.err = ds.err;
         if (r.e->dither) {
             a3.dith = c->dith[b % n_sets] + g0 * Tp;
@@ -659,16 +608,9 @@ struct CallPlan {
         af.x_pitch = x_pitch;
         af.sig = lp->chain ? lp->sig : 0;
         af.desc = fir && mixin ? dD : nullptr;      /* streams with different inputs: the kernels read each one's own */
-        if (mix) {
-            /* per-stream lists: signature and lr_same are per channel class (fir_cls) */
-            af.sig = 0;
-        } else {
-            /* mono input through a Master-only chain (signature count 1, mode MASTER, chain_in `in`:
-             * ICW_SIG_M) whose gains are bit-identical: L and R are one computation */
-            const IcwOp &m = lp->ops[0];
-            af.lr_same = nch == 1 && lp->chain && (lp->sig & ~ICW_SIG_UNIT) == ICW_SIG_M &&
-                        !memcmp(&m.gain[0], &m.gain[1], sizeof(double)) && m.unit_gain[0] == m.unit_gain[1];
-        }
+        /* per-stream lists: signature and lr_same are per channel class (fir_cls) */
+        if (mix) af.sig = 0;
+        else af.lr_same = nch == 1 && lr_same_master(*lp);
         return af;
     }
 
@@ -725,17 +667,6 @@ struct CallPlan {
         return ap;
     }
 
-    /* the same over streams with different inputs: every stream's own channels, its tile at its own frame size */
-    IcwPackMixArgs pack_mix_args(int b) const
-    {
-        IcwPackMixArgs m;
-        memset(&m, 0, sizeof(m));
-        m.p = pack_args(b);
-        m.desc = dD;
-        m.t0 = blocks[b].first;
-        return m;
-    }
-
     IcwAdvArgs adv_args() const
     {
         IcwAdvArgs av;
@@ -761,8 +692,13 @@ struct CallPlan {
 
     /* the steps of a call, in the order the entry points take them */
     void pick_k1();
+    hipError_t launch_unpack(int b, hipStream_t s) const;
     hipError_t launch_k1(const IcwK1Args &a1, hipStream_t s) const;
     hipError_t launch_k2(const IcwK2Args &a2, hipStream_t s) const;
+    hipError_t launch_fir_encode(int b, int cwf) const;
+    hipError_t launch_pack(int b, int cwf) const;
+    hipError_t launch_advance() const;
+    void stereo_diverged() const;
     int prepare_hruns();
     int join_legacy_stream() const;
     int stage_host_io(size_t in_row, size_t out_row);
@@ -808,7 +744,7 @@ void CallPlan::pick_k1()
          * row form only when every entry of the call is Kahan + reject */
         row_waves = mixed_waves(true);
         row_ok = true;
-        for (const HRun &r : hruns) row_ok = row_ok && r.e->kahan && r.e->subn;
+        for (const auto &r : hruns) row_ok = row_ok && r.e->kahan && r.e->subn;
     }
     k1_mode = c->tn.k1_mode;
     if (k1_mode < 0) k1_mode = (row_ok && row_waves <= (c->n_cu / 2) * c->tn.k1_wpc) ? 3 : 0;
@@ -825,11 +761,62 @@ hipError_t CallPlan::launch_k1(const IcwK1Args &a1, hipStream_t s) const
                                    : icw_launch_iir_state(&a1, hb->nord, hb->kahan, hb->subn, s);
 }
 
-/* the plan's K2 on stream s: one launch, or one per run of a call over different converters */
+/* K0 of block b on stream s; streams with different inputs: K0 takes each one's format from the table */
+hipError_t CallPlan::launch_unpack(int b, hipStream_t s) const
+{
+    IcwK0MixArgs m;
+    memset(&m, 0, sizeof(m));
+    m.k0 = k0_args(b);
+    m.desc = dD;
+    if (mixin) return icw_launch_unpack_mixed(&m, s);
+    return icw_launch_unpack(&m.k0, s);
+}
+
+/* KFE of block b on the caller's stream; streams with different inputs: its per-stream form */
+hipError_t CallPlan::launch_fir_encode(int b, int cwf) const
+{
+    const auto e = enc_args(b);
+    if (mixin) return icw_launch_fir_encode_mixed(&e, cwf, st);
+    return icw_launch_fir_encode(&e, cwf, st);
+}
+
+/* KIP of block b on the caller's stream; streams with different inputs: every stream's own channels, its
+ * tile at its own frame size */
+hipError_t CallPlan::launch_pack(int b, int cwf) const
+{
+    IcwPackMixArgs m;
+    memset(&m, 0, sizeof(m));
+    m.p = pack_args(b);
+    m.desc = dD;
+    m.t0 = blocks[b].first;
+    if (mixin) return icw_launch_iq_pack_mixed(&m, cwf, st);
+    return icw_launch_iq_pack(&m.p, cwf, nch > 1 ? 2 : 1, st);
+}
+
+/* icw_advance on the caller's stream, behind every kernel of the call; streams with different inputs wrap
+ * their frame counters at their own rates */
+hipError_t CallPlan::launch_advance() const
+{
+    IcwAdvMixArgs m;
+    memset(&m, 0, sizeof(m));
+    m.adv = adv_args();
+    m.desc = dD;
+    if (mixin) return icw_launch_advance_mixed(&m, st);
+    return icw_launch_advance(&m.adv, st);
+}
+
+/* after a call over real input: a stereo stream's left / right converters are no longer known equal */
+void CallPlan::stereo_diverged() const
+{
+    if (!cw && nch > 1)
+        for (int i = 0; i < count; ++i)
+            if (c->inputs.at(f0 + (size_t)i).nch > 1) c->lr_known[first + i] = 0;
+}
+
+/* the plan's K2 on stream s: one launch per run of the call's converters */
 hipError_t CallPlan::launch_k2(const IcwK2Args &a2, hipStream_t s) const
 {
-    if (!mixh) return icw_launch_output(&a2, hb->nord, hb->kahan, s);
-    for (const HRun &r : hruns) {
+    for (const auto &r : hruns) {
         const IcwK2Args ar = k2_run_args(a2, r);
         const hipError_t e = icw_launch_output(&ar, r.e->nord, r.e->kahan, s);
         if (e != hipSuccess) return e;
@@ -853,7 +840,7 @@ int CallPlan::prepare_hruns()
     std::vector<IcwK1Run> h(hruns.size());
     int wg = 0;
     for (size_t k = 0; k < hruns.size(); ++k) {
-        const HRun &r = hruns[k];
+        const auto &r = hruns[k];
         IcwK1Run d;
         memset(&d, 0, sizeof(d));
         d.wg0 = wg;
@@ -869,7 +856,7 @@ int CallPlan::prepare_hruns()
     std::vector<int32_t> rows;
     if (mix) {
         rows.assign(5 * S, 0);
-        for (const HRun &r : hruns) {
+        for (const auto &r : hruns) {
             int32_t *q = rows.data() + 5 * (size_t)r.s0;
             for (int i = 0; i < r.n; ++i) {
                 const size_t k = (size_t)(r.s0 + i);
@@ -1080,34 +1067,25 @@ int CallPlan::resolve_plan()
     }
     if (mixin) dD = c->d_inputs + f0;
     din = mixin && fmt >= ICW_FMT_CW_F64;
-    /* the render of the call's streams, resolved like the input */
-    const RenderEnt &r0 = c->renders.at(f0);
+    /* the render of the call's streams: the runs of its table; the first one's entry is the call's while
+     * it is the only one */
+    runs = c->renders.runs(f0, S);
+    const RenderEnt &r0 = *runs[0].e;
     rk = r0.rk;
     serial_render = r0.serial;
     render_type = r0.cfg.render_type;
-    osz = r0.osz();
-    mixr = !c->renders.uniform(f0, S);
-    if (mixr) {
-        serial_render = true;
-        for (int i = 0; i < count; ++i) {
-            const RenderEnt *e = &c->renders.at(f0 + (size_t)i);
-            if (runs.empty() || runs.back().e != e) runs.push_back(Run{i, 0, e});
-            ++runs.back().n;
-            osz = std::max(osz, e->osz());
-            if (e->serial) serial_gen += 2;
-            else any_par = true;
-        }
+    mixr = runs.size() > 1;
+    if (mixr) serial_render = true;
+    for (const auto &r : runs) {
+        osz = std::max(osz, r.e->osz());
+        if (r.e->serial) serial_gen += 2 * r.n;
+        else any_par = true;
     }
-    /* the Hilbert converter of the call's streams (hb: the first stream's entry), resolved like the input and
-     * the render.  A CWAVE-input call runs no recurrence and no output sums: it takes that entry and no runs */
-    mixh = fmt < ICW_FMT_CW_F64 && !c->hilbs.uniform(f0, S);
-    if (mixh)
-        for (int i = 0; i < count; ++i) {
-            const HilbEnt *e = &c->hilbs.at(f0 + (size_t)i);
-            if (hruns.empty() || hruns.back().e != e) hruns.push_back(HRun{i, 0, e});
-            ++hruns.back().n;
-            max_nord = std::max(max_nord, e->nord);
-        }
+    /* the Hilbert converter of the call's streams (hb: the first stream's entry), cut like the render.  A
+     * CWAVE-input call runs no recurrence and no output sums: it keeps that entry as its one run */
+    if (fmt < ICW_FMT_CW_F64) hruns = c->hilbs.runs(f0, S);
+    mixh = hruns.size() > 1;
+    for (const auto &r : hruns) max_nord = std::max(max_nord, r.e->nord);
     ssr = (unsigned long long)rate * ICW_HZ_SCALE;
     timing = flags & 4u;
     /* ICW_F_DEBUG_INPUT: K0's output of every launch block is copied aside (test hook, host dbg) */
@@ -1169,11 +1147,7 @@ int CallPlan::resolve_plan()
     /* a dithered render with the flat shaper, rendered frame-parallel in the output kernel (K2 / KF2 /
      * K5) from K3a's dither rows (needs_serial) */
     dith_par = !serial_render && render_type != ICW_RENDER_ROUND;
-    dither = render_type != ICW_RENDER_ROUND;     /* K3a: serial or frame-parallel render */
-    if (mixr) {
-        dither = false;                              /* K3a runs for the runs with a dithered entry */
-        for (const Run &r : runs) dither = dither || r.e->dither;
-    }
+    for (const auto &r : runs) dither = dither || r.e->dither;   /* K3a, serial or frame-parallel render: for the runs with a dithered entry */
     /* (with a dither generator, blocks of kMaxBlockFrames let K3a of the next block run beside KF2) */
     const bool fir_long = fir_fused && dev && !serial_render && !bus && !dith_par;
     Tb = std::min(n_frames, ((fir_fused || row_long) && !c->tn.block_env)
@@ -1440,7 +1414,7 @@ int CallPlan::run_stream1() const
     memset(&a5, 0, sizeof(a5));
     a5.k0 = k0_args(0);
     a5.k1 = k1_args(0);
-    a5.k2 = k2_args(0);
+    a5.k2 = k2_run_args(k2_args(0), hruns[0]);     /* one stream: one run */
     a5.adv = adv_args();
     a5.stamps = c->s1_stamps;
     a5.ovl = c->tn.s1_ovl ? 1 : 0;
@@ -1456,7 +1430,7 @@ int CallPlan::run_stream1() const
     }
     if (dith_par) {
         /* the dithered flat render: K3a of the call's block first, on the same stream */
-        const auto a3 = k3_args(0, a5.k2);
+        const auto a3 = k3_args(0, a5.k2, runs[0]);
         if (icw_launch_dither(&a3, st) != hipSuccess) return ICW_EDEVICE;
         a5.k2.dith = a3.dith;
         a5.k2.dith_pitch = a3.dith_pitch;
@@ -1466,7 +1440,7 @@ int CallPlan::run_stream1() const
     if (timing && (hipEventRecord(c->ev[1], st) != hipSuccess || hipEventRecord(c->ev[2], st) != hipSuccess ||
                       hipEventRecord(c->ev[3], st) != hipSuccess))
         return ICW_EDEVICE;
-    if (!cw && nch > 1) c->lr_known[first] = 0;
+    stereo_diverged();
     return ICW_OK;
 }
 
@@ -1489,7 +1463,6 @@ int CallPlan::launch_k0(int b) const
     if (fir_fused) return ICW_OK;                   /* KF2 converts inside the block's kernel */
     if (din) return io_in(b, sA);                   /* K2 reads the frames itself: no kernel, no k0done to wait for */
     const int p = b % n_sets;
-    const auto a0 = k0_args(b);
     if (b >= n_sets && !cw && sK != sA && hipStreamWaitEvent(sA, c->k1done[p], 0) != hipSuccess) return ICW_EDEVICE;
     hipStream_t s0 = (b == 0 && sF) ? sF : sA;         /* the fill: nothing else runs yet */
     /* the FIR converter runs on the caller's stream (K1's, idle without the IIR), so KF of the
@@ -1506,17 +1479,12 @@ int CallPlan::launch_k0(int b) const
         if (timing && hipEventRecord(c->ev[4 * b + 1], s0) != hipSuccess) return ICW_EDEVICE;
     } else {
         if (timing && hipEventRecord(c->ev_k0[2 * b], s0) != hipSuccess) return ICW_EDEVICE;
-        if (mixin) {
-            const auto m = k0_mix_args(b);
-            if (icw_launch_unpack_mixed(&m, s0) != hipSuccess) return ICW_EDEVICE;
-        } else if (icw_launch_unpack(&a0, s0) != hipSuccess) {
-            return ICW_EDEVICE;
-        }
+        if (launch_unpack(b, s0) != hipSuccess) return ICW_EDEVICE;
         if (timing && hipEventRecord(c->ev_k0[2 * b + 1], s0) != hipSuccess) return ICW_EDEVICE;
     }
     /* test hook: this block's rows aside before K1 may start (K1 waits for k0done) */
-    if (xin && hipMemcpy2DAsync(c->d_xin + a0.t0, (size_t)n_frames * sizeof(double), a0.xd, x_pitch * sizeof(double),
-                                   (size_t)a0.T * sizeof(double), S * 2, hipMemcpyDeviceToDevice, s0) != hipSuccess)
+    if (xin && hipMemcpy2DAsync(c->d_xin + blocks[b].first, (size_t)n_frames * sizeof(double), c->xd[p], x_pitch * sizeof(double),
+                                   (size_t)blocks[b].second * sizeof(double), S * 2, hipMemcpyDeviceToDevice, s0) != hipSuccess)
         return ICW_EDEVICE;
     if (hipEventRecord(c->k0done[p], s0) != hipSuccess) return ICW_EDEVICE;
     return ICW_OK;
@@ -1575,7 +1543,7 @@ int CallPlan::run_blocks() const
             /* K3a of this block on its own stream (it depends only on the generators' state, so it runs
              * ahead, beside the converter / output kernel of the block before); dith[p] was last read
              * by the output kernel of block b - n_sets */
-            const auto a3 = k3_args(b, a2);
+            const auto a3 = k3_args(b, a2, runs[0]);      /* (a frame-parallel render: one run) */
             if (b >= n_sets && sD != s2 && hipStreamWaitEvent(sD, c->k2done[p], 0) != hipSuccess) return ICW_EDEVICE;
             const hipError_t ed = icw_launch_dither(&a3, sD);
             if (ed != hipSuccess || hipEventRecord(c->ditdone[p], sD) != hipSuccess ||
@@ -1587,17 +1555,19 @@ int CallPlan::run_blocks() const
         if (timing && hipEventRecord(c->ev[4 * b + 2], s2) != hipSuccess) return ICW_EDEVICE;
         if (fir_fused) {
             const auto af = fir_args(b);
+            const auto ar = k2_run_args(a2, hruns[0]);      /* the converter's output: one run */
             if (io_in(b, s2) != ICW_OK) return ICW_EDEVICE;
             if (timing && hipEventRecord(c->ev[4 * b], s2) != hipSuccess) return ICW_EDEVICE;
-            if ((mix ? icw_launch_fir_graph_mix(&af, &a2, fir_cls, 2, c->tn.fir_sig, s2)
-                     : icw_launch_fir_graph(&af, &a2, in_step, c->tn.fir_sig, s2)) != hipSuccess)
+            if ((mix ? icw_launch_fir_graph_mix(&af, &ar, fir_cls, 2, c->tn.fir_sig, s2)
+                     : icw_launch_fir_graph(&af, &ar, in_step, c->tn.fir_sig, s2)) != hipSuccess)
                 return ICW_EDEVICE;
             if (timing && hipEventRecord(c->ev[4 * b + 1], s2) != hipSuccess) return ICW_EDEVICE;
         } else {
             if (fir_async && hipStreamWaitEvent(s2, c->k0done[p], 0) != hipSuccess) return ICW_EDEVICE;
             if (din) {
                 const auto ad = din_args();
-                if (icw_launch_output_cw(&a2, &ad, s2) != hipSuccess) return ICW_EDEVICE;
+                const auto ar = k2_run_args(a2, hruns[0]);  /* CWAVE input: one run */
+                if (icw_launch_output_cw(&ar, &ad, s2) != hipSuccess) return ICW_EDEVICE;
             } else if (launch_k2(a2, s2) != hipSuccess) {
                 return ICW_EDEVICE;
             }
@@ -1610,42 +1580,30 @@ int CallPlan::run_blocks() const
             const auto a4 = k4_args(b, a2);
             if (icw_launch_graph_serial(&a4, sR) != hipSuccess) return ICW_EDEVICE;
         }
-        if (mixr) {
-            /* streams with different renders: K3a of every run with a dithered entry on the dither stream
-             * (dith[p] was last read by the renders of block b - n_sets), then on the render stream the serial
-             * runs in order and KR for every frame-parallel stream */
+        if (serial_render) {
+            /* K3a of every run with a dithered entry on the dither stream (dith[p] was last read by the renders
+             * of block b - n_sets), then on the render stream the serial runs in order and KR for every
+             * frame-parallel stream.  A call with one render is the one run */
             if (dither) {
                 if (b >= n_sets && sD != sR && hipStreamWaitEvent(sD, c->k3done[p], 0) != hipSuccess) return ICW_EDEVICE;
-                for (const Run &r : runs) {
+                for (const auto &r : runs) {
                     if (!r.e->dither) continue;
-                    const auto a3 = k3_run_args(b, a2, r);
+                    const auto a3 = k3_args(b, a2, r);
                     if (icw_launch_dither(&a3, sD) != hipSuccess) return ICW_EDEVICE;
                 }
                 if (hipEventRecord(c->ditdone[p], sD) != hipSuccess ||
                     (sD != sR && hipStreamWaitEvent(sR, c->ditdone[p], 0) != hipSuccess))
                     return ICW_EDEVICE;
             }
-            for (const Run &r : runs) {
+            for (const auto &r : runs) {
                 if (!r.e->serial) continue;
-                const auto a3 = k3_run_args(b, a2, r);
+                const auto a3 = k3_args(b, a2, r);
                 if (icw_launch_render(&a3, sR) != hipSuccess) return ICW_EDEVICE;
             }
             if (any_par) {
                 const auto ar = kr_args(b, a2);
                 if (icw_launch_render_mixed(&ar, sR) != hipSuccess) return ICW_EDEVICE;
             }
-            if (hipEventRecord(c->k3done[p], sR) != hipSuccess) return ICW_EDEVICE;
-        } else if (serial_render) {
-            const auto a3 = k3_args(b, a2);
-            if (dither) {
-                /* K3a for this block on its own stream: dith[p] was last read by K3b of block b-2 */
-                if (b >= n_sets && sD != sR && hipStreamWaitEvent(sD, c->k3done[p], 0) != hipSuccess) return ICW_EDEVICE;
-                const hipError_t ed = icw_launch_dither(&a3, sD);
-                if (ed != hipSuccess || hipEventRecord(c->ditdone[p], sD) != hipSuccess ||
-                    (sD != sR && hipStreamWaitEvent(sR, c->ditdone[p], 0) != hipSuccess))
-                    return ICW_EDEVICE;
-            }
-            if (icw_launch_render(&a3, sR) != hipSuccess) return ICW_EDEVICE;
             if (hipEventRecord(c->k3done[p], sR) != hipSuccess) return ICW_EDEVICE;
         }
         if (timing && hipEventRecord(c->ev[4 * b + 3], serial_render ? sR : s2) != hipSuccess) return ICW_EDEVICE;
@@ -1659,26 +1617,14 @@ int CallPlan::run_blocks() const
         /* complex input: K0(b + n_sets) reuses xd[p], which K2(b) read */
         if (cw && b + n_sets < n_blocks && (rc0 = launch_k0(b + n_sets)) != ICW_OK) return rc0;
     }
-    if (!cw && nch > 1)
-        for (int i = 0; i < count; ++i)
-            if (c->inputs.at(f0 + (size_t)i).nch > 1) c->lr_known[first + i] = 0;   /* stereo: the halves diverge */
+    stereo_diverged();
     /* join: the caller's stream continues after every kernel of the call, then the call-start
      * position / phases / frame counters advance (icw_advance) */
     for (hipStream_t x : {sK, sA, sD, sR, sF, sC})
         if (x && x != st && (hipEventRecord(c->join, x) != hipSuccess || hipStreamWaitEvent(st, c->join, 0) != hipSuccess))
             return ICW_EDEVICE;
     if (fir && !fir_hist_back()) return ICW_EDEVICE;
-    const auto av = adv_args();
-    if (mixin) {
-        IcwAdvMixArgs m;
-        memset(&m, 0, sizeof(m));
-        m.adv = av;
-        m.desc = dD;
-        if (icw_launch_advance_mixed(&m, st) != hipSuccess) return ICW_EDEVICE;
-    } else if (icw_launch_advance(&av, st) != hipSuccess) {
-        return ICW_EDEVICE;
-    }
-    return ICW_OK;
+    return launch_advance() == hipSuccess ? ICW_OK : ICW_EDEVICE;
 }
 
 /* after the kernels: the host mirror of the frame counters, the results back to host pointers, the
@@ -1764,6 +1710,24 @@ int CallPlan::finish_call() const
     return hipGetLastError() == hipSuccess ? ICW_OK : ICW_EDEVICE;
 }
 
+/* The two encoders' shared opening: the argument check, then under the context's lock (lk, the caller's from
+ * here on) the refusals of what no encoder serves, the call's plan and its input and format checks
+ * (enc_format) for the encoder whose converter is the FIR one (fir) or the IIR.  Nothing has run when this
+ * fails. */
+int enc_begin(std::optional<CallPlan> &plan, std::unique_lock<std::mutex> &lk, bool fir, icw_ctx *c, int first, int count,
+              const void *in, size_t in_stride, void *out, size_t out_stride, int n_frames, uint32_t cw_format, unsigned flags,
+              void *hip_stream)
+{
+    if (!c || first < 0 || count <= 0 || first + count > c->n_streams || n_frames < 0 || !in || !out ||
+        (flags & ~ICW_F_DEVICE_PTRS))
+        return ICW_EINVAL;
+    lk = std::unique_lock<std::mutex>(c->mu);
+    if (c->inputs.size() > 1 && !c->enc_streams) return ICW_EUNSUPPORTED;   /* per-stream inputs: asked for (include/icw.h) */
+    if (c->hilbs.size() > 1) return ICW_EUNSUPPORTED;                   /* per-stream Hilbert converters: not served */
+    plan.emplace(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
+    return plan->enc_format(cw_format, (c->fir_M > 0) == fir);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1806,15 +1770,11 @@ int icw_cwave_frame_bytes(uint32_t cw_format, uint32_t channels)
 int icw_encode_cwave(icw_ctx *c, int first, int count, const void *in, size_t in_stride, void *out, size_t out_stride,
                      int n_frames, uint32_t cw_format, unsigned flags, void *hip_stream)
 {
-    if (!c || first < 0 || count <= 0 || first + count > c->n_streams || n_frames < 0 || !in || !out ||
-        (flags & ~ICW_F_DEVICE_PTRS))
-        return ICW_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (c->inputs.size() > 1 && !c->enc_streams) return ICW_EUNSUPPORTED;   /* per-stream inputs: asked for (include/icw.h) */
-    if (c->hilbs.size() > 1) return ICW_EUNSUPPORTED;                   /* per-stream Hilbert converters: not served */
-    CallPlan pl(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
-    int rc;
-    if ((rc = pl.enc_format(cw_format, c->fir_M > 0)) != ICW_OK) return rc;
+    std::unique_lock<std::mutex> lk;
+    std::optional<CallPlan> plan;
+    int rc = enc_begin(plan, lk, true, c, first, count, in, in_stride, out, out_stride, n_frames, cw_format, flags, hip_stream);
+    if (rc != ICW_OK) return rc;
+    CallPlan &pl = *plan;
     if (n_frames == 0) return ICW_OK;
     if (set_dev(c)) return ICW_EDEVICE;
     ++c->calls;
@@ -1824,11 +1784,8 @@ int icw_encode_cwave(icw_ctx *c, int first, int count, const void *in, size_t in
     if (!pl.dev && !pl.stage_copy_in()) return ICW_EDEVICE;
     pl.plan_uniform(kMaxFirBlockFrames);
     const int cwf = (int)(cw_format - ICW_FMT_CW_F64);
-    for (int b = 0; b < pl.n_blocks; ++b) {
-        const auto e = pl.enc_args(b);
-        if ((pl.mixin ? icw_launch_fir_encode_mixed(&e, cwf, pl.st) : icw_launch_fir_encode(&e, cwf, pl.st)) != hipSuccess)
-            return ICW_EDEVICE;
-    }
+    for (int b = 0; b < pl.n_blocks; ++b)
+        if (pl.launch_fir_encode(b, cwf) != hipSuccess) return ICW_EDEVICE;
     if (!pl.fir_hist_back()) return ICW_EDEVICE;
     if (icw_launch_enc_advance(c->st.pos + pl.f0, nullptr, count, (long long)n_frames, pl.st) != hipSuccess) return ICW_EDEVICE;
     if (pl.legacy && hipStreamSynchronize(pl.st) != hipSuccess) return ICW_EDEVICE;
@@ -1847,19 +1804,14 @@ int icw_encode_cwave(icw_ctx *c, int first, int count, const void *in, size_t in
 int icw_encode_cwave_iir(icw_ctx *c, int first, int count, const void *in, size_t in_stride, void *out, size_t out_stride,
                          int n_frames, uint32_t cw_format, unsigned flags, void *hip_stream)
 {
-    if (!c || first < 0 || count <= 0 || first + count > c->n_streams || n_frames < 0 || !in || !out ||
-        (flags & ~ICW_F_DEVICE_PTRS))
-        return ICW_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (c->inputs.size() > 1 && !c->enc_streams) return ICW_EUNSUPPORTED;   /* per-stream inputs: asked for (include/icw.h) */
-    if (c->hilbs.size() > 1) return ICW_EUNSUPPORTED;                   /* per-stream Hilbert converters: not served */
-    const icw_config &cfg = c->cfg;
-    CallPlan pl(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
-    int rc;
-    if ((rc = pl.enc_format(cw_format, c->fir_M <= 0)) != ICW_OK) return rc;
+    std::unique_lock<std::mutex> lk;
+    std::optional<CallPlan> plan;
+    int rc = enc_begin(plan, lk, false, c, first, count, in, in_stride, out, out_stride, n_frames, cw_format, flags, hip_stream);
+    if (rc != ICW_OK) return rc;
+    CallPlan &pl = *plan;
     const size_t S = pl.S;
     /* FC() arithmetic changes the values: refused, so K1 / K2 take no census (fes null, fcm false) */
-    if (cfg.fp_check) return ICW_EUNSUPPORTED;
+    if (c->cfg.fp_check) return ICW_EUNSUPPORTED;
     if (n_frames == 0) return ICW_OK;
     if (set_dev(c)) return ICW_EDEVICE;
     /* the K1 of a process call over these streams */
@@ -1880,27 +1832,14 @@ int icw_encode_cwave_iir(icw_ctx *c, int first, int count, const void *in, size_
     const DevState &ds = c->st;
     const int cwf = (int)(cw_format - ICW_FMT_CW_F64);
     for (int b = 0; b < pl.n_blocks; ++b) {
-        if (pl.mixin) {
-            const auto m0 = pl.k0_mix_args(b);
-            if (icw_launch_unpack_mixed(&m0, pl.st) != hipSuccess) return ICW_EDEVICE;
-        } else {
-            const auto a0 = pl.k0_args(b);
-            if (icw_launch_unpack(&a0, pl.st) != hipSuccess) return ICW_EDEVICE;
-        }
+        if (pl.launch_unpack(b, pl.st) != hipSuccess) return ICW_EDEVICE;
         const auto a1 = pl.k1_args(b);
         if (pl.launch_k1(a1, pl.st) != hipSuccess) return ICW_EDEVICE;
         const auto a2 = pl.enc_k2_args(b);
         if (pl.launch_k2(a2, pl.st) != hipSuccess) return ICW_EDEVICE;
-        if (pl.mixin) {
-            const auto mp = pl.pack_mix_args(b);
-            if (icw_launch_iq_pack_mixed(&mp, cwf, pl.st) != hipSuccess) return ICW_EDEVICE;
-        } else {
-            const auto ap = pl.pack_args(b);
-            if (icw_launch_iq_pack(&ap, cwf, pl.nch > 1 ? 2 : 1, pl.st) != hipSuccess) return ICW_EDEVICE;
-        }
+        if (pl.launch_pack(b, cwf) != hipSuccess) return ICW_EDEVICE;
     }
-    for (int i = 0; i < count; ++i)
-        if (c->inputs.at(pl.f0 + (size_t)i).nch > 1) c->lr_known[first + i] = 0;   /* stereo: the halves diverge */
+    pl.stereo_diverged();
     if (icw_launch_enc_advance(ds.pos + pl.f0, ds.hq_phase + pl.f0 * 2, count, (long long)n_frames, pl.st) != hipSuccess)
         return ICW_EDEVICE;
     if (pl.legacy && hipStreamSynchronize(pl.st) != hipSuccess) return ICW_EDEVICE;

@@ -6,7 +6,8 @@
  * A table always has at least one entry; a context whose streams all share a setting is a one-entry table
  * and not a special case.  The entries are pairwise distinct under the equality the setting is compared by,
  * every entry has a stream, and they are numbered in order of their first stream.  An edit builds a
- * candidate copy (assigned, mapped), which the setting's install puts in force or drops.
+ * candidate copy (assigned, mapped), which the setting's install puts in force or drops.  A call reads a
+ * setting as the runs of its range (runs): consecutive streams on one entry.
  */
 #ifndef ICW_STREAM_TABLE_H
 #define ICW_STREAM_TABLE_H
@@ -15,6 +16,34 @@
 #include <stdint.h>
 
 #include <vector>
+
+/* consecutive streams of a range on one entry: the first of them, relative to the range, and how many */
+template <class E> struct StreamRun {
+    int s0, n;
+    const E *e;
+};
+
+/* The runs of a range, in order.  One run is held in place, so a range on one entry allocates nothing;
+ * the vector is used only for more than one. */
+template <class E> struct StreamRuns {
+    StreamRun<E> one{};
+    std::vector<StreamRun<E>> more;
+    size_t count = 0;
+
+    /* n streams on entry e as one run */
+    static StreamRuns single(int n, const E *e)
+    {
+        StreamRuns r;
+        r.one = StreamRun<E>{0, n, e};
+        r.count = 1;
+        return r;
+    }
+
+    size_t size() const { return count; }
+    const StreamRun<E> *begin() const { return count > 1 ? more.data() : &one; }
+    const StreamRun<E> *end() const { return begin() + count; }
+    const StreamRun<E> &operator[](size_t k) const { return begin()[k]; }
+};
 
 template <class E> struct StreamTable {
     std::vector<E> ents;                  /* never empty; pairwise distinct; numbered in order of their first stream */
@@ -38,6 +67,29 @@ template <class E> struct StreamTable {
             for (size_t i = 1; i < count; ++i)
                 if (of[first + i] != of[first]) return false;
         return true;
+    }
+
+    /* streams [first, first + count) cut into the maximal runs of consecutive streams on one entry (none for
+     * an empty range); a one-entry table is not scanned */
+    StreamRuns<E> runs(size_t first, size_t count) const
+    {
+        if (count == 0) return StreamRuns<E>{};
+        StreamRuns<E> r = StreamRuns<E>::single((int)count, &at(first));
+        if (ents.size() == 1) return r;
+        StreamRun<E> *cur = &r.one;
+        cur->n = 1;
+        for (size_t i = 1; i < count; ++i) {
+            const E *e = &at(first + i);
+            if (e == cur->e) {
+                ++cur->n;
+                continue;
+            }
+            if (r.more.empty()) r.more.push_back(r.one);
+            r.more.push_back(StreamRun<E>{(int)i, 1, e});
+            cur = &r.more.back();
+        }
+        if (!r.more.empty()) r.count = r.more.size();
+        return r;
     }
 
     /* a candidate: this table with streams [first, first + count) on entry e */

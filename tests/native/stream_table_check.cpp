@@ -3,7 +3,9 @@
  * array, on the host: tables of 1, 2, 3 and 7 streams through random range assignments, whole-table
  * transforms that make entries collide, and resets; the entry is an int under an equality that identifies
  * some distinct values (equal modulo 5).  After every operation the table's invariants and every stream's
- * value are checked, and a candidate that is built and dropped must leave the table as it was.
+ * value are checked, and a candidate that is built and dropped must leave the table as it was; and runs() is
+ * cut for the empty range, a one-stream range, the whole table and three random ranges and checked against
+ * the model.
  * Built with -fsanitize=address,undefined and run directly (tests/test_stream_table.py).
  *
  *   stream_table_check [operations per table] [seed]      exit status 1 and a line per failure
@@ -48,9 +50,53 @@ static int failures;
         }                                             \
     } while (0)
 
+/* the ranges runs() is cut for draw from a generator of their own, so the operations stay the ones they were */
+static uint64_t range_state = 0x2545F4914F6CDD1Dull;
+static uint32_t range_rnd(uint32_t n)
+{
+    range_state = range_state * 6364136223846793005ull + 1442695040888963407ull;
+    return (uint32_t)(range_state >> 33) % n;
+}
+
+/* runs(first, count) against the model: the runs tile the range in order without a gap, every stream of a
+ * run is at the run's entry, neighbours differ in entry (each run is maximal), an empty range has none
+ * and a one-entry table exactly one */
+static void check_runs(const StreamTable<int> &t, const std::vector<int> &m, size_t first, size_t count, const char *op, long step)
+{
+    const StreamRuns<int> r = t.runs(first, count);
+    CHECK((r.size() == 0) == (count == 0), "%s step %ld: runs(%zu, %zu) has %zu", op, step, first, count, r.size());
+    CHECK(r.end() == r.begin() + r.size(), "%s step %ld: runs(%zu, %zu) end", op, step, first, count);
+    if (count > 0 && t.size() == 1) CHECK(r.size() == 1, "%s step %ld: runs(%zu, %zu) of one entry has %zu", op, step, first, count, r.size());
+    size_t at = 0, k = 0;
+    for (const StreamRun<int> &q : r) {
+        CHECK(&q == &r[k], "%s step %ld: runs(%zu, %zu) run %zu by index", op, step, first, count, k);
+        CHECK(q.n >= 1 && (size_t)q.s0 == at, "%s step %ld: runs(%zu, %zu) run %zu at %d for %d, expected at %zu", op, step, first, count, k, q.s0, q.n, at);
+        if (q.n < 1 || (size_t)q.s0 != at || at + (size_t)q.n > count) return;
+        for (size_t i = 0; i < (size_t)q.n; ++i) {
+            const size_t s = first + at + i;
+            CHECK(q.e == &t.at(s) && *q.e == m[s], "%s step %ld: runs(%zu, %zu) run %zu stream %zu", op, step, first, count, k, s);
+        }
+        if (k > 0) {
+            CHECK(q.e != r[k - 1].e && !same(m[first + at], m[first + at - 1]), "%s step %ld: runs(%zu, %zu) runs %zu and %zu on one entry", op, step, first, count, k - 1, k);
+        }
+        at += (size_t)q.n;
+        ++k;
+    }
+    CHECK(at == count, "%s step %ld: runs(%zu, %zu) cover %zu", op, step, first, count, at);
+}
+
 static void check(const StreamTable<int> &t, const std::vector<int> &m, const char *op, long step)
 {
     const size_t S = m.size();
+    if (t.of.size() == S && t.size() >= 1) {
+        check_runs(t, m, range_rnd((uint32_t)S + 1), 0, op, step);
+        check_runs(t, m, range_rnd((uint32_t)S), 1, op, step);
+        check_runs(t, m, 0, S, op, step);
+        for (int i = 0; i < 3; ++i) {
+            const size_t first = range_rnd((uint32_t)S);
+            check_runs(t, m, first, 1 + range_rnd((uint32_t)(S - first)), op, step);
+        }
+    }
     CHECK(t.of.size() == S && t.size() >= 1, "%s step %ld", op, step);
     size_t distinct = 0;
     for (size_t s = 0; s < S; ++s) {

@@ -2,8 +2,9 @@
 the host: tests/native/stream_table_check.cpp, built with AddressSanitizer and UBSan and run directly, drives
 tables of 1, 2, 3 and 7 streams through random range assignments, colliding whole-table transforms and
 resets, and checks after every operation each stream's value, that the entries are pairwise unequal, all
-used and numbered in order of their first stream, the entry count, and that a dropped candidate leaves the
-table unchanged."""
+used and numbered in order of their first stream, the entry count, that a dropped candidate leaves the
+table unchanged, and that runs() over the empty range, one stream, the whole table and random ranges tiles
+the range with maximal runs of one entry each (exactly one for a one-entry table)."""
 import subprocess
 from pathlib import Path
 
@@ -44,6 +45,20 @@ def test_header_compiles_alone(tmp_path):
 def test_checker_detects_broken_compaction(tmp_path, what, old, new):
     """negative controls: the same checker over a header whose compaction no longer merges equal entries, or
     no longer numbers the survivors by first stream, must fail"""
+    checker_fails_on(tmp_path, what, old, new)
+
+
+@pytest.mark.parametrize("what,old,new", [
+    ("two neighbouring runs of different entries merged", "if (e == cur->e) {", "if (e == cur->e || i == 2) {"),
+    ("one run split", "if (e == cur->e) {", "if (e == cur->e && i != 2) {"),
+])
+def test_checker_detects_broken_runs(tmp_path, what, old, new):
+    """negative controls: the same checker over a header whose runs() takes stream 2 of a range into the run
+    before it whatever its entry, or starts a new run there whatever its entry, must fail"""
+    checker_fails_on(tmp_path, what, old, new)
+
+
+def checker_fails_on(tmp_path, what, old, new):
     text = HEADER.read_text()
     assert text.count(old) == 1, what
     (tmp_path / "icw_stream_table.h").write_text(text.replace(old, new))
