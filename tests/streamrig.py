@@ -1,16 +1,22 @@
-"""Random edit sequences over the four per-stream tables of one context (test helper): DSP lists
-(icw_set_stream_graph), inputs real and CWAVE (icw_set_stream_input, icw_enable_stream_cwave), renders
-(icw_set_stream_render) and Hilbert converters (icw_set_stream_hilbert), with the context-wide setters, track
-opens and subset calls in between.  Three parts, so that everything but the execution on the device is checked
-on a CPU (tests/test_stream_random_host.py):
+"""The per-stream tests' shared harness (test helper): one call-and-compare, one meter check and two rigs over
+the four per-stream tables of one context -- DSP lists (icw_set_stream_graph), inputs real and CWAVE
+(icw_set_stream_input, icw_enable_stream_cwave), renders (icw_set_stream_render) and Hilbert converters
+(icw_set_stream_hilbert).  Every comparison is bit for bit; nothing has a tolerance.
 
-  make_plan(seed)   pure and deterministic: the stream count, the starting config, the environment switches and
-                    the list of ops.  Nothing here touches a context or the oracle.
+  call_streams      one icw_process_streams call and the same frames through one oracle.Stream per stream: the
+                    pre-render doubles, the rendered bytes, and the guard byte past every stream's own frames.
+  check_meters      clips, peak dB bits, de-subnorm counts and n_frame per stream, the FP census when asked.
+                    tests/test_streamrig_compare_host.py plants deviations in both on a CPU.
+  StreamRig         the hand-scripted rig of tests/test_gpu_stream_{graph,input,cwave,fir,render,hilbert}.py.
+  make_plan(seed)   random edit sequences, with the context-wide setters, track opens and subset calls in
+                    between; pure and deterministic: the stream count, the starting config, the environment
+                    switches and the list of ops.  Nothing here touches a context or the oracle.
   Table             the settings model: per stream its input, (list, bypass), (render, depth) and converter, and
                     the four counts as include/icw.h defines them.
-  Rig               runs a plan on a context (in_cwave_amd.lib.Context, or the host test's FakeContext) and on one
-                    oracle.Stream per stream, edit by edit as Rig.set / Rig.step of tests/test_gpu_stream_hilbert.py
-                    do, and compares after every op.  Every comparison is bit for bit; nothing has a tolerance.
+  Rig               runs a plan on a context (in_cwave_amd.lib.Context, or the FakeContext of
+                    tests/test_stream_random_host.py, so that everything but the execution on the device is
+                    checked on a CPU) and on one oracle.Stream per stream, edit by edit, and compares after
+                    every op.
 
 What a count counts (the header's words, with the doubts settled from icw_context.cpp):
   lists      distinct (normalised list, bypass flag) pairs.  prog_table_compact merges two entries when their
@@ -38,7 +44,7 @@ CW = abi.CW_FORMATS
 RATES = (44100, 48000, 96000)
 SWITCHES = {"ICW_K1_MODE": (None, "row", "plain"), "ICW_RENDER": (None, "serial", "row"), "ICW_BLOCK": (None, "256", "263")}
 N_SIG = 8 * 1100                    # frames a plan can feed one stream: 8 calls of 1 100 at the most
-NS_FIR20 = 6                        # a canned 20-tap FIR shaper, as tests/test_gpu_stream_render.py names it
+NS_FIR20 = 6                        # a canned 20-tap FIR shaper (sound_render.c: icw_ns_n[6] == 20)
 GUARD = 0xA5
 AXES = ("list", "input", "render", "hilbert")
 STREAM_SETTERS = ("set_stream_graph", "set_stream_input", "set_stream_render", "set_stream_hilbert")
@@ -86,6 +92,93 @@ def bits(a):
     return np.ascontiguousarray(a).view(np.uint64)
 
 
+def entry(rtype=abi.RENDER_ROUND, ns=abi.NSHAPE_FLAT, b24=False, quantz=abi.QUANTZ_MID_TREAD, dth=1.0, sb16=16, sb24=24):
+    """a render entry as icw_set_stream_render takes it: (RenderCfg, need24bits)"""
+    return render_cfg((dth, quantz, rtype, ns, sb16, sb24)), bool(b24)
+
+
+def shift_list(fr):
+    return [graph.master(inputs=("A",)), graph.shift(inputs=("in",), out="A", fr=fr)]
+
+
+# ------------------------------------------------------------------ one call, compared ----------------------
+def in_rows(raws):
+    """a call's input: every stream's frames at its own frame size, in rows of the widest"""
+    rows = np.zeros((len(raws), max(r.size for r in raws)), np.uint8)
+    for i, r in enumerate(raws):
+        rows[i, :r.size] = r
+    return rows
+
+
+def out_rows(n, osz, pad):
+    """a call's output: rows of the widest output frame plus pad bytes, filled with the guard byte"""
+    return np.full((len(osz), n * max(osz) + pad), GUARD, np.uint8)
+
+
+def _stream(what, labels, first, i):
+    return f"{what} stream {first + i}" + (f" {labels[i]}" if labels else "")
+
+
+def call_streams(ctx, sts, first, n, raws, osz, device=False, want_pre=True, timing=False, pad=0, what="", labels=None,
+                 wrapper=False):
+    """one call of n frames over streams [first, first + len(raws)) -- raws[i] the frames of stream first + i,
+    osz[i] its output frame size -- and the same frames through each stream's own oracle.Stream (sts[first + i]).
+    Bit for bit: the pre-render doubles where asked for (as uint64, so -0.0 is not +0.0), the rendered bytes,
+    their count, and the guard byte in all of the row past the stream's own frames, host and device pointers
+    alike (a host_only context takes the device-pointer call with host arrays).  wrapper: the host call goes
+    through ctx.process, not the entry point.  Returns the output rows.  labels[i] goes into stream
+    first + i's messages"""
+    count = len(raws)
+    rows, out = in_rows(raws), out_rows(n, osz, pad)
+    stride = out.shape[1]
+    pre = np.zeros((count, n, 2), np.float64) if want_pre else None
+    flags = (abi.F_DEBUG_PRE if want_pre else 0) | (abi.F_TIMING if timing else 0) | (abi.F_DEVICE_PTRS if device else 0)
+    if wrapper:
+        assert not device and not timing
+        out, pre = ctx.process(rows, n, first=first, count=count, want_pre=want_pre, out=out)
+    elif device and not getattr(ctx, "host_only", False):
+        import torch
+        d_in, d_out = torch.from_numpy(rows).cuda(), torch.from_numpy(out).cuda()
+        d_pre = torch.zeros((count, n, 2), dtype=torch.float64, device="cuda") if want_pre else None
+        torch.cuda.synchronize()
+        rc = ctx._lib.icw_process_streams(ctx.h, first, count, d_in.data_ptr(), rows.shape[1], d_out.data_ptr(), stride, n,
+                                          flags, d_pre.data_ptr() if want_pre else None, None)
+        assert rc == abi.OK, f"{what} icw_process_streams returned {rc}"
+        ctx.synchronize()
+        out = d_out.cpu().numpy()
+        pre = d_pre.cpu().numpy() if want_pre else None
+    else:
+        rc = ctx._lib.icw_process_streams(ctx.h, first, count, rows.ctypes.data, rows.shape[1], out.ctypes.data, stride, n,
+                                          flags, pre.ctypes.data if want_pre else None, None)
+        assert rc == abi.OK, f"{what} icw_process_streams returned {rc}"
+    for i in range(count):
+        w = _stream(what, labels, first, i)
+        ro, rp = sts[first + i].process(raws[i], n, want_pre=want_pre)
+        if want_pre:
+            bad = np.flatnonzero(bits(pre[i]) != bits(rp))
+            assert bad.size == 0, f"{w}: {bad.size} pre-render doubles differ, first at {bad[:4]}"
+        assert ro.size == n * osz[i], f"{w}: the oracle rendered {ro.size} bytes, {n} frames of {osz[i]} are {n * osz[i]}"
+        bad = np.flatnonzero(out[i, :ro.size] != ro)
+        assert bad.size == 0, f"{w}: {bad.size} rendered bytes differ, first at {bad[:4]}"
+        bad = np.flatnonzero(out[i, ro.size:] != GUARD)
+        assert bad.size == 0, f"{w}: {bad.size} bytes written past its {ro.size} bytes of frames, first at {ro.size + bad[:4]}"
+    return out
+
+
+def check_meters(ctx, sts, what="", census=False, first=0, labels=None):
+    """clips, peak dB bits, de-subnorm counts and n_frame of streams [first, first + len(sts)) against their
+    oracle streams sts, and the FP census when asked"""
+    for i, st in enumerate(sts):
+        s, w = first + i, _stream(what, labels, first, i)
+        m, r = ctx.meters(s), st.meters()
+        assert m["clips"] == r["clips"], f"{w}: clips {m} vs {r}"
+        assert bits(np.array(m["peak_db"])).tolist() == bits(np.array(r["peak_db"])).tolist(), f"{w}: peaks {m} vs {r}"
+        assert m["desubnorm"] == r["desubnorm"], f"{w}: de-subnorm count {m} vs {r}"
+        assert ctx.n_frame(s) == st.n_frame(), f"{w}: n_frame {ctx.n_frame(s)} vs {st.n_frame()}"
+        if census:
+            assert np.array_equal(ctx.fp_census(s), st.fp_census()), f"{w}: FP census"
+
+
 def normal_key(nodes, bypass):
     """a list as the context stores it: amod_init's L/R lock fan-out (graph_accept) applied, with the flag"""
     out = []
@@ -112,7 +205,7 @@ def normal_key(nodes, bypass):
 @lru_cache(maxsize=512)
 def signal(s, inp, silent=False):
     """stream s's test signal at an input: synth.stream_pcm, synth.stream_cwave for the CWAVE formats (as
-    tests/test_gpu_stream_cwave.py makes it); a silent stream is fed digital silence"""
+    StreamRig.signal makes it); a silent stream is fed digital silence"""
     rate, fmt, ch = inp
     gen = synth.stream_cwave if fmt in CW else synth.stream_pcm
     raw = gen(s, N_SIG, rate, channels=ch, fmt=fmt)
@@ -555,65 +648,146 @@ class Rig:
 
     def op_refuse_two_kinds(self, op):
         a = op.a
-        rows, out, stride = self.buffers(a["first"], a["count"], a["n"], 0)
+        span = range(a["first"], a["first"] + a["count"])
+        rows, out = in_rows([self.raw(s, a["n"]) for s in span]), out_rows(a["n"], [self.osz(s) for s in span], 0)
         rc = self.ctx._lib.icw_process_streams(self.ctx.h, a["first"], a["count"], rows.ctypes.data, rows.shape[1], out.ctypes.data,
-                                               stride, a["n"], 0, None, None)
+                                               out.shape[1], a["n"], 0, None, None)
         assert rc == abi.EUNSUPPORTED, f"{self.where(op)}: a call over real and CWAVE streams returned {rc}"
         assert (out == GUARD).all(), f"{self.where(op)}: the refused call wrote output"
         self.check_tables(op)
 
     # -- calls
-    def buffers(self, first, count, n, pad):
-        """input rows of the call's widest frame, each stream's frames at its own size; output rows of the
-        widest output frame plus pad bytes, filled with the guard byte"""
-        tab = self.tab
-        wide = max(frame_bytes(tab.inp[s]) for s in range(first, first + count))
-        rows = np.zeros((count, n * wide), np.uint8)
-        for i in range(count):
-            raw = self.raw(first + i, n)
-            rows[i, :raw.size] = raw
-        stride = n * max(6 if tab.rnd[s][1] else 4 for s in range(first, first + count)) + pad
-        return rows, np.full((count, stride), GUARD, np.uint8), stride
+    def osz(self, s):
+        return 6 if self.tab.rnd[s][1] else 4
 
     def op_process(self, op):
-        a, ctx, tab = op.a, self.ctx, self.tab
-        first, count, n, want_pre = a["first"], a["count"], a["n"], a["want_pre"]
-        where = self.where(op)
-        rows, out, stride = self.buffers(first, count, n, (self.plan.seed + len(self.log)) % 3)
-        pre = np.zeros((count, n, 2), np.float64) if want_pre else None
-        flags = abi.F_DEBUG_PRE if want_pre else 0
-        if a["device"] and not getattr(ctx, "host_only", False):
-            import torch
-            d_in, d_out = torch.from_numpy(rows).cuda(), torch.from_numpy(out).cuda()
-            d_pre = torch.zeros((count, n, 2), dtype=torch.float64, device="cuda") if want_pre else None
-            torch.cuda.synchronize()
-            rc = ctx._lib.icw_process_streams(ctx.h, first, count, d_in.data_ptr(), rows.shape[1], d_out.data_ptr(), stride, n,
-                                              flags | abi.F_DEVICE_PTRS, d_pre.data_ptr() if want_pre else None, None)
-            assert rc == abi.OK, f"{where}: icw_process_streams returned {rc}"
-            ctx.synchronize()
-            out = d_out.cpu().numpy()
-            pre = d_pre.cpu().numpy() if want_pre else None
-        else:
-            rc = ctx._lib.icw_process_streams(ctx.h, first, count, rows.ctypes.data, rows.shape[1], out.ctypes.data, stride, n,
-                                              flags | (abi.F_DEVICE_PTRS if a["device"] else 0), pre.ctypes.data if want_pre else None, None)
-            assert rc == abi.OK, f"{where}: icw_process_streams returned {rc}"
-        for i in range(count):
-            s = first + i
-            what = f"{where}: stream {s} (input {tab.inp[s]}, list {tab.lst[s]}, render {tab.rnd[s][0][2:4]} / {24 if tab.rnd[s][1] else 16} bit, converter {tab.hil[s]}) from frame {self.t[s]}"
-            ro, rp = self.sts[s].process(self.raw(s, n), n, want_pre=want_pre)
-            if want_pre:
-                bad = np.flatnonzero(bits(pre[i]) != bits(rp))
-                assert bad.size == 0, f"{what}: {bad.size} pre-render doubles differ, first at {bad[:4]}"
-            assert ro.size == n * (6 if tab.rnd[s][1] else 4), what
-            bad = np.flatnonzero(out[i, :ro.size] != ro)
-            assert bad.size == 0, f"{what}: {bad.size} rendered bytes differ, first at {bad[:4]}"
-            bad = np.flatnonzero(out[i, ro.size:] != GUARD)
-            assert bad.size == 0, f"{what}: {bad.size} bytes written past its {ro.size} bytes of frames, first at {ro.size + bad[:4]}"
+        a, tab = op.a, self.tab
+        first, count, n = a["first"], a["count"], a["n"]
+        where, span = self.where(op), range(a["first"], a["first"] + a["count"])
+        labels = [f"(input {tab.inp[s]}, list {tab.lst[s]}, render {tab.rnd[s][0][2:4]} / {24 if tab.rnd[s][1] else 16} bit, "
+                  f"converter {tab.hil[s]}) from frame {self.t[s]}" for s in span]
+        call_streams(self.ctx, self.sts, first, n, [self.raw(s, n) for s in span], [self.osz(s) for s in span], device=a["device"],
+                     want_pre=a["want_pre"], pad=(self.plan.seed + len(self.log)) % 3, what=where + ":", labels=labels)
+        for s in span:
             self.t[s] += n
-            m, r = ctx.meters(s), self.sts[s].meters()
-            assert m["clips"] == r["clips"], f"{what}: clips {m} vs {r}"
-            assert bits(np.array(m["peak_db"])).tolist() == bits(np.array(r["peak_db"])).tolist(), f"{what}: peaks {m} vs {r}"
-            assert m["desubnorm"] == r["desubnorm"], f"{what}: de-subnorm count {m} vs {r}"
-            assert ctx.n_frame(s) == self.sts[s].n_frame(), f"{what}: n_frame {ctx.n_frame(s)} vs {self.sts[s].n_frame()}"
+        check_meters(self.ctx, self.sts[first:first + count], where + ":", first=first, labels=labels)
         if self.after_call:
             self.after_call(self, op)
+
+
+class StreamRig:
+    """a hand-scripted context with one oracle.Stream and one test signal per stream, beside the plan-driven Rig.
+    Stream s runs lists[s] (bypass[s]), reads inputs[s] = (rate, fmt, channels), renders with renders[s] =
+    (RenderCfg, need24bits) and converts with settings[s] = (type, kahan, reject); a missing table or a None entry
+    is the context's own: cfg's, and the list `nodes` (lists[0] where not given).  silent: streams fed digital
+    silence; cwave: icw_enable_stream_cwave first; sig0: the first stream's signal seed; pad: the bytes step adds to
+    a call's output rows unless told otherwise.  Every stream keeps its own frame position t[s]"""
+
+    def __init__(self, icw, oracle, cfg, n_total, S=None, nodes=None, lists=None, bypass=None, inputs=None, renders=None,
+                 settings=None, silent=(), cwave=False, sig0=0, pad=0):
+        S = len(next(x for x in (lists, inputs, renders, settings, [None] * (S or 0)) if x is not None))
+        own = (cfg.hilbert_type, cfg.iir_kahan, cfg.iir_subnorm_reject)
+        lists, settings = lists or [None] * S, settings or [None] * S
+        nodes = nodes or lists[0] or graph.graph_shift_master()
+        lists = [nodes if nl is None else nl for nl in lists]
+        self.pad = pad
+        self.ctx = icw.Context(copy_cfg(cfg), nodes, S)
+        if cwave:
+            self.ctx.enable_stream_cwave()
+        self.sts = []
+        for s in range(S):
+            byp = bypass[s] if bypass else cfg.bypass_list
+            t, k, r = settings[s] or own
+            self.sts.append(oracle.Stream(copy_cfg(cfg, bypass_list=byp, hilbert_type=t, iir_kahan=k, iir_subnorm_reject=r), lists[s]))
+            if lists[s] is not nodes or byp != cfg.bypass_list:
+                assert self.ctx.set_stream_graph(lists[s], s, 1, byp)
+        self.cur = [own] * S
+        self.inputs = [(cfg.sample_rate, cfg.in_format, cfg.in_channels)] * S
+        for s, inp in enumerate(inputs or []):
+            if inp is not None:
+                self.set_input(s, *inp)
+        self.raw = [self.signal(sig0 + s, n_total, *inp) for s, inp in enumerate(self.inputs)]
+        for s in silent:
+            self.raw[s] = np.full_like(self.raw[s], 128 if self.inputs[s][1] == abi.FMT_U8 else 0)
+        self.osz = [2 * self.ctx.stream_render_size(s) for s in range(S)]
+        for s, e in enumerate(renders or []):
+            if e is not None:
+                self.set_render(s, e)
+        # runs of equal settings go in one call of the setter each; the oracles were created with theirs
+        s = 0
+        while s < S:
+            n = 1
+            while s + n < S and settings[s + n] == settings[s]:
+                n += 1
+            if settings[s] is not None:
+                self.ctx.set_stream_hilbert(*settings[s], first=s, count=n)
+                self.cur[s:s + n] = [settings[s]] * n
+            s += n
+        self.t = [0] * S
+
+    @staticmethod
+    def signal(seed, n, rate, fmt, ch):
+        """synth.stream_cwave's analytic signal for the CWAVE formats, synth.stream_pcm's for the real ones"""
+        return (synth.stream_cwave if fmt in CW else synth.stream_pcm)(seed, n, rate, channels=ch, fmt=fmt)
+
+    # -- edits over streams [s, s + count): the setter on the context, the reference's own calls on the oracles
+    def set_graph(self, s, nodes, count=1, bypass=0):
+        assert self.ctx.set_stream_graph(nodes, s, count, bypass)
+        for st in self.sts[s:s + count]:
+            assert st.set_graph(nodes, bypass)
+
+    def set_input(self, s, rate, fmt, ch, count=1):
+        self.ctx.set_stream_input(rate, fmt, ch, s, count)
+        for i in range(s, s + count):
+            self.sts[i].set_input(rate, fmt, ch)
+            self.inputs[i] = (rate, fmt, ch)
+
+    def set_render(self, s, e, count=1):
+        r, b24 = e
+        self.ctx.set_stream_render(r, b24, s, count)
+        for i in range(s, s + count):
+            self.sts[i].set_render(r)
+            self.sts[i].set_outbits(b24)
+            self.osz[i] = 6 if b24 else 4
+            assert self.ctx.stream_render_size(i) == (3 if b24 else 2)
+
+    def set_hilbert(self, s, e, count=1):
+        """hq_rp_create / iir_rp_setcfg on the oracles"""
+        self.ctx.set_stream_hilbert(*e, first=s, count=count)
+        for i in range(s, s + count):
+            self.sts[i].set_hilbert_filter(e[0])
+            self.sts[i].set_hilbert_config(e[1], e[2])
+            self.cur[i] = e
+
+    # -- calls
+    def fsz(self, s):
+        return abi.FMT_BYTES[self.inputs[s][1]] * self.inputs[s][2]
+
+    def frames(self, s, n, t=None):
+        t, f = self.t[s] if t is None else t, self.fsz(s)
+        return self.raw[s][t * f:(t + n) * f]
+
+    def rows(self, n, first, count, t=None):
+        """a call's input rows: every stream's n frames from its own position (from frame t, if given)"""
+        return in_rows([self.frames(first + i, n, t) for i in range(count)])
+
+    def step(self, n, first=0, count=None, device=False, what="", timing=False, pad=None, want_pre=True, advance=True,
+             wrapper=False):
+        """one call over streams [first, first + count), every stream checked against its oracle (call_streams);
+        advance=False leaves the frame positions where they are.  Returns the output rows"""
+        count = len(self.sts) - first if count is None else count
+        span = range(first, first + count)
+        labels = [f"{self.inputs[s]} converter {self.cur[s]} from frame {self.t[s]}" for s in span]
+        out = call_streams(self.ctx, self.sts, first, n, [self.frames(s, n) for s in span], self.osz[first:first + count],
+                           device=device, want_pre=want_pre, timing=timing, pad=self.pad if pad is None else pad, what=what,
+                           labels=labels, wrapper=wrapper)
+        if advance:
+            for s in span:
+                self.t[s] += n
+        return out
+
+    def check(self, what="", census=False):
+        check_meters(self.ctx, self.sts, what, census)
+
+    def close(self):
+        self.ctx.close()

@@ -9,7 +9,7 @@ import pytest
 
 from in_cwave_amd import abi, graph, synth
 
-from test_gpu_stream_input import Rig, bits, copy_cfg, shift_list
+from tests.streamrig import StreamRig, bits, copy_cfg, shift_list
 
 pytestmark = pytest.mark.gpu
 
@@ -19,28 +19,15 @@ RATES = (8000, 44100, 48000, 96000, 192000)
 INPUTS8 = [(RATES[(2 * k + ch) % 5], fmt, ch + 1) for k, fmt in enumerate(CW) for ch in range(2)]
 
 
-def signal(s, n, rate, fmt, ch):
-    gen = synth.stream_cwave if fmt in CW else synth.stream_pcm
-    return gen(s, n, rate, channels=ch, fmt=fmt)
+signal = StreamRig.signal
 
 
-class CwRig(Rig):
-    """test_gpu_stream_input's Rig on a context that asked for per-stream CWAVE inputs: CWAVE streams get
-    synth.stream_cwave's analytic signal, real ones synth.stream_pcm's"""
+class CwRig(StreamRig):
+    """the rig on a context that asked for per-stream CWAVE inputs: CWAVE streams get synth.stream_cwave's
+    analytic signal, real ones synth.stream_pcm's"""
 
-    def __init__(self, icw, oracle, cfg, inputs, lists, n_total, per_stream_lists=False):
-        S = len(inputs)
-        self.ctx = icw.Context(copy_cfg(cfg), lists[0], S)
-        self.ctx.enable_stream_cwave()
-        self.sts = [oracle.Stream(copy_cfg(cfg), lists[s]) for s in range(S)]
-        for s in range(S):
-            if per_stream_lists:
-                assert self.ctx.set_stream_graph(lists[s], s, 1, cfg.bypass_list)
-        self.inputs = [None] * S
-        for s, (rate, fmt, ch) in enumerate(inputs):
-            self.set_input(s, rate, fmt, ch)
-        self.raw = [signal(s, n_total, rate, fmt, ch) for s, (rate, fmt, ch) in enumerate(inputs)]
-        self.t = 0
+    def __init__(self, icw, oracle, cfg, inputs, lists, n_total):
+        super().__init__(icw, oracle, cfg, n_total, inputs=inputs, lists=lists, cwave=True)
 
     def device_step(self, n, stride, first=0, count=None):
         """one device-pointer call with the given in_stride over frames [t, t + n); returns (bytes, pre)"""
@@ -131,7 +118,6 @@ def test_fades_and_tail(icw, oracle):
     blob = [abi.StateBlob.from_buffer_copy(rig.ctx.get_state(s)) for s in range(2)]
     assert [(b.n_fade_in, b.n_fade_out) for b in blob] == [(7, 7), (10, 10)]
     rig.step(1500, what="tracks")
-    rig.t = 1500
     rig.step(500, first=1, count=1, what="the longer tail")
     rig.check("fades")
     rig.close()
@@ -161,7 +147,7 @@ def test_per_stream_lists_and_slabs(icw, oracle):
     a, b = shift_list(2.0), shift_list(3.5)
     inputs = [(44100, abi.FMT_CW_I16, 2), (44100, abi.FMT_CW_F64, 1), (48000, abi.FMT_CW_F32, 2), (48000, abi.FMT_CW_I16_F32, 2),
               (48000, abi.FMT_CW_I16, 1), (48000, abi.FMT_CW_F64, 2)]
-    rig = CwRig(icw, oracle, cfg, inputs, [a, a, a, a, b, b], 1300, per_stream_lists=True)
+    rig = CwRig(icw, oracle, cfg, inputs, [a, a, a, a, b, b], 1300)
     assert rig.ctx.stream_input_count() == 6 and rig.ctx.stream_graph_count() == 2
     rig.step(1100, what="slabs")
     rig.step(200, what="slabs")
@@ -210,7 +196,6 @@ def test_two_kinds_in_one_context(icw, oracle):
     def halves(n, what):
         rig.step(n, first=0, count=2, what=what + " real")
         rig.step(n, first=2, count=2, what=what + " cwave")
-        rig.t += n
 
     halves(301, "first")
     rows = rig.rows(64, 0, 4)
@@ -226,7 +211,6 @@ def test_two_kinds_in_one_context(icw, oracle):
     rig.raw[1] = signal(11, 2000, 48000, abi.FMT_CW_F32, 2)
     rig.step(250, first=1, count=3, what="stream 1 on CWAVE")
     rig.step(250, first=0, count=1, what="stream 0 alone")
-    rig.t += 250
     rig.set_input(1, *wav)
     rig.raw[1] = signal(1, 2000, *wav)
     halves(300, "stream 1 on WAV again")

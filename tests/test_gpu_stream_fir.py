@@ -15,7 +15,9 @@ import pytest
 from in_cwave_amd import abi, graph, synth
 from in_cwave_amd import lib as L
 
-from test_gpu_stream_input import INPUTS10, Rig, bits, copy_cfg, shift_list
+from tests.streamrig import StreamRig, copy_cfg, shift_list
+
+from test_gpu_stream_input import INPUTS10
 
 pytestmark = pytest.mark.gpu
 
@@ -30,8 +32,8 @@ def fir_form(request, monkeypatch):
     return request.param
 
 
-class FirRig(Rig):
-    """test_gpu_stream_input's Rig with the converter on: stream s has inputs[s] and runs lists[s]
+class FirRig(StreamRig):
+    """the rig with the converter on: stream s has inputs[s] and runs lists[s]
     (bypass[s]); fir_first: icw_set_fir_hilbert before the per-stream setters, else after them"""
 
     def __init__(self, icw, oracle, cfg, inputs, lists, n_total, order, fir_first=False, bypass=None):
@@ -51,36 +53,18 @@ class FirRig(Rig):
                 st.set_graph(lists[s], byp)
             st.set_fir(order, BETA)
             self.sts.append(st)
-        self.inputs = [None] * S
+        self.inputs, self.cur = [None] * S, [None] * S
         for s, (rate, fmt, ch) in enumerate(inputs):
             self.set_input(s, rate, fmt, ch)
         if not fir_first:
             self.ctx.set_fir_hilbert(order, BETA)
         self.raw = [synth.stream_pcm(s, n_total, rate, channels=ch, fmt=fmt) for s, (rate, fmt, ch) in enumerate(inputs)]
-        self.t = 0
+        self.osz = [2 * self.ctx.render_size] * S
+        self.t, self.pad = [0] * S, 0
 
-    def run(self, n, first=0, count=None, device=False, what=""):
+    def run(self, n, **kw):
         """a call without pre-render doubles (the signature form's condition): rendered bytes only"""
-        ctx, count = self.ctx, len(self.sts) - first if count is None else count
-        rows = self.rows(n, first, count)
-        if device:
-            import torch
-            osz = 2 * ctx.render_size
-            d_in = torch.from_numpy(rows).cuda()
-            d_out = torch.zeros((count, n * osz), dtype=torch.uint8, device="cuda")
-            torch.cuda.synchronize()
-            ctx.process_device(d_in, rows.shape[1], d_out, n * osz, n, first=first, count=count)
-            ctx.synchronize()
-            out = d_out.cpu().numpy()
-        else:
-            out, _ = ctx.process(rows, n, first=first, count=count)
-        for i in range(count):
-            s = first + i
-            f = self.fsz(s)
-            ro, _ = self.sts[s].process(self.raw[s][self.t * f:(self.t + n) * f], n)
-            assert np.array_equal(out[i], ro), f"{what} stream {s} {self.inputs[s]} from frame {self.t}: rendered bytes differ"
-        if first == 0 and count == len(self.sts):
-            self.t += n
+        self.step(n, want_pre=False, **kw)
 
     def go(self, n, pre, **kw):
         (self.step if pre else self.run)(n, **kw)
@@ -185,7 +169,6 @@ def test_sub_ranges(icw, oracle, monkeypatch):
     # streams 0-2: one entry; the oracles of 3-5 are not advanced, and neither is their history
     rig.step(900, first=0, count=3, what="shared range")
     rig.step(900, first=3, count=3, what="mixing range")
-    rig.t = 1600
     rig.run(1100, what="all again")
     rig.check("sub-ranges")
     rig.close()

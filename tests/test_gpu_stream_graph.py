@@ -7,54 +7,16 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from in_cwave_amd import abi, graph, synth
+from in_cwave_amd import abi, graph
 from tests import graphgen
+from tests.streamrig import StreamRig, bits, copy_cfg, shift_list
 
 pytestmark = pytest.mark.gpu
 
 
-def copy_cfg(cfg, **kw):
-    c = abi.Config.from_buffer_copy(cfg)
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def mixed_context(icw, cfg, lists, bypass=None):
-    """a context whose stream s runs lists[s] (bypass[s]), every list given through icw_set_stream_graph"""
-    ctx = icw.Context(copy_cfg(cfg, bypass_list=0), graph.graph_master_only(), len(lists))
-    for s, nl in enumerate(lists):
-        assert ctx.set_stream_graph(nl, s, 1, bypass[s] if bypass else cfg.bypass_list)
-    return ctx
-
-
-def oracles(oracle, cfg, lists, bypass=None):
-    return [oracle.Stream(copy_cfg(cfg, bypass_list=bypass[s]) if bypass else cfg, nl) for s, nl in enumerate(lists)]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def step(ctx, sts, raw, t0, n, first=0, count=None, what=""):
-    """n frames from frame t0 of raw through streams [first, first + count) and their oracles"""
-    count = len(sts) - first if count is None else count
-    fsz = ctx.fsz
-    out, pre = ctx.process(np.ascontiguousarray(raw[first:first + count, t0 * fsz:(t0 + n) * fsz]), n, first=first,
-                           count=count, want_pre=True)
-    for i in range(count):
-        ro, rp = sts[first + i].process(raw[first + i, t0 * fsz:(t0 + n) * fsz], n, want_pre=True)
-        bad = np.flatnonzero(bits(pre[i]) != bits(rp))
-        assert bad.size == 0, f"{what} stream {first + i} from frame {t0}: {bad.size} pre-render doubles differ, first at {bad[:4]}"
-        assert np.array_equal(out[i], ro), f"{what} stream {first + i} from frame {t0}: rendered bytes differ"
-
-
-def check_meters(ctx, sts, what=""):
-    for s, st in enumerate(sts):
-        m, r = ctx.meters(s), st.meters()
-        assert m["clips"] == r["clips"], (what, s, m, r)
-        assert bits(np.array(m["peak_db"])).tolist() == bits(np.array(r["peak_db"])).tolist(), (what, s, m, r)
-        assert m["desubnorm"] == r["desubnorm"], (what, s, m, r)
+def mixed(icw, oracle, cfg, lists, n_total, **kw):
+    """a rig whose stream s runs lists[s] (bypass[s]), every list given through icw_set_stream_graph"""
+    return StreamRig(icw, oracle, cfg, n_total, nodes=graph.graph_master_only(), lists=lists, **kw)
 
 
 def exec_reads(nodes):
@@ -81,10 +43,6 @@ def register_list(icw, cfg, rng, bypass=0, want_chain=None):
             return nodes
 
 
-def shift_list(fr):
-    return [graph.master(inputs=("A",)), graph.shift(inputs=("in",), out="A", fr=fr)]
-
-
 def test_mixed_lists(icw, oracle):
     """five streams, four lists (one shared by two streams that are not adjacent), chain and
     register-file programs in one launch; calls crossing K2's tiles and its 1 024-frame workgroup"""
@@ -92,16 +50,12 @@ def test_mixed_lists(icw, oracle):
     rng = np.random.default_rng(20260)
     lists = [graph.graph_shift_master(), graph.graph_master_only(), graph.graph_shift_master(),
              graph.graph_pm_shift_mix(), register_list(icw, cfg, rng, want_chain=False)]
-    raw = synth.batch_pcm(5, 1707, 48000)
-    ctx = mixed_context(icw, cfg, lists)
-    assert ctx.stream_graph_count() == 4
-    sts = oracles(oracle, cfg, lists)
-    t = 0
+    rig = mixed(icw, oracle, cfg, lists, 1707)
+    assert rig.ctx.stream_graph_count() == 4
     for n in (1100, 7, 600):
-        step(ctx, sts, raw, t, n, what="mixed")
-        t += n
-    check_meters(ctx, sts, "mixed")
-    ctx.close()
+        rig.step(n, what="mixed")
+    rig.check("mixed")
+    rig.close()
 
 
 @pytest.mark.parametrize("batch", range(4))
@@ -112,12 +66,10 @@ def test_random_lists(icw, oracle, batch):
         cfg = graphgen.random_config(rng)
         bypass = [int(rng.random() < 0.2) for _ in range(4)]
         lists = [register_list(icw, cfg, rng, bypass[s]) for s in range(4)]
-        raw = synth.batch_pcm(4, 300, cfg.sample_rate, first=seed * 4)
-        ctx = mixed_context(icw, cfg, lists, bypass)
-        sts = oracles(oracle, cfg, lists, bypass)
-        step(ctx, sts, raw, 0, 300, what=f"seed {seed}")
-        check_meters(ctx, sts, f"seed {seed}")
-        ctx.close()
+        rig = mixed(icw, oracle, cfg, lists, 300, bypass=bypass, sig0=seed * 4)
+        rig.step(300, what=f"seed {seed}")
+        rig.check(f"seed {seed}")
+        rig.close()
 
 
 def test_rotation_table_slabs(icw, oracle):
@@ -126,19 +78,19 @@ def test_rotation_table_slabs(icw, oracle):
     cfg = graph.default_config(48000)
     a, b = shift_list(2.0), shift_list(3.5)
     lists = [a, b, a, b, a, b]
-    raw = synth.batch_pcm(6, 1500, 48000)
-    ctx = mixed_context(icw, cfg, lists)
+    rig = mixed(icw, oracle, cfg, lists, 1500)
+    ctx = rig.ctx
     assert ctx.stream_graph_count() == 2
-    sts = oracles(oracle, cfg, lists)
-    step(ctx, sts, raw, 0, 500, what="in step")
+    rig.step(500, what="in step")
     ctx.stream_reset_framecnt(2)
-    sts[2].set_n_frame(0)
-    step(ctx, sts, raw, 500, 400, what="stream 2 out of step")
+    rig.sts[2].set_n_frame(0)
+    rig.step(400, what="stream 2 out of step")
     assert ctx.n_frame(2) == 400 and ctx.n_frame(0) == 900
-    step(ctx, sts, raw, 900, 300, first=2, count=3, what="streams 2-4")
-    step(ctx, sts, raw, 1200, 300, first=0, count=2, what="streams 0-1")
-    check_meters(ctx, sts, "slabs")
-    ctx.close()
+    rig.step(300, first=2, count=3, what="streams 2-4")
+    rig.t[0] = rig.t[1] = 1200
+    rig.step(300, first=0, count=2, what="streams 0-1")
+    rig.check("slabs")
+    rig.close()
 
 
 def test_per_stream_edits(icw, oracle):
@@ -147,10 +99,9 @@ def test_per_stream_edits(icw, oracle):
     cfg = graph.default_config(48000)
     full = [graph.master(inputs=("C",)), graph.mix(inputs=("in", "B"), out="C"), graph.shift(inputs=("in",), out="B")]
     cut = full[:2]                                   # the Mix then reads slot B from the bus
-    raw = synth.batch_pcm(2, 1600, 48000)
-    ctx = icw.Context(cfg, full, 2)
-    sts = oracles(oracle, cfg, [full, full])
-    step(ctx, sts, raw, 0, 400, what="both full")
+    rig = StreamRig(icw, oracle, cfg, 1600, S=2, nodes=full)
+    ctx, sts = rig.ctx, rig.sts
+    rig.step(400, what="both full")
     B = graph.slot("B")
     blob = [abi.StateBlob.from_buffer_copy(ctx.get_state(s)) for s in range(2)]
     assert all(any(blob[s].bus[B][k] != 0.0 for k in range(4)) for s in range(2))
@@ -161,7 +112,7 @@ def test_per_stream_edits(icw, oracle):
     after = [abi.StateBlob.from_buffer_copy(ctx.get_state(s)) for s in range(2)]
     assert [after[1].bus[B][k] for k in range(4)] == [0.0] * 4
     assert bytes(after[0].bus) == bytes(blob[0].bus)
-    step(ctx, sts, raw, 400, 400, what="stream 1 cut")
+    rig.step(400, what="stream 1 cut")
     # slot C (written every frame, kept on the bus) of stream 0 only
     Cs = graph.slot("C")
     ctx.clear_stream_bus_slot(Cs, 0, 1)
@@ -169,13 +120,13 @@ def test_per_stream_edits(icw, oracle):
     after = [abi.StateBlob.from_buffer_copy(ctx.get_state(s)) for s in range(2)]
     assert [after[0].bus[Cs][k] for k in range(4)] == [0.0] * 4
     assert any(after[1].bus[Cs][k] != 0.0 for k in range(4))
-    step(ctx, sts, raw, 800, 400, what="slot C of stream 0 cleared")
+    rig.step(400, what="slot C of stream 0 cleared")
     # bypass on stream 0 only
     assert ctx.set_stream_graph(full, 0, 1, bypass_list=1)
     assert sts[0].set_graph(full, 1)
-    step(ctx, sts, raw, 1200, 400, what="stream 0 bypassed")
-    check_meters(ctx, sts, "edits")
-    ctx.close()
+    rig.step(400, what="stream 0 bypassed")
+    rig.check("edits")
+    rig.close()
 
 
 def test_collapse_and_primitives(icw, oracle):
@@ -183,11 +134,10 @@ def test_collapse_and_primitives(icw, oracle):
     collapses the table, each stream's clears matched against its own old list; then they work again"""
     cfg = graph.default_config(48000)
     lists = [graph.graph_shift_master(), graph.graph_pm_shift_mix()]
-    raw = synth.batch_pcm(2, 1500, 48000)
-    ctx = mixed_context(icw, cfg, lists)
-    sts = oracles(oracle, cfg, lists)
+    rig = mixed(icw, oracle, cfg, lists, 1500)
+    ctx, sts = rig.ctx, rig.sts
     assert ctx.stream_graph_count() == 2
-    step(ctx, sts, raw, 0, 300, what="mixed")
+    rig.step(300, what="mixed")
     lib = ctx._lib
     extra = graph.mix(inputs=("in",), out="Q")
     assert lib.icw_graph_del_last(ctx.h) == abi.EUNSUPPORTED
@@ -195,37 +145,37 @@ def test_collapse_and_primitives(icw, oracle):
     assert lib.icw_graph_add_last(ctx.h, C.byref(extra)) == abi.EUNSUPPORTED
     assert lib.icw_graph_set_output_plug(ctx.h, 1, 5) == abi.EUNSUPPORTED
     assert ctx.stream_graph_count() == 2
-    step(ctx, sts, raw, 300, 300, what="after the refused primitives")
+    rig.step(300, what="after the refused primitives")
     new = [graph.master(inputs=("A",)), graph.shift(inputs=("in",), out="A", fr=5.0), graph.mix(inputs=("in",), out="D")]
     assert ctx.set_graph(new)
     for st in sts:
         assert st.set_graph(new)
     assert ctx.stream_graph_count() == 1
-    step(ctx, sts, raw, 600, 300, what="collapsed")
+    rig.step(300, what="collapsed")
     ctx.graph_del_last()
     for st in sts:
         st.del_lastdsp()
-    step(ctx, sts, raw, 900, 300, what="del_last after the collapse")
+    rig.step(300, what="del_last after the collapse")
     assert ctx.graph_add_last(extra)
     for st in sts:
         assert st.add_lastdsp(extra)
-    step(ctx, sts, raw, 1200, 300, what="add_last after the collapse")
-    check_meters(ctx, sts, "collapse")
-    ctx.close()
+    rig.step(300, what="add_last after the collapse")
+    rig.check("collapse")
+    rig.close()
 
 
 def test_same_list_for_all_is_one_entry(icw, oracle):
     """every stream given one list through the new call: one entry, a one-list context again"""
     cfg = graph.default_config(48000)
-    ctx = mixed_context(icw, cfg, [graph.graph_shift_master(), graph.graph_master_only(), graph.graph_pm_shift_mix()])
+    rig = mixed(icw, oracle, cfg, [graph.graph_shift_master(), graph.graph_master_only(), graph.graph_pm_shift_mix()], 500)
+    ctx = rig.ctx
     assert ctx.stream_graph_count() == 3
     assert ctx.set_stream_graph(graph.graph_pm_shift_mix())
     assert ctx.stream_graph_count() == 1
-    sts = oracles(oracle, cfg, [graph.graph_pm_shift_mix()] * 3)
-    raw = synth.batch_pcm(3, 500, 48000)
-    step(ctx, sts, raw, 0, 500, what="one entry")
+    rig.sts = [oracle.Stream(cfg, graph.graph_pm_shift_mix()) for _ in range(3)]
+    rig.step(500, what="one entry")
     ctx.graph_del_last()                              # the primitives work on it
-    ctx.close()
+    rig.close()
 
 
 MATRIX = {
@@ -249,46 +199,36 @@ def test_render_and_input_matrix(icw, oracle, case):
         cfg.render.render_type, cfg.render.nshape_type = render
     lists = [graph.graph_shift_master(), graph.graph_pm_shift_mix()]
     n = 700
-    raw = synth.batch_pcm(2, n, 48000, channels=cfg.in_channels, fmt=cfg.in_format)
-    ctx = mixed_context(icw, cfg, lists)
-    assert ctx.stream_graph_count() == 2
-    sts = oracles(oracle, cfg, lists)
-    step(ctx, sts, raw, 0, 450, what=case)
-    step(ctx, sts, raw, 450, n - 450, what=case)
-    check_meters(ctx, sts, case)
-    if cfg.fp_check:
-        for s, st in enumerate(sts):
-            assert np.array_equal(ctx.fp_census(s), st.fp_census()), (case, s)
-    ctx.close()
+    rig = mixed(icw, oracle, cfg, lists, n)
+    assert rig.ctx.stream_graph_count() == 2
+    rig.step(450, what=case)
+    rig.step(n - 450, what=case)
+    rig.check(case, census=bool(cfg.fp_check))
+    rig.close()
 
 
 def test_one_stream_context(icw, oracle):
     """576-frame blocks of a one-stream context (K5): icw_set_stream_graph(0, 1) between blocks is the
     oracle's set_graph"""
     cfg = graph.default_config(48000)
-    ctx = icw.Context(cfg, graph.graph_shift_master(), 1)
-    sts = [oracle.Stream(cfg, graph.graph_shift_master())]
-    raw = synth.batch_pcm(1, 4 * 576, 48000)
-    step(ctx, sts, raw, 0, 576, what="k5")
+    rig = StreamRig(icw, oracle, cfg, 4 * 576, S=1)
+    rig.step(576, what="k5")
     for k, nl in enumerate((graph.graph_pm_shift_mix(), graph.graph_master_only(), shift_list(7.25)), 1):
-        assert ctx.set_stream_graph(nl, 0, 1)
-        assert sts[0].set_graph(nl)
-        assert ctx.stream_graph_count() == 1
-        step(ctx, sts, raw, k * 576, 576, what=f"k5 block {k}")
-    check_meters(ctx, sts, "k5")
-    ctx.close()
+        rig.set_graph(0, nl)
+        assert rig.ctx.stream_graph_count() == 1
+        rig.step(576, what=f"k5 block {k}")
+    rig.check("k5")
+    rig.close()
 
 
 def test_one_stream_calls_of_a_mixed_context(icw, oracle):
     """a call over one stream of a mixed context runs that stream's own program (K5 for 576 frames)"""
     cfg = graph.default_config(48000)
     lists = [graph.graph_shift_master(), graph.graph_pm_shift_mix(), graph.graph_master_only()]
-    ctx = mixed_context(icw, cfg, lists)
-    sts = oracles(oracle, cfg, lists)
-    raw = synth.batch_pcm(3, 576, 48000)
+    rig = mixed(icw, oracle, cfg, lists, 576)
     for s in (1, 2, 0):
-        step(ctx, sts, raw, 0, 576, first=s, count=1, what="one stream of three")
-    ctx.close()
+        rig.step(576, first=s, count=1, what="one stream of three")
+    rig.close()
 
 
 def test_multi_block(icw, oracle, monkeypatch):
@@ -296,27 +236,21 @@ def test_multi_block(icw, oracle, monkeypatch):
     monkeypatch.setenv("ICW_BLOCK", "256")
     cfg = graph.default_config(48000)
     lists = [shift_list(2.0), graph.graph_pm_shift_mix()]
-    ctx = mixed_context(icw, cfg, lists)
-    sts = oracles(oracle, cfg, lists)
-    raw = synth.batch_pcm(2, 900, 48000)
-    step(ctx, sts, raw, 0, 900, what="four blocks")
-    check_meters(ctx, sts, "four blocks")
-    ctx.close()
+    rig = mixed(icw, oracle, cfg, lists, 900)
+    rig.step(900, what="four blocks")
+    rig.check("four blocks")
+    rig.close()
 
 
 def test_refusals_change_nothing(icw, oracle):
     cfg = graph.default_config(48000)
     lists = [graph.graph_shift_master(), graph.graph_pm_shift_mix()]
-    raw = synth.batch_pcm(2, 1800, 48000)
-    ctx = mixed_context(icw, cfg, lists)
-    sts = oracles(oracle, cfg, lists)
-    lib, t = ctx._lib, 0
+    rig = mixed(icw, oracle, cfg, lists, 1800)
+    ctx, lib = rig.ctx, rig.ctx._lib
 
     def still_the_same(what):
-        nonlocal t
         assert ctx.stream_graph_count() == 2
-        step(ctx, sts, raw, t, 300, what=what)
-        t += 300
+        rig.step(300, what=what)
 
     def raw_call(nodes, first, count):
         acc = C.c_int(-1)
@@ -344,26 +278,25 @@ def test_refusals_change_nothing(icw, oracle):
     assert raw_call([graph.master(), graph.master()], 1, 1) == (abi.EGRAPH, 0)
     assert ctx.set_stream_graph([graph.shift()], 0, 1) is False
     still_the_same("rejected lists")
-    ctx.close()
+    rig.close()
 
     # the FIR converter on: per-stream lists are refused, the context-wide list goes on
-    ctx = icw.Context(cfg, graph.graph_shift_master(), 2)
+    rig = StreamRig(icw, oracle, cfg, 300, S=2)
+    ctx = rig.ctx
     ctx.set_fir_hilbert(64, 8.0)
     arr = graph.node_array(graph.graph_master_only())
     assert ctx._lib.icw_set_stream_graph(ctx.h, 0, 1, arr, 1, 0, None) == abi.EUNSUPPORTED
     assert ctx.stream_graph_count() == 1
-    sts = oracles(oracle, cfg, [graph.graph_shift_master()] * 2)
-    for st in sts:
+    for st in rig.sts:
         st.set_fir(64, 8.0)
-    step(ctx, sts, raw, 0, 300, what="FIR converter on")
-    ctx.close()
+    rig.step(300, what="FIR converter on")
+    rig.close()
 
     # a bus-form list in force: per-stream lists are refused
-    ctx = icw.Context(cfg, graph.graph_leaky_feedback(), 2)
-    assert ctx._lib.icw_set_stream_graph(ctx.h, 0, 1, arr, 1, 0, None) == abi.EUNSUPPORTED
-    sts = oracles(oracle, cfg, [graph.graph_leaky_feedback()] * 2)
-    step(ctx, sts, raw, 0, 300, what="bus-form list in force")
-    ctx.close()
+    rig = StreamRig(icw, oracle, cfg, 300, S=2, nodes=graph.graph_leaky_feedback())
+    assert rig.ctx._lib.icw_set_stream_graph(rig.ctx.h, 0, 1, arr, 1, 0, None) == abi.EUNSUPPORTED
+    rig.step(300, what="bus-form list in force")
+    rig.close()
 
 
 def test_state_round_trip(icw, oracle):
@@ -372,17 +305,15 @@ def test_state_round_trip(icw, oracle):
     cfg = graph.default_config(48000)
     cfg.render.render_type = abi.RENDER_TPDF
     lists = [graph.graph_shift_master(), graph.graph_pm_shift_mix(), graph.graph_master_only()]
-    raw = synth.batch_pcm(3, 1000, 48000)
-    ctx = mixed_context(icw, cfg, lists)
-    sts = oracles(oracle, cfg, lists)
-    step(ctx, sts, raw, 0, 600, what="before the checkpoint")
-    blob = ctx.get_state(1)
-    ctx.close()
+    rig = mixed(icw, oracle, cfg, lists, 1000)
+    rig.step(600, what="before the checkpoint")
+    blob = rig.ctx.get_state(1)
+    rig.close()
     # stream 1's state goes to stream 0 of a two-stream context that runs its list there
-    other = mixed_context(icw, cfg, [lists[1], lists[0]])
+    other = mixed(icw, oracle, cfg, [lists[1], lists[0]], 1000).ctx
     other.set_state(0, blob)
-    fsz = other.fsz
-    out, pre = other.process(np.ascontiguousarray(raw[1:2, 600 * fsz:1000 * fsz]), 400, first=0, count=1, want_pre=True)
-    ro, rp = sts[1].process(raw[1, 600 * fsz:1000 * fsz], 400, want_pre=True)
+    raw = rig.frames(1, 400)
+    out, pre = other.process(raw[None, :], 400, first=0, count=1, want_pre=True)
+    ro, rp = rig.sts[1].process(raw, 400, want_pre=True)
     assert np.array_equal(bits(pre[0]), bits(rp)) and np.array_equal(out[0], ro)
     other.close()

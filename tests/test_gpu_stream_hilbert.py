@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from in_cwave_amd import abi, graph, synth
+from tests.streamrig import StreamRig, bits, copy_cfg, entry
 
 pytestmark = pytest.mark.gpu
 
@@ -20,129 +21,9 @@ KR = (1, 1)                                             # Kahan + reject: what t
 CALLS = (1003, 7, 1003)
 
 
-def copy_cfg(cfg, **kw):
-    c = abi.Config.from_buffer_copy(cfg)
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
 def by_runs(runs):
     """[(streams, (type, kahan, reject)), ...] -> one setting per stream"""
     return [e for n, e in runs for _ in range(n)]
-
-
-class Rig:
-    """a context whose stream s has the converter settings[s] = (type, kahan, reject) (None: the context's own),
-    with its oracles and every stream's own test signal; inputs[s] = (rate, fmt, channels), lists[s] and
-    renders[s] = (RenderCfg, need24bits) where those differ too; silent: streams fed digital silence"""
-
-    def __init__(self, icw, oracle, cfg, settings, n_total, lists=None, inputs=None, renders=None, silent=()):
-        S = len(settings)
-        lists = lists or [graph.graph_shift_master()] * S
-        self.ctx = icw.Context(copy_cfg(cfg), lists[0], S)
-        self.sts = []
-        for s, e in enumerate(settings):
-            t, k, r = e if e is not None else (cfg.hilbert_type, cfg.iir_kahan, cfg.iir_subnorm_reject)
-            self.sts.append(oracle.Stream(copy_cfg(cfg, hilbert_type=t, iir_kahan=k, iir_subnorm_reject=r), lists[s]))
-        self.cur = [(cfg.hilbert_type, cfg.iir_kahan, cfg.iir_subnorm_reject)] * S
-        self.inputs = [(cfg.sample_rate, cfg.in_format, cfg.in_channels)] * S
-        for s in range(S):
-            if lists[s] is not lists[0]:
-                assert self.ctx.set_stream_graph(lists[s], s, 1)
-            if inputs:
-                self.ctx.set_stream_input(*inputs[s], first=s, count=1)
-                self.sts[s].set_input(*inputs[s])
-                self.inputs[s] = inputs[s]
-        self.raw = [synth.stream_pcm(s, n_total, rate, channels=ch, fmt=fmt) for s, (rate, fmt, ch) in enumerate(self.inputs)]
-        for s in silent:
-            self.raw[s] = np.zeros_like(self.raw[s])
-        self.osz = [2 * self.ctx.stream_render_size(s) for s in range(S)]
-        for s, rd in enumerate(renders or []):
-            self.ctx.set_stream_render(rd[0], rd[1], s, 1)
-            self.sts[s].set_render(rd[0])
-            self.sts[s].set_outbits(rd[1])
-            self.osz[s] = 6 if rd[1] else 4
-        # runs of equal settings go in one call of the setter each
-        s = 0
-        while s < S:
-            n = 1
-            while s + n < S and settings[s + n] == settings[s]:
-                n += 1
-            if settings[s] is not None:
-                self.ctx.set_stream_hilbert(*settings[s], first=s, count=n)
-                self.cur[s:s + n] = [settings[s]] * n
-            s += n
-        self.t = [0] * S
-
-    def set(self, s, e, count=1):
-        """the setter on the context, hq_rp_create / iir_rp_setcfg on the oracles"""
-        self.ctx.set_stream_hilbert(*e, first=s, count=count)
-        for i in range(s, s + count):
-            self.sts[i].set_hilbert_filter(e[0])
-            self.sts[i].set_hilbert_config(e[1], e[2])
-            self.cur[i] = e
-
-    def fsz(self, s):
-        return abi.FMT_BYTES[self.inputs[s][1]] * self.inputs[s][2]
-
-    def rows(self, n, first, count):
-        wide = max(self.fsz(first + i) for i in range(count))
-        rows = np.zeros((count, n * wide), np.uint8)
-        for i in range(count):
-            s = first + i
-            f = self.fsz(s)
-            rows[i, :n * f] = self.raw[s][self.t[s] * f:(self.t[s] + n) * f]
-        return rows
-
-    def step(self, n, first=0, count=None, device=False, what="", timing=False):
-        ctx, count = self.ctx, len(self.sts) - first if count is None else count
-        rows = self.rows(n, first, count)
-        stride = n * max(self.osz[first:first + count])
-        flags = abi.F_DEBUG_PRE | (abi.F_TIMING if timing else 0)
-        if device:
-            import torch
-            d_in = torch.from_numpy(rows).cuda()
-            d_out = torch.zeros((count, stride), dtype=torch.uint8, device="cuda")
-            d_pre = torch.zeros((count, n, 2), dtype=torch.float64, device="cuda")
-            torch.cuda.synchronize()
-            rc = ctx._lib.icw_process_streams(ctx.h, first, count, d_in.data_ptr(), rows.shape[1], d_out.data_ptr(), stride,
-                                              n, flags | abi.F_DEVICE_PTRS, d_pre.data_ptr(), None)
-            assert rc == abi.OK, (what, rc)
-            ctx.synchronize()
-            out, pre = d_out.cpu().numpy(), d_pre.cpu().numpy()
-        else:
-            out = np.zeros((count, stride), np.uint8)
-            pre = np.zeros((count, n, 2), np.float64)
-            rc = ctx._lib.icw_process_streams(ctx.h, first, count, rows.ctypes.data, rows.shape[1], out.ctypes.data, stride,
-                                              n, flags, pre.ctypes.data, None)
-            assert rc == abi.OK, (what, rc)
-        for i in range(count):
-            s = first + i
-            f = self.fsz(s)
-            ro, rp = self.sts[s].process(self.raw[s][self.t[s] * f:(self.t[s] + n) * f], n, want_pre=True)
-            bad = np.flatnonzero(bits(pre[i]) != bits(rp))
-            assert bad.size == 0, f"{what} stream {s} {self.cur[s]} from frame {self.t[s]}: {bad.size} pre-render doubles differ, first at {bad[:4]}"
-            assert ro.size == n * self.osz[s]
-            bad = np.flatnonzero(out[i, :ro.size] != ro)
-            assert bad.size == 0, f"{what} stream {s} {self.cur[s]} from frame {self.t[s]}: {bad.size} rendered bytes differ, first at {bad[:4]}"
-            self.t[s] += n
-        return out
-
-    def check(self, what=""):
-        for s, st in enumerate(self.sts):
-            m, r = self.ctx.meters(s), st.meters()
-            assert m["clips"] == r["clips"], (what, s, m, r)
-            assert bits(np.array(m["peak_db"])).tolist() == bits(np.array(r["peak_db"])).tolist(), (what, s, m, r)
-            assert m["desubnorm"] == r["desubnorm"], (what, s, m, r)
-            assert self.ctx.n_frame(s) == st.n_frame(), (what, s)
-
-    def close(self):
-        self.ctx.close()
 
 
 # runs of 3 / 1 / 5 / 2 streams, orders 15 / 20 / 18 / 19: none a multiple of the 2 streams a wave pair holds
@@ -153,7 +34,7 @@ def row_every_order(icw, oracle, device, what):
     cfg = graph.default_config(FS)
     # stream 1 is silent and shares its waves with stream 0: every sum is rejected, the speculative blocks
     # hand over to the exact ones
-    rig = Rig(icw, oracle, cfg, by_runs(ROW_RUNS), sum(CALLS), silent=(1,))
+    rig = StreamRig(icw, oracle, cfg, sum(CALLS), settings=by_runs(ROW_RUNS), silent=(1,))
     assert rig.ctx.stream_hilbert_count() == 4
     for n in CALLS:
         rig.step(n, device=device, what=what)
@@ -180,7 +61,7 @@ LANE_RUNS = [(33, (3, 0, 1)), (1, (5, 1, 0)), (31, (0, 1, 1)), (5, (4, 0, 0))]
 def test_lane_form(icw, oracle, monkeypatch):
     monkeypatch.setenv("ICW_K1_MODE", "plain")
     cfg = graph.default_config(FS)
-    rig = Rig(icw, oracle, cfg, by_runs(LANE_RUNS), sum(CALLS))
+    rig = StreamRig(icw, oracle, cfg, sum(CALLS), settings=by_runs(LANE_RUNS))
     assert rig.ctx.stream_hilbert_count() == 4
     for n in CALLS:
         rig.step(n, what="lane form")
@@ -192,7 +73,7 @@ def test_lane_form(icw, oracle, monkeypatch):
 def test_auto_takes_the_lane_form_without_kahan_and_reject(icw, oracle):
     """automatic mode, one entry of the call baseline: a batch this small would take the row form"""
     cfg = graph.default_config(FS)
-    rig = Rig(icw, oracle, cfg, by_runs([(2, (1,) + KR), (3, (4, 0, 1)), (1, (0,) + KR)]), 1400)
+    rig = StreamRig(icw, oracle, cfg, 1400, settings=by_runs([(2, (1,) + KR), (3, (4, 0, 1)), (1, (0,) + KR)]))
     rig.step(1003, what="auto, one baseline entry")
     assert rig.ctx.last_k1_kernel() == abi.K1_LANE
     rig.step(397, first=0, count=2, what="auto, a Kahan + reject run alone")
@@ -206,7 +87,7 @@ def test_mono_dedup(icw, oracle, monkeypatch, form):
     """6 mono streams in runs of 1 / 3 / 2: the left chains only, in both forms"""
     monkeypatch.setenv("ICW_K1_MODE", form)
     cfg = graph.default_config(FS, channels=1)
-    rig = Rig(icw, oracle, cfg, by_runs([(1, (4,) + KR), (3, (0,) + KR), (2, (2,) + KR)]), sum(CALLS))
+    rig = StreamRig(icw, oracle, cfg, sum(CALLS), settings=by_runs([(1, (4,) + KR), (3, (0,) + KR), (2, (2,) + KR)]))
     for n in CALLS:
         rig.step(n, what=f"mono, {form}")
         assert rig.ctx.last_k1_kernel() == (abi.K1_ROW if form == "row" else abi.K1_LANE)
@@ -220,7 +101,7 @@ def test_subset_and_one_stream_calls(icw, oracle, monkeypatch):
     monkeypatch.setenv("ICW_K1_MODE", "row")
     monkeypatch.setenv("ICW_STREAM1", "1")
     cfg = graph.default_config(FS)
-    rig = Rig(icw, oracle, cfg, by_runs(ROW_RUNS), 4000)
+    rig = StreamRig(icw, oracle, cfg, 4000, settings=by_runs(ROW_RUNS))
     rig.step(300, what="whole batch")
     rig.step(301, first=2, count=5, what="[2, 7) across three runs")
     inside = rig.step(700, first=5, count=3, timing=True, what="inside the run of five")
@@ -232,7 +113,7 @@ def test_subset_and_one_stream_calls(icw, oracle, monkeypatch):
     rig.close()
     # the same streams in one-setting contexts of their type: the same calls before, then the call
     for t, s, n, frames, (got, k1, launches) in ((2, 5, 3, 700, (inside, k1_in, l_in)), (4, 3, 1, 576, (one, k1_one, l_one))):
-        ref = Rig(icw, oracle, copy_cfg(cfg, hilbert_type=t), [None] * 11, 4000)
+        ref = StreamRig(icw, oracle, copy_cfg(cfg, hilbert_type=t), 4000, settings=[None] * 11)
         assert ref.ctx.stream_hilbert_count() == 1
         ref.step(300, what="one-setting context")
         ref.step(301, first=2, count=5, what="one-setting context")
@@ -252,12 +133,12 @@ def test_count_one_is_todays_path(icw, oracle, monkeypatch):
     e = (4, 0, 1)
     res = []
     for how in ("stream", "context", "stream by stream"):
-        rig = Rig(icw, oracle, cfg, [None] * 4, 1500)
+        rig = StreamRig(icw, oracle, cfg, 1500, settings=[None] * 4)
         if how == "stream":
-            rig.set(0, e, count=4)
+            rig.set_hilbert(0, e, count=4)
         elif how == "stream by stream":
             for s in (2, 0, 3, 1):
-                rig.set(s, e)
+                rig.set_hilbert(s, e)
         else:
             rig.ctx.set_hilbert_filter(e[0])
             rig.ctx.set_hilbert_config(e[1], e[2])
@@ -282,7 +163,7 @@ def test_context_wide_setters_on_a_mixed_context(icw, oracle):
     counters restart"""
     cfg = graph.default_config(FS)
     settings = by_runs([(2, (0,) + KR), (2, (4, 0, 1)), (1, (2, 1, 0)), (1, (4,) + KR)])
-    rig = Rig(icw, oracle, cfg, settings, 3000, silent=(3,))
+    rig = StreamRig(icw, oracle, cfg, 3000, settings=settings, silent=(3,))
     rig.step(500, what="mixed")
     rig.ctx.set_hilbert_filter(4)
     for s, st in enumerate(rig.sts):
@@ -292,7 +173,7 @@ def test_context_wide_setters_on_a_mixed_context(icw, oracle):
     rig.step(611, what="after icw_set_hilbert_filter")
     rig.check("after icw_set_hilbert_filter")
     assert rig.sts[3].meters()["desubnorm"] > 0         # a kept stream's counter went on
-    rig.set(0, (1,) + KR)
+    rig.set_hilbert(0, (1,) + KR)
     rig.ctx.set_hilbert_config(1, 1)
     for s, st in enumerate(rig.sts):
         st.set_hilbert_config(1, 1)
@@ -314,29 +195,23 @@ def test_edits_between_calls(icw, oracle):
     """a range changes type mid-sequence: only those streams restart; a configuration-only change keeps the
     rings and restarts the counters; an unchanged setting restarts the counters all the same"""
     cfg = graph.default_config(FS)
-    rig = Rig(icw, oracle, cfg, [None] * 5, 3000, silent=(2,))
+    rig = StreamRig(icw, oracle, cfg, 3000, settings=[None] * 5, silent=(2,))
     rig.step(700, what="one setting")
-    rig.set(1, (2,) + KR, count=2)
+    rig.set_hilbert(1, (2,) + KR, count=2)
     assert rig.ctx.stream_hilbert_count() == 2
     rig.step(650, what="streams 1, 2 at type 2")
     rig.check("after the type change")
-    rig.set(2, (2, 0, 1), count=2)                    # stream 2 keeps its rings, stream 3 restarts
+    rig.set_hilbert(2, (2, 0, 1), count=2)                    # stream 2 keeps its rings, stream 3 restarts
     assert rig.ctx.stream_hilbert_count() == 3
     rig.step(333, what="configuration change")
-    rig.set(2, (2, 0, 1))                             # unchanged: the counters restart
+    rig.set_hilbert(2, (2, 0, 1))                             # unchanged: the counters restart
     rig.step(500, what="the same setting again")
     rig.check("after the configuration change")
-    rig.set(1, (cfg.hilbert_type,) + KR, count=3)
+    rig.set_hilbert(1, (cfg.hilbert_type,) + KR, count=3)
     assert rig.ctx.stream_hilbert_count() == 1
     rig.step(200, what="one setting again")
     rig.check("edits")
     rig.close()
-
-
-def entry(rtype=abi.RENDER_ROUND, ns=abi.NSHAPE_FLAT, b24=False):
-    r = abi.RenderCfg()
-    r.dth_bits, r.quantz_type, r.render_type, r.nshape_type, r.sign_bits16, r.sign_bits24 = 1.0, abi.QUANTZ_MID_TREAD, rtype, ns, 16, 24
-    return r, bool(b24)
 
 
 def test_with_per_stream_lists_inputs_and_renders(icw, oracle):
@@ -349,7 +224,7 @@ def test_with_per_stream_lists_inputs_and_renders(icw, oracle):
     r16, r24s = entry(), entry(abi.RENDER_TPDF, abi.NSHAPE_MEW44, True)
     renders = [r16, r24s, r24s, r16]
     settings = [(0,) + KR, (4, 0, 1), (4, 0, 1), (2, 1, 0)]
-    rig = Rig(icw, oracle, cfg, settings, 1200, lists=lists, inputs=inputs, renders=renders)
+    rig = StreamRig(icw, oracle, cfg, 1200, settings=settings, lists=lists, inputs=inputs, renders=renders)
     assert (rig.ctx.stream_hilbert_count(), rig.ctx.stream_graph_count(), rig.ctx.stream_input_count(),
             rig.ctx.stream_render_count()) == (3, 2, 4, 2)
     rig.step(700, what="combined")
@@ -362,11 +237,11 @@ def test_state_blob_round_trip(icw, oracle):
     """a type-4 stream's blob from a mixed context into another context's stream set to the same entry; the
     blob records the stream's own order, and a stream of another order refuses it"""
     cfg = graph.default_config(FS)
-    a = Rig(icw, oracle, cfg, by_runs([(2, (0,) + KR), (1, (4,) + KR), (1, (2,) + KR)]), 2000)
+    a = StreamRig(icw, oracle, cfg, 2000, settings=by_runs([(2, (0,) + KR), (1, (4,) + KR), (1, (2,) + KR)]))
     a.step(700, what="source")
     blob = a.ctx.get_state(2)
     assert [abi.StateBlob.from_buffer_copy(a.ctx.get_state(s)).nord for s in range(4)] == [15, 15, 20, 18]
-    b = Rig(icw, oracle, cfg, [None, (4,) + KR, (1, 0, 1)], 2000)
+    b = StreamRig(icw, oracle, cfg, 2000, settings=[None, (4,) + KR, (1, 0, 1)])
     buf = (C.c_uint8 * len(blob)).from_buffer_copy(blob)
     for s in (0, 2):
         assert b.ctx._lib.icw_set_state(b.ctx.h, s, buf, len(blob)) == abi.EINVAL
@@ -385,7 +260,7 @@ def test_state_blob_round_trip(icw, oracle):
 
 def test_refusals_change_nothing(icw, oracle):
     cfg = graph.default_config(FS)
-    rig = Rig(icw, oracle, cfg, [(0,) + KR, (4, 0, 1), (2, 1, 0)], 6000)
+    rig = StreamRig(icw, oracle, cfg, 6000, settings=[(0,) + KR, (4, 0, 1), (2, 1, 0)])
     ctx, lib = rig.ctx, rig.ctx._lib
 
     def still_the_same(what):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from in_cwave_amd import abi, graph, synth
+from tests.streamrig import StreamRig, bits, copy_cfg, shift_list
 
 pytestmark = pytest.mark.gpu
 
@@ -14,100 +15,6 @@ FORMATS = (abi.FMT_U8, abi.FMT_I16, abi.FMT_I24, abi.FMT_I32, abi.FMT_F32)
 RATES = (8000, 44100, 48000, 96000, 192000)
 # five formats x mono / stereo, the rates dealt so that neighbours differ and every rate is used twice
 INPUTS10 = [(RATES[(2 * k + ch) % 5], fmt, ch + 1) for k, fmt in enumerate(FORMATS) for ch in range(2)]
-
-
-def copy_cfg(cfg, **kw):
-    c = abi.Config.from_buffer_copy(cfg)
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-class Rig:
-    """a context whose stream s has inputs[s] = (rate, fmt, channels) and runs lists[s], with its oracles
-    and every stream's own test signal"""
-
-    def __init__(self, icw, oracle, cfg, inputs, lists, n_total, per_stream_lists=False):
-        S = len(inputs)
-        self.ctx = icw.Context(copy_cfg(cfg), lists[0], S)
-        self.sts = []
-        for s, (rate, fmt, ch) in enumerate(inputs):
-            if per_stream_lists:
-                assert self.ctx.set_stream_graph(lists[s], s, 1, cfg.bypass_list)
-            st = oracle.Stream(copy_cfg(cfg), lists[s])
-            self.sts.append(st)
-        self.inputs = [None] * S
-        for s, (rate, fmt, ch) in enumerate(inputs):
-            self.set_input(s, rate, fmt, ch)
-        self.raw = [synth.stream_pcm(s, n_total, rate, channels=ch, fmt=fmt) for s, (rate, fmt, ch) in enumerate(inputs)]
-        self.t = 0
-
-    def set_input(self, s, rate, fmt, ch):
-        self.ctx.set_stream_input(rate, fmt, ch, s, 1)
-        self.sts[s].set_input(rate, fmt, ch)
-        self.inputs[s] = (rate, fmt, ch)
-
-    def fsz(self, s):
-        return abi.FMT_BYTES[self.inputs[s][1]] * self.inputs[s][2]
-
-    def rows(self, n, first, count, t=None):
-        """the call's input: every stream's n frames from frame t at its own frame size, in rows of the widest"""
-        t = self.t if t is None else t
-        wide = max(self.fsz(first + i) for i in range(count))
-        rows = np.zeros((count, n * wide), np.uint8)
-        for i in range(count):
-            f = self.fsz(first + i)
-            rows[i, :n * f] = self.raw[first + i][t * f:(t + n) * f]
-        return rows
-
-    def step(self, n, first=0, count=None, device=False, what="", advance=True):
-        ctx, count = self.ctx, len(self.sts) - first if count is None else count
-        rows = self.rows(n, first, count)
-        if device:
-            import torch
-            osz = 2 * ctx.render_size
-            d_in = torch.from_numpy(rows).cuda()
-            d_out = torch.zeros((count, n * osz), dtype=torch.uint8, device="cuda")
-            d_pre = torch.zeros((count, n, 2), dtype=torch.float64, device="cuda")
-            torch.cuda.synchronize()
-            rc = ctx._lib.icw_process_streams(ctx.h, first, count, d_in.data_ptr(), rows.shape[1], d_out.data_ptr(), n * osz,
-                                              n, abi.F_DEVICE_PTRS | abi.F_DEBUG_PRE, d_pre.data_ptr(), None)
-            assert rc == abi.OK, rc
-            ctx.synchronize()
-            out, pre = d_out.cpu().numpy(), d_pre.cpu().numpy()
-        else:
-            out, pre = ctx.process(rows, n, first=first, count=count, want_pre=True)
-        for i in range(count):
-            s = first + i
-            f = self.fsz(s)
-            ro, rp = self.sts[s].process(self.raw[s][self.t * f:(self.t + n) * f], n, want_pre=True)
-            bad = np.flatnonzero(bits(pre[i]) != bits(rp))
-            assert bad.size == 0, (f"{what} stream {s} {self.inputs[s]} from frame {self.t}: {bad.size} pre-render doubles "
-                                   f"differ, first at {bad[:4]}")
-            assert np.array_equal(out[i], ro), f"{what} stream {s} {self.inputs[s]} from frame {self.t}: rendered bytes differ"
-        if advance and first == 0 and count == len(self.sts):
-            self.t += n
-
-    def check(self, what="", census=False):
-        for s, st in enumerate(self.sts):
-            m, r = self.ctx.meters(s), st.meters()
-            assert m["clips"] == r["clips"], (what, s, m, r)
-            assert bits(np.array(m["peak_db"])).tolist() == bits(np.array(r["peak_db"])).tolist(), (what, s, m, r)
-            assert m["desubnorm"] == r["desubnorm"], (what, s, m, r)
-            assert self.ctx.n_frame(s) == st.n_frame(), (what, s)
-            if census:
-                assert np.array_equal(self.ctx.fp_census(s), st.fp_census()), (what, s)
-
-    def close(self):
-        self.ctx.close()
-
-
-def shift_list(fr):
-    return [graph.master(inputs=("A",)), graph.shift(inputs=("in",), out="A", fr=fr)]
 
 
 @pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
@@ -120,10 +27,10 @@ def test_matrix(icw, oracle, case, device):
     if case == "c4_unscaled":
         cfg.frmod_scaled = 0
         nodes = graph.graph_pm_shift_mix()
-    rig = Rig(icw, oracle, cfg, INPUTS10, [nodes] * 10, 2500 + 577 + 1)
+    rig = StreamRig(icw, oracle, cfg, 2500 + 577 + 1, inputs=INPUTS10, lists=[nodes] * 10)
     assert rig.ctx.stream_input_count() == 10
     for n in (2500, 577, 1):
-        rig.step(n, device=device, what=case)
+        rig.step(n, device=device, what=case, wrapper=not device)      # host: through lib.Context.process
     rig.check(case)
     rig.close()
 
@@ -134,14 +41,14 @@ def test_rotation_table_keyed_by_list_and_rate(icw, oracle):
     cfg = graph.default_config(48000)
     a, b = shift_list(2.0), shift_list(3.5)
     inputs = [(44100, abi.FMT_I16, 2)] * 2 + [(48000, abi.FMT_I16, 2)] * 4
-    rig = Rig(icw, oracle, cfg, inputs, [a, a, a, a, b, b], 1300, per_stream_lists=True)
+    rig = StreamRig(icw, oracle, cfg, 1300, inputs=inputs, lists=[a, a, a, a, b, b])
     assert rig.ctx.stream_input_count() == 2 and rig.ctx.stream_graph_count() == 2
     rig.step(1100, what="slabs")
     rig.step(200, what="slabs")
     # one list, two rates: the one-entry program table
     rig.check("slabs")
     rig.close()
-    rig = Rig(icw, oracle, cfg, inputs[:4], [a] * 4, 700)
+    rig = StreamRig(icw, oracle, cfg, 700, inputs=inputs[:4], lists=[a] * 4)
     assert rig.ctx.stream_input_count() == 2 and rig.ctx.stream_graph_count() == 1
     rig.step(700, what="one list, two rates")
     rig.check("one list, two rates")
@@ -152,7 +59,7 @@ def test_counter_wrap(icw, oracle):
     """two streams at different rates, each within 100 frames of its own rate x 1 000 wrap"""
     cfg = graph.default_config(48000)
     inputs = [(8000, abi.FMT_I16, 2), (44100, abi.FMT_F32, 1)]
-    rig = Rig(icw, oracle, cfg, inputs, [graph.graph_shift_master()] * 2, 300)
+    rig = StreamRig(icw, oracle, cfg, 300, inputs=inputs)
     for s, (rate, _, _) in enumerate(inputs):
         nf = rate * abi.HZ_SCALE - 60 - 17 * s
         blob = abi.StateBlob.from_buffer_copy(rig.ctx.get_state(s))
@@ -170,7 +77,7 @@ def test_fades_and_tail(icw, oracle):
     take each stream's own rate, and each track runs to the end of its own tail"""
     cfg = graph.default_config(48000)
     inputs = [(1500, abi.FMT_I16, 2), (2000, abi.FMT_I24, 1)]
-    rig = Rig(icw, oracle, cfg, inputs, [graph.graph_shift_master()] * 2, 1000)
+    rig = StreamRig(icw, oracle, cfg, 1000, inputs=inputs)
     totals = []
     for s, (rate, fmt, ch) in enumerate(inputs):
         rig.ctx.stream_open(s, 1000, 5, 5, 1)
@@ -181,7 +88,6 @@ def test_fades_and_tail(icw, oracle):
     blob = [abi.StateBlob.from_buffer_copy(rig.ctx.get_state(s)) for s in range(2)]
     assert [(b.n_fade_in, b.n_fade_out) for b in blob] == [(7, 7), (10, 10)]
     rig.step(1500, what="tracks")
-    rig.t = 1500
     rig.step(500, first=1, count=1, what="the longer tail")
     rig.check("fades")
     rig.close()
@@ -192,7 +98,7 @@ def test_mono_bookkeeping(icw, oracle):
     and one stream switched mono -> stereo -> mono between calls"""
     cfg = graph.default_config(48000)
     mono = [(44100, abi.FMT_I16, 1), (48000, abi.FMT_F32, 1), (96000, abi.FMT_I24, 1), (8000, abi.FMT_U8, 1)]
-    rig = Rig(icw, oracle, cfg, mono, [graph.graph_shift_master()] * 4, 2000)
+    rig = StreamRig(icw, oracle, cfg, 2000, inputs=mono)
     rig.step(600, what="all mono")
     rig.step(300, what="all mono")
     # stream 2 becomes stereo: its signal is regenerated for the new frame, from the same frame on
@@ -229,7 +135,7 @@ def test_other_paths(icw, oracle, case):
     inputs = [(44100, abi.FMT_I16, 2), (96000, abi.FMT_F32, 1), (44100, abi.FMT_I32, 2)]
     if case == "bus_form":
         assert icw.graph_form(cfg, nodes) == 1
-    rig = Rig(icw, oracle, cfg, inputs, [nodes] * 3, 1150)
+    rig = StreamRig(icw, oracle, cfg, 1150, inputs=inputs, nodes=nodes)
     assert rig.ctx.stream_input_count() == 3
     rig.step(700, what=case)
     rig.step(450, what=case)
@@ -270,7 +176,7 @@ def test_refusals_change_nothing(icw, oracle):
     cfg = graph.default_config(48000)
     nodes = graph.graph_shift_master()
     inputs = [(44100, abi.FMT_I16, 2), (96000, abi.FMT_F32, 1)]
-    rig = Rig(icw, oracle, cfg, inputs, [nodes] * 2, 3000)
+    rig = StreamRig(icw, oracle, cfg, 3000, inputs=inputs, nodes=nodes)
     ctx, lib = rig.ctx, rig.ctx._lib
 
     def still_the_same(what):
@@ -350,7 +256,7 @@ def test_list_edits_between_calls(icw, oracle):
     back, and the list primitives"""
     cfg = graph.default_config(48000)
     inputs = [(44100, abi.FMT_I16, 2), (96000, abi.FMT_F32, 1), (44100, abi.FMT_I16, 2), (96000, abi.FMT_F32, 1)]
-    rig = Rig(icw, oracle, cfg, inputs, [graph.graph_master_only()] * 4, 3000)
+    rig = StreamRig(icw, oracle, cfg, 3000, inputs=inputs, nodes=graph.graph_master_only())
     assert rig.ctx.stream_input_count() == 2 and rig.ctx.stream_graph_count() == 1
     rig.step(300, what="master only")
     no_chain = [graph.master(inputs=("A", "B")), graph.shift(inputs=("in",), out="A", fr=3.0), graph.mix(inputs=("in",), out="B")]

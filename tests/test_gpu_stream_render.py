@@ -9,17 +9,11 @@ import numpy as np
 import pytest
 
 from in_cwave_amd import abi, graph, synth
+from tests.streamrig import NS_FIR20, StreamRig, bits, copy_cfg, entry
 
 pytestmark = pytest.mark.gpu
 
 FS = 48000
-NS_FIR20 = 6          # a canned 20-tap FIR shaper (sound_render.c: icw_ns_n[6] == 20)
-
-
-def entry(rtype=abi.RENDER_ROUND, ns=abi.NSHAPE_FLAT, b24=False, quantz=abi.QUANTZ_MID_TREAD, dth=1.0, sb16=16, sb24=24):
-    r = abi.RenderCfg()
-    r.dth_bits, r.quantz_type, r.render_type, r.nshape_type, r.sign_bits16, r.sign_bits24 = dth, quantz, rtype, ns, sb16, sb24
-    return r, bool(b24)
 
 
 R16_ROUND = entry()
@@ -33,123 +27,21 @@ ENTRIES7 = [R16_ROUND, R24_TPDF_MEW, R16_TPDF, R16_TPDF, R24_ROUND, R16_GAUSS_FI
 SERIAL7 = [False, True, False, False, False, True, False]
 
 
-def copy_cfg(cfg, **kw):
-    c = abi.Config.from_buffer_copy(cfg)
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
 def loud_list(fr=2.0):
     """Shift + Master, the Master loud enough that the -12 dBFS test tones clip"""
     return [graph.master(inputs=("A",), gain=3.0), graph.shift(inputs=("in",), out="A", fr=fr)]
 
 
-class Rig:
-    """a context whose stream s renders with entries[s] (None: the context's own), with its oracles and every
-    stream's own test signal; inputs[s] = (rate, fmt, channels) and lists[s] where those differ too"""
-
-    def __init__(self, icw, oracle, cfg, entries, n_total, lists=None, inputs=None, cwave=False):
-        S = len(entries)
-        lists = lists or [loud_list()] * S
-        self.ctx = icw.Context(copy_cfg(cfg), lists[0], S)
-        self.sts = [oracle.Stream(copy_cfg(cfg), lists[s]) for s in range(S)]
-        self.inputs = [(cfg.sample_rate, cfg.in_format, cfg.in_channels)] * S
-        if cwave:
-            self.ctx.enable_stream_cwave()
-        for s in range(S):
-            if lists[s] is not lists[0]:
-                assert self.ctx.set_stream_graph(lists[s], s, 1)
-            if inputs:
-                self.ctx.set_stream_input(*inputs[s], first=s, count=1)
-                self.sts[s].set_input(*inputs[s])
-                self.inputs[s] = inputs[s]
-        gen = synth.stream_cwave if cwave else synth.stream_pcm
-        self.raw = [gen(s, n_total, rate, channels=ch, fmt=fmt) for s, (rate, fmt, ch) in enumerate(self.inputs)]
-        self.osz = [2 * self.ctx.stream_render_size(s) for s in range(S)]
-        for s, e in enumerate(entries):
-            if e is not None:
-                self.set(s, e)
-        self.t = [0] * S
-
-    def set(self, s, e, count=1):
-        r, b24 = e
-        self.ctx.set_stream_render(r, b24, s, count)
-        for i in range(s, s + count):
-            self.sts[i].set_render(r)
-            self.sts[i].set_outbits(b24)
-            self.osz[i] = 6 if b24 else 4
-            assert self.ctx.stream_render_size(i) == (3 if b24 else 2)
-
-    def fsz(self, s):
-        return abi.FMT_BYTES[self.inputs[s][1]] * self.inputs[s][2]
-
-    def rows(self, n, first, count):
-        wide = max(self.fsz(first + i) for i in range(count))
-        rows = np.zeros((count, n * wide), np.uint8)
-        for i in range(count):
-            s = first + i
-            f = self.fsz(s)
-            rows[i, :n * f] = self.raw[s][self.t[s] * f:(self.t[s] + n) * f]
-        return rows
-
-    def step(self, n, first=0, count=None, device=False, what="", timing=False, pad=1):
-        """one call over streams [first, first + count), rows of the widest frame plus `pad` bytes (an odd
-        out_stride), every stream checked against its oracle at its own frame size"""
-        ctx, count = self.ctx, len(self.sts) - first if count is None else count
-        rows = self.rows(n, first, count)
-        stride = n * max(self.osz[first:first + count]) + pad
-        flags = abi.F_DEBUG_PRE | (abi.F_TIMING if timing else 0)
-        if device:
-            import torch
-            d_in = torch.from_numpy(rows).cuda()
-            d_out = torch.zeros((count, stride), dtype=torch.uint8, device="cuda")
-            d_pre = torch.zeros((count, n, 2), dtype=torch.float64, device="cuda")
-            torch.cuda.synchronize()
-            rc = ctx._lib.icw_process_streams(ctx.h, first, count, d_in.data_ptr(), rows.shape[1], d_out.data_ptr(), stride,
-                                              n, flags | abi.F_DEVICE_PTRS, d_pre.data_ptr(), None)
-            assert rc == abi.OK, (what, rc)
-            ctx.synchronize()
-            out, pre = d_out.cpu().numpy(), d_pre.cpu().numpy()
-        else:
-            out = np.zeros((count, stride), np.uint8)
-            pre = np.zeros((count, n, 2), np.float64)
-            rc = ctx._lib.icw_process_streams(ctx.h, first, count, rows.ctypes.data, rows.shape[1], out.ctypes.data, stride,
-                                              n, flags, pre.ctypes.data, None)
-            assert rc == abi.OK, (what, rc)
-        for i in range(count):
-            s = first + i
-            f = self.fsz(s)
-            ro, rp = self.sts[s].process(self.raw[s][self.t[s] * f:(self.t[s] + n) * f], n, want_pre=True)
-            bad = np.flatnonzero(bits(pre[i]) != bits(rp))
-            assert bad.size == 0, f"{what} stream {s} from frame {self.t[s]}: {bad.size} pre-render doubles differ, first at {bad[:4]}"
-            assert ro.size == n * self.osz[s]
-            bad = np.flatnonzero(out[i, :ro.size] != ro)
-            assert bad.size == 0, f"{what} stream {s} from frame {self.t[s]}: {bad.size} rendered bytes differ, first at {bad[:4]}"
-            if not device:
-                assert not out[i, ro.size:].any(), f"{what} stream {s}: bytes written past its frames"
-            self.t[s] += n
-        return out
-
-    def check(self, what=""):
-        for s, st in enumerate(self.sts):
-            m, r = self.ctx.meters(s), st.meters()
-            assert m["clips"] == r["clips"], (what, s, m, r)
-            assert bits(np.array(m["peak_db"])).tolist() == bits(np.array(r["peak_db"])).tolist(), (what, s, m, r)
-            assert m["desubnorm"] == r["desubnorm"], (what, s, m, r)
-            assert self.ctx.n_frame(s) == st.n_frame(), (what, s)
-
-    def close(self):
-        self.ctx.close()
+def render_rig(icw, oracle, cfg, entries, n_total, lists=None, **kw):
+    """a context whose stream s renders with entries[s] (None: the context's own) and runs the loud list, or
+    lists[s]; a call's output rows get one byte more than the widest frames need (an odd out_stride) unless
+    the call says pad=0"""
+    return StreamRig(icw, oracle, cfg, n_total, renders=entries, lists=lists or [loud_list()] * len(entries), pad=1, **kw)
 
 
 def matrix(icw, oracle, device, what):
     cfg = graph.default_config(FS)
-    rig = Rig(icw, oracle, cfg, ENTRIES7, 577 + 2049 + 20)
+    rig = render_rig(icw, oracle, cfg, ENTRIES7, 577 + 2049 + 20)
     assert rig.ctx.stream_render_count() == 6
     assert rig.ctx.render_size == 3 and [rig.ctx.stream_render_size(s) for s in range(7)] == [2, 3, 2, 2, 3, 2, 3]
     for n in (577, 2049, 20):
@@ -190,7 +82,7 @@ def test_subset_and_one_stream_calls(icw, oracle, monkeypatch):
     monkeypatch.setenv("ICW_K1_MODE", "row")
     monkeypatch.setenv("ICW_STREAM1", "1")
     cfg = graph.default_config(FS)
-    rig = Rig(icw, oracle, cfg, ENTRIES7, 4000)
+    rig = render_rig(icw, oracle, cfg, ENTRIES7, 4000)
     rig.step(300, what="whole batch")
     rig.step(700, first=2, count=2, what="inside one run")
     rig.step(301, first=1, count=4, what="serial, a run of two, frame-parallel")
@@ -202,7 +94,7 @@ def test_subset_and_one_stream_calls(icw, oracle, monkeypatch):
     rig.check("subsets")
     rig.close()
     # the same stream in a one-render context: the same calls, then the one-stream call
-    one = Rig(icw, oracle, copy_cfg(cfg, need24bits=1, render=R24_ROUND[0]), [None] * 7, 4000)
+    one = render_rig(icw, oracle, copy_cfg(cfg, need24bits=1, render=R24_ROUND[0]), [None] * 7, 4000)
     assert one.ctx.stream_render_count() == 1
     one.t[4] = 300 + 301 + 259
     ref = one.sts[4]
@@ -223,13 +115,13 @@ def test_count_one_is_todays_path(icw, oracle, monkeypatch):
     cfg = graph.default_config(FS)
     res = []
     for how in ("stream", "context", "stream by stream"):
-        rig = Rig(icw, oracle, cfg, [None] * 4, 1500)
+        rig = render_rig(icw, oracle, cfg, [None] * 4, 1500)
         r, b24 = R24_TPDF_MEW
         if how == "stream":
-            rig.set(0, R24_TPDF_MEW, count=4)
+            rig.set_render(0, R24_TPDF_MEW, count=4)
         elif how == "stream by stream":
             for s in (2, 0, 3, 1):
-                rig.set(s, R24_TPDF_MEW)
+                rig.set_render(s, R24_TPDF_MEW)
         else:
             rig.ctx.set_render(r)
             rig.ctx.set_outbits(b24)
@@ -251,7 +143,7 @@ def test_context_wide_setters_on_a_mixed_context(icw, oracle):
     """icw_set_render on a mixed context gives every stream the new setting, keeps each stream's depth and
     restarts the shaping; icw_set_outbits gives every stream the new depth and keeps its setting"""
     cfg = graph.default_config(FS)
-    rig = Rig(icw, oracle, cfg, ENTRIES7, 3000)
+    rig = render_rig(icw, oracle, cfg, ENTRIES7, 3000)
     rig.step(500, what="mixed")
     r, _ = entry(abi.RENDER_RPDF, abi.NSHAPE_FW44, dth=0.75)
     rig.ctx.set_render(r)
@@ -259,8 +151,8 @@ def test_context_wide_setters_on_a_mixed_context(icw, oracle):
         st.set_render(r)
     assert rig.ctx.stream_render_count() == 2 and rig.ctx.render_size == 3
     rig.step(611, what="after icw_set_render")
-    rig.set(3, R16_TPDF)
-    rig.set(6, R24_STPDF_RISER)
+    rig.set_render(3, R16_TPDF)
+    rig.set_render(6, R24_STPDF_RISER)
     assert rig.ctx.stream_render_count() == 4
     rig.ctx.set_outbits(0)
     for s, st in enumerate(rig.sts):
@@ -282,20 +174,20 @@ def test_edits_between_calls(icw, oracle):
     ROUND + flat (the render state is created by the first edit): its shaping restarts, its MT19937 words go
     on, its peak folds against the old bound, and its neighbours carry on untouched"""
     cfg = graph.default_config(FS)
-    rig = Rig(icw, oracle, cfg, [None] * 3, 3000)
+    rig = render_rig(icw, oracle, cfg, [None] * 3, 3000)
     assert abi.StateBlob.from_buffer_copy(rig.ctx.get_state(1)).has_render == 0
     rig.step(700, what="ROUND")
-    rig.set(1, entry(abi.RENDER_TPDF, abi.NSHAPE_MEW44))
+    rig.set_render(1, entry(abi.RENDER_TPDF, abi.NSHAPE_MEW44))
     assert rig.ctx.stream_render_count() == 2
     assert abi.StateBlob.from_buffer_copy(rig.ctx.get_state(1)).has_render == 1
     rig.step(650, what="TPDF + MEW44")
     rig.check("after the first edit")
-    rig.set(1, entry(abi.RENDER_TPDF, abi.NSHAPE_MEW44))          # unchanged: the shaping restarts all the same
+    rig.set_render(1, entry(abi.RENDER_TPDF, abi.NSHAPE_MEW44))          # unchanged: the shaping restarts all the same
     rig.step(333, what="the same entry again")
-    rig.set(1, R24_ROUND)
+    rig.set_render(1, R24_ROUND)
     rig.step(500, what="24-bit ROUND")
     rig.check("after the second edit")
-    rig.set(1, (abi.RenderCfg.from_buffer_copy(bytes(cfg.render)), False))     # its neighbours' render
+    rig.set_render(1, (abi.RenderCfg.from_buffer_copy(bytes(cfg.render)), False))     # its neighbours' render
     assert rig.ctx.stream_render_count() == 1
     rig.step(200, what="one render again")
     rig.check("edits")
@@ -313,7 +205,7 @@ def test_with_per_stream_lists_and_inputs(icw, oracle, kind):
         inputs = [(44100, abi.FMT_CW_F64, 2), (96000, abi.FMT_CW_I16, 1), (48000, abi.FMT_CW_F32, 2), (48000, abi.FMT_CW_I16_F32, 2)]
     lists = [loud_list(fr) for fr in (2.0, -3.5, 7.25, 0.5)]
     entries = [R24_TPDF_MEW, R16_TPDF, R16_ROUND, R24_STPDF_RISER]
-    rig = Rig(icw, oracle, cfg, entries, 1200, lists=lists, inputs=inputs, cwave=kind == "cwave")
+    rig = render_rig(icw, oracle, cfg, entries, 1200, lists=lists, inputs=inputs, cwave=kind == "cwave")
     assert (rig.ctx.stream_render_count(), rig.ctx.stream_graph_count(), rig.ctx.stream_input_count()) == (4, 4, 4)
     rig.step(700, what=kind)
     rig.step(500, device=True, what=kind)
@@ -327,7 +219,7 @@ def test_forced_dither_rejects(icw, oracle, which):
     words temper to 0 and force the rejection (mt_jrnd.c:245-256), so K3f redoes that generator alone"""
     cfg = graph.default_config(FS)
     e = R24_TPDF_MEW if which == "serial" else R16_TPDF
-    rig = Rig(icw, oracle, cfg, [R16_ROUND, e, e, R24_ROUND], 3000)
+    rig = render_rig(icw, oracle, cfg, [R16_ROUND, e, e, R24_ROUND], 3000)
     rig.step(700, what="before")
     blob = abi.StateBlob.from_buffer_copy(rig.ctx.get_state(2))
     assert blob.has_render == 1
@@ -348,7 +240,7 @@ def test_forced_dither_rejects(icw, oracle, which):
 
 def test_refusals_change_nothing(icw, oracle):
     cfg = graph.default_config(FS)
-    rig = Rig(icw, oracle, cfg, [R16_TPDF, R24_TPDF_MEW, R16_ROUND], 6000)
+    rig = render_rig(icw, oracle, cfg, [R16_TPDF, R24_TPDF_MEW, R16_ROUND], 6000)
     ctx, lib = rig.ctx, rig.ctx._lib
     r, _ = R16_ROUND
 

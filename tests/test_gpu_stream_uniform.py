@@ -10,20 +10,13 @@ import numpy as np
 import pytest
 
 from in_cwave_amd import abi, graph, synth
+from tests.streamrig import NS_FIR20, entry
 
 pytestmark = pytest.mark.gpu
 
 S = 3
 N = 600
 FS = 48000
-NS_FIR20 = 6          # a canned 20-tap FIR shaper
-
-
-def render(rtype=abi.RENDER_ROUND, ns=abi.NSHAPE_FLAT, dth=1.0, sb16=16, sb24=24):
-    r = abi.RenderCfg()
-    r.dth_bits, r.quantz_type, r.render_type, r.nshape_type = dth, abi.QUANTZ_MID_TREAD, rtype, ns
-    r.sign_bits16, r.sign_bits24 = sb16, sb24
-    return r
 
 
 # Master loud enough that the -12 dBFS test tones clip; the Mix reads slot B, which the Shift writes
@@ -60,12 +53,12 @@ def ed_input(rate, fmt, ch):
 
 
 EDITS = [
-    ed_render(render(abi.RENDER_TPDF, abi.NSHAPE_MEW44), True),        # dither + shaping; 16 -> 24 moves hi
-    ed_render(render(abi.RENDER_TPDF, abi.NSHAPE_MEW44), False),       # the depth alone
-    ed_render(render(abi.RENDER_GAUSS, NS_FIR20, dth=1.5, sb16=14), False),   # hi moves at one depth
+    ed_render(*entry(abi.RENDER_TPDF, abi.NSHAPE_MEW44, True)),       # dither + shaping; 16 -> 24 moves hi
+    ed_render(*entry(abi.RENDER_TPDF, abi.NSHAPE_MEW44)),             # the depth alone
+    ed_render(*entry(abi.RENDER_GAUSS, NS_FIR20, dth=1.5, sb16=14)),  # hi moves at one depth
     ed_hilbert(3, 1, 1),                                               # the type: rings restart
     ed_hilbert(3, 0, 1),                                               # the summation alone: rings stay
-    ed_render(render(), False),                                        # back to ROUND + flat
+    ed_render(*entry()),                                              # back to ROUND + flat
     ed_graph(CUT),                                                     # a matched clear
     ed_input(44100, abi.FMT_I24, 1),
     ed_hilbert(1, 1, 0),
