@@ -116,6 +116,7 @@ FIR_MAX_ORDER = 4096     # ICW_FIR_MAX_ORDER: largest k_M of icw_set_fir_hilbert
 # icw_batch_opts.reserved_ is the flags word (0: today's grouping, one context per input format)
 BATCH_MERGE_INPUTS = 1   # ICW_BATCH_MERGE_INPUTS: all real-input files in one context per device
 BATCH_MERGE_CWAVE = 2    # ICW_BATCH_MERGE_CWAVE: all CWAVE files in one context per device (the bits are independent)
+BATCH_MERGE_BUS = 4      # ICW_BATCH_MERGE_BUS: a group's bus-form files in one context, each stream with its own list
 
 
 # icw_cwave_enc_opts.reserved_ / icw_cwave_enc_iir_opts.reserved_: the same for the file encoders
@@ -176,6 +177,7 @@ SIGNATURES = {
     "icw_enable_stream_fir": (_i, [_vp, _i]),
     "icw_enable_stream_encode": (_i, [_vp, _i]),
     "icw_enable_stream_cwave": (_i, [_vp, _i]),
+    "icw_enable_stream_bus": (_i, [_vp, _i]),
     "icw_set_graph": (_i, [_vp, C.POINTER(Node), _i, _i, C.POINTER(_i)]),
     "icw_set_stream_graph": (_i, [_vp, _i, _i, C.POINTER(Node), _i, _i, C.POINTER(_i)]),
     "icw_clear_stream_bus_slot": (_i, [_vp, _i, _i, _i]),

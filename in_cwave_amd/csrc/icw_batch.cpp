@@ -172,7 +172,8 @@ struct FileLists {
     const icw_node *const *nodes = nullptr;
     const int *n_nodes = nullptr;
     const int *bypass = nullptr;       /* nullable: cfg->bypass_list */
-    bool per_stream = false;           /* the group's lists may differ (all register form) */
+    bool per_stream = false;           /* the group's lists may differ (all register form, or bus: all bus form) */
+    bool bus = false;                  /* ICW_BATCH_MERGE_BUS: the group's files carry bus-form lists, each its own */
     int32_t k_M = 0;                   /* icw_transcode_files_fir: the FIR converter for real-input groups (0: the IIR) */
     double k_beta = 0.0;
 };
@@ -399,6 +400,8 @@ int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::v
     /* a merged group of CWAVE files: per-stream CWAVE inputs are the context's to ask for */
     if (wi.fmt >= ICW_FMT_CW_F64 && (o.reserved_ & ICW_BATCH_MERGE_CWAVE) && (rc = icw_enable_stream_cwave(ctx, 1)) != ICW_OK)
         return rc;
+    /* a merged group of bus-form files: per-stream bus-form lists are the context's to ask for */
+    if (fl.bus && (rc = icw_enable_stream_bus(ctx, 1)) != ICW_OK) return rc;
     for (int s = 1; s < S && fl.per_stream; ++s) {
         const int i = jobs[s]->idx;
         rc = icw_set_stream_graph(ctx, s, 1, fl.nodes[i], fl.n_nodes[i], fl.bypass ? fl.bypass[i] : cfg0.bypass_list,
@@ -810,7 +813,12 @@ int transcode_lists(const icw_config *cfg, const icw_node *const *nodes, const i
     o.device = -1;
     if (opts) o = *opts;
     /* the group key's last part: -1 for the register-form lists, which share a context whatever
-     * they are; a bus-form list (context-wide only) groups with the files that carry the same one */
+     * they are; a bus-form list groups with the files that carry the same one -- or, with
+     * ICW_BATCH_MERGE_BUS, all bus-form lists share a context of their own (-2: icw_enable_stream_bus, every
+     * stream its file's list).  The register-form files keep theirs: in a call forced into bus form they
+     * would lose the frame-parallel K2.  Beside the FIR converter the bit does nothing: it refuses bus-form
+     * lists beside others */
+    const bool merge_bus = (o.reserved_ & ICW_BATCH_MERGE_BUS) && k_M == 0 && !cfg->fp_check;
     std::vector<int> form(n > 0 ? n : 1, 0);
     std::vector<int> bus_first;                     /* file index of each distinct bus-form list */
     auto same = [&](int a, int b) {
@@ -828,6 +836,7 @@ int transcode_lists(const icw_config *cfg, const icw_node *const *nodes, const i
         },
         [&](int i) {
             int key = -1;
+            if (form[i] == 1 && merge_bus) return -2;
             if (form[i] == 1) {
                 for (size_t k = 0; k < bus_first.size() && key < 0; ++k)
                     if (same(bus_first[k], i)) key = (int)k;
@@ -844,6 +853,7 @@ int transcode_lists(const icw_config *cfg, const icw_node *const *nodes, const i
             fl.n_nodes = n_nodes;
             fl.bypass = bypass_list;
             fl.per_stream = key < 0;
+            fl.bus = key == -2;
             fl.k_M = k_M;
             fl.k_beta = k_beta;
             return run_group(*cfg, nullptr, 0, g, o, st, sts, fl);

@@ -145,7 +145,7 @@ void free_all(icw_ctx *c)
 {
     DevState &s = c->st;
     void *ptrs[] = {c->enc_clipped, c->s1_stamps, s.mt, s.mt_idx, s.rs, s.lr_equal, s.fes, s.err, s.hist, s.sncnt, s.hq_phase, s.pos, s.fade,
-                    s.n_frame, s.bus, s.clips, s.peak_bits, c->d_prog, c->d_progs, c->d_pid, c->d_inputs, c->d_rtab, c->d_hpc, c->trig, c->d_in, c->d_out,
+                    s.n_frame, s.bus, s.clips, s.peak_bits, c->d_prog, c->d_progs, c->d_bprogs, c->d_bruns, c->d_pid, c->d_inputs, c->d_rtab, c->d_hpc, c->trig, c->d_in, c->d_out,
                     c->d_pre, c->d_xin,
                     c->d_fir_g, c->fir_hist[0], c->fir_hist[1], c->dwords, c->dbk, c->dflag};
     for (void *p : ptrs)
@@ -286,8 +286,12 @@ RenderEnt make_render(const icw_ctx *c, const icw_render_cfg &r, int is24)
     icw_config cfg = c->cfg;
     cfg.render = r;
     cfg.need24bits = e.is24;
-    e.serial = needs_serial(cfg, e.rk, c->prog, c->tn.dith_par);
-    e.rstate = needs_render_state(cfg, e.rk, c->prog, c->tn.dith_par);
+    /* it follows the list while the context has one; with bus-form lists beside others (bus_lists) it is the
+     * render's own -- a call adds its form -- and the state is kept for the calls that run serial */
+    static const IcwProg reg_form{};
+    const IcwProg &lp = c->bus_lists ? reg_form : c->prog;
+    e.serial = needs_serial(cfg, e.rk, lp, c->tn.dith_par);
+    e.rstate = needs_render_state(cfg, e.rk, lp, c->tn.dith_par) || c->bus_lists;
     e.dither = r.render_type != ICW_RENDER_ROUND;
     return e;
 }
@@ -353,7 +357,7 @@ int install_renders(icw_ctx *c, StreamTable<RenderEnt> &t, int first, int count)
 {
     const size_t n = t.size(), S = (size_t)c->n_streams;
     /* more than one render: K3's FP_CHECK form, K4 and the FIR converter's fused render take one */
-    if (n > 1 && (c->fir_M > 0 || c->cfg.fp_check || c->prog.is_bus)) return ICW_EUNSUPPORTED;
+    if (n > 1 && (c->fir_M > 0 || c->cfg.fp_check || c->prog.is_bus || c->bus_lists)) return ICW_EUNSUPPORTED;
     bool rstate = false;
     for (const RenderEnt &e : t.ents) rstate |= e.rstate;
     int rc;
@@ -398,7 +402,7 @@ bool same_list(const ListEnt &a, const ListEnt &b)
            (a.nodes.empty() || !memcmp(a.nodes.data(), b.nodes.data(), a.nodes.size() * sizeof(icw_node)));
 }
 
-/* the list table's mirrors: entry 0 (with several entries is_bus = 0, which is all the render setters ask of it) */
+/* the list table's mirrors: entry 0 (with several entries the render setters ask bus_lists, not its is_bus) */
 void mirror_lists(icw_ctx *c)
 {
     const ListEnt &e = c->lists.ents[0];
@@ -415,6 +419,11 @@ int install_lists(icw_ctx *c, StreamTable<ListEnt> &t)
 {
     const size_t n = t.size();
     IcwProg *fresh = nullptr;
+    /* bus-form lists beside others: a call over them renders serial whatever the render is */
+    bool bus_lists = false;
+    for (const ListEnt &e : t.ents) bus_lists = bus_lists || (n > 1 && e.prog.is_bus);
+    int rs;
+    if (bus_lists && (rs = ensure_render_state(c)) != ICW_OK) return rs;
     if (n > 1) {
         std::vector<IcwProg> h(n);                   /* the contiguous array d_progs holds */
         for (size_t k = 0; k < n; ++k) h[k] = t.ents[k].prog;
@@ -441,6 +450,8 @@ int install_lists(icw_ctx *c, StreamTable<ListEnt> &t)
     }
     c->lists = std::move(t);
     mirror_lists(c);
+    c->bus_lists = bus_lists;
+    ++c->lists_gen;                       /* the mixed K4's programs and runs follow the lists too */
     /* c->mix and the selection rows are built from the lists (prepare_mix): rebuilt by the next call */
     c->pid_valid = false;
     return ICW_OK;
@@ -492,8 +503,10 @@ int apply_graph(icw_ctx *c, const std::vector<icw_node> &nv, int bypass, const s
     if (rc) return rc;
     /* a bus-form list runs K4, one lane per stream on one program into one serial render, and one K2
      * instance: refused while the lists, the renders or the converters differ (include/icw.h; the host
-     * collapses with a register-form list first) */
-    if (L.prog.is_bus && (c->lists.size() > 1 || c->renders.size() > 1 || c->hilbs.size() > 1)) return ICW_EUNSUPPORTED;
+     * collapses with a register-form list first).  With icw_enable_stream_bus differing lists do not refuse
+     * it: the table collapses to this list as to any other */
+    if (L.prog.is_bus && ((c->lists.size() > 1 && !c->bus_streams) || c->renders.size() > 1 || c->hilbs.size() > 1))
+        return ICW_EUNSUPPORTED;
     /* How the render runs follows the list only here, and only for the one render of a one-render context: a
      * bus-form list makes it serial.  Several renders stand beside register-form lists alone (above), which
      * change none of them, and the per-stream list setter takes register-form lists only -- so neither
@@ -597,7 +610,7 @@ int install_hilberts(icw_ctx *c, StreamTable<HilbEnt> &t, int first, int count)
     const size_t n = t.size(), S = (size_t)c->n_streams;
     /* more than one setting: the FIR converter replaces the IIR for every stream, K1f (FP_CHECK) and the
      * bus-form path run one instance */
-    if (n > 1 && (c->fir_M > 0 || c->cfg.fp_check || c->prog.is_bus)) return ICW_EUNSUPPORTED;
+    if (n > 1 && (c->fir_M > 0 || c->cfg.fp_check || c->prog.is_bus || c->bus_lists)) return ICW_EUNSUPPORTED;
     double *fresh = nullptr;
     const size_t pc_bytes = n * 20 * sizeof(double), run_bytes = S * sizeof(IcwK1Run);
     if (n > 1) {
@@ -874,6 +887,8 @@ int icw_set_fir_hilbert(icw_ctx *c, int32_t M, double beta)
     if (M > 0 && c->renders.size() > 1) return ICW_EUNSUPPORTED;
     /* nor beside per-stream Hilbert converters (icw_set_stream_hilbert): it replaces the IIR for every stream */
     if (M > 0 && c->hilbs.size() > 1) return ICW_EUNSUPPORTED;
+    /* nor beside bus-form lists that stand beside others (icw_enable_stream_bus): the mixed K4 follows K2 */
+    if (M > 0 && c->bus_lists) return ICW_EUNSUPPORTED;
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
     c->pid_valid = false;                 /* with the converter on, every (list, rate) pair has a slab */
     for (double *&h : c->fir_hist)
@@ -912,6 +927,17 @@ int icw_enable_stream_fir(icw_ctx *c, int on)
     /* off while the two are in force together would leave a state the setters refuse to build */
     if (!on && c->fir_M > 0 && (c->lists.size() > 1 || c->inputs.size() > 1)) return ICW_EUNSUPPORTED;
     c->fir_streams = on != 0;
+    return ICW_OK;
+}
+
+/* bus-form lists beside other lists, on or off (include/icw.h) */
+int icw_enable_stream_bus(icw_ctx *c, int on)
+{
+    if (!c) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    /* off while a bus-form entry stands beside others would leave a table the setters refuse to build */
+    if (!on && c->bus_lists) return ICW_EUNSUPPORTED;
+    c->bus_streams = on != 0;
     return ICW_OK;
 }
 
@@ -1027,17 +1053,32 @@ int icw_set_stream_graph(icw_ctx *c, int first, int count, const icw_node *nodes
     if (!ok) return ICW_EGRAPH;
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
-    /* K4 runs one lane per stream on a scalar program: bus-form lists stay context-wide; the FIR
+    /* K4 runs one lane per stream on a scalar program: bus-form lists stay context-wide until
+     * icw_enable_stream_bus said otherwise (the mixed K4 then runs a wave per run of one list); the FIR
      * converter serves per-stream lists once icw_enable_stream_fir said so */
-    if ((c->fir_M > 0 && !c->fir_streams) || c->prog.is_bus) return ICW_EUNSUPPORTED;
+    if ((c->fir_M > 0 && !c->fir_streams) || (c->prog.is_bus && !c->bus_streams)) return ICW_EUNSUPPORTED;
     ListEnt L;
     int rc = compile_list(c, nv, bypass_list ? 1 : 0, L);
     if (rc) return rc;
-    if (L.prog.is_bus) return ICW_EUNSUPPORTED;
+    if (L.prog.is_bus && !c->bus_streams) return ICW_EUNSUPPORTED;
     const std::vector<std::vector<int>> per = matched_clears_per_entry(c, nv);
     const std::vector<int32_t> old_of = c->lists.of;
     StreamTable<ListEnt> t = c->lists.assigned((size_t)first, (size_t)count, L, same_list);
+    bool any_bus = false;
+    for (const ListEnt &e : t.ents) any_bus = any_bus || e.prog.is_bus;
+    /* a bus-form list runs one K2 instance into one serial render, as behind icw_set_graph; beside other
+     * lists it stands neither beside the FIR converter nor in an FP_CHECK context (include/icw.h) */
+    if (any_bus && (c->renders.size() > 1 || c->hilbs.size() > 1)) return ICW_EUNSUPPORTED;
+    if (any_bus && t.size() > 1 && (c->fir_M > 0 || c->cfg.fp_check)) return ICW_EUNSUPPORTED;
+    if (any_bus && (rc = ensure_render_state(c)) != ICW_OK) return rc;
     if ((rc = install_lists(c, t)) != ICW_OK) return rc;
+    /* the one render follows the lists, as behind icw_set_graph: serial behind one bus-form list, its own
+     * beside several (make_render) */
+    if (c->bus_streams && c->renders.size() == 1) {
+        const RenderEnt r0 = c->renders.ents[0];
+        c->renders.ents[0] = make_render(c, r0.cfg, r0.is24);
+        mirror_renders(c);
+    }
     return clear_matched(c, old_of, first, count, per);
 }
 

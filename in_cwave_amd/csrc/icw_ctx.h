@@ -72,15 +72,20 @@ struct CuSplit {
     hipStream_t k1 = nullptr, rest = nullptr, dith = nullptr, render = nullptr;
 };
 
-/* one entry of the context's list table: the compiled program and the normalised list it came from */
+/* one entry of the context's list table: the compiled program -- register or, with icw_enable_stream_bus
+ * beside other entries too, bus form -- and the normalised list it came from.  A register-form entry has a
+ * bus-form twin, compiled by the first call that runs it beside a bus-form stream (bus_twin) */
 struct ListEnt {
     IcwProg prog{};
     std::vector<icw_node> nodes;
+    IcwProg twin{};
+    bool has_twin = false;
 };
 
 /* one entry of the context's render table: the setting as given, its constants and how it runs behind the
  * list in force.  With more than one entry no list is bus form and FP_CHECK is off (both refused), so
- * `serial` is the render's own */
+ * `serial` is the render's own; it is the render's own too while bus-form lists stand beside others
+ * (icw_ctx.bus_lists, one render entry): a call then adds its own form (CallPlan::resolve_plan) */
 struct RenderEnt {
     icw_render_cfg cfg{};
     int is24 = 0;
@@ -131,7 +136,8 @@ struct icw_ctx {
      * cfg.hilbert_type / iir_kahan / iir_subnorm_reject / nord / pc / pd / d0 (converters); serial_render and
      * render_state are "some render entry needs it"; cfg.sample_rate / in_format / in_channels are the one
      * input, and while the inputs differ the one last in force alone.
-     * The device keeps tables only for more than one entry: d_progs (the entries' programs; never bus form),
+     * The device keeps tables only for more than one entry: d_progs (the entries' programs; bus form among
+     * them only with icw_enable_stream_bus),
      * d_inputs (one descriptor per stream), d_rtab + d_rof (entries, then the index row, one allocation),
      * d_hpc (below).  A one-entry context launches from d_prog and the scalar arguments. */
     StreamTable<ListEnt> lists;
@@ -140,6 +146,17 @@ struct icw_ctx {
     StreamTable<HilbEnt> hilbs;
     IcwProg *d_progs = nullptr;
     size_t d_progs_cap = 0;               /* entries d_progs has room for */
+    /* icw_enable_stream_bus: bus-form lists are served beside other lists.  Off on a fresh context, where the
+     * list setters keep the refusals they always had.  bus_lists: the table has several entries and one of
+     * them is bus form (install_lists) -- the state the render, converter, FIR and FP_CHECK refusals ask for.
+     * A call over several entries of which one is bus form runs every stream in bus form through the mixed K4:
+     * d_bprogs holds every entry's bus-form program (its own, or the twin) and d_bruns the call's runs, both
+     * built by the first such call and kept while the lists (lists_gen) and the call's range stay */
+    bool bus_streams = false, bus_lists = false;
+    IcwProg *d_bprogs = nullptr;
+    IcwK4Run *d_bruns = nullptr;          /* [n_streams] */
+    unsigned long long lists_gen = 0, bprogs_gen = ~0ull, brun_gen = ~0ull;
+    int brun_first = 0, brun_count = 0, brun_n = 0, brun_wgs = 0, brun_W = 0;
     /* a call over streams with different lists or inputs: K2's [5][count] selection rows, then the
      * rotation table's [3][n_slabs] (IcwK2Args.prog_id, IcwTrigArgs.slabs), rebuilt when the lists, the
      * inputs or the range change */

@@ -194,6 +194,25 @@ struct IcwK4Args {
     const IcwInDesc *desc;         /* streams with different inputs: [n_streams], each stream's own rate */
 };
 
+/* One run of a bus-form call over streams with different lists (icw_enable_stream_bus): consecutive streams
+ * of one list entry.  The mixed serial graph kernel (icw_graph_serial_mixed) gets the call's runs as a device
+ * table, ordered by wg0; a workgroup -- one wave -- belongs to the last run whose wg0 is not above its index,
+ * so its program stays one scalar pointer.  A run is rounded up to whole waves: no wave holds two runs. */
+struct IcwK4Run {
+    int32_t wg0;                   /* first workgroup of the run */
+    int32_t s0, n;                 /* first stream (index into the call's range) and streams */
+    int32_t entry;                 /* the run's program: k4.prog + entry */
+};
+
+/* Arguments of the mixed serial graph kernel: K4's, with k4.prog the table of the entries' bus-form programs */
+struct IcwK4MixArgs {
+    IcwK4Args k4;
+    const IcwK4Run *runs;          /* [n_runs] */
+    int32_t n_runs;
+    int32_t W;                     /* lanes a row of the LDS bus holds: the launch's widest run in a workgroup
+                                      (icw_k4_cut_runs), 1 .. 64 */
+};
+
 /* Arguments of the IIR state kernel (one lane = one DF-II chain). */
 struct IcwK1Args {
     const double *xd;              /* K0 output: per-chain filter inputs */

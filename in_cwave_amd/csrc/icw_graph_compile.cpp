@@ -375,6 +375,48 @@ int build_prog(const icw_config &cfg, std::vector<icw_node> nodes, IcwProg &P)
     return ICW_OK;
 }
 
+/* The bus form of any accepted list, also of one build_prog compiles to the register form: a register-form
+ * list is a valid input to the reference's per-frame loop too, which K4 runs.  A call over streams of both
+ * forms runs every stream in this one (ListEnt's twin). */
+int build_prog_bus(const icw_config &cfg, std::vector<icw_node> nodes, IcwProg &P)
+{
+    if (cfg.frmod_scaled)
+        for (auto &n : nodes)
+            if (n.mode == ICW_MODE_PM)
+                for (int ch = 0; ch < 2; ++ch) n.pm_freq[ch] = scaled_fr(n.pm_freq[ch]);
+    const int rc = compile_bus(nodes, cfg.bypass_list, P);
+    if (rc) return rc;
+    if (cfg.frmod_scaled)
+        for (int i = 0; i < P.n_ops; ++i)
+            if (P.ops[i].mode == ICW_MODE_SHIFT)
+                for (int ch = 0; ch < 2; ++ch) P.ops[i].f[ch] = scaled_fr(P.ops[i].f[ch]);
+    return ICW_OK;
+}
+
+/* The runs of the mixed K4 (IcwK4Run): streams [0, count) of a call, stream i on list entry ent[i], cut into
+ * the maximal runs of consecutive streams on one entry.  A run takes whole one-wave workgroups of 64 lanes,
+ * so no wave holds two runs; wg0 ascends.  Returns the launch's workgroups; *W is the lanes a row of the
+ * LDS bus must hold -- the widest run's lanes in a workgroup, min(64, n) -- rounded up to a power of two, so
+ * that a row starts at a multiple of its own length and a half-wave's 32 consecutive doubles fall on the 64
+ * banks once, as K4's 64-lane rows do. */
+int icw_k4_cut_runs(const int32_t *ent, int count, std::vector<IcwK4Run> &runs, int *W)
+{
+    runs.clear();
+    int wg = 0, widest = 0;
+    for (int i = 0; i < count;) {
+        int j = i + 1;
+        while (j < count && ent[j] == ent[i]) ++j;
+        runs.push_back(IcwK4Run{wg, i, j - i, ent[i]});
+        wg += (j - i + 63) / 64;
+        widest = std::max(widest, std::min(64, j - i));
+        i = j;
+    }
+    int w = 1;
+    while (w < widest) w <<= 1;
+    if (W) *W = w;
+    return wg;
+}
+
 /* A render with the flat shaper is elementwise: ns_empty returns 0.0 (sound_render.c:396-400), so
  * prev_ns_err stays 0.0 (:800) and sound_render_value (:754-809) is a function of the sample and its
  * dither term alone.  ROUND draws no dither; RPDF / TPDF / STPDF / GAUSS take theirs from K3a (the

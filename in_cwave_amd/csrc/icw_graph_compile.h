@@ -28,6 +28,8 @@ unsigned fmt_size(unsigned fmt);
 bool graph_accept(std::vector<icw_node> &n);
 icw_node default_master();
 int build_prog(const icw_config &cfg, std::vector<icw_node> nodes, IcwProg &P);
+int build_prog_bus(const icw_config &cfg, std::vector<icw_node> nodes, IcwProg &P);
+int icw_k4_cut_runs(const int32_t *ent, int count, std::vector<IcwK4Run> &runs, int *W);
 void render_consts(const icw_render_cfg &cfg, int is24, bool spec, IcwRenderK &k);
 bool needs_serial(const icw_config &cfg, const IcwRenderK &rk, const IcwProg &P, bool dith_par);
 bool needs_render_state(const icw_config &cfg, const IcwRenderK &rk, const IcwProg &P, bool dith_par);

@@ -142,7 +142,7 @@ int prepare_mix(icw_ctx *c, int first, int count, bool fir, hipStream_t st)
         pair_of[(size_t)i] = k;
     }
     IcwProg &M = c->mix;
-    M.is_bus = c->prog.is_bus;               /* (several lists: none is bus form) */
+    M.is_bus = 0;                            /* a call with one bus-form stream runs every stream in bus form */
     M.needs_omega = 0;
     M.n_trig = 0;
     M.chain = 1;
@@ -151,6 +151,7 @@ int prepare_mix(icw_ctx *c, int first, int count, bool fir, hipStream_t st)
     int n_slabs = 0;
     for (Pair &q : pairs) {
         const IcwProg &P = c->lists.ents[(size_t)q.e].prog;
+        M.is_bus |= P.is_bus;
         M.needs_omega |= P.needs_omega;
         if (!P.chain) {
             M.chain = 0;
@@ -272,6 +273,12 @@ struct CallPlan {
     size_t slab_stride = 0;
     /* the mode flags */
     bool cw = false, fir = false, fir_fused = false, fir_async = false, bus = false, fcm = false, dedup = false;
+    /* bus, over several list entries (icw_enable_stream_bus): the mixed K4 over the call's runs of one entry
+     * (prepare_bus_runs: its workgroups and the lanes of a bus row), every entry in bus form.  call_render: the
+     * context's one render entry as this call runs it, serial behind a bus-form call (bus_lists) */
+    bool busmix = false;
+    int bwgs = 0, bW = 0;
+    RenderEnt call_render{};
     bool dither = false, dith_par = false, table = false, in_step = false, s1 = false;
     int k1_mode = 0, row_waves = 0;
     /* the resolved Hilbert converter, cut into runs like the render; K2 is one launch per run.  One run: the
@@ -566,6 +573,19 @@ struct CallPlan {
         return a4;
     }
 
+    /* the same over the call's runs of one list entry each (busmix) */
+    IcwK4MixArgs k4_mix_args(int b, const IcwK2Args &a2) const
+    {
+        IcwK4MixArgs m;
+        memset(&m, 0, sizeof(m));
+        m.k4 = k4_args(b, a2);
+        m.k4.prog = c->d_bprogs;
+        m.runs = c->d_bruns;
+        m.n_runs = c->brun_n;
+        m.W = bW;
+        return m;
+    }
+
     /* the rotation table of block b: the factors of every active Shift / PM channel per frame */
     IcwTrigArgs trig_args(int b) const
     {
@@ -700,6 +720,7 @@ struct CallPlan {
     hipError_t launch_advance() const;
     void stereo_diverged() const;
     int prepare_hruns();
+    int prepare_bus_runs();
     int join_legacy_stream() const;
     int stage_host_io(size_t in_row, size_t out_row);
     bool stage_copy_in() const;
@@ -882,6 +903,62 @@ int CallPlan::prepare_hruns()
     c->hrun_pid_gen = c->pid_gen;
     c->hrun_n = (int)hruns.size();
     c->hrun_wgs = hwgs = wg;
+    return ICW_OK;
+}
+
+/* A bus-form call over several list entries: every entry's bus-form program on the device -- its own, or for
+ * a register-form entry the twin, compiled here the first time -- and the call's runs of one entry each
+ * (icw_k4_cut_runs).  The programs are kept while the lists stay (every list edit waits for the context's work
+ * first, so nothing reads the old ones), the runs while the lists and the call's range stay; rebuilt runs are
+ * ordered after the earlier calls on st, which may still read the old ones. */
+int CallPlan::prepare_bus_runs()
+{
+    const size_t n = c->lists.size();
+    if (c->bprogs_gen != c->lists_gen) {
+        std::vector<IcwProg> h(n);
+        for (size_t k = 0; k < n; ++k) {
+            ListEnt &e = c->lists.ents[k];
+            if (!e.prog.is_bus && !e.has_twin) {
+                icw_config tc = c->cfg;
+                tc.bypass_list = e.prog.bypass;
+                const int rc = build_prog_bus(tc, e.nodes, e.twin);
+                if (rc != ICW_OK) return rc;
+                e.has_twin = true;
+            }
+            h[k] = e.prog.is_bus ? e.prog : e.twin;
+        }
+        IcwProg *fresh = nullptr;
+        if (hipMalloc((void **)&fresh, n * sizeof(IcwProg)) != hipSuccess) return ICW_ENOMEM;
+        if (hipMemcpy(fresh, h.data(), n * sizeof(IcwProg), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(fresh);
+            return ICW_EDEVICE;
+        }
+        if (c->d_bprogs) (void)hipFree(c->d_bprogs);
+        c->d_bprogs = fresh;
+        c->bprogs_gen = c->lists_gen;
+    }
+    /* (no clearing fill: it would run on the null stream, which st does not wait for, and could land on the
+     * runs copied below; every run a launch reads has been written) */
+    if (!c->d_bruns && hipMalloc((void **)&c->d_bruns, (size_t)c->n_streams * sizeof(IcwK4Run)) != hipSuccess) {
+        c->d_bruns = nullptr;
+        return ICW_ENOMEM;
+    }
+    if (c->brun_gen != c->lists_gen || c->brun_first != first || c->brun_count != count) {
+        std::vector<IcwK4Run> h;
+        int W = 0;
+        const int wgs = icw_k4_cut_runs(c->lists.of.data() + f0, count, h, &W);
+        if (hipMemcpyAsync(c->d_bruns, h.data(), h.size() * sizeof(IcwK4Run), hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return ICW_EDEVICE;
+        c->brun_gen = c->lists_gen;
+        c->brun_first = first;
+        c->brun_count = count;
+        c->brun_n = (int)h.size();
+        c->brun_wgs = wgs;
+        c->brun_W = W;
+    }
+    bwgs = c->brun_wgs;
+    bW = c->brun_W;
     return ICW_OK;
 }
 
@@ -1118,6 +1195,17 @@ int CallPlan::resolve_plan()
     const IcwProg &LP = *lp;
     n_slabs = mix ? c->pid_slabs : 1;
     bus = LP.is_bus;
+    busmix = bus && mix && c->lists.size() > 1;
+    if (c->bus_lists) {
+        /* bus-form lists beside others: the one render entry holds the render's own form, and a bus-form
+         * call renders serial behind K4 whatever it is; a register-form call keeps its usual kernels */
+        call_render = *runs[0].e;
+        call_render.serial = call_render.serial || bus;
+        runs = StreamRuns<RenderEnt>::single(count, &call_render);
+        serial_render = call_render.serial;
+        serial_gen = call_render.serial ? 2 * count : 0;
+        any_par = !call_render.serial;
+    }
     fcm = cfg.fp_check != 0;
     pick_k1();
     if (!cw) c->last_k1 = k1_mode;
@@ -1287,6 +1375,10 @@ int CallPlan::size_scratch()
     n_sets = std::min(n_blocks, c->tn.max_sets);
     if (mixh) {
         const int rc = prepare_hruns();
+        if (rc != ICW_OK) return rc;
+    }
+    if (busmix) {
+        const int rc = prepare_bus_runs();
         if (rc != ICW_OK) return rc;
     }
     for (int p = 0; p < n_sets && !fir_fused; ++p) {
@@ -1576,7 +1668,10 @@ int CallPlan::run_blocks() const
         /* the serial part (K4, K3b) on sR after K2(b): it then overlaps K2(b+1) instead of
          * delaying it on sA */
         if (serial_render && sR != s2 && hipStreamWaitEvent(sR, c->k2done[p], 0) != hipSuccess) return ICW_EDEVICE;
-        if (bus) {
+        if (busmix) {
+            const auto m4 = k4_mix_args(b, a2);
+            if (icw_launch_graph_serial_mixed(&m4, bwgs, sR) != hipSuccess) return ICW_EDEVICE;
+        } else if (bus) {
             const auto a4 = k4_args(b, a2);
             if (icw_launch_graph_serial(&a4, sR) != hipSuccess) return ICW_EDEVICE;
         }

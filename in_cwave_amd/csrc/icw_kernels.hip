@@ -12,7 +12,7 @@
  *                   window (frame-parallel), the fs/4 un-mix (lpf_hilbert_quad.c:129-156), the
  *                   DSP graph (adv_modulator.c:637-751) and the elementwise render
  *                   (sound_render.c:691-809, ROUND/flat).  Coalesced tile loads via LDS.
- *   icw_graph_serial   K4 (serial form).
+ *   icw_graph_serial   K4 (serial form); icw_graph_serial_mixed: the same over streams with different programs.
  * The dither generator and the renders (K3a / K3b / K3c) live in icw_render.hip.
  */
 #include <hip/hip_runtime.h>
@@ -537,6 +537,88 @@ __global__ __launch_bounds__(64) void icw_graph_serial(IcwK4Args a)
     for (int k = 0; k < ICW_N_INPUTS * 4; ++k) gb[k] = bus[k][lane];
 }
 
+/* the mixed K4's bus in LDS: rows [slot * 4 + component] of W doubles, one per lane (b is the lane's column) */
+struct IcwBusW {
+    double *b;
+    int W;
+    __device__ __forceinline__ double &operator[](int k) const { return b[k * W]; }
+};
+
+/* one stream's frames of a block through its bus-form program P, in order: K4's body statement for
+ * statement, over a bus whose rows have the launch's length.  K4 keeps its own text: routed through this
+ * function its two instances no longer compiled to the instructions they had */
+template <bool MIXIN, class BUS>
+__device__ __forceinline__ void icw_graph_serial_run(const IcwK4Args &a, icw_cprog *P, int s, const BUS &bus)
+{
+    double *gb = a.bus + (size_t)s * ICW_N_INPUTS * 4;
+    for (int k = 0; k < ICW_N_INPUTS * 4; ++k) bus[k] = gb[k];
+    const unsigned long long n0 = a.n_frame[s];
+    unsigned long long ssr = a.ssr;
+    uint32_t rate = a.sample_rate;
+    if constexpr (MIXIN) {
+        ssr = a.desc[s].ssr;
+        rate = a.desc[s].sample_rate;
+    }
+    const double *iq = a.iq + (size_t)s * a.T * 4;
+    double *pre = a.pre + (size_t)s * a.pre_stride;
+    for (int t = 0; t < a.T; ++t) {
+        const double omega = P->needs_omega ? icw_omega(n0, a.t0 + t, a.scaled, ssr, rate) : 0.0;
+        bus[0] = iq[(size_t)t * 4 + 0];
+        bus[1] = iq[(size_t)t * 4 + 1];
+        bus[2] = iq[(size_t)t * 4 + 2];
+        bus[3] = iq[(size_t)t * 4 + 3];
+        double lOut = 0.0, rOut = 0.0;
+        for (int oi = 0; oi < P->n_ops; ++oi) {
+            icw_cop &op = P->ops[oi];
+            IcwLR d;
+            if (P->bypass) {
+                d.lre = bus[0]; d.lim = bus[1]; d.rre = bus[2]; d.rim = bus[3];
+            } else {
+                d.lre = d.lim = d.rre = d.rim = 0.0;
+                const uint32_t m = op.in_mask;
+                for (int k = 0; k < ICW_N_INPUTS; ++k) {
+                    if (!((m >> k) & 1u)) continue;
+                    d.lre += bus[k * 4 + 0]; d.lim += bus[k * 4 + 1];
+                    d.rre += bus[k * 4 + 2]; d.rim += bus[k * 4 + 3];
+                }
+            }
+            IcwLR o;
+            if (icw_exec_op(op, d, omega, o, lOut, rOut)) {
+                const int q = op.out_slot * 4;
+                bus[q + 0] = o.lre; bus[q + 1] = o.lim; bus[q + 2] = o.rre; bus[q + 3] = o.rim;
+            }
+        }
+        pre[(size_t)t * 2] = lOut;
+        pre[(size_t)t * 2 + 1] = rOut;
+    }
+    for (int k = 0; k < ICW_N_INPUTS * 4; ++k) gb[k] = bus[k];
+}
+
+/* K4 over streams with different bus-form programs (icw_enable_stream_bus): the call's streams cut into runs
+ * of one list entry (IcwK4Run, icw_device.h).  A workgroup is one wave and finds its run by a binary search
+ * over the runs' first workgroups -- scalar loads through the constant address space -- so the program is a
+ * scalar pointer as in K4, and the body is K4's.  The bus rows hold m.W lanes, the launch's widest run in a
+ * workgroup, in dynamic LDS: a call whose streams each carry their own list has one lane per workgroup, and
+ * at 64-lane rows (55 296 bytes) two of them would fill a CU's LDS.  [slot][lane] order as in K4: the lanes
+ * of a wave read consecutive doubles. */
+template <bool MIXIN>
+__global__ __launch_bounds__(64) void icw_graph_serial_mixed(IcwK4MixArgs m)
+{
+    extern __shared__ __attribute__((aligned(16))) double busw[];   /* [ICW_N_INPUTS * 4][m.W] */
+    const __attribute__((address_space(4))) IcwK4Run *r = (const __attribute__((address_space(4))) IcwK4Run *)m.runs;
+    int lo = 0, hi = m.n_runs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (r[mid].wg0 <= (int)blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    r += lo;
+    const int lane = ((int)blockIdx.x - r->wg0) * 64 + (int)threadIdx.x;     /* the stream's index in its run */
+    const int s = r->s0 + lane;
+    if (lane >= r->n || (int)threadIdx.x >= m.W || s >= m.k4.n_streams) return;
+    icw_graph_serial_run<MIXIN>(m.k4, icw_prog_c(m.k4.prog) + r->entry, s, IcwBusW{busw + threadIdx.x, m.W});
+}
+
 /* Call-end bookkeeping: the reader position, the Hilbert phases (not for complex input -- the
  * converters were not called) and the modulator frame counter advance by the call's frames. */
 __device__ __forceinline__ void icw_advance_stream(const IcwAdvArgs &a, int s)
@@ -805,6 +887,16 @@ extern "C" hipError_t icw_launch_graph_serial(const IcwK4Args *a, hipStream_t st
 {
     if (a->desc) hipLaunchKernelGGL(icw_graph_serial<true>, dim3((a->n_streams + 63) / 64), dim3(64), 0, st, *a);
     else hipLaunchKernelGGL(icw_graph_serial<false>, dim3((a->n_streams + 63) / 64), dim3(64), 0, st, *a);
+    return hipGetLastError();
+}
+
+/* the mixed K4: n_wgs one-wave workgroups over the runs (the host cut them: icw_k4_cut_runs) */
+extern "C" hipError_t icw_launch_graph_serial_mixed(const IcwK4MixArgs *m, int n_wgs, hipStream_t st)
+{
+    if (!m->runs || m->n_runs <= 0 || n_wgs <= 0 || m->W < 1 || m->W > 64) return hipErrorInvalidValue;
+    const size_t lds = (size_t)ICW_N_INPUTS * 4 * (size_t)m->W * sizeof(double);
+    if (m->k4.desc) hipLaunchKernelGGL(icw_graph_serial_mixed<true>, dim3(n_wgs), dim3(64), lds, st, *m);
+    else hipLaunchKernelGGL(icw_graph_serial_mixed<false>, dim3(n_wgs), dim3(64), lds, st, *m);
     return hipGetLastError();
 }
 

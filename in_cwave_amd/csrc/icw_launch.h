@@ -23,6 +23,8 @@ hipError_t icw_launch_output(const IcwK2Args *a, int nord, int kahan, hipStream_
 hipError_t icw_launch_output_cw(const IcwK2Args *a, const IcwDinArgs *d, hipStream_t st);
 hipError_t icw_launch_trig_table(const IcwTrigArgs *a, hipStream_t st);
 hipError_t icw_launch_graph_serial(const IcwK4Args *a, hipStream_t st);
+/* K4 over the runs of a call whose streams carry different bus-form programs: n_wgs one-wave workgroups */
+hipError_t icw_launch_graph_serial_mixed(const IcwK4MixArgs *m, int n_wgs, hipStream_t st);
 hipError_t icw_launch_advance(const IcwAdvArgs *a, hipStream_t st);
 hipError_t icw_launch_advance_mixed(const IcwAdvMixArgs *a, hipStream_t st);
 hipError_t icw_launch_stream1(const IcwS1Args *a, int nord, hipStream_t st);

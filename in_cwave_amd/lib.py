@@ -170,6 +170,11 @@ class Context:
         """icw_enable_stream_fir: per-stream lists and inputs beside the FIR converter (off on a fresh context)"""
         _check(self._lib.icw_enable_stream_fir(self.h, int(bool(on))), "icw_enable_stream_fir")
 
+    def enable_stream_bus(self, on=True):
+        """icw_enable_stream_bus: set_stream_graph takes bus-form lists (feedback, delays, more than 16 nodes),
+        each stream with its own, and set_graph takes one while the lists differ (off on a fresh context)"""
+        _check(self._lib.icw_enable_stream_bus(self.h, int(bool(on))), "icw_enable_stream_bus")
+
     def enable_stream_encode(self, on=True):
         """icw_enable_stream_encode: the CWAVE encoders serve streams with different inputs (off on a fresh
         context)"""
@@ -574,9 +579,10 @@ def wav_parse_file(path):
     return info
 
 
-def _batch_flags(merge_inputs, merge_cwave):
+def _batch_flags(merge_inputs, merge_cwave, merge_bus=False):
     """icw_batch_opts.reserved_: the ICW_BATCH_* bits"""
-    return (abi.BATCH_MERGE_INPUTS if merge_inputs else 0) | (abi.BATCH_MERGE_CWAVE if merge_cwave else 0)
+    return ((abi.BATCH_MERGE_INPUTS if merge_inputs else 0) | (abi.BATCH_MERGE_CWAVE if merge_cwave else 0) |
+            (abi.BATCH_MERGE_BUS if merge_bus else 0))
 
 
 def transcode_files(cfg, nodes, in_paths, out_paths, fade_in_ms=0, fade_out_ms=0, sec_align=0,
@@ -602,9 +608,10 @@ def graph_form(cfg, nodes, bypass_list=0):
 
 
 def transcode_files_lists(cfg, node_lists, in_paths, out_paths, bypass_lists=None, fade_in_ms=0, fade_out_ms=0,
-                          sec_align=0, block_frames=0, device=-1, merge_inputs=False, merge_cwave=False):
+                          sec_align=0, block_frames=0, device=-1, merge_inputs=False, merge_cwave=False, merge_bus=False):
     """icw_transcode_files_lists: file i through its own list node_lists[i] (bypass_lists[i] where
-    given); returns (rc, stats, per-file status)"""
+    given); returns (rc, stats, per-file status).  merge_bus: ICW_BATCH_MERGE_BUS, a group's bus-form files in
+    one context"""
     n = len(in_paths)
     assert len(node_lists) == n and len(out_paths) == n and (bypass_lists is None or len(bypass_lists) == n)
     ins = (C.c_char_p * max(1, n))(*[str(p).encode() for p in in_paths])
@@ -614,7 +621,7 @@ def transcode_files_lists(cfg, node_lists, in_paths, out_paths, bypass_lists=Non
     cnt = (C.c_int * max(1, n))(*[len(nl) for nl in node_lists])
     byp = (C.c_int * max(1, n))(*[int(b) for b in bypass_lists]) if bypass_lists is not None else None
     o = abi.BatchOpts(fade_in_ms, fade_out_ms, sec_align, block_frames, device,
-                      _batch_flags(merge_inputs, merge_cwave))
+                      _batch_flags(merge_inputs, merge_cwave, merge_bus))
     st = abi.BatchStats()
     status = (C.c_int * max(1, n))()
     rc = load().icw_transcode_files_lists(C.byref(cfg), ptrs, cnt, byp, ins, outs, n, C.byref(o), C.byref(st), status)

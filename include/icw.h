@@ -355,7 +355,35 @@ int icw_set_render(icw_ctx *ctx, const icw_render_cfg *render);
  * converter on, streams that share a chain signature -- 256
  * Shift frequencies of one list shape -- stay on its signature kernel in one launch.  Not served: icw_group (its lists stay
  * context-wide), the icw_amod_* drop-in and the encoders (they run no list).  The state blob does not
- * carry a list: icw_set_state expects the stream's list to be set as it was. */
+ * carry a list: icw_set_state expects the stream's list to be set as it was.
+ *   icw_enable_stream_bus(ctx, 1)  serves bus-form lists per stream from then on -- feedback loops, one-frame
+ *                                  delays, lists of more than 16 nodes, each stream with its own: the first
+ *                                  and the third refusal above fall.  icw_set_stream_graph takes bus-form
+ *                                  lists (also while the list in force is one), icw_set_graph takes one
+ *                                  while the lists differ and collapses the table to count 1 as ever, and
+ *                                  the position-matched clearing and icw_clear_stream_bus_slot work per
+ *                                  stream as for register-form lists.  A call whose streams share one list
+ *                                  entry launches what a one-list context launches; a call over several
+ *                                  bus-form entries runs the serial graph kernel's per-stream form, a wave
+ *                                  per run of consecutive streams on one entry, and the one serial render
+ *                                  behind it.  A call over register-form and bus-form streams is served:
+ *                                  every stream of that call runs in bus form (a register-form list is a
+ *                                  valid input to the reference's per-frame loop), and the persistent bus
+ *                                  is the same either way, so a register-form stream called alone, or with
+ *                                  other register-form streams, takes its usual kernels again.
+ *                                  A fresh context has it off and refuses exactly as listed above, so a
+ *                                  host that relies on the refusals sees no change.  (ctx, 0) turns it off
+ *                                  again; ICW_EUNSUPPORTED, changing nothing, while the count is above 1
+ *                                  and some entry is bus form.  NULL ctx: ICW_EINVAL.
+ *                                  Still refused (ICW_EUNSUPPORTED, nothing changes) while a bus-form
+ *                                  entry is in force beside a count above 1, or on the call that would
+ *                                  create that state: icw_set_stream_render / icw_set_stream_hilbert that
+ *                                  leave their count above 1 (and a bus-form list while either count is
+ *                                  above 1, as icw_set_graph refuses it); icw_set_fir_hilbert(k_M > 0),
+ *                                  and the list while the converter is on; a cfg.fp_check context; the
+ *                                  list primitives, as ever while the lists differ.  Not served: icw_group
+ *                                  and the icw_amod_* drop-in. */
+int icw_enable_stream_bus(icw_ctx *ctx, int on);
 int icw_set_stream_graph(icw_ctx *ctx, int first, int count, const icw_node *nodes, int n_nodes,
                          int bypass_list, int *accepted);
 int icw_clear_stream_bus_slot(icw_ctx *ctx, int first, int count, int slot);
@@ -594,7 +622,7 @@ const char *icw_strerror(int status);
  *   2  icw_mod_context_fopen takes need24bits (its 11th argument, in_cwave.c:212) -- a binding built
  *      against version 1 would pass an undefined bit depth.
  * Entry points that were only added (the per-stream setters and their opt-ins, icw_enable_stream_cwave,
- * icw_last_dither_chunks the latest) leave it: a binding built against an earlier header of version 2 still
+ * icw_last_dither_chunks, icw_enable_stream_bus the latest) leave it: a binding built against an earlier header of version 2 still
  * calls what it knows. */
 #define ICW_ABI_VERSION 2
 int icw_abi_version(void);

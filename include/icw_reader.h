@@ -65,9 +65,17 @@ typedef struct icw_batch_opts {
  * formats, mono and stereo, at several rates decodes at full batch width.  Honoured by icw_transcode_files,
  * _lists, _devices and _fir (there the CWAVE context runs without the converter, as CWAVE groups do).  The
  * bits are independent; without a bit that kind of file is grouped as before, and the output bytes are the
- * same either way. */
+ * same either way.
+ * ICW_BATCH_MERGE_BUS: icw_transcode_files_lists puts the bus-form files of a group into ONE context, which
+ * has icw_enable_stream_bus on and gives every stream its file's list, instead of one context per distinct
+ * bus-form list; with ICW_BATCH_MERGE_INPUTS that is all real-input bus-form files.  Register-form files keep
+ * their own context (in a call forced into bus form they would lose the frame-parallel output kernel).  The
+ * output bytes are the same with and without the bit.  icw_transcode_files and _devices carry one list, so
+ * there is nothing for the bit to merge; icw_transcode_files_fir ignores it (the converter refuses bus-form
+ * lists beside others), as does a cfg.fp_check call. */
 #define ICW_BATCH_MERGE_INPUTS 1
 #define ICW_BATCH_MERGE_CWAVE  2
+#define ICW_BATCH_MERGE_BUS    (1 << 2)   /* 4: the third bit of the flags word */
 
 typedef struct icw_batch_stats {
     int32_t  n_files, n_groups;         /* files transcoded; contexts used (one per input format) */
