@@ -133,6 +133,20 @@ class BatchStats(C.Structure):
                 ("frames_out", C.c_uint64), ("wall_s", C.c_double), ("io_s", C.c_double)]
 
 
+POOL_AS_GIVEN, POOL_LONGEST_FIRST = 0, 1     # ICW_POOL_*: icw_pool_opts.order
+
+
+class PoolOpts(C.Structure):
+    """icw_pool_opts (include/icw_reader.h)"""
+    _fields_ = [("batch", BatchOpts), ("slots", C.c_int32), ("order", C.c_int32)]
+
+
+class PoolStats(C.Structure):
+    """icw_pool_stats (include/icw_reader.h)"""
+    _fields_ = [("batch", BatchStats), ("slots", C.c_int32), ("refills", C.c_int32), ("blocks", C.c_uint64),
+                ("slot_blocks", C.c_uint64), ("busy_slot_blocks", C.c_uint64)]
+
+
 class CwaveEncOpts(C.Structure):
     """icw_cwave_enc_opts (include/icw_reader.h)"""
     _fields_ = [("k_M", C.c_int32), ("align", C.c_int32), ("k_beta", C.c_double), ("cw_format", C.c_uint32),
@@ -266,6 +280,11 @@ SIGNATURES = {
     "icw_transcode_files_fir": (_i, [C.POINTER(Config), C.POINTER(C.POINTER(Node)), C.POINTER(_i), C.POINTER(_i),
                                      C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, C.c_int32, C.c_double,
                                      C.POINTER(BatchOpts), C.POINTER(BatchStats), C.POINTER(_i)]),
+    "icw_transcode_files_pool": (_i, [C.POINTER(Config), C.POINTER(C.POINTER(Node)), C.POINTER(_i), C.POINTER(_i),
+                                      C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _i, C.POINTER(PoolOpts),
+                                      C.POINTER(PoolStats), C.POINTER(Meters), C.POINTER(_i)]),
+    "icw_pool_plan": (_i, [C.POINTER(C.c_int64), _i, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                           C.POINTER(C.c_int64), C.POINTER(PoolStats)]),
     "icw_group_create": (_i, [C.POINTER(Config), C.POINTER(Node), _i, _i, C.POINTER(_i), _i, C.POINTER(_vp),
                               C.POINTER(_i)]),
     "icw_group_destroy": (_i, [_vp]),

@@ -22,6 +22,7 @@
 
 #include "../../include/icw_cwave.h"
 #include "../../include/icw_reader.h"
+#include "icw_pool_plan.h"
 
 namespace {
 
@@ -147,6 +148,7 @@ struct Job {
     int64_t total = 0;        /* n_samples + tail */
     int64_t read = 0;         /* data frames read so far */
     int64_t written = 0;      /* output frames written so far */
+    int slot = -1;            /* icw_transcode_files_pool: the slot the plan gives it */
 };
 
 void wav_header(unsigned char *h, uint32_t rate, int bytes_per_sample, uint64_t frames)
@@ -250,14 +252,34 @@ struct GroupPipe {
     const size_t fsz, osz;                /* bytes per input frame (the group's widest: the rows' pitch) / output frame */
     const size_t in_b, out_b;
     std::vector<size_t> ofs;              /* merged encode: every stream's own output frame (<= osz, the rows' pitch); empty: osz */
+    /* A slot is a stream of the context and a row of the buffers.  cur: the job each slot reads from (a group:
+     * its file, for the whole job; a pool: whatever the plan has put there, nullptr while it is idle).
+     * held[p]: the job each slot held when input buffer p was read; wheld[p]: the same for output buffer p, taken
+     * over from held[p] when the block is queued.  Block k is written after block k + 1 has been read and
+     * queued, so who owned a slot in block k is remembered with buffer k & 1, not looked up from the slot's owner
+     * of the moment -- and apart from the input side's map, which block k + 2 overwrites before block k is
+     * written.  zb: the zero sample of the slot's last input, what an idle slot is fed. */
+    std::vector<Job *> cur, held[2], wheld[2];
+    std::vector<unsigned char> zb;
+    bool close_done = false;              /* a pool closes a file with its last block, not with the call */
     unsigned char *hin[2] = {nullptr, nullptr}, *hout[2] = {nullptr, nullptr}, *din[2] = {nullptr, nullptr},
                   *dout[2] = {nullptr, nullptr};
     hipStream_t cs = nullptr, ks = nullptr;
     hipEvent_t h2d[2] = {nullptr, nullptr}, comp[2] = {nullptr, nullptr}, d2h[2] = {nullptr, nullptr};
 
     GroupPipe(std::vector<Job *> &jobs_, int B_, size_t fsz_, size_t osz_, icw_batch_stats &st_, int *status_)
-        : jobs(jobs_), st(st_), status(status_), S((int)jobs_.size()), B(B_), fsz(fsz_), osz(osz_),
-          in_b((size_t)S * B_ * fsz_), out_b((size_t)S * B_ * osz_) {}
+        : GroupPipe(jobs_, (int)jobs_.size(), B_, fsz_, osz_, st_, status_)
+    {
+        cur = jobs;
+        for (int s = 0; s < S; ++s) zb[(size_t)s] = zero_byte(jobs[(size_t)s]->info.fmt);
+    }
+    /* S_ slots, all idle: a pool, whose jobs come and go (cur) */
+    GroupPipe(std::vector<Job *> &jobs_, int S_, int B_, size_t fsz_, size_t osz_, icw_batch_stats &st_, int *status_)
+        : jobs(jobs_), st(st_), status(status_), S(S_), B(B_), fsz(fsz_), osz(osz_),
+          in_b((size_t)S * B_ * fsz_), out_b((size_t)S * B_ * osz_), cur((size_t)S_, nullptr), zb((size_t)S_, 0)
+    {
+        held[0] = held[1] = wheld[0] = wheld[1] = cur;
+    }
     GroupPipe(const GroupPipe &) = delete;
 
     ~GroupPipe()
@@ -295,9 +317,15 @@ struct GroupPipe {
     void read_frames(unsigned char *buf, int nfr)
     {
         const double t0 = now_s();
+        held[buf == hin[1]] = cur;
         for (int s = 0; s < S; ++s) {
-            Job &j = *jobs[s];
             unsigned char *row = buf + (size_t)s * B * fsz;
+            if (!cur[(size_t)s]) {
+                memset(row, zb[(size_t)s], (size_t)B * fsz);
+                continue;
+            }
+            Job &j = *cur[(size_t)s];
+            zb[(size_t)s] = zero_byte(j.info.fmt);
             const size_t jf = j.info.frame_bytes;                          /* the file's own frame (<= fsz) */
             const int64_t want = std::min<int64_t>(nfr, std::max<int64_t>(0, j.info.n_samples - j.read));
             size_t got = 0;
@@ -317,13 +345,22 @@ struct GroupPipe {
         const double t0 = now_s();
         const unsigned char *buf = hout[k & 1];
         for (int s = 0; s < S; ++s) {
-            Job &j = *jobs[s];
+            if (!wheld[k & 1][(size_t)s]) continue;
+            Job &j = *wheld[k & 1][(size_t)s];
             const int64_t n = std::min<int64_t>(B, j.total - j.written);
-            if (n <= 0 || status[j.idx] != ICW_OK) continue;
-            if (fwrite(buf + (size_t)s * B * osz, ofs.empty() ? osz : ofs[(size_t)s], (size_t)n, j.out) != (size_t)n)
-                status[j.idx] = ICW_EINVAL;
+            if (n <= 0) continue;
+            if (status[j.idx] == ICW_OK) {
+                if (fwrite(buf + (size_t)s * B * osz, ofs.empty() ? osz : ofs[(size_t)s], (size_t)n, j.out) != (size_t)n)
+                    status[j.idx] = ICW_EINVAL;
+                st.frames_out += (uint64_t)n;
+            }
             j.written += n;
-            st.frames_out += (uint64_t)n;
+            if (close_done && j.written == j.total) {
+                fclose(j.in);
+                j.in = nullptr;
+                if (fclose(j.out) != 0 && status[j.idx] == ICW_OK) status[j.idx] = ICW_EINVAL;
+                j.out = nullptr;
+            }
         }
         st.io_s += now_s() - t0;
     }
@@ -333,10 +370,21 @@ struct GroupPipe {
     template <class Compute, class After>
     int run(int nb, Compute compute, After after)
     {
+        return run(nb, compute, after, [](int) {}, [](int) { return (int)ICW_OK; });
+    }
+
+    /* the same for a pool: assign(k) changes the slots' jobs (cur) before block k is read; prepare(k) brings
+     * the context's streams in line with them before block k is queued (it waits for the context's work) */
+    template <class Compute, class After, class Assign, class Prepare>
+    int run(int nb, Compute compute, After after, Assign assign, Prepare prepare)
+    {
         int rc = ICW_OK;
+        assign(0);
         read_frames(hin[0], B);
         for (int k = 0; k < nb && rc == ICW_OK; ++k) {
             const int p = k & 1;
+            if ((rc = prepare(k)) != ICW_OK) break;
+            wheld[p] = held[p];
             /* H2D(k): d_in[p] was last read by compute(k-2); d_out[p] by D2H(k-2), which compute(k) waits for */
             if (k >= 2 && (hipStreamWaitEvent(cs, comp[p], 0) != hipSuccess || hipStreamWaitEvent(ks, d2h[p], 0) != hipSuccess))
                 rc = ICW_EDEVICE;
@@ -354,6 +402,7 @@ struct GroupPipe {
              * write block k-1 (after its D2H) */
             if (k + 1 < nb) {
                 if (k >= 1 && hipEventSynchronize(h2d[(k + 1) & 1]) != hipSuccess) { rc = ICW_EDEVICE; break; }
+                assign(k + 1);
                 read_frames(hin[(k + 1) & 1], B);
             }
             if (k >= 1) {
@@ -445,6 +494,123 @@ int run_group(const icw_config &cfg0, const icw_node *nodes, int n_nodes, std::v
                 },
                 [](int, int) { return (int)ICW_OK; });
     if (rc == ICW_OK) rc = icw_synchronize(ctx);
+    return rc;
+}
+
+/* files a and b of a lists call carry the same list */
+bool same_file_list(const FileLists &fl, int cfg_bypass, int a, int b)
+{
+    const int ba = fl.bypass ? fl.bypass[a] : cfg_bypass, bb = fl.bypass ? fl.bypass[b] : cfg_bypass;
+    return fl.n_nodes[a] == fl.n_nodes[b] && !ba == !bb &&
+           (fl.n_nodes[a] == 0 || !memcmp(fl.nodes[a], fl.nodes[b], (size_t)fl.n_nodes[a] * sizeof(icw_node)));
+}
+
+/* One pool of icw_transcode_files_pool: the files of one kind through one context of plan.slots streams.  The
+ * plan (icw_pool_plan.h) says which slot every file runs in and the block in which it starts; this executes
+ * it.  At a block boundary the slots' jobs change on the host side first (assign: before the block is read),
+ * then, all refills of the boundary together and before the block is queued, the context follows (prepare):
+ * the ended files' meters; the new file's input and list where they differ from what the slot holds;
+ * icw_stream_init for a slot that has held a file; icw_stream_open last, since it takes the fades at the
+ * stream's rate. */
+int run_pool(const icw_config &cfg0, std::vector<Job *> &jobs, const icw_pool_opts &po, const FileLists &fl,
+             icw_batch_stats &st, icw_pool_stats &ps, icw_meters *meters, int *status)
+{
+    const icw_batch_opts &o = po.batch;
+    const int n = (int)jobs.size();
+    const int B = o.block_frames > 0 ? o.block_frames : 65536;
+    std::vector<int64_t> totals((size_t)n);
+    size_t fsz = 0;
+    for (int q = 0; q < n; ++q) {
+        Job &j = *jobs[(size_t)q];
+        /* xwave_reader_create's virtual zero tail (xwave_reader.c:688-697) */
+        int64_t tail = 0;
+        if (o.sec_align) {
+            const int64_t mt = (int64_t)j.info.sample_rate * (int64_t)o.sec_align, fr = j.info.n_samples % mt;
+            tail = fr ? mt - fr : 0;
+        }
+        totals[(size_t)q] = j.total = j.info.n_samples + tail;
+        fsz = std::max<size_t>(fsz, j.info.frame_bytes);
+    }
+    IcwPoolPlan plan;
+    int rc = icw_pool_make_plan(totals.data(), n, po.slots, B, po.order, plan);
+    if (rc != ICW_OK) return rc;
+    const int S = plan.slots, nb = (int)plan.blocks;
+    std::vector<std::vector<Job *>> starts((size_t)nb + 1), ends((size_t)nb + 1);
+    for (int q : plan.queue) {
+        Job *j = jobs[(size_t)q];
+        j->slot = plan.slot[(size_t)q];
+        starts[(size_t)plan.start[(size_t)q]].push_back(j);
+        ends[(size_t)(plan.start[(size_t)q] + plan.n_blocks[(size_t)q])].push_back(j);
+    }
+    /* the context starts on the input and the list of the first file to run; every slot holds them until a
+     * file brings its own */
+    const Job &j0 = *jobs[(size_t)plan.queue[0]];
+    icw_config cfg = cfg0;
+    cfg.sample_rate = j0.info.sample_rate;
+    cfg.in_format = j0.info.fmt;
+    cfg.in_channels = j0.info.channels;
+    if (fl.bypass) cfg.bypass_list = fl.bypass[j0.idx];
+    icw_ctx *ctx = nullptr;
+    int accepted = 0;
+    if ((rc = icw_create(&cfg, fl.nodes[j0.idx], fl.n_nodes[j0.idx], S, o.device, &ctx, &accepted)) != ICW_OK) return rc;
+    std::unique_ptr<icw_ctx, int (*)(icw_ctx *)> guard(ctx, icw_destroy);
+    if (j0.info.fmt >= ICW_FMT_CW_F64 && (rc = icw_enable_stream_cwave(ctx, 1)) != ICW_OK) return rc;
+    if (fl.bus && (rc = icw_enable_stream_bus(ctx, 1)) != ICW_OK) return rc;
+    const int rs = icw_render_size(ctx), osz = 2 * rs;
+    std::vector<const Job *> in_of((size_t)S, &j0), list_of((size_t)S, &j0);   /* whose input / list a slot holds */
+    std::vector<char> used((size_t)S, 0);
+    GroupPipe pp(jobs, S, B, fsz, (size_t)osz, st, status);
+    pp.close_done = true;
+    if (!pp.alloc()) return ICW_ENOMEM;
+    const auto read_meters = [&](int k) {
+        int r = ICW_OK;
+        for (Job *j : ends[(size_t)k])
+            if (meters && r == ICW_OK) r = icw_get_meters(ctx, j->slot, 0, &meters[j->idx]);
+        return r;
+    };
+    rc = pp.run(nb,
+                [&](int p) {
+                    return icw_process_streams(ctx, 0, S, pp.din[p], (size_t)B * fsz, pp.dout[p], (size_t)B * osz, B,
+                                               ICW_F_DEVICE_PTRS, nullptr, pp.ks);
+                },
+                [](int, int) { return (int)ICW_OK; },
+                [&](int k) {
+                    for (Job *j : ends[(size_t)k]) pp.cur[(size_t)j->slot] = nullptr;
+                    for (Job *j : starts[(size_t)k]) {
+                        pp.cur[(size_t)j->slot] = j;
+                        unsigned char hdr[44];
+                        wav_header(hdr, j->info.sample_rate, rs, (uint64_t)j->total);
+                        if (fwrite(hdr, 1, 44, j->out) != 44) status[j->idx] = ICW_EINVAL;
+                        if (fseeko(j->in, j->info.data_offset, SEEK_SET)) status[j->idx] = ICW_EINVAL;
+                    }
+                },
+                [&](int k) {
+                    int r = read_meters(k);
+                    for (Job *j : starts[(size_t)k]) {
+                        if (r != ICW_OK) break;
+                        const size_t s = (size_t)j->slot;
+                        const icw_wav_info &ji = j->info, &si = in_of[s]->info;
+                        if (ji.sample_rate != si.sample_rate || ji.fmt != si.fmt || ji.channels != si.channels)
+                            r = icw_set_stream_input(ctx, j->slot, 1, ji.sample_rate, ji.fmt, ji.channels);
+                        in_of[s] = j;
+                        if (r == ICW_OK && !same_file_list(fl, cfg0.bypass_list, list_of[s]->idx, j->idx))
+                            r = icw_set_stream_graph(ctx, j->slot, 1, fl.nodes[j->idx], fl.n_nodes[j->idx],
+                                                     fl.bypass ? fl.bypass[j->idx] : cfg0.bypass_list, &accepted);
+                        list_of[s] = j;
+                        if (r == ICW_OK && used[s]) r = icw_stream_init(ctx, j->slot, 1);
+                        used[s] = 1;
+                        if (r == ICW_OK)
+                            r = icw_stream_open(ctx, j->slot, ji.n_samples, o.fade_in_ms, o.fade_out_ms, o.sec_align, 0, 0);
+                    }
+                    return r;
+                });
+    if (rc == ICW_OK) rc = icw_synchronize(ctx);
+    if (rc == ICW_OK) rc = read_meters(nb);
+    ps.slots = std::max(ps.slots, plan.slots);
+    ps.refills += plan.refills;
+    ps.blocks += plan.blocks;
+    ps.slot_blocks += plan.slot_blocks;
+    ps.busy_slot_blocks += plan.busy_slot_blocks;
     return rc;
 }
 
@@ -879,6 +1045,47 @@ int icw_transcode_files_fir(const icw_config *cfg, const icw_node *const *nodes,
 {
     if (k_M < 2 || k_M > ICW_FIR_MAX_ORDER || (k_M & 1) || !(k_beta >= 0.0 && k_beta < 1e3)) return ICW_EINVAL;
     return transcode_lists(cfg, nodes, n_nodes, bypass_list, in_paths, out_paths, n, k_M, k_beta, opts, stats, status);
+}
+
+/* icw_transcode_files_lists through pools of opts->slots streams (include/icw_reader.h) */
+int icw_transcode_files_pool(const icw_config *cfg, const icw_node *const *nodes, const int *n_nodes,
+                             const int *bypass_list, const char *const *in_paths, const char *const *out_paths,
+                             int n, const icw_pool_opts *opts, icw_pool_stats *stats, icw_meters *meters, int *status)
+{
+    if (!cfg || n < 0 || (n > 0 && (!in_paths || !out_paths || !nodes || !n_nodes))) return ICW_EINVAL;
+    icw_pool_opts po;
+    memset(&po, 0, sizeof(po));
+    po.batch.device = -1;
+    if (opts) po = *opts;
+    if (po.slots < 0 || (po.order != ICW_POOL_AS_GIVEN && po.order != ICW_POOL_LONGEST_FIRST)) return ICW_EINVAL;
+    if (cfg->fp_check) return ICW_EUNSUPPORTED;
+    if (meters && n > 0) memset(meters, 0, (size_t)n * sizeof(icw_meters));
+    icw_pool_stats ps;
+    memset(&ps, 0, sizeof(ps));
+    std::vector<int> form(n > 0 ? n : 1, 0);
+    /* the kinds: real input or CWAVE (the frame of the call keeps them apart), and within each the form of the
+     * list -- register (-1) or bus (-2), as ICW_BATCH_MERGE_BUS keeps them apart */
+    const int rc = for_file_groups(
+        in_paths, out_paths, n, &ps.batch, status,
+        [&](int i, Job &j) {
+            if (n_nodes[i] < 0 || (n_nodes[i] > 0 && !nodes[i])) return (int)ICW_EINVAL;
+            form[i] = icw_graph_form(cfg, nodes[i], n_nodes[i], bypass_list ? bypass_list[i] : cfg->bypass_list);
+            if (form[i] < 0) return form[i];            /* ICW_EGRAPH: the rest of the call goes on */
+            return accept_wav(in_paths[i], out_paths[i], &j.info);
+        },
+        [&](int i) { return form[i] == 1 ? -2 : -1; },
+        [&](int key, std::vector<Job *> &g, icw_batch_stats &st, int *sts) {
+            FileLists fl;
+            fl.nodes = nodes;
+            fl.n_nodes = n_nodes;
+            fl.bypass = bypass_list;
+            fl.per_stream = true;
+            fl.bus = key == -2;
+            return run_pool(*cfg, g, po, fl, st, ps, meters, sts);
+        },
+        ICW_BATCH_MERGE_INPUTS | ICW_BATCH_MERGE_CWAVE);
+    if (stats) *stats = ps;
+    return rc;
 }
 
 }  /* extern "C" */

@@ -788,7 +788,12 @@ int icw_stream_init(icw_ctx *c, int first, int count)
     DevState &s = c->st;
     const size_t f = (size_t)first, n = (size_t)count;
     hipStream_t st = c->stream;
-    bool ok = reset_rings(c, f, n, st);
+    /* a stream that has run (a pool slot between two files, icw_transcode_files_pool): its kernels are on
+     * several streams, the caller's among them, and none of them may still write the state reset here */
+    bool ok = quiesce(c) == hipSuccess;
+    ok &= reset_rings(c, f, n, st);
+    /* the encoders' saturation counts (icw_encode_clipped), where a call has made them */
+    if (c->enc_clipped) ok &= hipMemsetAsync(c->enc_clipped + f, 0, n * sizeof(unsigned long long), st) == hipSuccess;
     ok &= hipMemsetAsync(s.pos + f, 0, n * sizeof(long long), st) == hipSuccess;
     ok &= hipMemsetAsync(s.n_frame + f, 0, n * sizeof(unsigned long long), st) == hipSuccess;
     for (size_t i = 0; i < n; ++i) c->nf_host[f + i] = 0;

@@ -649,6 +649,44 @@ def transcode_files_fir(cfg, node_lists, in_paths, out_paths, k_M, k_beta=8.0, b
     return rc, st, [status[i] for i in range(n)]
 
 
+def pool_plan(totals, slots, block_frames=0, order=abi.POOL_AS_GIVEN):
+    """icw_pool_plan (host only): the plan icw_transcode_files_pool executes for one pool of files of `totals`
+    frames (tails included); returns (rc, per-file slots, per-file start blocks, stats) -- slot and start are -1
+    for a file without frames"""
+    n = len(totals)
+    tot = (C.c_int64 * max(1, n))(*[int(t) for t in totals])
+    slot = (C.c_int32 * max(1, n))()
+    start = (C.c_int64 * max(1, n))()
+    st = abi.PoolStats()
+    rc = load().icw_pool_plan(tot, n, int(slots), int(block_frames), int(order), slot, start, C.byref(st))
+    return rc, [slot[i] for i in range(n)], [start[i] for i in range(n)], st
+
+
+def transcode_files_pool(cfg, node_lists, in_paths, out_paths, slots=0, order=abi.POOL_AS_GIVEN, bypass_lists=None,
+                         fade_in_ms=0, fade_out_ms=0, sec_align=0, block_frames=0, device=-1, want_meters=True):
+    """icw_transcode_files_pool: transcode_files_lists through pools of `slots` streams, a slot refilled with the
+    next file of the queue as its file ends; returns (rc, pool stats, per-file status, per-file meters as
+    Context.meters gives them -- None with want_meters False)"""
+    n = len(in_paths)
+    assert len(node_lists) == n and len(out_paths) == n and (bypass_lists is None or len(bypass_lists) == n)
+    ins = (C.c_char_p * max(1, n))(*[str(p).encode() for p in in_paths])
+    outs = (C.c_char_p * max(1, n))(*[str(p).encode() for p in out_paths])
+    arrs = [graph_nodes(nl) for nl in node_lists]
+    ptrs = (C.POINTER(abi.Node) * max(1, n))(*[C.cast(a, C.POINTER(abi.Node)) for a in arrs])
+    cnt = (C.c_int * max(1, n))(*[len(nl) for nl in node_lists])
+    byp = (C.c_int * max(1, n))(*[int(b) for b in bypass_lists]) if bypass_lists is not None else None
+    o = abi.PoolOpts(abi.BatchOpts(fade_in_ms, fade_out_ms, sec_align, block_frames, device, 0), int(slots), int(order))
+    st = abi.PoolStats()
+    status = (C.c_int * max(1, n))()
+    mt = (abi.Meters * max(1, n))() if want_meters else None
+    rc = load().icw_transcode_files_pool(C.byref(cfg), ptrs, cnt, byp, ins, outs, n, C.byref(o), C.byref(st), mt, status)
+    meters = None
+    if want_meters:
+        meters = [{"clips": (m.clips[0], m.clips[1]), "peak_db": (m.peak_db[0], m.peak_db[1]), "desubnorm": m.desubnorm}
+                  for m in list(mt)[:n]]
+    return rc, st, [status[i] for i in range(n)], meters
+
+
 def cwave_frame_bytes(cw_format, channels):
     """icw_cwave_frame_bytes: bytes of one CWAVE frame for an input of `channels` channels (0: invalid)"""
     return int(load().icw_cwave_frame_bytes(cw_format, channels))

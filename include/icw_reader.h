@@ -117,6 +117,66 @@ int icw_transcode_files_fir(const icw_config *cfg, const icw_node *const *nodes,
                             const int *bypass_list, const char *const *in_paths, const char *const *out_paths, int n,
                             int32_t k_M, double k_beta, const icw_batch_opts *opts, icw_batch_stats *stats, int *status);
 
+/* ---- a fixed pool of stream slots, refilled as files end ---- */
+#define ICW_POOL_AS_GIVEN      0        /* files start in the order of the call's arrays */
+#define ICW_POOL_LONGEST_FIRST 1        /* by frames (tail included), descending; equal lengths keep their order */
+
+typedef struct icw_pool_opts {
+    icw_batch_opts batch;               /* fades, sec_align, block_frames, device; the MERGE bits are ignored: a
+                                           pool merges by construction */
+    int32_t slots;                      /* streams per pool context; 0 or >= the kind's file count: one slot per file */
+    int32_t order;                      /* ICW_POOL_* */
+} icw_pool_opts;
+
+typedef struct icw_pool_stats {
+    icw_batch_stats batch;              /* n_groups counts pool contexts */
+    int32_t  slots;                     /* widest pool used */
+    int32_t  refills;                   /* files opened in a slot that had held another */
+    uint64_t blocks;                    /* launch calls, summed over the pools */
+    uint64_t slot_blocks, busy_slot_blocks;   /* slots * blocks; those in which the slot held frames of a file */
+} icw_pool_stats;
+
+/* icw_transcode_files_lists through pools of `slots` streams: a context no wider than the chip needs,
+ * whatever the library's size, and no slot-blocks spent on files that have ended while the longest still
+ * runs.  A slot whose file has ended is re-initialised (icw_stream_init: the state of a fresh context's
+ * stream, every piece of it) and opens the next file of the queue at the next block boundary; the staging
+ * buffers are slots * block_frames frames.
+ * nodes / n_nodes / bypass_list are per file, as in icw_transcode_files_lists (NULL bypass_list: cfg's).
+ * A call covers streams of one kind, so the files run in one pool context per kind, each of min(slots, files
+ * of that kind) streams: real-input files with register-form lists; real-input files with bus-form lists
+ * (icw_enable_stream_bus); CWAVE files (icw_enable_stream_cwave) -- those too apart by the form of their
+ * lists, as ICW_BATCH_MERGE_BUS keeps them.
+ * Per-file semantics are icw_transcode_files_lists' own: every file a fresh stream, fades and the sec_align
+ * tail at the file's own rate, a 44-byte header and `total` frames, the same refusals and per-file status --
+ * and the bytes of every output file equal what icw_transcode_files_lists writes for it, whatever slots,
+ * order, block_frames and the file's neighbours are.
+ * The schedule is a plan made before the first block (icw_pool_plan: the same function): a file starts at a
+ * block boundary in the lowest-numbered free slot, files start in queue order, a slot is free from the block
+ * after the one that holds its file's last frame (tail included).  stats are the plan's.  A file refused at
+ * parse or open time takes no slot; one that fails mid-way (short read) keeps its status and its slot until
+ * its planned end.  A slot with no file is fed the zero sample of its last input; its output is written
+ * nowhere and counted in nothing.
+ * meters (nullable, n entries): entry i gets file i's clips, peaks and de-subnorm count, read with
+ * icw_get_meters after the file's last block and before its slot is re-initialised (a pool makes them
+ * unrecoverable afterwards).  The last block is whole: up to block_frames - 1 frames of the zero sample
+ * beyond `total` have gone through the stream by then.  Entries of files that took no slot are zero.
+ * Returns ICW_EINVAL for slots < 0 or an unknown order (nothing runs, nothing is written) and
+ * ICW_EUNSUPPORTED for cfg->fp_check; else ICW_OK if every file was transcoded, else one of the files'
+ * errors, as icw_transcode_files_lists returns it.
+ * Not offered: the FIR converter, the three CWAVE encoders, icw_transcode_files_devices / icw_group, and
+ * per-file renders or Hilbert settings (the file entry points take none). */
+int icw_transcode_files_pool(const icw_config *cfg, const icw_node *const *nodes, const int *n_nodes,
+                             const int *bypass_list, const char *const *in_paths, const char *const *out_paths,
+                             int n, const icw_pool_opts *opts, icw_pool_stats *stats, icw_meters *meters, int *status);
+
+/* The plan icw_transcode_files_pool executes for ONE pool (host arithmetic; no device is touched).  total[i]:
+ * file i's frames, tail included; a file with total <= 0 takes no slot.  slot / start_block (nullable, n
+ * entries): file i's slot and the block in which it starts, -1 for a file that takes none.  stats (nullable):
+ * slots, refills, blocks, slot_blocks and busy_slot_blocks of the plan; `batch` is zeroed.  block_frames 0:
+ * 65536.  Returns ICW_EINVAL for slots < 0, block_frames < 0 or an unknown order. */
+int icw_pool_plan(const int64_t *total, int n, int32_t slots, int32_t block_frames, int32_t order,
+                  int32_t *slot, int64_t *start_block, icw_pool_stats *stats);
+
 /* ---- convert: WAV files -> CWAVE files (the external converter cwave.h:56-58 names) ---- */
 /* icw_cwave_enc_opts.reserved_ / icw_cwave_enc_iir_opts.reserved_ are the flags word (0: one context per
  * (rate, format, channels) group).  ICW_ENC_MERGE_INPUTS: every accepted file goes into ONE context, each
