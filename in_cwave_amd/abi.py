@@ -147,6 +147,22 @@ class PoolStats(C.Structure):
                 ("slot_blocks", C.c_uint64), ("busy_slot_blocks", C.c_uint64)]
 
 
+BATCH_TIMING = 8         # ICW_BATCH_TIMING: icw_transcode_files_jobs times every block's kernels (JobsStats.kernel_s)
+
+
+class FileJob(C.Structure):
+    """icw_file_job (include/icw_reader.h): one file's list, render with depth and Hilbert converter"""
+    _fields_ = [("nodes", C.POINTER(Node)), ("n_nodes", C.c_int32), ("bypass_list", C.c_int32), ("render", RenderCfg),
+                ("need24bits", C.c_int32), ("hilbert_type", C.c_uint32), ("iir_kahan", C.c_int32),
+                ("iir_subnorm_reject", C.c_int32)]
+
+
+class JobsStats(C.Structure):
+    """icw_jobs_stats (include/icw_reader.h)"""
+    _fields_ = [("pool", PoolStats), ("classes", C.c_int32), ("hilbert_runs_max", C.c_int32),
+                ("render_runs_max", C.c_int32), ("kernel_s", C.c_double)]
+
+
 class CwaveEncOpts(C.Structure):
     """icw_cwave_enc_opts (include/icw_reader.h)"""
     _fields_ = [("k_M", C.c_int32), ("align", C.c_int32), ("k_beta", C.c_double), ("cw_format", C.c_uint32),
@@ -285,6 +301,12 @@ SIGNATURES = {
                                       C.POINTER(PoolStats), C.POINTER(Meters), C.POINTER(_i)]),
     "icw_pool_plan": (_i, [C.POINTER(C.c_int64), _i, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                            C.POINTER(C.c_int64), C.POINTER(PoolStats)]),
+    "icw_file_job_from_config": (None, [C.POINTER(Config), C.POINTER(Node), _i, C.POINTER(FileJob)]),
+    "icw_transcode_files_jobs": (_i, [C.POINTER(Config), C.POINTER(FileJob), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
+                                      _i, C.POINTER(PoolOpts), C.POINTER(JobsStats), C.POINTER(Meters), C.POINTER(_i)]),
+    "icw_pool_plan_classes": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_int32), _i, C.c_int32, C.c_int32, C.c_int32,
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(JobsStats)]),
+    "icw_file_job_classes": (_i, [C.POINTER(FileJob), _i, _i, C.POINTER(C.c_int32)]),
     "icw_group_create": (_i, [C.POINTER(Config), C.POINTER(Node), _i, _i, C.POINTER(_i), _i, C.POINTER(_vp),
                               C.POINTER(_i)]),
     "icw_group_destroy": (_i, [_vp]),

@@ -512,8 +512,17 @@ bool same_file_list(const FileLists &fl, int cfg_bypass, int a, int b)
  * the ended files' meters; the new file's input and list where they differ from what the slot holds;
  * icw_stream_init for a slot that has held a file; icw_stream_open last, since it takes the fades at the
  * stream's rate. */
+/* icw_transcode_files_jobs: file i's own render and converter beside its list (jobs null: the pool proper).  The
+ * plan then keeps every class of files in a range of slots of its own (icw_pool_make_plan_classes); each range
+ * gets its class's setting once, before block 0, and a refill stays what it is. */
+struct PoolJobs {
+    const icw_file_job *jobs = nullptr;   /* indexed like the files */
+    bool timing = false;                  /* ICW_BATCH_TIMING */
+    icw_jobs_stats *js = nullptr;
+};
+
 int run_pool(const icw_config &cfg0, std::vector<Job *> &jobs, const icw_pool_opts &po, const FileLists &fl,
-             icw_batch_stats &st, icw_pool_stats &ps, icw_meters *meters, int *status)
+             icw_batch_stats &st, icw_pool_stats &ps, icw_meters *meters, int *status, const PoolJobs &pj = PoolJobs())
 {
     const icw_batch_opts &o = po.batch;
     const int n = (int)jobs.size();
@@ -532,8 +541,33 @@ int run_pool(const icw_config &cfg0, std::vector<Job *> &jobs, const icw_pool_op
         fsz = std::max<size_t>(fsz, j.info.frame_bytes);
     }
     IcwPoolPlan plan;
-    int rc = icw_pool_make_plan(totals.data(), n, po.slots, B, po.order, plan);
-    if (rc != ICW_OK) return rc;
+    IcwClassPlan cplan;
+    std::vector<const icw_file_job *> class_job;          /* jobs: a job of every class, in layout order */
+    int rc = ICW_OK;
+    if (pj.jobs) {
+        /* a bus-form context holds one class (the caller's grouping); else the classes of the files' settings */
+        std::vector<icw_file_job> gj;
+        for (const Job *j : jobs) gj.push_back(pj.jobs[j->idx]);
+        const std::vector<char> take((size_t)n, 1);
+        std::vector<int32_t> pos((size_t)n, 0);
+        std::vector<std::pair<int, int>> settings(1);
+        const bool cw = jobs[0]->info.fmt >= ICW_FMT_CW_F64;
+        const int K = fl.bus ? 1 : icw_pool_job_classes(gj.data(), take.data(), n, cw, pos, &settings);
+        if ((rc = icw_pool_make_plan_classes(totals.data(), pos.data(), n, K, po.slots, B, po.order, cplan)) != ICW_OK) return rc;
+        plan = cplan.pool;
+        class_job.assign((size_t)K, nullptr);
+        for (int q = n - 1; q >= 0; --q) class_job[(size_t)pos[(size_t)q]] = &pj.jobs[jobs[(size_t)q]->idx];
+        int hruns = cw ? 0 : 1, rruns = 1;
+        for (int c = 1; c < K; ++c) {
+            hruns += !cw && settings[(size_t)c].first != settings[(size_t)c - 1].first;
+            rruns += settings[(size_t)c].second != settings[(size_t)c - 1].second;
+        }
+        pj.js->classes += K;
+        pj.js->hilbert_runs_max = std::max(pj.js->hilbert_runs_max, hruns);
+        pj.js->render_runs_max = std::max(pj.js->render_runs_max, rruns);
+    } else if ((rc = icw_pool_make_plan(totals.data(), n, po.slots, B, po.order, plan)) != ICW_OK) {
+        return rc;
+    }
     const int S = plan.slots, nb = (int)plan.blocks;
     std::vector<std::vector<Job *>> starts((size_t)nb + 1), ends((size_t)nb + 1);
     for (int q : plan.queue) {
@@ -550,18 +584,43 @@ int run_pool(const icw_config &cfg0, std::vector<Job *> &jobs, const icw_pool_op
     cfg.in_format = j0.info.fmt;
     cfg.in_channels = j0.info.channels;
     if (fl.bypass) cfg.bypass_list = fl.bypass[j0.idx];
+    if (pj.jobs) {
+        /* the context starts on the first file's setting too: a bus-form context keeps it, it has one class */
+        const icw_file_job &fj = pj.jobs[j0.idx];
+        cfg.render = fj.render;
+        cfg.need24bits = fj.need24bits;
+        cfg.hilbert_type = fj.hilbert_type;
+        cfg.iir_kahan = fj.iir_kahan;
+        cfg.iir_subnorm_reject = fj.iir_subnorm_reject;
+    }
     icw_ctx *ctx = nullptr;
     int accepted = 0;
     if ((rc = icw_create(&cfg, fl.nodes[j0.idx], fl.n_nodes[j0.idx], S, o.device, &ctx, &accepted)) != ICW_OK) return rc;
     std::unique_ptr<icw_ctx, int (*)(icw_ctx *)> guard(ctx, icw_destroy);
     if (j0.info.fmt >= ICW_FMT_CW_F64 && (rc = icw_enable_stream_cwave(ctx, 1)) != ICW_OK) return rc;
     if (fl.bus && (rc = icw_enable_stream_bus(ctx, 1)) != ICW_OK) return rc;
-    const int rs = icw_render_size(ctx), osz = 2 * rs;
+    /* every class's range gets its setting, once: the ranges never change class */
+    for (size_t c = 0; pj.jobs && !fl.bus && c < class_job.size(); ++c) {
+        const icw_file_job &fj = *class_job[c];
+        const int first = cplan.first[c], count = cplan.share[c];
+        if (j0.info.fmt < ICW_FMT_CW_F64 &&
+            (rc = icw_set_stream_hilbert(ctx, first, count, fj.hilbert_type, fj.iir_kahan, fj.iir_subnorm_reject)) != ICW_OK)
+            return rc;
+        if ((rc = icw_set_stream_render(ctx, first, count, &fj.render, fj.need24bits)) != ICW_OK) return rc;
+    }
+    const int rs = icw_render_size(ctx), osz = 2 * rs;    /* the widest in force: the rows' pitch */
     std::vector<const Job *> in_of((size_t)S, &j0), list_of((size_t)S, &j0);   /* whose input / list a slot holds */
     std::vector<char> used((size_t)S, 0);
     GroupPipe pp(jobs, S, B, fsz, (size_t)osz, st, status);
     pp.close_done = true;
+    /* every slot's own sample size, constant like its class: its files' headers and the bytes written of a row */
+    std::vector<int> slot_rs((size_t)S, rs);
+    for (int s = 0; pj.jobs && s < S; ++s) {
+        slot_rs[(size_t)s] = icw_stream_render_size(ctx, s);
+        pp.ofs.push_back(2 * (size_t)slot_rs[(size_t)s]);
+    }
     if (!pp.alloc()) return ICW_ENOMEM;
+    const unsigned flags = ICW_F_DEVICE_PTRS | (pj.timing ? ICW_F_TIMING : 0u);
     const auto read_meters = [&](int k) {
         int r = ICW_OK;
         for (Job *j : ends[(size_t)k])
@@ -570,8 +629,13 @@ int run_pool(const icw_config &cfg0, std::vector<Job *> &jobs, const icw_pool_op
     };
     rc = pp.run(nb,
                 [&](int p) {
-                    return icw_process_streams(ctx, 0, S, pp.din[p], (size_t)B * fsz, pp.dout[p], (size_t)B * osz, B,
-                                               ICW_F_DEVICE_PTRS, nullptr, pp.ks);
+                    int r = icw_process_streams(ctx, 0, S, pp.din[p], (size_t)B * fsz, pp.dout[p], (size_t)B * osz, B, flags,
+                                                nullptr, pp.ks);
+                    double ms[2] = {0.0, 0.0};
+                    int launches[2];
+                    if (r == ICW_OK && pj.timing && (r = icw_last_timing(ctx, ms, launches)) == ICW_OK)
+                        pj.js->kernel_s += (ms[0] + ms[1]) * 1e-3;
+                    return r;
                 },
                 [](int, int) { return (int)ICW_OK; },
                 [&](int k) {
@@ -579,7 +643,7 @@ int run_pool(const icw_config &cfg0, std::vector<Job *> &jobs, const icw_pool_op
                     for (Job *j : starts[(size_t)k]) {
                         pp.cur[(size_t)j->slot] = j;
                         unsigned char hdr[44];
-                        wav_header(hdr, j->info.sample_rate, rs, (uint64_t)j->total);
+                        wav_header(hdr, j->info.sample_rate, slot_rs[(size_t)j->slot], (uint64_t)j->total);
                         if (fwrite(hdr, 1, 44, j->out) != 44) status[j->idx] = ICW_EINVAL;
                         if (fseeko(j->in, j->info.data_offset, SEEK_SET)) status[j->idx] = ICW_EINVAL;
                     }
@@ -1085,6 +1149,88 @@ int icw_transcode_files_pool(const icw_config *cfg, const icw_node *const *nodes
         },
         ICW_BATCH_MERGE_INPUTS | ICW_BATCH_MERGE_CWAVE);
     if (stats) *stats = ps;
+    return rc;
+}
+
+void icw_file_job_from_config(const icw_config *cfg, const icw_node *nodes, int n_nodes, icw_file_job *job)
+{
+    if (!cfg || !job) return;
+    memset(job, 0, sizeof(*job));
+    job->nodes = nodes;
+    job->n_nodes = n_nodes;
+    job->bypass_list = cfg->bypass_list;
+    job->render = cfg->render;
+    job->need24bits = cfg->need24bits;
+    job->hilbert_type = cfg->hilbert_type;
+    job->iir_kahan = cfg->iir_kahan;
+    job->iir_subnorm_reject = cfg->iir_subnorm_reject;
+}
+
+/* icw_transcode_files_pool with file i's own render and Hilbert converter (include/icw_reader.h) */
+int icw_transcode_files_jobs(const icw_config *cfg, const icw_file_job *jobs, const char *const *in_paths,
+                             const char *const *out_paths, int n, const icw_pool_opts *opts, icw_jobs_stats *stats,
+                             icw_meters *meters, int *status)
+{
+    if (!cfg || n < 0 || (n > 0 && (!in_paths || !out_paths || !jobs))) return ICW_EINVAL;
+    icw_pool_opts po;
+    memset(&po, 0, sizeof(po));
+    po.batch.device = -1;
+    if (opts) po = *opts;
+    if (po.slots < 0 || (po.order != ICW_POOL_AS_GIVEN && po.order != ICW_POOL_LONGEST_FIRST)) return ICW_EINVAL;
+    if (cfg->fp_check) return ICW_EUNSUPPORTED;
+    if (meters && n > 0) memset(meters, 0, (size_t)n * sizeof(icw_meters));
+    icw_jobs_stats js;
+    memset(&js, 0, sizeof(js));
+    std::vector<const icw_node *> nodes((size_t)(n > 0 ? n : 1), nullptr);
+    std::vector<int> n_nodes((size_t)(n > 0 ? n : 1), 0), bypass((size_t)(n > 0 ? n : 1), 0), form((size_t)(n > 0 ? n : 1), 0);
+    std::vector<char> cwf((size_t)(n > 0 ? n : 1), 0);
+    for (int i = 0; i < n; ++i) {
+        nodes[(size_t)i] = jobs[i].nodes;
+        n_nodes[(size_t)i] = jobs[i].n_nodes;
+        bypass[(size_t)i] = jobs[i].bypass_list;
+    }
+    PoolJobs pj;
+    pj.jobs = jobs;
+    pj.timing = (po.batch.reserved_ & ICW_BATCH_TIMING) != 0;
+    pj.js = &js;
+    /* the kinds are the pool's -- real input or CWAVE, register form (-1) -- but a bus-form list runs in a context
+     * of the files of its kind that carry its setting: key k >= 0, the k-th distinct one of them */
+    std::vector<int> bus_first;
+    const auto same_setting = [&](int a, int b) {
+        const char one[2] = {1, 1};
+        const icw_file_job two[2] = {jobs[a], jobs[b]};
+        std::vector<int32_t> pos;
+        return cwf[(size_t)a] == cwf[(size_t)b] && icw_pool_job_classes(two, one, 2, cwf[(size_t)a] != 0, pos, nullptr) == 1;
+    };
+    const int rc = for_file_groups(
+        in_paths, out_paths, n, &js.pool.batch, status,
+        [&](int i, Job &j) {
+            if (n_nodes[(size_t)i] < 0 || (n_nodes[(size_t)i] > 0 && !nodes[(size_t)i]) || !icw_pool_job_ok(jobs[i]))
+                return (int)ICW_EINVAL;
+            form[(size_t)i] = icw_graph_form(cfg, nodes[(size_t)i], n_nodes[(size_t)i], bypass[(size_t)i]);
+            if (form[(size_t)i] < 0) return form[(size_t)i];   /* ICW_EGRAPH: the rest of the call goes on */
+            const int r = accept_wav(in_paths[i], out_paths[i], &j.info);
+            cwf[(size_t)i] = r == ICW_OK && j.info.fmt >= ICW_FMT_CW_F64;
+            return r;
+        },
+        [&](int i) {
+            if (form[(size_t)i] != 1) return -1;
+            for (size_t k = 0; k < bus_first.size(); ++k)
+                if (same_setting(bus_first[k], i)) return (int)k;
+            bus_first.push_back(i);
+            return (int)bus_first.size() - 1;
+        },
+        [&](int key, std::vector<Job *> &g, icw_batch_stats &st, int *sts) {
+            FileLists fl;
+            fl.nodes = nodes.data();
+            fl.n_nodes = n_nodes.data();
+            fl.bypass = bypass.data();
+            fl.per_stream = true;
+            fl.bus = key >= 0;
+            return run_pool(*cfg, g, po, fl, st, js.pool, meters, sts, pj);
+        },
+        ICW_BATCH_MERGE_INPUTS | ICW_BATCH_MERGE_CWAVE);
+    if (stats) *stats = js;
     return rc;
 }
 

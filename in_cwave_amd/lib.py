@@ -687,6 +687,69 @@ def transcode_files_pool(cfg, node_lists, in_paths, out_paths, slots=0, order=ab
     return rc, st, [status[i] for i in range(n)], meters
 
 
+def file_job(cfg, nodes):
+    """icw_file_job_from_config: the job of a file that is to be transcoded as `cfg` (an abi.Config: its render,
+    need24bits, Hilbert fields and bypass_list) with the list `nodes`; the FileJob keeps its node array alive"""
+    arr = graph_nodes(nodes)
+    job = abi.FileJob()
+    load().icw_file_job_from_config(C.byref(cfg), arr, len(nodes), C.byref(job))
+    job.keep_nodes = arr
+    return job
+
+
+def _job_array(jobs):
+    arr = (abi.FileJob * max(1, len(jobs)))()
+    for i, j in enumerate(jobs):
+        arr[i] = j
+    return arr
+
+
+def file_job_classes(jobs, cwave=False):
+    """icw_file_job_classes (host only): (number of classes, every job's class as its position in the layout of a
+    pool context that holds these jobs; -1 for a job whose fields are out of range)"""
+    n = len(jobs)
+    cls = (C.c_int32 * max(1, n))()
+    k = load().icw_file_job_classes(_job_array(jobs), n, int(bool(cwave)), cls)
+    return k, [cls[i] for i in range(n)]
+
+
+def pool_plan_classes(totals, classes, slots, block_frames=0, order=abi.POOL_AS_GIVEN):
+    """icw_pool_plan_classes (host only): pool_plan with file i of class classes[i], every class in a contiguous
+    range of slots of its own; returns (rc, per-file slots, per-file start blocks, JobsStats)"""
+    n = len(totals)
+    assert len(classes) == n
+    tot = (C.c_int64 * max(1, n))(*[int(t) for t in totals])
+    cls = (C.c_int32 * max(1, n))(*[int(c) for c in classes])
+    slot = (C.c_int32 * max(1, n))()
+    start = (C.c_int64 * max(1, n))()
+    st = abi.JobsStats()
+    rc = load().icw_pool_plan_classes(tot, cls, n, int(slots), int(block_frames), int(order), slot, start, C.byref(st))
+    return rc, [slot[i] for i in range(n)], [start[i] for i in range(n)], st
+
+
+def transcode_files_jobs(cfg, jobs, in_paths, out_paths, slots=0, order=abi.POOL_AS_GIVEN, fade_in_ms=0, fade_out_ms=0,
+                         sec_align=0, block_frames=0, device=-1, timing=False, want_meters=True):
+    """icw_transcode_files_jobs: transcode_files_pool with file i's own job (file_job: list, render and depth,
+    Hilbert converter); cfg gives frmod_scaled and the seeds.  timing: ICW_BATCH_TIMING.  Returns (rc, JobsStats,
+    per-file status, per-file meters as transcode_files_pool gives them)"""
+    n = len(in_paths)
+    assert len(jobs) == n and len(out_paths) == n
+    ins = (C.c_char_p * max(1, n))(*[str(p).encode() for p in in_paths])
+    outs = (C.c_char_p * max(1, n))(*[str(p).encode() for p in out_paths])
+    arr = _job_array(jobs)
+    o = abi.PoolOpts(abi.BatchOpts(fade_in_ms, fade_out_ms, sec_align, block_frames, device,
+                                   abi.BATCH_TIMING if timing else 0), int(slots), int(order))
+    st = abi.JobsStats()
+    status = (C.c_int * max(1, n))()
+    mt = (abi.Meters * max(1, n))() if want_meters else None
+    rc = load().icw_transcode_files_jobs(C.byref(cfg), arr, ins, outs, n, C.byref(o), C.byref(st), mt, status)
+    meters = None
+    if want_meters:
+        meters = [{"clips": (m.clips[0], m.clips[1]), "peak_db": (m.peak_db[0], m.peak_db[1]), "desubnorm": m.desubnorm}
+                  for m in list(mt)[:n]]
+    return rc, st, [status[i] for i in range(n)], meters
+
+
 def cwave_frame_bytes(cw_format, channels):
     """icw_cwave_frame_bytes: bytes of one CWAVE frame for an input of `channels` channels (0: invalid)"""
     return int(load().icw_cwave_frame_bytes(cw_format, channels))

@@ -445,8 +445,9 @@ int icw_set_hilbert_config(icw_ctx *ctx, int kahan, int subnorm_reject);
  *                     - a cfg.fp_check context;
  *                     - a bus-form list in force, and icw_set_graph (or a list primitive) with a bus-form
  *                       list.
- * Not served: icw_group and the icw_amod_* drop-in (their render stays context-wide), and per-file renders
- * in icw_transcode_files*.  The two encoders run no render and are not concerned.  The state blob does not
+ * Not served: icw_group and the icw_amod_* drop-in (their render stays context-wide).  Per-file renders are
+ * icw_transcode_files_jobs (icw_reader.h); the other icw_transcode_files* entry points take one render.  The two
+ * encoders run no render and are not concerned.  The state blob does not
  * carry the render selection, as it carries neither list nor input: icw_set_state expects the stream's
  * render to be set as it was. */
 int icw_set_stream_render(icw_ctx *ctx, int first, int count, const icw_render_cfg *render, int need24bits);
@@ -494,8 +495,9 @@ int icw_stream_render_size(const icw_ctx *ctx, int s); /* bytes per output chann
  *                       list;
  *                     and, while the count is above 1, the two context encoders icw_encode_cwave and
  *                     icw_encode_cwave_iir.
- * Not served: icw_group and the icw_amod_* drop-in (their converter stays context-wide), and per-file
- * converter settings in icw_transcode_files*. */
+ * Not served: icw_group and the icw_amod_* drop-in (their converter stays context-wide).  Per-file converter
+ * settings are icw_transcode_files_jobs (icw_reader.h), which keeps the streams of one setting adjacent; the
+ * other icw_transcode_files* entry points take one setting. */
 int icw_set_stream_hilbert(icw_ctx *ctx, int first, int count, uint32_t type, int kahan, int subnorm_reject);
 int icw_stream_hilbert_count(const icw_ctx *ctx);     /* distinct (type, kahan, reject) in force; 1 on a fresh context */
 

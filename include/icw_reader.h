@@ -163,8 +163,8 @@ typedef struct icw_pool_stats {
  * Returns ICW_EINVAL for slots < 0 or an unknown order (nothing runs, nothing is written) and
  * ICW_EUNSUPPORTED for cfg->fp_check; else ICW_OK if every file was transcoded, else one of the files'
  * errors, as icw_transcode_files_lists returns it.
- * Not offered: the FIR converter, the three CWAVE encoders, icw_transcode_files_devices / icw_group, and
- * per-file renders or Hilbert settings (the file entry points take none). */
+ * Not offered: the FIR converter, the three CWAVE encoders, icw_transcode_files_devices / icw_group.  Per-file
+ * renders and Hilbert settings: icw_transcode_files_jobs below. */
 int icw_transcode_files_pool(const icw_config *cfg, const icw_node *const *nodes, const int *n_nodes,
                              const int *bypass_list, const char *const *in_paths, const char *const *out_paths,
                              int n, const icw_pool_opts *opts, icw_pool_stats *stats, icw_meters *meters, int *status);
@@ -176,6 +176,93 @@ int icw_transcode_files_pool(const icw_config *cfg, const icw_node *const *nodes
  * 65536.  Returns ICW_EINVAL for slots < 0, block_frames < 0 or an unknown order. */
 int icw_pool_plan(const int64_t *total, int n, int32_t slots, int32_t block_frames, int32_t order,
                   int32_t *slot, int64_t *start_block, icw_pool_stats *stats);
+
+/* ---- the pool with per-file settings: every file a job of its own in_cwave.cfg ---- */
+/* What a job takes from its configuration: the DSP list and, beyond what icw_transcode_files_pool carries per
+ * file, the render with its depth and the Hilbert converter. */
+typedef struct icw_file_job {
+    const icw_node *nodes; int32_t n_nodes; int32_t bypass_list;
+    icw_render_cfg render; int32_t need24bits;
+    uint32_t hilbert_type; int32_t iir_kahan, iir_subnorm_reject;
+} icw_file_job;
+
+typedef struct icw_jobs_stats {
+    icw_pool_stats pool;
+    int32_t classes;                       /* distinct settings, summed over the pool contexts */
+    int32_t hilbert_runs_max, render_runs_max;   /* the most runs any one call was cut into (from the plan) */
+    double  kernel_s;                      /* with ICW_BATCH_TIMING: icw_last_timing summed over the blocks; else 0 */
+} icw_jobs_stats;
+
+/* icw_batch_opts.reserved_ bit of icw_transcode_files_jobs alone: every block's call runs with ICW_F_TIMING and
+ * stats->kernel_s sums what icw_last_timing reports (the recurrence and the output kernel), in seconds.  The call
+ * then waits for every block's kernels, so its wall time is not that of a run without the bit; the bytes are.
+ * Every other file entry point ignores the bit, icw_transcode_files_pool included. */
+#define ICW_BATCH_TIMING 8
+
+/* job <- the per-job fields of a configuration (icw_config_load's icw_file_config.cfg, or a hand-made one): its
+ * render, need24bits, hilbert_type, iir_kahan, iir_subnorm_reject and bypass_list, with the list given. */
+void icw_file_job_from_config(const icw_config *cfg, const icw_node *nodes, int n_nodes, icw_file_job *job);
+
+/* icw_transcode_files_pool with file i's own job: its list, its render and depth, its Hilbert converter.  A host
+ * whose jobs come from several in_cwave.cfg files makes ONE call, and the files share pool contexts as wide as
+ * the chip needs, instead of one call -- one narrow context -- per distinct setting.
+ * cfg supplies what stays context-wide: frmod_scaled, the seeds, fp_check (ICW_EUNSUPPORTED, as the pool);
+ * its render, need24bits, Hilbert and list fields are not read.
+ * Kinds are the pool's, one pool context each: real input with register-form lists, real input with bus-form
+ * lists, CWAVE input by the form of the list.  Within a kind, files of one setting are one CLASS:
+ *   - real input, register form: equal (hilbert_type, kahan, reject) and equal (render, depth) -- the equalities
+ *     of icw_set_stream_hilbert and icw_set_stream_render;
+ *   - CWAVE input, register form: equal (render, depth) alone -- no recurrence runs, so two files that differ
+ *     only in Hilbert fields are one class;
+ *   - bus-form lists cannot stand beside differing renders or converters in one context (icw.h lists the
+ *     refusals): each class of them runs in a pool context of its own, its setting installed context-wide.
+ *     stats->pool.batch.n_groups counts contexts.
+ * The plan (icw_pool_plan_classes below; icw_file_job_classes gives the classes) keeps every class in one
+ * contiguous range of slots for the whole run, so the streams of one setting are neighbours whatever the order of
+ * the files: a call is cut into as many Hilbert runs as the context has distinct Hilbert settings (classes that
+ * share one are laid out side by side) and at most as many render runs as it has classes.  Before block 0 each
+ * range gets its setting once (icw_set_stream_hilbert on real input, icw_set_stream_render on every range); a
+ * refill is the pool's: input and list setters, icw_stream_init, icw_stream_open.
+ * Limits: a range is never handed to another class, also when its queue is empty -- the price shows in
+ * stats->pool.busy_slot_blocks / slot_blocks; a pool is at least as wide as it has classes, also when opts->slots
+ * is smaller (stats->pool.slots reports the width used); frmod_scaled, the seeds and fp_check are not per file.
+ * Output: every file's header carries its own depth (block align 4 or 6); staging rows are sized by the widest
+ * frame of the context.  The bytes of every output file, header included, are those icw_transcode_files_lists
+ * writes for that file with a config that carries the job's settings, whatever slots, order, block_frames and
+ * the neighbours are.  meters as in the pool, each against its stream's own bound.
+ * Per-file status as in the pool; a job whose render fields or hilbert_type are out of range gets ICW_EINVAL, a
+ * rejected list ICW_EGRAPH: such a file takes no slot, belongs to no class, and the rest completes.
+ * Not offered: what the pool does not offer. */
+int  icw_transcode_files_jobs(const icw_config *cfg, const icw_file_job *jobs, const char *const *in_paths,
+                              const char *const *out_paths, int n, const icw_pool_opts *opts,
+                              icw_jobs_stats *stats, icw_meters *meters, int *status);
+
+/* icw_pool_plan with classes: the plan icw_transcode_files_jobs executes for ONE pool context (host arithmetic).
+ * cls[i] >= 0: file i's class; a file with total <= 0 takes no slot and its class counts for nothing.  K: the
+ * distinct classes among the files that take a slot.
+ * Every class gets one contiguous range of slots, fixed for the whole run; the ranges follow each other from
+ * slot 0 in the order of each class's first file in the arrays.  The width is min(slots, files), all files for
+ * slots 0, raised to K where it would be smaller.  A class's share of it is apportioned by largest remainder in
+ * proportion to its busy slot-blocks, the sum of ceil(total / block_frames) over its files: a class whose
+ * proportional part is below 1 gets one slot and the others share the rest in proportion; whole parts first,
+ * then the leftover slots to the largest remainders, ties to the class laid out first.  A class given more than
+ * its file count keeps its file count, and the slots so freed are apportioned among the other classes by the
+ * same rule.  Within its range a class is planned as icw_pool_plan plans a pool of that many slots: lowest free
+ * slot, queue order (as given or longest first, stable) among the class's files, a slot free from the block after
+ * its file's last.  With one class the plan and its statistics are icw_pool_plan's.
+ * stats (nullable): pool.slots (the width used), refills, blocks (the longest range's), slot_blocks,
+ * busy_slot_blocks; classes = K; the classes are opaque here, so hilbert_runs_max = render_runs_max = K;
+ * pool.batch and kernel_s are zeroed.  Returns ICW_EINVAL for what icw_pool_plan refuses and for a negative class
+ * of a file that takes a slot. */
+int icw_pool_plan_classes(const int64_t *total, const int32_t *cls, int n, int32_t slots, int32_t block_frames,
+                          int32_t order, int32_t *slot, int64_t *start_block, icw_jobs_stats *stats);
+
+/* The classes icw_transcode_files_jobs makes of the jobs of one pool context (host arithmetic): cls[i] is job
+ * i's class as its position in the layout, -1 for a job whose fields are out of range; cwave != 0: the CWAVE rule
+ * (render and depth alone).  Classes are ordered by the first appearance of their Hilbert setting, then of their
+ * render, so classes that share a Hilbert setting are neighbours.  Files ordered by cls (stable) and given to
+ * icw_pool_plan_classes give the transcoder's plan.  Returns the number of classes, or ICW_EINVAL. */
+int icw_file_job_classes(const icw_file_job *jobs, int n, int cwave, int32_t *cls);
 
 /* ---- convert: WAV files -> CWAVE files (the external converter cwave.h:56-58 names) ---- */
 /* icw_cwave_enc_opts.reserved_ / icw_cwave_enc_iir_opts.reserved_ are the flags word (0: one context per
