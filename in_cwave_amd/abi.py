@@ -205,6 +205,8 @@ SIGNATURES = {
     "icw_stream_input_count": (_i, [_vp]),
     "icw_set_fir_hilbert": (_i, [_vp, C.c_int32, C.c_double]),
     "icw_enable_stream_fir": (_i, [_vp, _i]),
+    "icw_set_stream_fir": (_i, [_vp, _i, _i, C.c_int32, C.c_double]),
+    "icw_stream_fir_count": (_i, [_vp]),
     "icw_enable_stream_encode": (_i, [_vp, _i]),
     "icw_enable_stream_cwave": (_i, [_vp, _i]),
     "icw_enable_stream_bus": (_i, [_vp, _i]),

@@ -135,9 +135,9 @@ double bessel_i0(double x)
 bool fir_clear(icw_ctx *c, size_t f, size_t n, hipStream_t st)
 {
     bool ok = true;
-    const size_t row = 2 * (size_t)c->fir_M;
+    const size_t at = c->fir_off[f], len = c->fir_off[f + n] - at;     /* every stream's rows at its own order */
     for (double *h : c->fir_hist)
-        if (h) ok &= hipMemsetAsync(h + f * row, 0, n * row * sizeof(double), st) == hipSuccess;
+        if (h && len) ok &= hipMemsetAsync(h + at, 0, len * sizeof(double), st) == hipSuccess;
     return ok;
 }
 
@@ -147,7 +147,7 @@ void free_all(icw_ctx *c)
     void *ptrs[] = {c->enc_clipped, c->s1_stamps, s.mt, s.mt_idx, s.rs, s.lr_equal, s.fes, s.err, s.hist, s.sncnt, s.hq_phase, s.pos, s.fade,
                     s.n_frame, s.bus, s.clips, s.peak_bits, c->d_prog, c->d_progs, c->d_bprogs, c->d_bruns, c->d_pid, c->d_inputs, c->d_rtab, c->d_hpc, c->trig, c->d_in, c->d_out,
                     c->d_pre, c->d_xin,
-                    c->d_fir_g, c->fir_hist[0], c->fir_hist[1], c->dwords, c->dbk, c->dflag};
+                    c->d_fir_g, c->d_fconv, c->fir_hist[0], c->fir_hist[1], c->dwords, c->dbk, c->dflag};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (int p = 0; p < kSets; ++p) {
@@ -648,6 +648,115 @@ int install_hilberts(icw_ctx *c, StreamTable<HilbEnt> &t, int first, int count)
     return ICW_OK;
 }
 
+/* ---- the FIR converter table (icw_set_fir_hilbert, icw_set_stream_fir) ---- */
+
+bool same_fir(const FirEnt &a, const FirEnt &b) { return a.M == b.M && !memcmp(&a.beta, &b.beta, sizeof(double)); }
+
+/* Install a candidate FIR converter table (the caller holds c->mu and has waited for the context's work); the
+ * streams [first, first + count) start from a zero history.  Everything the device needs -- the entries' taps,
+ * the two history buffers at the new orders, the streams' descriptors while the entries are several -- is
+ * built in fresh memory first, so a failure leaves the old converters in force.  The history is re-laid by
+ * the new orders: a stream outside the range keeps its order, so the streams before the range keep their
+ * offsets and the streams after it move as one piece; both pieces are copied from the buffer in force
+ * (fir_par) into the fresh buffer 0, the range itself stays zero, and the parity restarts. */
+int install_firs(icw_ctx *c, StreamTable<FirEnt> &t, int first, int count)
+{
+    const size_t n = t.size(), S = (size_t)c->n_streams, f = (size_t)first, e = f + (size_t)count;
+    const bool on = t.ents[0].M > 0;                  /* all FIR or none: every entry is, or the one is off */
+    std::vector<double> g;
+    std::vector<size_t> off(S + 1, 0);
+    int mmax = 0;
+    for (FirEnt &x : t.ents) {
+        if (!on) break;
+        x.goff = g.size();
+        x.nt = (x.M / 2 + 1) / 2;
+        g.resize(x.goff + (size_t)((x.nt + 1) & ~1));   /* every entry's taps 16-byte aligned */
+        if (icw_fir_taps(x.M, x.beta, g.data() + x.goff, x.nt) != x.nt) return ICW_EINVAL;
+        mmax = std::max(mmax, x.M);
+    }
+    for (size_t s = 0; s < S; ++s) off[s + 1] = off[s] + 2 * (size_t)t.at(s).M;
+    double *fg = nullptr, *h0 = nullptr, *h1 = nullptr;
+    IcwFirConv *fd = nullptr;
+    int32_t *pid = nullptr;
+    const auto drop = [&](int rc) {
+        for (void *p : {(void *)fg, (void *)h0, (void *)h1, (void *)fd, (void *)pid})
+            if (p) (void)hipFree(p);
+        return rc;
+    };
+    if (on) {
+        int rc = dalloc(&fg, g.size());
+        rc |= dalloc(&h0, off[S]);
+        rc |= dalloc(&h1, off[S]);
+        /* several entries: every call takes the per-stream kernels, which read K2's selection rows */
+        if (n > 1 && !c->d_pid) rc |= dalloc(&pid, S * kPidWords);
+        if (n > 1 && hipMalloc((void **)&fd, S * sizeof(IcwFirConv)) != hipSuccess) rc |= ICW_ENOMEM;
+        if (rc != ICW_OK) return drop(rc == ICW_ENOMEM ? ICW_ENOMEM : ICW_EDEVICE);
+        bool ok = hipMemcpy(fg, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+        const double *old = c->fir_hist[c->fir_par];
+        if (old && c->fir_M > 0) {
+            const std::vector<size_t> &oo = c->fir_off;
+            if (oo[f]) ok = ok && hipMemcpy(h0, old, oo[f] * sizeof(double), hipMemcpyDeviceToDevice) == hipSuccess;
+            if (oo[S] > oo[e])
+                ok = ok && hipMemcpy(h0 + off[e], old + oo[e], (oo[S] - oo[e]) * sizeof(double), hipMemcpyDeviceToDevice) == hipSuccess;
+        }
+        if (n > 1) {
+            std::vector<IcwFirConv> h(S);
+            for (size_t s = 0; s < S; ++s) {
+                const FirEnt &x = t.at(s);
+                h[s].M = x.M;
+                h[s].nt = x.nt;
+                h[s].g = fg + x.goff;
+                h[s].hoff = off[s];
+            }
+            ok = ok && hipMemcpy(fd, h.data(), S * sizeof(IcwFirConv), hipMemcpyHostToDevice) == hipSuccess;
+        }
+        /* the fills and copies above ran on the null stream: all of them done before a call on the context's
+         * or the caller's stream may read the fresh buffers */
+        ok = ok && hipDeviceSynchronize() == hipSuccess;
+        if (!ok) return drop(ICW_EDEVICE);
+    }
+    for (void *p : {(void *)c->d_fir_g, (void *)c->fir_hist[0], (void *)c->fir_hist[1], (void *)c->d_fconv})
+        if (p) (void)hipFree(p);
+    c->d_fir_g = fg;
+    c->fir_hist[0] = h0;
+    c->fir_hist[1] = h1;
+    c->d_fconv = fd;
+    if (pid) c->d_pid = pid;
+    c->fir_par = 0;
+    c->fir_off = std::move(off);
+    c->fir_Mmax = mmax;
+    c->firs = std::move(t);
+    c->fir_M = c->firs.ents[0].M;
+    c->fir_nt = c->firs.ents[0].nt;
+    c->fir_beta = on ? c->firs.ents[0].beta : 0.0;
+    c->pid_valid = false;                 /* with the converter on, every (list, rate) pair has a slab */
+    return ICW_OK;
+}
+
+/* icw_set_fir_hilbert (every stream) and icw_set_stream_fir (a range): the refusals both share, the candidate
+ * table, the install */
+int set_fir_range(icw_ctx *c, int first, int count, int32_t M, double beta)
+{
+    /* beside per-stream lists or inputs only once the host has asked for it (icw_enable_stream_fir): the
+     * converter's kernels then run their per-stream form */
+    if (M > 0 && !c->fir_streams && (c->lists.size() > 1 || c->inputs.size() > 1)) return ICW_EUNSUPPORTED;
+    /* nor beside per-stream CWAVE inputs (icw_enable_stream_cwave): the converter's per-stream kernels read
+     * real formats only, and icw_set_stream_input refuses to build that state from its side */
+    if (M > 0 && c->inputs.size() > 1 && any_cwave(c->inputs)) return ICW_EUNSUPPORTED;
+    /* nor beside per-stream renders (icw_set_stream_render): the fused converter renders with one */
+    if (M > 0 && c->renders.size() > 1) return ICW_EUNSUPPORTED;
+    /* nor beside per-stream Hilbert converters (icw_set_stream_hilbert): it replaces the IIR for every stream */
+    if (M > 0 && c->hilbs.size() > 1) return ICW_EUNSUPPORTED;
+    /* nor beside bus-form lists that stand beside others (icw_enable_stream_bus): the mixed K4 follows K2 */
+    if (M > 0 && c->bus_lists) return ICW_EUNSUPPORTED;
+    if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
+    FirEnt x;
+    x.M = M;
+    x.beta = M > 0 ? beta : 0.0;
+    StreamTable<FirEnt> t = c->firs.assigned((size_t)first, (size_t)count, x, same_fir);
+    return install_firs(c, t, first, count);
+}
+
 }  // namespace
 
 extern "C" {
@@ -704,6 +813,8 @@ int icw_create(const icw_config *cfg, const icw_node *nodes, int n_nodes, int n_
     c->inputs.reset((size_t)n_streams, make_input(cfg->sample_rate, cfg->in_format, cfg->in_channels));
     c->hilbs.reset((size_t)n_streams, make_hilb(cfg->hilbert_type, cfg->iir_kahan, cfg->iir_subnorm_reject));
     mirror_hilbs(c);
+    c->firs.reset((size_t)n_streams, FirEnt{});
+    c->fir_off.assign((size_t)n_streams + 1, 0);
     c->renders.reset((size_t)n_streams, make_render(c, cfg->render, cfg->need24bits));
     mirror_renders(c);
     for (int ch = 0; ch < 2; ++ch) {
@@ -882,46 +993,31 @@ int icw_set_fir_hilbert(icw_ctx *c, int32_t M, double beta)
     if (!c || (M != 0 && (M < 2 || M > ICW_FIR_MAX_ORDER || (M & 1))) || !(beta >= 0.0 && beta < 1e3))
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    /* beside per-stream lists or inputs only once the host has asked for it (icw_enable_stream_fir): the
-     * converter's kernels then run their per-stream form */
-    if (M > 0 && !c->fir_streams && (c->lists.size() > 1 || c->inputs.size() > 1)) return ICW_EUNSUPPORTED;
-    /* nor beside per-stream CWAVE inputs (icw_enable_stream_cwave): the converter's per-stream kernels read
-     * real formats only, and icw_set_stream_input refuses to build that state from its side */
-    if (M > 0 && c->inputs.size() > 1 && any_cwave(c->inputs)) return ICW_EUNSUPPORTED;
-    /* nor beside per-stream renders (icw_set_stream_render): the fused converter renders with one */
-    if (M > 0 && c->renders.size() > 1) return ICW_EUNSUPPORTED;
-    /* nor beside per-stream Hilbert converters (icw_set_stream_hilbert): it replaces the IIR for every stream */
-    if (M > 0 && c->hilbs.size() > 1) return ICW_EUNSUPPORTED;
-    /* nor beside bus-form lists that stand beside others (icw_enable_stream_bus): the mixed K4 follows K2 */
-    if (M > 0 && c->bus_lists) return ICW_EUNSUPPORTED;
-    if (set_dev(c) || quiesce(c) != hipSuccess) return ICW_EDEVICE;
-    c->pid_valid = false;                 /* with the converter on, every (list, rate) pair has a slab */
-    for (double *&h : c->fir_hist)
-        if (h) { (void)hipFree(h); h = nullptr; }
-    if (c->d_fir_g) { (void)hipFree(c->d_fir_g); c->d_fir_g = nullptr; }
-    c->fir_M = c->fir_nt = 0;
-    c->fir_beta = 0.0;
-    c->fir_par = 0;
-    if (M == 0) return ICW_OK;
-    std::vector<double> g((size_t)(M / 2 + 1) / 2);
-    const int nt = icw_fir_taps(M, beta, g.data(), (int)g.size());
-    if (nt <= 0) return ICW_EINVAL;
-    const size_t hb = (size_t)c->n_streams * 2 * (size_t)M;
-    int rc = dalloc(&c->d_fir_g, (size_t)nt);
-    rc |= dalloc(&c->fir_hist[0], hb);
-    rc |= dalloc(&c->fir_hist[1], hb);
-    if (rc != ICW_OK || hipMemcpy(c->d_fir_g, g.data(), (size_t)nt * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-        for (double *&h : c->fir_hist)
-            if (h) { (void)hipFree(h); h = nullptr; }
-        if (c->d_fir_g) { (void)hipFree(c->d_fir_g); c->d_fir_g = nullptr; }
-        return rc == ICW_ENOMEM ? ICW_ENOMEM : ICW_EDEVICE;
-    }
-    c->fir_M = M;
-    c->fir_nt = nt;
-    c->fir_beta = beta;
-    bool ok = fir_clear(c, 0, (size_t)c->n_streams, c->stream);
-    ok &= hipStreamSynchronize(c->stream) == hipSuccess;
-    return ok ? ICW_OK : ICW_EDEVICE;
+    /* every stream: a context whose converters differed is a one-converter context again */
+    return set_fir_range(c, 0, c->n_streams, M, beta);
+}
+
+/* icw_set_fir_hilbert for streams [first, first + count) (include/icw.h) */
+int icw_set_stream_fir(icw_ctx *c, int first, int count, int32_t M, double beta)
+{
+    if (!c || first < 0 || count <= 0 || first > c->n_streams - count || M < 0 || M > ICW_FIR_MAX_ORDER || (M & 1) ||
+        !(beta >= 0.0 && beta < 1e3))
+        return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    /* the per-stream kernel instances serve it: asked for like per-stream lists and inputs beside the converter */
+    if (!c->fir_streams || c->cfg.fp_check) return ICW_EUNSUPPORTED;
+    /* all FIR or none: whether K1 runs is the call's decision, so a range goes neither off beside streams that
+     * stay on nor on beside streams that stay off */
+    const bool whole = first == 0 && count == c->n_streams;
+    if (!whole && (M == 0 || c->fir_M == 0)) return ICW_EUNSUPPORTED;
+    return set_fir_range(c, first, count, M, beta);
+}
+
+int icw_stream_fir_count(const icw_ctx *c)
+{
+    if (!c) return ICW_EINVAL;
+    std::lock_guard<std::mutex> lk(const_cast<icw_ctx *>(c)->mu);
+    return (int)c->firs.size();
 }
 
 /* per-stream lists and inputs beside the FIR converter, on or off (include/icw.h) */
@@ -931,6 +1027,7 @@ int icw_enable_stream_fir(icw_ctx *c, int on)
     std::lock_guard<std::mutex> lk(c->mu);
     /* off while the two are in force together would leave a state the setters refuse to build */
     if (!on && c->fir_M > 0 && (c->lists.size() > 1 || c->inputs.size() > 1)) return ICW_EUNSUPPORTED;
+    if (!on && c->firs.size() > 1) return ICW_EUNSUPPORTED;
     c->fir_streams = on != 0;
     return ICW_OK;
 }
@@ -1390,8 +1487,9 @@ struct IcwBlob {
 };
 constexpr uint64_t kBlobMagic = 0x33574349ull;   /* "ICW3" */
 
-/* with the FIR Hilbert converter on, its history (2 x k_M doubles, oldest first) follows the blob */
-size_t icw_state_size(const icw_ctx *c) { return c ? sizeof(IcwBlob) + 2 * (size_t)c->fir_M * sizeof(double) : 0; }
+/* with the FIR Hilbert converter on, the stream's history (2 x its own k_M doubles, oldest first) follows the
+ * blob; the size is that of the largest order in force, so one buffer serves every stream */
+size_t icw_state_size(const icw_ctx *c) { return c ? sizeof(IcwBlob) + 2 * (size_t)c->fir_Mmax * sizeof(double) : 0; }
 
 int icw_get_state(icw_ctx *c, int s, void *blob, size_t size)
 {
@@ -1403,7 +1501,7 @@ int icw_get_state(icw_ctx *c, int s, void *blob, size_t size)
     b.magic = kBlobMagic;
     b.nord = (uint32_t)c->hilbs.at((size_t)s).nord;     /* the stream's own order */
     b.has_render = c->render_state ? 1u : 0u;
-    b.fir_M = (uint32_t)c->fir_M;
+    b.fir_M = (uint32_t)c->firs.at((size_t)s).M;        /* the stream's own order */
     long long fd[3];
     bool ok = quiesce(c) == hipSuccess;
     ok &= hipMemcpy(&b.n_frame, c->st.n_frame + s, 8, hipMemcpyDeviceToHost) == hipSuccess;
@@ -1421,25 +1519,31 @@ int icw_get_state(icw_ctx *c, int s, void *blob, size_t size)
         ok &= hipMemcpy(b.rs, c->st.rs + (size_t)s * 2 * ICW_RSTATE, sizeof(b.rs), hipMemcpyDeviceToHost) == hipSuccess;
     }
     b.n_samples = fd[0]; b.n_fade_in = fd[1]; b.n_fade_out = fd[2];
-    if (c->fir_M) {
-        const size_t hrow = 2 * (size_t)c->fir_M;
-        ok &= hipMemcpy((unsigned char *)blob + sizeof(b), c->fir_hist[c->fir_par] + (size_t)s * hrow,
+    if (b.fir_M) {
+        const size_t hrow = 2 * (size_t)b.fir_M;
+        ok &= hipMemcpy((unsigned char *)blob + sizeof(b), c->fir_hist[c->fir_par] + c->fir_off[(size_t)s],
                         hrow * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
     }
     if (!ok) return ICW_EDEVICE;
     memcpy(blob, &b, sizeof(b));
+    /* the blob is sized by the largest order in force: what lies past this stream's own history is zero */
+    const size_t used = sizeof(b) + 2 * (size_t)b.fir_M * sizeof(double);
+    memset((unsigned char *)blob + used, 0, icw_state_size(c) - used);
     return ICW_OK;
 }
 
 int icw_set_state(icw_ctx *c, int s, const void *blob, size_t size)
 {
-    if (!c || !blob || size < icw_state_size(c) || s < 0 || s >= c->n_streams) return ICW_EINVAL;
+    if (!c || !blob || size < sizeof(IcwBlob) || s < 0 || s >= c->n_streams) return ICW_EINVAL;
     IcwBlob b;
     memcpy(&b, blob, sizeof(b));
+    /* a blob need hold no more than its own stream's history: one taken in a context whose largest order was
+     * the stream's fits a stream of that order in a context that also holds larger ones */
+    if (b.fir_M > ICW_FIR_MAX_ORDER || size < sizeof(IcwBlob) + 2 * (size_t)b.fir_M * sizeof(double)) return ICW_EINVAL;
     /* a blob holds the state of the render and converter forms in force when it was saved: the
      * serial-render words exist only with a dithered / shaped render, the FIR history only at its order */
     if (b.magic != kBlobMagic || b.nord != (uint32_t)c->hilbs.at((size_t)s).nord || b.has_render != (c->render_state ? 1u : 0u) ||
-        b.fir_M != (uint32_t)c->fir_M)
+        b.fir_M != (uint32_t)c->firs.at((size_t)s).M)
         return ICW_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (set_dev(c)) return ICW_EDEVICE;
@@ -1465,9 +1569,9 @@ int icw_set_state(icw_ctx *c, int s, const void *blob, size_t size)
         ok &= hipMemcpy(c->st.mt_idx + (size_t)s * 2, b.mt_idx, sizeof(b.mt_idx), hipMemcpyHostToDevice) == hipSuccess;
         ok &= hipMemcpy(c->st.rs + (size_t)s * 2 * ICW_RSTATE, b.rs, sizeof(b.rs), hipMemcpyHostToDevice) == hipSuccess;
     }
-    if (c->fir_M) {
-        const size_t hrow = 2 * (size_t)c->fir_M;
-        ok &= hipMemcpy(c->fir_hist[c->fir_par] + (size_t)s * hrow, (const unsigned char *)blob + sizeof(b),
+    if (b.fir_M) {
+        const size_t hrow = 2 * (size_t)b.fir_M;
+        ok &= hipMemcpy(c->fir_hist[c->fir_par] + c->fir_off[(size_t)s], (const unsigned char *)blob + sizeof(b),
                         hrow * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
     }
     return ok ? ICW_OK : ICW_EDEVICE;

@@ -103,6 +103,15 @@ struct HilbEnt {
     double pc[20]{}, pd[20]{}, d0 = 0.0;
 };
 
+/* one entry of the context's FIR converter table: the setting as given (M 0: the converter is off, the one
+ * entry of such a table), its taps and where they start in d_fir_g.  Entries are compared by (M, the bit
+ * pattern of beta) */
+struct FirEnt {
+    int M = 0, nt = 0;
+    double beta = 0.0;
+    size_t goff = 0;                      /* doubles into d_fir_g */
+};
+
 /* workgroups of wg_waves waves that a run of n streams takes in a mixed recurrence launch: whole wave
  * pairs of 4 chain slots per filter in the row form, whole 128-lane groups of 32 streams (64 under the
  * mono dedup) in the lane form, then whole workgroups */
@@ -125,25 +134,29 @@ struct icw_ctx {
     IcwRenderK rk{};
     IcwProg prog{};
     IcwProg *d_prog = nullptr;
-    /* The four per-stream settings -- DSP lists (icw_set_stream_graph), inputs (icw_set_stream_input), renders
-     * (icw_set_stream_render) and Hilbert converters (icw_set_stream_hilbert) -- are one StreamTable each: the
+    /* The five per-stream settings -- DSP lists (icw_set_stream_graph), inputs (icw_set_stream_input), renders
+     * (icw_set_stream_render), Hilbert converters (icw_set_stream_hilbert) and FIR converters
+     * (icw_set_stream_fir) -- are one StreamTable each: the
      * distinct values in force and every stream's index.  A context whose streams share a setting holds a
      * one-entry table; nothing asks whether a table is "there".  Every edit, context-wide or per-stream,
      * builds a candidate table and goes through the setting's install (icw_context.cpp), which puts the
      * device side in place first and then swaps the table in.
      * The fields the rest of the library reads are mirrors of entry 0, each written by its table's mirror_*
      * function alone: nodes / prog / cfg.bypass_list (lists), cfg.render / cfg.need24bits / rk (renders) and
-     * cfg.hilbert_type / iir_kahan / iir_subnorm_reject / nord / pc / pd / d0 (converters); serial_render and
+     * cfg.hilbert_type / iir_kahan / iir_subnorm_reject / nord / pc / pd / d0 (converters) and fir_M / fir_nt /
+     * fir_beta (FIR converters); serial_render and
      * render_state are "some render entry needs it"; cfg.sample_rate / in_format / in_channels are the one
      * input, and while the inputs differ the one last in force alone.
      * The device keeps tables only for more than one entry: d_progs (the entries' programs; bus form among
      * them only with icw_enable_stream_bus),
      * d_inputs (one descriptor per stream), d_rtab + d_rof (entries, then the index row, one allocation),
-     * d_hpc (below).  A one-entry context launches from d_prog and the scalar arguments. */
+     * d_hpc (below), d_fconv (one descriptor per stream).  A one-entry context launches from d_prog and the
+     * scalar arguments. */
     StreamTable<ListEnt> lists;
     StreamTable<IcwInDesc> inputs;
     StreamTable<RenderEnt> renders;
     StreamTable<HilbEnt> hilbs;
+    StreamTable<FirEnt> firs;
     IcwProg *d_progs = nullptr;
     size_t d_progs_cap = 0;               /* entries d_progs has room for */
     /* icw_enable_stream_bus: bus-form lists are served beside other lists.  Off on a fresh context, where the
@@ -257,13 +270,19 @@ struct icw_ctx {
     /* the dither generator's chunks of the last icw_process_* call's first launch block and their length
      * (icw_last_dither_chunks; 0: no generator ran) */
     int last_dchunks = 0, last_dchunk_frames = 0;
-    /* FIR Hilbert converter (icw_set_fir_hilbert): order (0: the quadrature IIR), taps, and the
-     * per-stream input history [streams][2][M], double-buffered by launch block (fir_par) */
-    int fir_M = 0, fir_nt = 0;
+    /* FIR Hilbert converter (icw_set_fir_hilbert, icw_set_stream_fir): the mirror of entry 0 of firs -- order
+     * (0: the quadrature IIR; every entry is then off), taps, beta -- the entries' taps one after the other
+     * (FirEnt.goff), and the per-stream input history, double-buffered by launch block (fir_par): stream s
+     * holds [2][M_s] doubles from fir_off[s] on, fir_off the running sum of 2 M_s ([streams + 1]; one entry:
+     * [streams][2][M]).  fir_Mmax: the largest order in force (the state blob's size).  d_fconv: every
+     * stream's descriptor, while the table has several entries */
+    int fir_M = 0, fir_nt = 0, fir_Mmax = 0;
     double fir_beta = 0.0;
     double *d_fir_g = nullptr;
     double *fir_hist[2] = {};
     int fir_par = 0;
+    std::vector<size_t> fir_off;
+    IcwFirConv *d_fconv = nullptr;
     /* icw_enable_stream_fir: per-stream lists and inputs are served beside the converter.  Off on a fresh
      * context, where the three setters keep the refusals they always had */
     bool fir_streams = false;

@@ -56,6 +56,16 @@ struct IcwK0MixArgs {
     const IcwInDesc *desc;         /* [n_streams] of the launch */
 };
 
+/* One stream's FIR converter (icw_set_stream_fir): a row of the context's device table [n_streams], kept
+ * while the streams' converters differ.  The history buffers hold stream after stream, [2][M] doubles each at
+ * the stream's own M, so a stream's rows start at the sum of the orders before it (one converter: s * 2 * M,
+ * the layout it always was). */
+struct IcwFirConv {
+    int32_t M, nt;                 /* the stream's order and taps */
+    const double *g;               /* [nt] its entry's taps */
+    unsigned long long hoff;       /* doubles from a history buffer's start to the stream's rows */
+};
+
 /* Arguments of the FIR Hilbert converter kernels (KF / KF2, the CWAVE converter of cwave.h:40,56-58:
  * a Kaiser-windowed Hilbert FIR of order M = k_M, window parameter k_beta).  A workgroup stages the
  * inputs x[t - M .. t + tile) of its channels (unpacked and faded like K0, the M before the block
@@ -90,6 +100,10 @@ struct IcwFirArgs {
      * map[x] of the call (a launch covers one channel class, IcwFirClass) */
     const IcwInDesc *desc;
     const int32_t *map;
+    /* conv -- nullable [n_streams of the call] (icw_set_stream_fir, several converters in force): the stream's
+     * own M, nt and g replace the three above, which then hold the widest entry of the launch for its LDS
+     * size; hist_in / hist_out are the two whole buffers and the stream's rows lie hoff doubles into them */
+    const IcwFirConv *conv;
 };
 
 /* One channel class of a FIR call over streams with different lists or inputs (icw_launch_fir_graph_mix):
@@ -102,6 +116,7 @@ struct IcwFirClass {
     int32_t lr_same;               /* mono: IcwFirArgs.lr_same holds for every stream */
     int32_t trig;                  /* some stream's program has an active Shift / PM node */
     int32_t in_step;               /* every stream is in step with its slab's reference stream */
+    int32_t M, nt;                 /* IcwFirArgs.conv: the widest order and taps among the class's streams (0: the call's) */
 };
 
 /* Arguments of the CWAVE encoder (KFE): KF's, with the packed file frames as the output (xd unused) */

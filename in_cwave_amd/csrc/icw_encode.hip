@@ -112,6 +112,7 @@ template <int CWF>
 __global__ __launch_bounds__(256) void icw_fir_encode_mixed(IcwEncArgs e)
 {
     icw_fir_own_input(e.f, blockIdx.y);
+    icw_fir_own_conv(e.f, blockIdx.y);
     if (e.f.nch > 1) icw_fir_encode_ps<CWF, 2>(e);
     else icw_fir_encode_ps<CWF, 1>(e);
 }
@@ -290,7 +291,7 @@ static hipError_t launch_fir_encode_mixed_t(const IcwEncArgs *e, hipStream_t st)
 extern "C" hipError_t icw_launch_fir_encode_mixed(const IcwEncArgs *e, int cwf, hipStream_t st)
 {
     const int M = e->f.M, nt = e->f.nt;
-    if (!e->f.desc || !e->out || !e->clipped || e->f.n_streams <= 0) return hipErrorInvalidValue;
+    if ((!e->f.desc && !e->f.conv) || !e->out || !e->clipped || e->f.n_streams <= 0) return hipErrorInvalidValue;
     if (M < 2 || M > ICW_FIR_MAX_M || (M & 1) || nt < 1 || 2 * nt - 1 > M / 2 || e->f.T <= 0) return hipErrorInvalidValue;
     switch (cwf) {
     case 0: return launch_fir_encode_mixed_t<0>(e, st);

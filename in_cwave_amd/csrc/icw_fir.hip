@@ -28,7 +28,8 @@
 /* The per-stream form of the FIR kernels (PS; streams with different lists or inputs, as K2's MIX): the
  * workgroup is one stream, so what it selects is wave-uniform and comes in by scalar loads through the
  * constant address space.  The PS = false instances are the kernels of a one-list, one-input call.
- * (icw_fir_own_input, the stream's own input: icw_fir_dev.h, shared with the encoder.) */
+ * (icw_fir_own_input and icw_fir_own_conv, the stream's own input and converter: icw_fir_dev.h, shared with the
+ * encoder.) */
 typedef const __attribute__((address_space(4))) int32_t icw_csel;
 
 /* KF: the converter alone, one workgroup per channel and 2048-frame tile of a stream; I / Q rows
@@ -42,6 +43,7 @@ __device__ __forceinline__ void icw_fir_hilbert_body(IcwFirArgs a)
     if constexpr (PS) {
         /* the grid has the widest stream's channels: a mono stream's second column has nothing to do */
         icw_fir_own_input(a, s);
+        icw_fir_own_conv(a, s);
         if (ch >= (a.nch > 1 ? 2 : 1)) return;
     }
     const int tt = blockIdx.x * TF;
@@ -170,6 +172,7 @@ __global__ __launch_bounds__(256, ICW_FIR_OCC) void icw_fir_graph(IcwFirArgs f, 
         /* the launch's class of streams through its map, then the stream's own input */
         if (f.map) s = ((icw_csel *)f.map)[blockIdx.x];
         icw_fir_own_input(f, s);
+        icw_fir_own_conv(f, s);
     }
     constexpr int nchc = NC;
     const int TF = 256 * ICW_FIR_R / nchc;
@@ -414,6 +417,7 @@ __global__ __launch_bounds__(256, NC == 2 ? ICW_FIR_SIG_OCC : ICW_FIR_SIG_OCC1) 
     if constexpr (PS) {
         if (f.map) s = ((icw_csel *)f.map)[blockIdx.x];
         icw_fir_own_input(f, s);
+        icw_fir_own_conv(f, s);
     }
     const int tt = blockIdx.y * TF;
     const int M = f.M, c = M >> 1;
@@ -607,12 +611,13 @@ extern "C" hipError_t icw_launch_fir(const IcwFirArgs *a, hipStream_t st)
     constexpr int TF = 256 * ICW_FIR_R;
     const size_t lds = fir_lds(a->M, a->nt, 1, TF, 0);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    /* streams with different inputs (a->desc): the instance that reads each stream's own; a->nch is then
-     * the widest stream's */
-    const void *fn = a->desc ? (const void *)icw_fir_hilbert_mixed : (const void *)icw_fir_hilbert;
+    /* streams with different inputs (a->desc) or converters (a->conv): the instance that reads each stream's
+     * own; a->nch, a->M and a->nt are then the widest stream's */
+    const bool ps = a->desc || a->conv;
+    const void *fn = ps ? (const void *)icw_fir_hilbert_mixed : (const void *)icw_fir_hilbert;
     if (fir_lds_attr(fn, lds) != hipSuccess) return hipErrorInvalidValue;
     dim3 grid((a->T + TF - 1) / TF, a->nch > 1 ? 2 : 1, a->n_streams);
-    if (a->desc) hipLaunchKernelGGL(icw_fir_hilbert_mixed, grid, dim3(256), lds, st, *a);
+    if (ps) hipLaunchKernelGGL(icw_fir_hilbert_mixed, grid, dim3(256), lds, st, *a);
     else hipLaunchKernelGGL(icw_fir_hilbert, grid, dim3(256), lds, st, *a);
     return hipGetLastError();
 }
@@ -706,7 +711,7 @@ static hipError_t launch_fir_graph(const IcwFirArgs *f, const IcwK2Args *a, int 
 extern "C" hipError_t icw_launch_fir_graph(const IcwFirArgs *f, const IcwK2Args *a, int in_step, int sig_on,
                                            hipStream_t st)
 {
-    if (f->desc || f->map || a->prog_id) return hipErrorInvalidValue;   /* icw_launch_fir_graph_mix's call */
+    if (f->desc || f->map || f->conv || a->prog_id) return hipErrorInvalidValue;   /* icw_launch_fir_graph_mix's call */
     return launch_fir_graph<false>(f, a, in_step, sig_on, st);
 }
 
@@ -730,6 +735,10 @@ extern "C" hipError_t icw_launch_fir_graph_mix(const IcwFirArgs *f, const IcwK2A
         fc.map = c.map;
         fc.sig = c.sig;
         fc.lr_same = c.nch == 1 ? c.lr_same : 0;
+        if (f->conv && c.M > 0) {                    /* LDS for the widest converter among the class's streams */
+            fc.M = c.M;
+            fc.nt = c.nt;
+        }
         IcwK2Args ac = *a;
         ac.trig = c.trig ? 1 : 0;
         const hipError_t e = launch_fir_graph<true>(&fc, &ac, c.in_step, sig_on, st);

@@ -266,6 +266,23 @@ __device__ __forceinline__ void icw_fir_own_input(IcwFirArgs &f, int s)
     }
 }
 
+/* the stream's own converter replaces the launch's (icw_set_stream_fir): order, taps, and its rows of the two
+ * history buffers -- hoff doubles into them, laid so that the staging's (s * 2 + ch) * M lands there; a null
+ * table leaves the launch's one converter.  What depends on M (icw_fir_sh / _av / _px, the LDS carve-up) is
+ * computed after this, per workgroup, inside the launch's LDS, which is sized for its widest entry */
+__device__ __forceinline__ void icw_fir_own_conv(IcwFirArgs &f, int s)
+{
+    if (f.conv) {
+        const __attribute__((address_space(4))) IcwFirConv *d = (const __attribute__((address_space(4))) IcwFirConv *)f.conv + s;
+        f.M = d->M;
+        f.nt = d->nt;
+        f.g = d->g;
+        const ptrdiff_t off = (ptrdiff_t)d->hoff - (ptrdiff_t)s * 2 * f.M;
+        f.hist_in += off;
+        f.hist_out += off;
+    }
+}
+
 /* The taps through the constant address space: every lane of a wave reads the same tap, so they
  * come in by scalar loads into SGPRs (the FMA takes one SGPR operand) and leave the LDS pipe to the
  * inputs -- which bounds the sums: 52 -> 44 LDS reads per 8-tap block of a lane's 8 outputs. */

@@ -273,6 +273,11 @@ struct CallPlan {
     size_t slab_stride = 0;
     /* the mode flags */
     bool cw = false, fir = false, fir_fused = false, fir_async = false, bus = false, fcm = false, dedup = false;
+    /* fir over a context with several FIR converters (icw_set_stream_fir): the per-stream kernels read each
+     * stream's own from the context's table, and fir_M / fir_nt are the widest among the call's streams (the
+     * launches' LDS); one converter: the context's */
+    bool firmix = false;
+    int fir_M = 0, fir_nt = 0;
     /* bus, over several list entries (icw_enable_stream_bus): the mixed K4 over the call's runs of one entry
      * (prepare_bus_runs: its workgroups and the lanes of a bus row), every entry in bus form.  call_render: the
      * context's one render entry as this call runs it, serial behind a bus-form call (bus_lists) */
@@ -618,12 +623,14 @@ struct CallPlan {
         IcwFirArgs af;
         memset(&af, 0, sizeof(af));
         reader_args(af, b);
-        af.M = c->fir_M;
-        af.nt = c->fir_nt;
+        af.M = fir_M;
+        af.nt = fir_nt;
         af.g = c->d_fir_g;
-        const size_t hrow = 2 * (size_t)c->fir_M;
-        af.hist_in = c->fir_hist[(c->fir_par + b) & 1] + f0 * hrow;
-        af.hist_out = c->fir_hist[(c->fir_par + b + 1) & 1] + f0 * hrow;
+        /* the rows of the call's first stream; firmix: the whole buffers, every stream finds its own rows */
+        const size_t h0 = firmix ? 0 : c->fir_off[f0];
+        af.hist_in = c->fir_hist[(c->fir_par + b) & 1] + h0;
+        af.hist_out = c->fir_hist[(c->fir_par + b + 1) & 1] + h0;
+        af.conv = firmix ? c->d_fconv + f0 : nullptr;
         af.xd = c->xd[b % n_sets];
         af.x_pitch = x_pitch;
         af.sig = lp->chain ? lp->sig : 0;
@@ -636,7 +643,7 @@ struct CallPlan {
 
     /* where block b's frames go: the one-input kernels get the block's first frame (the host knows the one
      * frame size); the per-stream ones the call's first frame and apply the offset at their stream's own */
-    unsigned char *enc_out(int b) const { return d_out + (mixin ? 0 : (size_t)blocks[b].first * efb); }
+    unsigned char *enc_out(int b) const { return d_out + (mixin || firmix ? 0 : (size_t)blocks[b].first * efb); }
 
     /* KFE of block b: KF's arguments, the packed frames as the output.  It packs frames instead of writing
      * K2's rows, and no graph follows it: no row buffer, no chain signature */
@@ -728,6 +735,7 @@ struct CallPlan {
     size_t out_row_bytes(size_t i) const;
     bool copy_out_own() const;
     bool fir_hist_back() const;
+    void resolve_fir();
     int enc_format(uint32_t cw_fmt, bool fir_ok);
     int enc_buffers();
     int enc_mix_lists();
@@ -793,11 +801,11 @@ hipError_t CallPlan::launch_unpack(int b, hipStream_t s) const
     return icw_launch_unpack(&m.k0, s);
 }
 
-/* KFE of block b on the caller's stream; streams with different inputs: its per-stream form */
+/* KFE of block b on the caller's stream; streams with different inputs or converters: its per-stream form */
 hipError_t CallPlan::launch_fir_encode(int b, int cwf) const
 {
     const auto e = enc_args(b);
-    if (mixin) return icw_launch_fir_encode_mixed(&e, cwf, st);
+    if (mixin || firmix) return icw_launch_fir_encode_mixed(&e, cwf, st);
     return icw_launch_fir_encode(&e, cwf, st);
 }
 
@@ -1033,9 +1041,25 @@ bool CallPlan::copy_out_own() const
 bool CallPlan::fir_hist_back() const
 {
     if (!(n_blocks & 1)) return true;
-    const size_t hrow = 2 * (size_t)c->fir_M;
-    return hipMemcpyAsync(c->fir_hist[c->fir_par] + f0 * hrow, c->fir_hist[c->fir_par ^ 1] + f0 * hrow,
-                          S * hrow * sizeof(double), hipMemcpyDeviceToDevice, st) == hipSuccess;
+    const size_t at = c->fir_off[f0], len = c->fir_off[f0 + S] - at;     /* the call's streams, each at its own order */
+    return hipMemcpyAsync(c->fir_hist[c->fir_par] + at, c->fir_hist[c->fir_par ^ 1] + at, len * sizeof(double),
+                          hipMemcpyDeviceToDevice, st) == hipSuccess;
+}
+
+/* the FIR converter of the call's streams (fir is set): the context's one, or -- several in force -- the table,
+ * with the widest order and taps of the call.  A call whose own streams share an entry takes the table too:
+ * the bytes are the same, and the history is then found one way */
+void CallPlan::resolve_fir()
+{
+    fir_M = c->fir_M;
+    fir_nt = c->fir_nt;
+    firmix = fir && c->firs.size() > 1;
+    if (!firmix) return;
+    fir_M = fir_nt = 0;
+    for (size_t i = 0; i < S; ++i) {
+        fir_M = std::max(fir_M, c->firs.at(f0 + i).M);
+        fir_nt = std::max(fir_nt, c->firs.at(f0 + i).nt);
+    }
 }
 
 /* The encoders' input and format checks.  The input of the call's streams is resolved as resolve_plan
@@ -1061,6 +1085,7 @@ int CallPlan::enc_format(uint32_t cw_fmt, bool fir_ok)
     }
     if (mixin) dD = c->d_inputs + f0;
     fir = c->fir_M > 0;
+    resolve_fir();
     cw_format = cw_fmt;
     efb = icw_cwave_frame_bytes(cw_fmt, nch);
     if (fmt >= ICW_FMT_CW_F64 || !fir_ok || efb == 0) return ICW_EINVAL;
@@ -1180,12 +1205,13 @@ int CallPlan::resolve_plan()
      * the block continues as CWAVE input does */
     fir = c->fir_M > 0 && fmt < ICW_FMT_CW_F64;
     cw = fmt >= ICW_FMT_CW_F64 || fir;
+    resolve_fir();
     /* the list of the call's streams: the one table entry all of them run, or -- streams with different
      * lists or inputs -- the table with K2's per-stream selection (prepare_mix).  The device holds the table
      * only for more than one entry; a one-list context launches from d_prog */
     lp = &c->lists.at(f0).prog;
     dP = c->lists.size() > 1 ? c->d_progs : c->d_prog;
-    mix = mixin || !c->lists.uniform(f0, S);
+    mix = mixin || firmix || !c->lists.uniform(f0, S);
     if (!mix) dP += c->lists.index(f0);
     if (mix) {
         const int rc = prepare_mix(c, first, count, fir, st);
@@ -1220,12 +1246,20 @@ int CallPlan::resolve_plan()
     /* (per-stream lists: LP is the mixed program, its n_regs the largest of the call's streams; every
      * channel class present must fit) */
     const int fir_regs = LP.chain ? 0 : LP.n_regs;
-    bool fir_fits = icw_fir_graph_lds(c->fir_M, c->fir_nt, (int)nch, fir_regs) > 0;
-    if (fir && mix)
-        for (int k = 0; k < 2; ++k) {
-            fir_cls[k] = c->pid_cls[k];
-            if (fir_cls[k].n > 0 && !icw_fir_graph_lds(c->fir_M, c->fir_nt, k + 1, fir_regs)) fir_fits = false;
+    bool fir_fits = icw_fir_graph_lds(fir_M, fir_nt, (int)nch, fir_regs) > 0;
+    if (fir && mix) {
+        for (int k = 0; k < 2; ++k) fir_cls[k] = c->pid_cls[k];
+        /* several converters: each class's launch is sized by the widest entry among its own streams */
+        for (size_t i = 0; firmix && i < S; ++i) {
+            IcwFirClass &fc = fir_cls[c->inputs.at(f0 + i).nch > 1 ? 1 : 0];
+            fc.M = std::max(fc.M, (int32_t)c->firs.at(f0 + i).M);
+            fc.nt = std::max(fc.nt, (int32_t)c->firs.at(f0 + i).nt);
         }
+        for (int k = 0; k < 2; ++k) {
+            const IcwFirClass &fc = fir_cls[k];
+            if (fc.n > 0 && !icw_fir_graph_lds(firmix ? fc.M : fir_M, firmix ? fc.nt : fir_nt, k + 1, fir_regs)) fir_fits = false;
+        }
+    }
     fir_fused = fir && c->tn.fir_fuse && fir_fits && !LP.is_bus;
     /* The row kernel without a serial render (C2) has K2 at ~0.16 of K1r's time per frame: 65 536-frame
      * blocks (a quarter of the launches, of their gaps and prologues) ending in a steep tail
@@ -1819,6 +1853,7 @@ int enc_begin(std::optional<CallPlan> &plan, std::unique_lock<std::mutex> &lk, b
     lk = std::unique_lock<std::mutex>(c->mu);
     if (c->inputs.size() > 1 && !c->enc_streams) return ICW_EUNSUPPORTED;   /* per-stream inputs: asked for (include/icw.h) */
     if (c->hilbs.size() > 1) return ICW_EUNSUPPORTED;                   /* per-stream Hilbert converters: not served */
+    if (c->firs.size() > 1 && !c->enc_streams) return ICW_EUNSUPPORTED;    /* per-stream FIR converters: asked for, as inputs are */
     plan.emplace(c, first, count, in, in_stride, out, out_stride, n_frames, flags, hip_stream);
     return plan->enc_format(cw_format, (c->fir_M > 0) == fir);
 }

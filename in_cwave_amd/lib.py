@@ -170,6 +170,16 @@ class Context:
         """icw_enable_stream_fir: per-stream lists and inputs beside the FIR converter (off on a fresh context)"""
         _check(self._lib.icw_enable_stream_fir(self.h, int(bool(on))), "icw_enable_stream_fir")
 
+    def set_stream_fir(self, order, beta=8.0, first=0, count=None):
+        """icw_set_stream_fir: the FIR Hilbert converter (order k_M, Kaiser beta) of streams [first, first + count)
+        for the next calls; their FIR history restarts, the other streams keep theirs"""
+        count = self.n_streams - first if count is None else count
+        _check(self._lib.icw_set_stream_fir(self.h, int(first), int(count), int(order), float(beta)), "icw_set_stream_fir")
+
+    def stream_fir_count(self):
+        """icw_stream_fir_count: distinct (k_M, k_beta) in force (1 on a fresh context and with the converter off)"""
+        return int(self._lib.icw_stream_fir_count(self.h))
+
     def enable_stream_bus(self, on=True):
         """icw_enable_stream_bus: set_stream_graph takes bus-form lists (feedback, delays, more than 16 nodes),
         each stream with its own, and set_graph takes one while the lists differ (off on a fresh context)"""

@@ -512,7 +512,48 @@ int icw_stream_hilbert_count(const icw_ctx *ctx);     /* distinct (type, kahan, 
  * for complex samples).  k_M = 0 restores the reference's own quadrature IIR Hilbert (the default).
  * k_M even, 2..ICW_FIR_MAX_ORDER.  Every stream's FIR history (its last k_M inputs) starts at zero;
  * icw_stream_init / icw_stream_reset_hilbert / icw_stream_open(clr_hilb) clear it too.
- * The converter is context-wide -- one k_M, one k_beta.
+ * icw_set_fir_hilbert gives every stream the converter -- one k_M, one k_beta -- or turns it off with 0.
+ * Per-stream FIR converters: a batch whose streams each carry their own (k_M, k_beta), as every CWAVE header
+ * records its own, in ONE context, so a host that encodes or decodes a library at several orders keeps the
+ * batch width.
+ *   icw_set_stream_fir        icw_set_fir_hilbert for streams [first, first + count) only, in force from the
+ *                             next call on (the context's work is waited for).  The streams of the range
+ *                             start from a zero FIR history, also when the setting is unchanged (as
+ *                             icw_set_fir_hilbert does for every stream); every stream outside the range keeps
+ *                             its history bit for bit, whatever the edit does to the largest order in force.
+ *                             The context keeps the distinct (k_M, bit pattern of k_beta) entries, each with
+ *                             its taps, and an index per stream; streams given the same pair share one entry,
+ *                             unused entries go, and one entry left is a one-converter context again, which
+ *                             issues the launches it always did.
+ *   icw_stream_fir_count      distinct (k_M, k_beta) in force; 1 on a fresh context and with the converter off.
+ * icw_set_fir_hilbert keeps its meaning, every stream, and leaves one entry.  In a context with more than one
+ * entry every converter call takes the kernels' per-stream form -- also a call whose own streams share an
+ * entry; the bytes are the same either way.  A workgroup is one stream and works at its stream's own order; a
+ * launch's LDS is sized by the widest order among its streams, and where some stream of a call does not fit
+ * the fused kernel the call runs the converter and the output kernel apart, as a one-converter call does.
+ * All FIR or none: k_M == 0 is accepted only for the whole context (first == 0, count == n_streams), where it
+ * is icw_set_fir_hilbert(ctx, 0, ..); k_M > 0 on a proper sub-range of a context whose converter is off is
+ * refused.
+ * The state blob is sized by the largest order in force (icw_state_size), records the stream's own order and
+ * carries that many history doubles per channel (the rest of the blob is zero); icw_set_state takes a blob of
+ * at least the fixed part plus its own order's history, and returns ICW_EINVAL when the blob's order is not
+ * the target stream's.  It does not carry the selection, as it carries no other.
+ * icw_encode_cwave writes stream s with stream s's own converter once the host asked for both
+ * icw_enable_stream_encode and icw_enable_stream_fir (ICW_EUNSUPPORTED while the count is above 1 without
+ * the former); the frames are byte for byte those a one-converter context of that pair writes.
+ * Limits, each refusal changing nothing:
+ *   ICW_EINVAL        a range outside the context; k_M odd, negative or above ICW_FIR_MAX_ORDER; k_beta outside
+ *                     [0, 1e3).
+ *   ICW_EUNSUPPORTED  - icw_enable_stream_fir not on (the per-stream kernel instances serve this);
+ *                     - the two all-or-none cases above;
+ *                     - a cfg.fp_check context;
+ *                     - what icw_set_fir_hilbert(k_M > 0) refuses: per-stream CWAVE inputs, a bus-form list
+ *                       beside others, per-stream renders or per-stream IIR Hilbert settings with a count
+ *                       above 1;
+ *                     icw_set_stream_render and icw_set_stream_hilbert keep refusing while the converter is
+ *                     on, and icw_enable_stream_fir(ctx, 0) is refused while the FIR count is above 1.
+ * Not served: icw_group, the icw_amod_* drop-in and every file entry point (icw_reader.h: they keep their one
+ * k_M).
  *   icw_enable_stream_fir(ctx, 1)  serves per-stream lists (icw_set_stream_graph) and per-stream inputs
  *                                  (icw_set_stream_input) beside the converter from then on: the three
  *                                  setters work in any order, the converter on or off at any count, and
@@ -526,6 +567,8 @@ int icw_stream_hilbert_count(const icw_ctx *ctx);     /* distinct (type, kahan, 
 #define ICW_FIR_MAX_ORDER 4096
 int icw_set_fir_hilbert(icw_ctx *ctx, int32_t k_M, double k_beta);
 int icw_enable_stream_fir(icw_ctx *ctx, int on);
+int icw_set_stream_fir(icw_ctx *ctx, int first, int count, int32_t k_M, double k_beta);
+int icw_stream_fir_count(const icw_ctx *ctx);   /* distinct (k_M, k_beta) in force; 1 on a fresh context and with the converter off */
 /* The taps of that design: g[k] = g_{2k+1}, k < nt = (k_M/2 + 1)/2.  Returns nt (or ICW_EINVAL). */
 int icw_fir_taps(int32_t k_M, double k_beta, double *g, int n);
 
@@ -624,7 +667,7 @@ const char *icw_strerror(int status);
  *   2  icw_mod_context_fopen takes need24bits (its 11th argument, in_cwave.c:212) -- a binding built
  *      against version 1 would pass an undefined bit depth.
  * Entry points that were only added (the per-stream setters and their opt-ins, icw_enable_stream_cwave,
- * icw_last_dither_chunks, icw_enable_stream_bus the latest) leave it: a binding built against an earlier header of version 2 still
+ * icw_last_dither_chunks, icw_enable_stream_bus, icw_set_stream_fir the latest) leave it: a binding built against an earlier header of version 2 still
  * calls what it knows. */
 #define ICW_ABI_VERSION 2
 int icw_abi_version(void);

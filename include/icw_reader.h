@@ -112,7 +112,9 @@ int icw_transcode_files_lists(const icw_config *cfg, const icw_node *const *node
  * and lists beside the converter, include/icw.h).  k_M and k_beta as icw_set_fir_hilbert takes them with
  * the converter on: k_M even, 2..ICW_FIR_MAX_ORDER (0 is refused: that call is icw_transcode_files_lists),
  * 0 <= k_beta < 1e3; anything else returns ICW_EINVAL before a file is opened -- nothing runs, nothing is
- * written, stats and status are left alone. */
+ * written, stats and status are left alone.
+ * Not offered: a converter per file.  Every context of the call gets the one (k_M, k_beta); a context whose
+ * streams each carry their own is icw_set_stream_fir's (icw.h). */
 int icw_transcode_files_fir(const icw_config *cfg, const icw_node *const *nodes, const int *n_nodes,
                             const int *bypass_list, const char *const *in_paths, const char *const *out_paths, int n,
                             int32_t k_M, double k_beta, const icw_batch_opts *opts, icw_batch_stats *stats, int *status);
@@ -164,7 +166,9 @@ typedef struct icw_pool_stats {
  * ICW_EUNSUPPORTED for cfg->fp_check; else ICW_OK if every file was transcoded, else one of the files'
  * errors, as icw_transcode_files_lists returns it.
  * Not offered: the FIR converter, the three CWAVE encoders, icw_transcode_files_devices / icw_group.  Per-file
- * renders and Hilbert settings: icw_transcode_files_jobs below. */
+ * renders and Hilbert settings: icw_transcode_files_jobs below.  Per-file FIR converters (icw_set_stream_fir,
+ * icw.h, serves them in a context): no file entry point -- icw_transcode_files_fir and icw_cwave_encode_files keep
+ * their one k_M, and neither the pool nor the jobs call runs the converter. */
 int icw_transcode_files_pool(const icw_config *cfg, const icw_node *const *nodes, const int *n_nodes,
                              const int *bypass_list, const char *const *in_paths, const char *const *out_paths,
                              int n, const icw_pool_opts *opts, icw_pool_stats *stats, icw_meters *meters, int *status);
@@ -299,7 +303,8 @@ typedef struct icw_cwave_enc_opts {
  * 2^32 frames or more, or an I/O error; the rest of the batch still completes.  clipped (nullable, n
  * entries) gets the file's saturated / NaN int16 samples.  Returns ICW_EINVAL for bad options (nothing
  * runs), else ICW_OK if every file was encoded, else one of the files' errors.
- * Not covered: V1 headers. */
+ * Not covered: V1 headers.  Not offered: a converter per file (one k_M and k_beta for the batch; per-stream
+ * converters are icw_set_stream_fir with icw_encode_cwave, icw.h). */
 int icw_cwave_encode_files(const char *const *in_paths, const char *const *out_paths, int n,
                            const icw_cwave_enc_opts *opts, icw_batch_stats *stats, uint64_t *clipped, int *status);
 
